@@ -19,6 +19,9 @@ Prints ONE JSON line (rank 0).  Extra objects in it:
                   the timed region itself)
   knn          -- the fused 1-NN kernel at the YCB symmetric-loss size (R=500, Q=500 000)
   cpu_baseline -- the CPU oracle (a port of the reference path) timed on this host, bounded sample
+
+--dump-outputs DIR writes the poses of the last timed step as .npy files; the inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -204,6 +207,17 @@ def bucket_poses(buckets, groups):
             out[bi][lo:hi] = p[o:o + hi - lo]
             o += hi - lo
     return out
+
+
+def dump_outputs(path, groups, buckets, total, rank, gdev):
+    """--dump-outputs: what the step's caller receives, (pose_wo_refine, pose), for every object of the stream (all ranks'
+    shards gathered) in stream order, written by rank 0 as DIR/<name>.npy, float64 [total, 7]."""
+    idx = [i for g in groups for bi, lo, hi in g["part"] for i in buckets[bi]["idx"][lo:hi]]
+    for k, name in enumerate(("pose_wo_refine", "pose")):
+        full = sharding.gather_poses(idx, torch.cat([g["out"][k] for g in groups]).to(gdev), total)
+        if rank == 0:
+            os.makedirs(path, exist_ok=True)
+            np.save(os.path.join(path, name + ".npy"), full.cpu().numpy())
 
 
 def profile_gemm(pe, groups, steps):
@@ -832,7 +846,11 @@ def main():
     ap.add_argument("--no-knn", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only to rehearse "
                                                       "the multi-rank path with several ranks on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the poses the last timed step returned to "
+                                                          "DIR/pose_wo_refine.npy and DIR/pose.npy (float64 [objects, 7], stream order)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     globals()["ITERS"] = args.refine_iters
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -959,6 +977,8 @@ def main():
         witness = {"ranks_seen": len(seen), "distinct_devices": len(ids), "backend": args.backend + (" (RCCL)" if args.backend == "nccl" else ""),
                    "per_rank_poses_per_s": {"min": round(min(rates), 1), "max": round(max(rates), 1)},
                    "device_uuids": sorted(ids)}
+    if args.dump_outputs:      # before profile_gemm's re-run overwrites instance 0's outputs
+        dump_outputs(args.dump_outputs, insts[(args.steps - 1) % len(insts)].groups, buckets, poses_per_step * world, rank, gdev)
 
     if rank == 0:
         total_poses = poses_per_step * world * args.steps

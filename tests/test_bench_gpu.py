@@ -5,15 +5,25 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_json_contract():
+def _dumped_poses(d, n):
+    """--dump-outputs: the last timed step's (pose_wo_refine, pose) of all n objects, float64 [n, 7], unit quaternions first"""
+    for name in ("pose_wo_refine", "pose"):
+        p = np.load(os.path.join(d, name + ".npy"))
+        assert p.dtype == np.float64 and p.shape == (n, 7) and np.isfinite(p).all(), name
+        assert np.allclose(np.linalg.norm(p[:, :4], axis=1), 1.0, atol=1e-5), name      # no row left unfilled
+
+
+def test_bench_json_contract(tmp_path):
     env = dict(os.environ, DF_BENCH_CPU_BUDGET_S="2")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--per-bucket", "4"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--per-bucket", "4",
+                          "--dump-outputs", str(tmp_path)],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -40,15 +50,16 @@ def test_bench_json_contract():
     for k in ("knn", "train", "entry_point", "latency_single_object"):
         assert k in d, k
     assert d["entry_point"]["lost"] == 0 and d["entry_point"]["entry_point_poses_per_s"] > 0
+    _dumped_poses(tmp_path, d["config"]["objects_per_step_per_gpu"])
 
 
-def test_bench_starts_its_own_ranks():
+def test_bench_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher: the parent starts two rank processes itself (gloo, both on the one card of a
     test box -- a rehearsal of the N-GPU command the driver issues) and relays rank 0's line with n_gpus == 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(DF_BENCH_DEVICE="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-                          "--per-bucket", "2", "--inflight", "2"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                          "--per-bucket", "2", "--inflight", "2", "--dump-outputs", str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -57,6 +68,7 @@ def test_bench_starts_its_own_ranks():
     poses = d["config"]["objects_per_step_per_gpu"] * 2 * d["steps"]                  # whole-job aggregate over both ranks
     assert abs(d["value"] - poses / (d["ms_per_step"] * d["steps"] / 1e3)) <= 0.01 * d["value"]
     assert "roofline" in d and "cpu_baseline" not in d                                 # the CPU leg runs at N = 1 only
+    _dumped_poses(tmp_path, d["config"]["objects_per_step_per_gpu"] * 2)                # both ranks' objects, gathered by rank 0
 
 
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
