@@ -15,6 +15,10 @@ constexpr int DF_MAX_CROP = 3200;      // largest crop side the network entry po
 
 int set_error(int code, const char *fmt, ...);   // records a thread-local message, returns code
 int check_launch(const char *what);              // hipGetLastError() -> DF_ERR_LAUNCH
+// Raises `kernel`'s dynamic-LDS limit (above the 64 KiB default) to `bytes` on the current device.  The attribute is per device (a process
+// may drive several) and is set the first time a (device, kernel) pair is seen; safe to call from several host threads.  DF_OK, or
+// DF_ERR_LAUNCH with the message recorded.
+int raise_lds_limit(const void *kernel, int bytes);
 
 // Development switches (A/B runs of kernel variants, verbose profiles) exist only in the DF_DEV build (libdfusion_hip_dev.so, compiled
 // with -DDF_DEV and loaded by tests that compare variants): the shipped library reads no environment.

@@ -1,5 +1,10 @@
 #include "common.h"
 
+#include <mutex>
+#include <set>
+#include <utility>
+#include <vector>
+
 namespace df {
 
 static thread_local char g_err[512] = "";
@@ -15,6 +20,23 @@ int set_error(int code, const char *fmt, ...) {
 int check_launch(const char *what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(DF_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
+  return DF_OK;
+}
+
+int raise_lds_limit(const void *kernel, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<int, const void *>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return set_error(DF_ERR_LAUNCH, "raise_lds_limit: hipGetDevice: %s", hipGetErrorString(e));
+  std::lock_guard<std::mutex> g(mu);
+  if (done.count({dev, kernel})) return DF_OK;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();      // reported here: not again by the next check_launch
+    return set_error(DF_ERR_LAUNCH, "raise_lds_limit: %d bytes of dynamic LDS: %s", bytes, hipGetErrorString(e));
+  }
+  done.insert({dev, kernel});
   return DF_OK;
 }
 
@@ -46,8 +68,8 @@ extern "C" int df_shader_clock_mhz(double *mhz_out, df_stream_t stream) {
   if (hipMalloc(&d, (size_t)blocks * 2 * sizeof(unsigned long long)) != hipSuccess) return df::set_error(DF_ERR_LAUNCH, "shader_clock_mhz: hipMalloc failed");
   hipStream_t st = df::to_stream(stream);
   hipLaunchKernelGGL(df::clock_probe_kernel, dim3(blocks), dim3(256), 0, st, d, 20000, 1.0f);
-  static unsigned long long h[2048];
-  hipError_t e = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, st);
+  std::vector<unsigned long long> h((size_t)blocks * 2);
+  hipError_t e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   hipFree(d);
   if (e != hipSuccess) return df::set_error(DF_ERR_LAUNCH, "shader_clock_mhz: %s", hipGetErrorString(e));

@@ -88,8 +88,9 @@ int launch_wgrad_multi(const ConvParams &p, int nseg, const WgradSeg *segs, floa
                        int accumulate = 0);
 
 #ifdef DF_DEV
-// development build only (csrc/split_gemm.hip): DF_GEMM_SPLIT_BF16=1 routes eligible plain-GEMM launches to the bf16 x 6 experiment
-bool try_split_gemm(const ConvParams &p, hipStream_t st);
+// development build only (csrc/split_gemm.hip): DF_GEMM_SPLIT_BF16=1 routes eligible plain-GEMM launches to the bf16 x 6 experiment.
+// 1 when the launch was taken (results in p.out), 0 when not eligible (the caller goes on to the fp32 kernels), or a DF_ERR_* code
+int try_split_gemm(const ConvParams &p, hipStream_t st);
 void split_gemm_invalidate();      // cached weight planes are cut again at their next use (a parameter was loaded / a network destroyed)
 #endif
 

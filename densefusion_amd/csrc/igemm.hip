@@ -1413,9 +1413,13 @@ int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used) {
   if (M * (long)p.out_ld >= (1L << 40) || (long)p.B * p.H * p.W >= (1L << 31))
     return set_error(DF_ERR_ARG, "conv: tensor too large for 32-bit pixel indexing");
 #ifdef DF_DEV
-  if (!p.splitk_ws && try_split_gemm(p, st)) {
-    if (splitk_used) *splitk_used = 1;
-    return check_launch("split gemm");
+  if (!p.splitk_ws) {
+    const int taken = try_split_gemm(p, st);
+    if (taken < 0) return taken;
+    if (taken) {
+      if (splitk_used) *splitk_used = 1;
+      return check_launch("split gemm");
+    }
   }
 #endif
   const TileCfg c = pick_cfg(p);
@@ -1444,20 +1448,8 @@ int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used) {
     return set_error(DF_ERR_ARG, "conv: rows_per_group must be a multiple of %d", c.bm);
   const long tiles = ((M + c.bm - 1) / c.bm) * ((p.Cout + c.bn - 1) / c.bn);
   dim3 grid((unsigned)tiles, 1, p.zcount);
-  // v1's 128x128 tile double-buffers 72 KiB of dynamic LDS: above the 64 KiB default cap.  The attribute is per device (a process
-  // may drive several): set once for every device a launch is seen on.  (v4's single k-tile buffer is 36 KiB at most.)
-  {
-    static bool attr_done[64] = {};
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_done[dev]) {
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&igemm_f32_kernel<128, 128, 2, 2>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * LDK * (int)sizeof(float));
-      hipFuncSetAttribute(reinterpret_cast<const void *>(&igemm_f32_v2_kernel<128, 128, 2, 2, 32>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * 36 * (int)sizeof(float));
-      attr_done[dev] = true;
-    }
-  }
+  // v1's and v2's 128x128 tiles double-buffer 72 KiB of dynamic LDS: above the 64 KiB default cap, raised just before their launches.
+  // (The 64x64 tiles take 36 KiB, v4's single k-tile buffer 36 KiB at most.)
   constexpr size_t ROW = 36 * sizeof(float);      // one padded k-tile row (BKT = 32)
   // workgroups per CU of the v4 kernel: 4 / 5 / 6 (the register budget amdgpu_waves_per_eu leaves each: 128 / 102 / 85 VGPRs + AGPRs)
   static const bool no_pure = df::dev_getenv("DF_IGEMM_NOPURE") != nullptr;      // dev switch: the general loader for every launch; read once
@@ -1488,9 +1480,12 @@ int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used) {
   // grids under two workgroups per CU: the software-pipelined kernel (training, 1 / 8 frames per pass: 142 -> 154 / 670 -> 696 frames/s)
   static const long lowocc = df::dev_getenv("DF_IGEMM_LOWOCC") ? atol(df::dev_getenv("DF_IGEMM_LOWOCC")) : 512;    // dev switch; read once
   if (v4 && S == 1 && tiles * p.zcount < lowocc && c.bn == c.bm) {
-    if (c.bm == 128)
-      hipLaunchKernelGGL((igemm_f32_v2_kernel<128, 128, 2, 2, 32>), grid, dim3(256), (size_t)2 * 256 * 36 * sizeof(float), st, pl);
-    else
+    if (c.bm == 128) {
+      constexpr int lds = 2 * 256 * 36 * (int)sizeof(float);
+      const int rc = raise_lds_limit(reinterpret_cast<const void *>(&igemm_f32_v2_kernel<128, 128, 2, 2, 32>), lds);
+      if (rc != DF_OK) return rc;
+      hipLaunchKernelGGL((igemm_f32_v2_kernel<128, 128, 2, 2, 32>), grid, dim3(256), (size_t)lds, st, pl);
+    } else
       hipLaunchKernelGGL((igemm_f32_v2_kernel<64, 64, 2, 2, 32>), grid, dim3(256), (size_t)2 * 128 * 36 * sizeof(float), st, pl);
   } else if (v4) {
     auto launch = [&](auto bm, auto bn, auto occ, size_t rows) {
@@ -1513,7 +1508,10 @@ int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used) {
                          p.out, p.out_ld, p.out_coff, p.bias, p.res, p.res_ld, p.res_coff, p.act, p.prelu);
     }
   } else if (c.bm == 128) {
-    hipLaunchKernelGGL((igemm_f32_kernel<128, 128, 2, 2>), grid, dim3(256), (size_t)2 * 256 * LDK * sizeof(float), st, p);
+    constexpr int lds = 2 * 256 * LDK * (int)sizeof(float);
+    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&igemm_f32_kernel<128, 128, 2, 2>), lds);
+    if (rc != DF_OK) return rc;
+    hipLaunchKernelGGL((igemm_f32_kernel<128, 128, 2, 2>), grid, dim3(256), (size_t)lds, st, p);
   } else {
     hipLaunchKernelGGL((igemm_f32_kernel<64, 64, 2, 2>), grid, dim3(256), (size_t)2 * 128 * LDK * sizeof(float), st, p);
   }
@@ -1705,19 +1703,15 @@ static int launch_wgrad_segs(ConvParams p, int nseg, const WgradSeg *segs, float
     constexpr size_t lds128 = (size_t)32 * (132 + 132) * 4, lds64 = (size_t)32 * (68 + 132) * 4;
     auto go = [&](auto tn, size_t lds) {
       constexpr int TN = decltype(tn)::value;
-      static bool attr_done[64] = {};
-      int dev = 0;
-      hipGetDevice(&dev);
-      if (dev >= 0 && dev < 64 && !attr_done[dev]) {
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&wgrad_f32_v2_kernel<TN, WGRAD_OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_done[dev] = true;
-      }
+      const int rc = raise_lds_limit(reinterpret_cast<const void *>(&wgrad_f32_v2_kernel<TN, WGRAD_OCC>), (int)lds);
+      if (rc != DF_OK) return rc;
       hipLaunchKernelGGL((wgrad_f32_v2_kernel<TN, WGRAD_OCC>), dim3((unsigned)(w.tiles * w.split)), dim3(256), lds, st, pk, part, w.steps, w.split, (unsigned)in_bytes,
                          (unsigned)out_bytes, tab);
+      return DF_OK;
     };
     using std::integral_constant;
-    if (p.Cout >= 128) go(integral_constant<int, 128>{}, lds128);
-    else go(integral_constant<int, 64>{}, lds64);
+    const int rc = p.Cout >= 128 ? go(integral_constant<int, 128>{}, lds128) : go(integral_constant<int, 64>{}, lds64);
+    if (rc != DF_OK) return rc;
   } else {
     // the small-shape kernel decodes one geometry: one launch per bucket into consecutive partial slices
     int z = 0;

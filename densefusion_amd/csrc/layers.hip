@@ -229,18 +229,6 @@ __global__ __launch_bounds__(TPB) void psp_prior_sum_kernel(const float *__restr
 // nine 1x1 products Y_tap = W_tap . x are taken at LOW resolution (one GEMM with N = 9*Cout, a quarter of
 // the conv's FLOPs) and this kernel does the 9-tap x 4-corner interpolation of Y at the output pixels.
 // y: [B][h][w][9*Cout] (tap-major channel blocks); out: [B][2h][2w][Cout].
-struct Tap3 { int i0[3], i1[3]; float w0[3], w1[3]; bool ok[3]; };
-__device__ inline Tap3 taps_for(int P, float scale, int in_size, int out_size) {
-  Tap3 t;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const int q = P + d - 1;
-    t.ok[d] = (unsigned)q < (unsigned)out_size;
-    src_ac(t.ok[d] ? q : 0, scale, in_size, t.i0[d], t.i1[d], t.w0[d], t.w1[d]);
-  }
-  return t;
-}
-
 // LDS-tiled: a workgroup owns an 8 x 16 tile of output pixels and 16 output channels.  The
 // low-resolution rows / columns its 3x3 taps interpolate from (<= 7 x 11 pixels) are staged in LDS once, all nine tap
 // blocks of the 16 channels (44 KB), so the 36 vector reads per output vector come from LDS and global traffic drops

@@ -440,24 +440,22 @@ __global__ __launch_bounds__(LB) void ycb_dist_kernel(const double *__restrict__
   if (tid == 0) { add_out[b] = s_red[0][0] / (double)M; adi_out[b] = s_red[1][0] / (double)M; }
 }
 
-// 150 KB of dynamic LDS for the kernels that keep a whole point set resident: a per-DEVICE attribute (a process may drive
-// several devices), set the first time a launch is seen on a device
-void loss_lds_attrs();
+// 150 KB of dynamic LDS for the kernels that keep a whole point set resident (raise_lds_limit: once per device)
+int loss_lds_attrs();
 
 int check_m(int M, const char *what) {
   if (M <= 0 || (size_t)M * 16 > 150 * 1024) return set_error(DF_ERR_ARG, "%s: num_points_mesh must be in [1, 9600] (got %d)", what, M);
   return DF_OK;
 }
 
-void loss_lds_attrs() {
-  static bool done[64] = {};
-  int dev = 0;
-  hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || done[dev]) return;
+int loss_lds_attrs() {
   const void *ks[] = {reinterpret_cast<const void *>(&add_dis_kernel), reinterpret_cast<const void *>(&add_dis_sym_kernel),
                       reinterpret_cast<const void *>(&add_metric_kernel), reinterpret_cast<const void *>(&ycb_dist_kernel)};
-  for (const void *k : ks) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  done[dev] = true;
+  for (const void *k : ks) {
+    const int rc = raise_lds_limit(k, 150 * 1024);
+    if (rc != DF_OK) return rc;
+  }
+  return DF_OK;
 }
 
 }  // namespace
@@ -474,7 +472,8 @@ int launch_loss_frames(int B, const int *symmetric, const float *pred_r, const f
   int rc = check_m(M, "loss_forward");
   if (rc != DF_OK) return rc;
   const size_t lds = (size_t)M * 16;
-  loss_lds_attrs();
+  rc = loss_lds_attrs();
+  if (rc != DF_OK) return rc;
   const int ppb = M >= LB * SYM_QPL ? 1 : std::min(LB, (LB * SYM_QPL) / M);      // (the per-pose totals are kept by tid < ppb <= LB)
   const size_t lds2 = (size_t)LB * SYM_QPL * 4 + (size_t)ppb * 4;
   const bool fused = N >= 2 && lds2 <= 150 * 1024;
@@ -528,7 +527,8 @@ int launch_loss_refine_frames(int B, const int *symmetric, const float *pred_r, 
   if (B <= 0 || N <= 0) return set_error(DF_ERR_ARG, "loss_refine_forward: B and N must be >= 1");
   int rc = check_m(M, "loss_refine_forward");
   if (rc != DF_OK) return rc;
-  loss_lds_attrs();
+  rc = loss_lds_attrs();
+  if (rc != DF_OK) return rc;
   for (int b0 = 0; b0 < B; b0 += LOSS_MAX_FRAMES) {
     FrameTab all{}, sym{}, non{};
     all.N = sym.N = non.N = 1; all.M = sym.M = non.M = M;          // one pose per frame: the per-frame strides of add_dis_kernel with N = 1
@@ -580,7 +580,8 @@ extern "C" int df_loss_forward(const float *pred_r, const float *pred_t, const f
     int rc = check_m(M, "loss_forward");
     if (rc != DF_OK) return rc;
     hipStream_t st = to_stream(stream);
-    loss_lds_attrs();
+    rc = loss_lds_attrs();
+    if (rc != DF_OK) return rc;
     const int ppb = M >= LB * SYM_QPL ? 1 : std::min(LB, (LB * SYM_QPL) / M);
     const size_t lds2 = (size_t)LB * SYM_QPL * 4 + (size_t)ppb * 4;
     const FrameTab one = one_frame(N, M);
@@ -625,7 +626,8 @@ extern "C" int df_loss_refine_forward(const float *pred_r, const float *pred_t, 
   int rc = check_m(M, "loss_refine_forward");
   if (rc != DF_OK) return rc;
   hipStream_t st = to_stream(stream);
-  loss_lds_attrs();
+  rc = loss_lds_attrs();
+  if (rc != DF_OK) return rc;
   hipLaunchKernelGGL(add_dis_kernel, dim3(1), dim3(LB), (size_t)M * 16, st, pred_r, pred_t, (const float *)nullptr, target,
                      model_points, M, symmetric, dis_out, sel_out, one_frame(1, M));
   hipLaunchKernelGGL(recentre_kernel, dim3(cdiv(N + M, LB)), dim3(LB), 0, st, pred_r, pred_t, points, target, N, M, new_points, new_target, one_frame(1, M));
@@ -638,7 +640,8 @@ extern "C" int df_add_metric(const double *pose, const float *model_points, cons
   if (B <= 0) return set_error(DF_ERR_ARG, "add_metric: B must be >= 1");
   int rc = check_m(M, "add_metric");
   if (rc != DF_OK) return rc;
-  loss_lds_attrs();
+  rc = loss_lds_attrs();
+  if (rc != DF_OK) return rc;
   hipLaunchKernelGGL(add_metric_kernel, dim3(B), dim3(LB), (size_t)M * 16, to_stream(stream), pose, model_points, target, symmetric, M, dis_out);
   return check_launch("add_metric");
 }
@@ -647,7 +650,8 @@ extern "C" int df_ycb_distances(const double *rt_est, const double *rt_gt, const
                                 double *adi_out, df_stream_t stream) {
   if (!rt_est || !rt_gt || !pts || !add_out || !adi_out) return set_error(DF_ERR_ARG, "ycb_distances: null pointer");
   if (B <= 0 || M <= 0 || (size_t)M * 24 > 150 * 1024) return set_error(DF_ERR_ARG, "ycb_distances: need B >= 1 and 1 <= M <= 6400");
-  loss_lds_attrs();
+  const int rc = loss_lds_attrs();
+  if (rc != DF_OK) return rc;
   hipLaunchKernelGGL(ycb_dist_kernel, dim3(B), dim3(LB), (size_t)M * 24, to_stream(stream), rt_est, rt_gt, pts, M, add_out, adi_out);
   return check_launch("ycb_distances");
 }

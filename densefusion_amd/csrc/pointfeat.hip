@@ -192,13 +192,8 @@ __global__ __launch_bounds__(PF_THREADS) void pointfeat_kernel(const PointFeatPa
 template <bool DO_X, bool DO_E>
 int launch_t(const PointFeatParams &p, hipStream_t st) {
   const size_t lds = ((DO_X ? W2F + 256 : 0) + (DO_E ? W2F + WE1F : 0) + 4 * (A1F > 32 * 68 ? A1F : 32 * 68)) * sizeof(float);
-  static bool attr_done[64] = {};
-  int dev = 0;
-  hipGetDevice(&dev);
-  if (dev >= 0 && dev < 64 && !attr_done[dev]) {
-    hipFuncSetAttribute(reinterpret_cast<const void *>(&pointfeat_kernel<DO_X, DO_E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done[dev] = true;
-  }
+  const int rc = raise_lds_limit(reinterpret_cast<const void *>(&pointfeat_kernel<DO_X, DO_E>), (int)lds);
+  if (rc != DF_OK) return rc;
   const int tiles = (int)((long)p.B * p.Npad / PF_ROWS);
   hipLaunchKernelGGL((pointfeat_kernel<DO_X, DO_E>), dim3(tiles < 512 ? tiles : 512), dim3(PF_THREADS), lds, st, p, tiles);
   return check_launch("pointfeat");

@@ -406,25 +406,24 @@ Planes weight_planes(const float *w, long elems, bool constant, hipStream_t st) 
 
 }  // namespace
 
-// true when the launch was taken (results in p.out); false: not eligible, the caller goes on to the fp32 kernels
 void split_gemm_invalidate() {
   std::lock_guard<std::mutex> g(g_mu);
   ++g_epoch;
 }
 
-bool try_split_gemm(const ConvParams &p, hipStream_t st) {
+int try_split_gemm(const ConvParams &p, hipStream_t st) {
   static const bool on = dev_getenv("DF_GEMM_SPLIT_BF16") != nullptr;
   static const bool verbose = dev_getenv("DF_GEMM_SPLIT_VERBOSE") != nullptr;
-  if (!on) return false;
+  if (!on) return 0;
   const long M = (long)p.B * p.OH * p.OW;
   const int K = p.Cin;
   const bool ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.up == 1 && p.H == p.OH && p.W == p.OW && (p.out || p.colsum) && !(p.colsum && p.res) && p.splitk <= 1 &&
                   p.Cout % SBN == 0 && K % SBK == 0 && K >= SBK && M >= 1 && (p.rows_per_group == 0 ? p.bias_group_ld == 0 : p.rows_per_group % SBM == 0) && (p.z_wgt % 2) == 0;
   if (verbose) fprintf(stderr, "[df-split] M=%ld N=%d K=%d z%d -> %s\n", M, p.Cout, K, p.zcount, ok ? "bf16 x 6" : "fp32");
-  if (!ok) return false;
+  if (!ok) return 0;
   const long elems = (long)(p.zcount - 1) * p.z_wgt + (long)p.Cout * K;
   const Planes pl = weight_planes(p.wgt, elems, p.wgt_const, st);
-  if (!pl.ptr) return false;
+  if (!pl.ptr) return 0;
   SplitArgs a{};
   a.in = p.in; a.wpl = pl.ptr; a.bias = p.bias; a.res = p.res; a.prelu = p.prelu; a.out = p.out; a.colsum = p.colsum;
   a.M = M; a.wplane = pl.plane; a.N = p.Cout; a.K = K; a.in_ld = p.in_ld; a.in_coff = p.in_coff; a.out_ld = p.out_ld; a.out_coff = p.out_coff;
@@ -436,13 +435,8 @@ bool try_split_gemm(const ConvParams &p, hipStream_t st) {
   // measured per shape: the 256-row form wins from K = 384 up (189 against 172 TFLOP/s on 139 000 x 2 304 x 1 024), the 128-row form below
   const bool v2 = variant == 2 && K >= 384 && (p.rows_per_group == 0 || p.rows_per_group % 256 == 0);
   if (v2) {
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_done[dev]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_split_bf16_v2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * V2_STAGE);
-      attr_done[dev] = true;
-    }
+    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm_split_bf16_v2_kernel), 2 * V2_STAGE);
+    if (rc != DF_OK) return rc;
     a.tiles_m = (int)((M + 255) / 256);
     const unsigned grid = (unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n);
     hipLaunchKernelGGL(gemm_split_bf16_v2_kernel, dim3(grid, 1, p.zcount), dim3(512), 2 * V2_STAGE, st, a);
@@ -451,7 +445,7 @@ bool try_split_gemm(const ConvParams &p, hipStream_t st) {
     const unsigned grid = (unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n);
     hipLaunchKernelGGL(gemm_split_bf16_kernel, dim3(grid, 1, p.zcount), dim3(256), 0, st, a);
   }
-  return true;
+  return 1;
 }
 
 }  // namespace df

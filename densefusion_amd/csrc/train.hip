@@ -104,39 +104,6 @@ __global__ __launch_bounds__(TB) void add2d_kernel(float *__restrict__ dst, int 
   }
 }
 
-// AdaptiveAvgPool2d(s) backward, lib/pspnet.py:16: bin i covers [floor(i*H/s), ceil((i+1)*H/s)); dx is a [B*H*W][C] view
-__global__ __launch_bounds__(TB) void pool_bwd_kernel(const float *__restrict__ dy, float *__restrict__ dx, int dx_ld, int B, int H, int W, int C4,
-                                                      int s, int accumulate) {
-  GRID_STRIDE(i, (long)B * H * W * C4) {
-    const int c = (int)(i % C4) * 4;
-    long r = i / C4;
-    const long pix = r;
-    const int xx = (int)(r % W); r /= W;
-    const int yy = (int)(r % H);
-    const int b = (int)(r / H);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int bi = 0; bi < s; ++bi) {
-      const int y0 = (bi * H) / s, y1 = ((bi + 1) * H + s - 1) / s;
-      if (yy < y0 || yy >= y1) continue;
-      for (int bj = 0; bj < s; ++bj) {
-        const int x0 = (bj * W) / s, x1 = ((bj + 1) * W + s - 1) / s;
-        if (xx < x0 || xx >= x1) continue;
-        const f32x4 v = reinterpret_cast<const f32x4 *>(dy)[((long)(b * s + bi) * s + bj) * C4 + c / 4];
-        const float cnt = (float)((y1 - y0) * (x1 - x0));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += v[e] / cnt;
-      }
-    }
-    float *d = dx + pix * dx_ld + c;
-    if (accumulate) {
-      const f32x4 o = *reinterpret_cast<const f32x4 *>(d);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = o[e] + acc[e];
-    }
-    *reinterpret_cast<f32x4 *>(d) = acc;
-  }
-}
-
 // bilinear source (ATen UpSample semantics, fp32): align != 0 -> src = dst*(in-1)/(out-1); else half-pixel, clamped at 0
 __device__ inline void bil_src(int dst, int in_size, int out_size, int align, int &i0, int &i1, float &l0, float &l1) {
   float s;
@@ -159,217 +126,10 @@ __device__ inline void bil_cands(int q, int in_size, int out_size, int align, in
   if (hi > out_size - 1 || q == in_size - 1) hi = out_size - 1;
 }
 
-// y[b][oy][ox][c] = bilinear resample of x [B][H][W][C] to (OH, OW); y is a [B*OH*OW][C] view of width y_ld
-__global__ __launch_bounds__(TB) void bilinear_fwd_kernel(const float *__restrict__ x, float *__restrict__ y, int y_ld, int B, int H, int W, int C4,
-                                                          int OH, int OW, int align) {
-  GRID_STRIDE(i, (long)B * OH * OW * C4) {
-    const int c = (int)(i % C4) * 4;
-    long r = i / C4;
-    const long pix = r;
-    const int ox = (int)(r % OW); r /= OW;
-    const int oy = (int)(r % OH);
-    const int b = (int)(r / OH);
-    int y0, y1, x0, x1;
-    float wy0, wy1, wx0, wx1;
-    bil_src(oy, H, OH, align, y0, y1, wy0, wy1);
-    bil_src(ox, W, OW, align, x0, x1, wx0, wx1);
-    const float *p = x + (long)b * H * W * C4 * 4 + c;
-    const f32x4 v00 = *reinterpret_cast<const f32x4 *>(p + ((long)y0 * W + x0) * C4 * 4), v01 = *reinterpret_cast<const f32x4 *>(p + ((long)y0 * W + x1) * C4 * 4);
-    const f32x4 v10 = *reinterpret_cast<const f32x4 *>(p + ((long)y1 * W + x0) * C4 * 4), v11 = *reinterpret_cast<const f32x4 *>(p + ((long)y1 * W + x1) * C4 * 4);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = wy0 * (wx0 * v00[e] + wx1 * v01[e]) + wy1 * (wx0 * v10[e] + wx1 * v11[e]);
-    *reinterpret_cast<f32x4 *>(y + pix * y_ld + c) = o;
-  }
-}
-// adjoint as a gather: dx[b][q] = sum over the destination pixels that read q of weight * dy.  Workgroup = 8 channel vectors x 32
-// pixel lanes: lane l takes the candidate destination pixels l, l + 32, ... of q's (row range) x (column range) window, the 32 partial
-// sums meet in LDS and are added in lane order -- a fixed order, and 32 load chains per output instead of one (the 1 x 1 pyramid stage
-// gathers the whole map into one pixel: with 8 row lanes it was the longest glue kernel of a mixed-size training window)
-__global__ __launch_bounds__(TB) void bilinear_bwd_kernel(const float *__restrict__ dy, int dy_ld, float *__restrict__ dx, int B, int H, int W, int C4,
-                                                          int OH, int OW, int align) {
-  __shared__ f32x4 s_p[32][8];
-  const int col = threadIdx.x & 7, pl = threadIdx.x >> 3;
-  const int cgroups = (C4 + 7) / 8;
-  for (long job = blockIdx.x; job < (long)B * H * W * cgroups; job += gridDim.x) {
-    const int cg = (int)(job % cgroups);
-    long r = job / cgroups;
-    const long pix = r;
-    const int qx = (int)(r % W); r /= W;
-    const int qy = (int)(r % H);
-    const int b = (int)(r / H);
-    const int c4 = cg * 8 + col;
-    int ylo, yhi, xlo, xhi;
-    bil_cands(qy, H, OH, align, ylo, yhi);
-    bil_cands(qx, W, OW, align, xlo, xhi);
-    const int nx = xhi - xlo + 1, total = (yhi - ylo + 1) * nx;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    if (c4 < C4)
-      for (int idx = pl; idx < total; idx += 32) {
-        const int oy = ylo + idx / nx, ox = xlo + idx % nx;
-        int y0, y1, x0, x1;
-        float wy0, wy1, wx0, wx1;
-        bil_src(oy, H, OH, align, y0, y1, wy0, wy1);
-        if (y0 != qy && y1 != qy) continue;
-        bil_src(ox, W, OW, align, x0, x1, wx0, wx1);
-        if (x0 != qx && x1 != qx) continue;
-        const float wy = (y0 == qy ? wy0 : 0.f) + (y1 == qy ? wy1 : 0.f);
-        const float wx = (x0 == qx ? wx0 : 0.f) + (x1 == qx ? wx1 : 0.f);
-        const f32x4 g = *reinterpret_cast<const f32x4 *>(dy + ((long)(b * OH + oy) * OW + ox) * dy_ld + c4 * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += (wy * wx) * g[e];
-      }
-    s_p[pl][col] = acc;
-    __syncthreads();
-    if (pl == 0 && c4 < C4) {
-#pragma unroll 4
-      for (int l = 1; l < 32; ++l)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += s_p[l][col][e];
-      reinterpret_cast<f32x4 *>(dx)[pix * C4 + c4] = acc;
-    }
-    __syncthreads();
-  }
-}
-
-// Adjoint of layers.hip upconv_gather (PSPUpsample through the low-resolution per-tap products): g [B][2h][2w][Cout] is the
-// gradient of the pre-activation; dY[b][qy][qx][tap][c] = sum over the upsampled positions u = P + tap - 1 (inside the image) that
-// interpolate from (qy, qx) of weight(u -> q) * g[P]
-__global__ __launch_bounds__(TB) void upconv_gather_bwd_kernel(const float *__restrict__ g, float *__restrict__ dY, int B, int h, int w, int Cout) {
-  const int C4 = Cout / 4, OH = 2 * h, OW = 2 * w;
-  GRID_STRIDE(i, (long)B * h * w * 9 * C4) {
-    const int c = (int)(i % C4) * 4;
-    long r = i / C4;
-    const int tap = (int)(r % 9); r /= 9;
-    const int qx = (int)(r % w); r /= w;
-    const int qy = (int)(r % h);
-    const int b = (int)(r / h);
-    const int dy = tap / 3, dx = tap - dy * 3;
-    int ylo, yhi, xlo, xhi;
-    bil_cands(qy, h, OH, 1, ylo, yhi);
-    bil_cands(qx, w, OW, 1, xlo, xhi);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int uy = ylo; uy <= yhi; ++uy) {
-      const int py = uy - dy + 1;
-      if ((unsigned)py >= (unsigned)OH) continue;
-      int y0, y1;
-      float wy0, wy1;
-      bil_src(uy, h, OH, 1, y0, y1, wy0, wy1);
-      if (y0 != qy && y1 != qy) continue;
-      const float wy = (y0 == qy ? wy0 : 0.f) + (y1 == qy ? wy1 : 0.f);
-      for (int ux = xlo; ux <= xhi; ++ux) {
-        const int px = ux - dx + 1;
-        if ((unsigned)px >= (unsigned)OW) continue;
-        int x0, x1;
-        float wx0, wx1;
-        bil_src(ux, w, OW, 1, x0, x1, wx0, wx1);
-        if (x0 != qx && x1 != qx) continue;
-        const float wx = (x0 == qx ? wx0 : 0.f) + (x1 == qx ? wx1 : 0.f);
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(g + ((long)(b * OH + py) * OW + px) * Cout + c);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += (wy * wx) * v[e];
-      }
-    }
-    reinterpret_cast<f32x4 *>(dY)[i] = acc;
-  }
-}
-
-// Adjoint of layers.hip up3_patch (the 3x3 patch of the bilinearly upsampled half-resolution map at every chosen pixel):
-// dU[b][qy][qx][c] = sum over points n (ascending) and taps (ascending) whose upsampled position interpolates from (qy, qx) of
-// weight * dpatch[b][n][tap][c] -- a gather, so no atomics.  Three launches: decode every point's pixel and the range of
-// half-resolution rows / columns its patch can touch; per half-resolution row the ordered list of points that touch it; then a
-// thread per (pixel, 4 channels) walks its row's list (a few dozen points instead of all N).
-// tab[b][n] = {py | px << 16, rlo | rhi << 16, clo | chi << 16, 0}: the chosen pixel of point n and the range of half-resolution rows /
-// columns its 3 x 3 patch of upsampled positions interpolates from
-__global__ __launch_bounds__(TB) void up3_decode_kernel(const int64_t *__restrict__ choose, int4 *__restrict__ tab, int B, int h, int wd, int N) {
-  const int OH = 2 * h, OW = 2 * wd, HW = OH * OW;
-  GRID_STRIDE(i, (long)B * N) {
-    long pix = choose[i];
-    pix = pix < 0 ? 0 : (pix >= HW ? HW - 1 : pix);
-    const int py = (int)(pix / OW), px = (int)(pix % OW);
-    int i0, i1, rlo, rhi, clo, chi;
-    float l0, l1;
-    bil_src(max(py - 1, 0), h, OH, 1, rlo, i1, l0, l1);
-    bil_src(min(py + 1, OH - 1), h, OH, 1, i0, rhi, l0, l1);
-    bil_src(max(px - 1, 0), wd, OW, 1, clo, i1, l0, l1);
-    bil_src(min(px + 1, OW - 1), wd, OW, 1, i0, chi, l0, l1);
-    tab[i] = make_int4(py | (px << 16), rlo | (rhi << 16), clo | (chi << 16), 0);
-  }
-}
-
-// rows[b][qy][...] = the points (ascending n) whose patch touches half-resolution row qy, cnt[b][qy] their number: a workgroup per row
-// scans the table once, 256 points per round, and compacts the hits in order (wave ballots + a scan over the 4 waves)
-__global__ __launch_bounds__(TB) void up3_rowlist_kernel(const int4 *__restrict__ tab, int *__restrict__ rows, int *__restrict__ cnt, int h, int N) {
-  __shared__ int s_w[4];
-  const int b = blockIdx.y, qy = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int *out = rows + ((size_t)b * h + qy) * N;
-  int base = 0;
-  for (int n0 = 0; n0 < N; n0 += TB) {
-    const int n = n0 + threadIdx.x;
-    bool hit = false;
-    if (n < N) {
-      const int4 e = tab[(size_t)b * N + n];
-      hit = qy >= (e.y & 0xffff) && qy <= (e.y >> 16);
-    }
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) s_w[wave] = __popcll(m);
-    __syncthreads();
-    int before = base;
-    for (int w2 = 0; w2 < wave; ++w2) before += s_w[w2];
-    if (hit) out[before + __popcll(m & ((1ull << lane) - 1ull))] = n;
-    base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) cnt[b * h + qy] = base;
-}
-
-__global__ __launch_bounds__(TB) void up3_patch_bwd_kernel(const float *__restrict__ dpatch, const int4 *__restrict__ tab, const int *__restrict__ rows,
-                                                           const int *__restrict__ cnt, float *__restrict__ dU, int h, int wd, int N, int Npad) {
-  const int OH = 2 * h, OW = 2 * wd;
-  const int b = blockIdx.z, qy = blockIdx.y;
-  const int c4 = threadIdx.x & 15, qx = blockIdx.x * (TB / 16) + (threadIdx.x >> 4);
-  if (qx >= wd) return;
-  const int *list = rows + ((size_t)b * h + qy) * N;
-  const int count = cnt[b * h + qy];
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int i = 0; i < count; ++i) {
-    const int j = list[i];
-    const int4 e4 = tab[(size_t)b * N + j];
-    if (qx < (e4.z & 0xffff) || qx > (e4.z >> 16)) continue;
-    const float *row = dpatch + ((size_t)b * Npad + j) * 576 + c4 * 4;
-    const int py = e4.x & 0xffff, px = e4.x >> 16;
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy) {
-      const int uy = py + dy - 1;
-      if ((unsigned)uy >= (unsigned)OH) continue;
-      int y0, y1;
-      float wy0, wy1;
-      bil_src(uy, h, OH, 1, y0, y1, wy0, wy1);
-      if (y0 != qy && y1 != qy) continue;
-      const float wy = (y0 == qy ? wy0 : 0.f) + (y1 == qy ? wy1 : 0.f);
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        const int ux = px + dx - 1;
-        if ((unsigned)ux >= (unsigned)OW) continue;
-        int x0, x1;
-        float wx0, wx1;
-        bil_src(ux, wd, OW, 1, x0, x1, wx0, wx1);
-        if (x0 != qx && x1 != qx) continue;
-        const float wx = (x0 == qx ? wx0 : 0.f) + (x1 == qx ? wx1 : 0.f);
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(row + (dy * 3 + dx) * 64);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] += (wy * wx) * v[e];
-      }
-    }
-  }
-  *reinterpret_cast<f32x4 *>(dU + (((size_t)b * h + qy) * wd + qx) * 64 + c4 * 4) = acc;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Memory-bound kernels over ALL crop-size buckets of a level in one launch: a bucket table travels in the kernel arguments, an element
 // finds its bucket by a scan of <= 16 row bounds (the buckets' pixel rows are concatenated, bucket g = B[g] maps of H[g] x W[g] from
-// row row0[g]; its frames are b0[g] .. of the pass).  Same arithmetic per element as the per-bucket kernels above.
+// row row0[g]; its frames are b0[g] .. of the pass).
 // ------------------------------------------------------------------------------------------------
 constexpr int TAB_MAX = 16;
 struct BTab {
@@ -406,8 +166,9 @@ __global__ __launch_bounds__(TB) void channel_scale_multi_kernel(const float *__
   }
 }
 
-// AdaptiveAvgPool2d adjoint of the FOUR pyramid stages (sizes 1, 2, 3, 6) at once: dx[pix] (+)= sum_s sum over the stage's bins that contain
-// the pixel of dy_s[frame][bin] / |bin| (stages ascending, bins row-major: a fixed order); dy_s = [frames][s*s][C] blocks
+// AdaptiveAvgPool2d adjoint of the FOUR pyramid stages (sizes 1, 2, 3, 6) at once, lib/pspnet.py:16: bin i of stage s covers
+// [floor(i*H/s), ceil((i+1)*H/s)); dx[pix] (+)= sum_s sum over the stage's bins that contain the pixel of dy_s[frame][bin] / |bin| (stages
+// ascending, bins row-major: a fixed order); dy_s = [frames][s*s][C] blocks
 struct Ptr4 { const float *p[4]; };
 struct MPtr4 { float *p[4]; };
 __global__ __launch_bounds__(TB) void pool_bwd_all_kernel(const Ptr4 dy, float *__restrict__ dx, int dx_ld, int C4, int accumulate, const BTab tab) {
@@ -476,8 +237,11 @@ __global__ __launch_bounds__(TB) void bilinear_fwd_all_kernel(const Ptr4 z, floa
   }
 }
 
-// their adjoint, all four stages and all buckets: job = (stage, frame, stage pixel q, group of 8 channel vectors); 32 pixel lanes per output
-// like bilinear_bwd_kernel (same candidate order, same fixed reduction); dz_si = [frames][s*s][C]
+// their adjoint as a gather, all four stages and all buckets: dz_si[frame][q] = sum over the destination pixels that read stage pixel q of
+// weight * dy; dz_si = [frames][s*s][C].  job = (stage, frame, q, group of 8 channel vectors); workgroup = 8 channel vectors x 32 pixel lanes:
+// lane l takes the candidate destination pixels l, l + 32, ... of q's (row range) x (column range) window, the 32 partial sums meet in LDS
+// and are added in lane order -- a fixed order, and 32 load chains per output instead of one (the 1 x 1 stage gathers the whole map into
+// one pixel: with 8 row lanes it was the longest glue kernel of a mixed-size training window)
 __global__ __launch_bounds__(TB) void bilinear_bwd_all_kernel(const float *__restrict__ dy, int dy_ld, const MPtr4 dz, int frames, int C4, const BTab tab) {
   __shared__ f32x4 s_p[32][8];
   const int col = threadIdx.x & 7, pl = threadIdx.x >> 3;
@@ -528,7 +292,10 @@ __global__ __launch_bounds__(TB) void bilinear_bwd_all_kernel(const float *__res
   }
 }
 
-// upconv_gather_bwd_kernel over all buckets: g rows live at the upsampled level (4 x the low-resolution rows of each bucket)
+// Adjoint of layers.hip upconv_gather (PSPUpsample through the low-resolution per-tap products) over all buckets: g [B][2h][2w][Cout] is
+// the gradient of the pre-activation, its rows live at the upsampled level (4 x the low-resolution rows of each bucket);
+// dY[b][qy][qx][tap][c] = sum over the upsampled positions u = P + tap - 1 (inside the image) that interpolate from (qy, qx) of
+// weight(u -> q) * g[P]
 __global__ __launch_bounds__(TB) void upconv_gather_bwd_multi_kernel(const float *__restrict__ gsrc, float *__restrict__ dY, int Cout, const BTab tab) {
   const int C4 = Cout / 4;
   const long r_lo = tab.row0[0], nrow = tab.row1[tab.n - 1] - r_lo;
@@ -549,7 +316,7 @@ __global__ __launch_bounds__(TB) void upconv_gather_bwd_multi_kernel(const float
     bil_cands(qy, h, OH, 1, ylo, yhi);
     bil_cands(qx, w, OW, 1, xlo, xhi);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    // the column candidates' weights once per thread (they were recomputed under every row candidate); same products, same order
+    // the column candidates' weights once per thread (not under every row candidate); the products are added in candidate order
     constexpr int MAXC = 8;      // (a source column feeds at most 5 upsampled columns at scale 2)
     float wxs[MAXC];
     int pxs[MAXC];
@@ -676,8 +443,15 @@ __global__ __launch_bounds__(TB) void col2im_multi_kernel(const float *__restric
   }
 }
 
-// the three up_3 patch-adjoint kernels over all buckets (tab = the half-resolution level; frames of all buckets in one grid, rows / columns
-// beyond a bucket's map exit): row lists and counts are laid out with the LARGEST map height hmax per frame
+// Adjoint of layers.hip up3_patch (the 3x3 patch of the bilinearly upsampled half-resolution map at every chosen pixel):
+// dU[b][qy][qx][c] = sum over points n (ascending) and taps (ascending) whose upsampled position interpolates from (qy, qx) of
+// weight * dpatch[b][n][tap][c] -- a gather, so no atomics.  Three launches: decode every point's pixel and the range of
+// half-resolution rows / columns its patch can touch; per half-resolution row the ordered list of points that touch it; then a
+// thread per (pixel, 4 channels) walks its row's list (a few dozen points instead of all N).  All buckets in one grid (tab = the
+// half-resolution level; rows / columns beyond a bucket's map exit): row lists and counts are laid out with the LARGEST map height hmax
+// per frame.
+// tabo[b][n] = {py | px << 16, rlo | rhi << 16, clo | chi << 16, 0}: the chosen pixel of point n and the range of half-resolution rows /
+// columns its 3 x 3 patch of upsampled positions interpolates from
 __global__ __launch_bounds__(TB) void up3_decode_multi_kernel(const int64_t *__restrict__ choose, int4 *__restrict__ tabo, int frames, int N, const BTab tab) {
   GRID_STRIDE(i, (long)frames * N) {          // (choose / tabo start at the table's first frame)
     const int g = tab_of_frame(tab, tab.b0[0] + (int)(i / N));
@@ -695,6 +469,8 @@ __global__ __launch_bounds__(TB) void up3_decode_multi_kernel(const int64_t *__r
     tabo[i] = make_int4(py | (px << 16), rlo | (rhi << 16), clo | (chi << 16), 0);
   }
 }
+// rows[b][qy][...] = the points (ascending n) whose patch touches half-resolution row qy, cnt[b][qy] their number: a workgroup per row
+// scans the table once, 256 points per round, and compacts the hits in order (wave ballots + a scan over the 4 waves)
 __global__ __launch_bounds__(TB) void up3_rowlist_multi_kernel(const int4 *__restrict__ tabi, int *__restrict__ rows, int *__restrict__ cnt, int hmax, int N,
                                                                const BTab tab) {
   __shared__ int s_w[4];
@@ -1140,8 +916,6 @@ struct Trainer {
   long flip_total = 0;
 #ifdef DF_DEV
   std::vector<std::string> ev_desc;      // shape of every profiled launch (DF_PROFILE_VERBOSE)
-  hipStream_t side = nullptr;            // DF_TRAIN_OVERLAP experiment
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 #endif
   FlipTile *flip_tiles = nullptr;  // the tiled form's segment table
   int flip_ntiles = 0;
@@ -1346,13 +1120,6 @@ struct Step {
   std::deque<Act> acts;
   std::deque<Lv> lvs;
   std::vector<std::function<void()>> tape;
-#ifdef DF_DEV
-  // development experiment (DF_TRAIN_OVERLAP=1): a layer's weight gradient on a side stream beside its data gradient; joined before the layer's
-  // backward closure ends, so no buffer hazard crosses a layer (profiles/r04_experiments/README.md)
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool keep_wgrad_ws = false;
-#endif
 
   void *bytes(size_t b) {
     b = (b + 255) & ~size_t(255);
@@ -1508,32 +1275,15 @@ void wgrad(Step &s, ConvParams f, const std::vector<WgradSeg> &segs, View gy, fl
   const size_t mark = s.off;
   const size_t need = wgrad_multi_workspace_bytes(f, (int)segs.size(), segs.data());
   void *ws = s.bytes(need);
-  hipStream_t st = s.st;
-  bool keep = false;
-#ifdef DF_DEV
-  keep = s.keep_wgrad_ws;
-  if (keep && s.live() && s.side) {      // fork: the side stream starts where the main stream is now
-    hipEventRecord(s.ev_fork, s.st);
-    hipStreamWaitEvent(s.side, s.ev_fork, 0);
-    st = s.side;
-  }
-#endif
   if (s.live()) {
     double M = 0;
     for (const WgradSeg &g : segs) M += (double)g.B * g.OH * g.OW;
     s.prof_begin();
-    s.fail(launch_wgrad_multi(f, (int)segs.size(), segs.data(), dw, db, ws, need, st, 1));
+    s.fail(launch_wgrad_multi(f, (int)segs.size(), segs.data(), dw, db, ws, need, s.st, 1));
     s.prof_end(GK_WGRAD, 2.0 * M * f.Cout * f.KH * f.KW * f.Cin, &f, (long)M);
   }
-#ifdef DF_DEV
-  if (keep && s.live() && s.side) {
-    hipEventRecord(s.ev_join, s.side);
-    static const bool sync_dbg = df::dev_getenv("DF_TRAIN_OVERLAP_SYNC") != nullptr;      // A/B: the side stream drained at once (no concurrency left)
-    if (sync_dbg) hipStreamSynchronize(s.side);
-  }
-#endif
   s.dbg("wgrad");
-  if (!keep) s.off = mark;          // (overlap experiment: the partial slices stay allocated until the layer's closure joins the side stream)
+  s.off = mark;
 }
 // a launch that is one bucket by itself (plain GEMMs over rows; `f` carries B / H / W / OH / OW)
 void wgrad(Step &s, const ConvParams &f, View gy, float *dw, float *db) {
@@ -1651,13 +1401,6 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
     Step &s = *sp;
     s.dbg("conv bwd begin", cw.name);
     if (act != ACT_NONE) launch_act_bwd(s, y, act, slope, act == ACT_PRELU ? s.gr(cw.slope) : nullptr);
-#ifdef DF_DEV
-    static const bool overlap = df::dev_getenv("DF_TRAIN_OVERLAP") != nullptr;
-    s.keep_wgrad_ws = overlap && need_dx;
-    bool acc_early = false;
-    if (s.keep_wgrad_ws) acc_early = s.grad_of(x);      // x's gradient buffer outlives the layer: it is taken BELOW the slices that are released at the join
-    const size_t mark_layer = s.off;
-#endif
     {   // weight gradient: one contraction over every bucket's pixels
       std::vector<WgradSeg> segs;
       if (flat) segs.push_back(WgradSeg{(int)x->rows(), 1, 1, 1, 1, 0, 0});
@@ -1667,11 +1410,7 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
       wgrad(s, f, segs, y->g, s.gr(cw.name, cw.woff), cw.bias.empty() ? nullptr : s.gr(cw.bias, cw.boff));
     }
     if (need_dx) {
-#ifdef DF_DEV
-      const bool acc = s.keep_wgrad_ws ? acc_early : s.grad_of(x);
-#else
       const bool acc = s.grad_of(x);
-#endif
       if (flat) dgrad(s, (*plan)[0], y->g, x->g, s.pf(cw.name, cw.woff), acc);
       else {
         std::vector<int> direct;
@@ -1715,13 +1454,6 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
         wino_pass(s, y->g, cout, s.dry || !wino_ok ? nullptr : s.t->wino_buf + wit->second.bwd, x->g, cin, acc ? x->g.d : nullptr, x->g.ld, ACT_NONE, GK_DGRAD);
       }
     }
-#ifdef DF_DEV
-    if (s.keep_wgrad_ws) {      // join: nothing after this layer may touch dY / the slices before its weight gradient is done
-      if (s.live() && s.side) hipStreamWaitEvent(s.st, s.ev_join, 0);
-      s.off = mark_layer;
-      s.keep_wgrad_ws = false;
-    }
-#endif
     if (res) {
       if (!res->gset) { res->g = y->g; res->gset = true; }          // the residual's gradient IS this (masked) gradient: alias, no copy
       else if (s.live()) hipLaunchKernelGGL(add2d_kernel, dim3(nblk(y->rows() * (y->C / 4))), dim3(TB), 0, s.st, res->g.d, res->g.ld, y->g.d, y->g.ld,
@@ -2431,16 +2163,6 @@ extern "C" int df_posenet_train_step_multi(df_trainer *h, const float *flat_para
   rc = check_flips(t, flat_param, (long)param_version, to_stream(stream));
   if (rc != DF_OK) return rc;
   Step s{&t, to_stream(stream), false, static_cast<char *>(ws)};
-#ifdef DF_DEV
-  if (df::dev_getenv("DF_TRAIN_OVERLAP")) {
-    if (!t.side) {
-      hipStreamCreateWithFlags(&t.side, hipStreamNonBlocking);
-      hipEventCreateWithFlags(&t.ev_fork, hipEventDisableTiming);
-      hipEventCreateWithFlags(&t.ev_join, hipEventDisableTiming);
-    }
-    s.side = t.side; s.ev_fork = t.ev_fork; s.ev_join = t.ev_join;
-  }
-#endif
   s.cap = ws_bytes; s.P = flat_param; s.G = flat_grad;
   PoseNetIO io{nb, B, H, W, img, M, cloud, target, model_points, choose, obj, symmetric_host, w, dropout, seed, loss_out, dis_out, new_points, new_target,
                out_r, out_t, out_c, emb};
