@@ -414,3 +414,44 @@ def test_multi_bucket_convolution_is_bit_identical_to_per_bucket_launches(cin, c
     assert (dw.cpu().double() - dw_ref).abs().max().item() <= 2e-5 * scale
     db_ref = dy.double().sum(0).cpu()
     assert (db.cpu().double() - db_ref).abs().max().item() <= 2e-5 * db_ref.abs().max().item()
+
+
+def test_multi_bucket_convolution_past_the_per_launch_bucket_limits():
+    """35 buckets: more than CONV_MAX_BUCKETS (16) per df_conv2d_nhwc_multi launch and WGRAD_MAX_SEGS (32) per weight-gradient launch, so
+    both split into chunks; later weight-gradient chunks must add to the first (accumulate = 0: the first overwrites NaN-filled buffers).
+    Forward bit-identical to per-bucket launches; weight and bias gradients against the fp64 sum over all buckets."""
+    import ctypes
+    from densefusion_amd import _lib
+    from densefusion_amd.ops import conv2d_nhwc
+    L = _lib.lib()
+    cin, cout, k, pad = 64, 64, 3, 1
+    g = torch.Generator().manual_seed(35)
+    sizes = [(1 + i % 3, 5 + (i * 7) % 11, 4 + (i * 5) % 13) for i in range(35)]
+    w = (torch.randn(cout, k, k, cin, generator=g) * 0.05).cuda()
+    bias = torch.randn(cout, generator=g).cuda()
+    xs = [torch.randn(b, h, wd, cin, generator=g).cuda() for b, h, wd in sizes]
+    want = [conv2d_nhwc(x, w, bias, stride=1, pad=pad, dil=1, act=1) for x in xs]
+    xcat = torch.cat([x.reshape(-1, cin) for x in xs]).contiguous()
+    rows = sum(b * h * wd for b, h, wd in sizes)
+    out = torch.full((rows, cout), float("nan"), device="cuda")
+    d = _multi_desc(xcat, w, out, 1, pad, 1, 1, bias, None)
+    arr = ctypes.c_int * len(sizes)
+    cB, cH, cW = arr(*[s[0] for s in sizes]), arr(*[s[1] for s in sizes]), arr(*[s[2] for s in sizes])
+    _lib.check(L.df_conv2d_nhwc_multi(ctypes.byref(d), len(sizes), cB, cH, cW, _lib.current_stream()), "conv2d_nhwc_multi")
+    assert torch.equal(out.cpu(), torch.cat([t.reshape(-1, cout) for t in want]).cpu())
+    dy = torch.randn(rows, cout, generator=g).cuda()
+    dw, db = torch.full_like(w, float("nan")), torch.full((cout,), float("nan"), device="cuda")
+    d.out = None
+    need = L.df_conv2d_wgrad_multi_workspace_bytes(ctypes.byref(d), len(sizes), cB, cH, cW)
+    ws = torch.empty(max(int(need), 4), dtype=torch.uint8, device="cuda")
+    _lib.check(L.df_conv2d_wgrad_nhwc_multi(ctypes.byref(d), len(sizes), cB, cH, cW, dy.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            _lib.current_stream()), "conv2d_wgrad_multi")
+    dw_ref, r0 = torch.zeros(cout, cin, k, k, dtype=torch.float64), 0
+    for x, (b, h, wd) in zip(xs, sizes):
+        gy = dy[r0:r0 + b * h * wd].reshape(b, h, wd, cout).permute(0, 3, 1, 2).double().cpu()
+        dw_ref += torch.nn.grad.conv2d_weight(x.permute(0, 3, 1, 2).double().cpu(), (cout, cin, k, k), gy, padding=pad)
+        r0 += b * h * wd
+    dw_ref = dw_ref.permute(0, 2, 3, 1)
+    assert (dw.cpu().double() - dw_ref).abs().max().item() <= 2e-5 * dw_ref.abs().max().item()
+    db_ref = dy.double().sum(0).cpu()
+    assert (db.cpu().double() - db_ref).abs().max().item() <= 2e-5 * db_ref.abs().max().item()

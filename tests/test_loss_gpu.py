@@ -201,7 +201,8 @@ def test_stacked_frames_give_each_frames_own_numbers(refine):
         crit.forward_frames(q, pt, pc, tgt, mp, ids[:3], pts, 0.015, refine)
 
 
-def test_more_stacked_frames_than_one_launch_table_holds():
+@pytest.mark.parametrize("refine", [False, True])
+def test_more_stacked_frames_than_one_launch_table_holds(refine):
     """65 frames: the frame table of a launch holds 60, the rest goes to a second round of launches -- same numbers frame by frame."""
     from densefusion_amd.lib.loss import Loss
     B, N, M = 65, 48, 40
@@ -213,7 +214,7 @@ def test_more_stacked_frames_than_one_launch_table_holds():
     pts = C(rng.standard_normal((B, N, 3)).astype(np.float32) * 0.1)
     ids = [7 if b % 3 == 0 else 2 for b in range(B)]
     crit = Loss(M, [7])
-    loss, dis, npts, ntg = crit.forward_frames(q, pt, pc, tgt, mp, ids, pts, 0.015, False)
+    loss, dis, npts, ntg = crit.forward_frames(q, pt, pc, tgt, mp, ids, pts, 0.015, refine)
     for b in (0, 1, 59, 60, 63, 64):
-        one = crit(q[b:b + 1], pt[b:b + 1], pc[b:b + 1], tgt[b:b + 1], mp[b:b + 1], torch.tensor([[ids[b]]]), pts[b:b + 1], 0.015, False)
+        one = crit(q[b:b + 1], pt[b:b + 1], pc[b:b + 1], tgt[b:b + 1], mp[b:b + 1], torch.tensor([[ids[b]]]), pts[b:b + 1], 0.015, refine)
         assert torch.equal(one[0].reshape(()), loss[b]) and torch.equal(one[1].reshape(()), dis[b]) and torch.equal(one[2][0], npts[b]), b

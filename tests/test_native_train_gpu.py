@@ -219,6 +219,7 @@ def test_native_step_at_the_ycb_training_shape_with_adam_and_a_hipgraph():
     with pytest.raises(RuntimeError, match="freeze the Dropout2d masks"):
         tr.step_posenet(f["img"], f["cloud"], f["choose"], f["obj"], f["target"], f["model_points"], sym, 0.015, dropout=True, graph_safe=True)
     # default seeds: a hash of (torch seed, lane, call) -- no two equal across lanes and calls
+    torch.manual_seed(20240)                  # the check does not depend on what an earlier test left in the torch seed
     a, b = _trainer("posenet", N, K, sd), _trainer("posenet", N, K, sd)
     b._salt = 1
     seeds = [t._next_seed() for _ in range(2000) for t in (a, b)]
