@@ -59,6 +59,12 @@ SIGNATURES = {
     "df_maxpool3s2_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "df_maxpool2x2_idx": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "df_maxunpool2x2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "df_bn_workspace_bytes": (_sz, [_i64, _i]),
+    "df_bn_relu_fwd_train": (_i, [_vp] * 10 + [_i64, _i, _f, _f, _vp, _sz, _vp]),
+    "df_bn_relu_bwd": (_i, [_vp, _vp, _i, _i] + [_vp] * 8 + [_i64, _i, _vp, _sz, _vp]),
+    "df_maxunpool2x2_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "df_cross_entropy_workspace_bytes": (_sz, [_i64]),
+    "df_cross_entropy_nhwc": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "df_maxpool3s2_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "df_adaptive_avgpool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "df_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -9,7 +9,15 @@ Different: the submodules are parameter containers only.  ``eval()`` forward fol
 (w' = w g / sqrt(var + eps), b' = (b - mean) g / sqrt(var + eps) + beta), keeps activations channels-last and runs
 conv + bias + ReLU as one launch of the fp32-MFMA kernel (the >= 256-channel layers through the Winograd domain), the
 2x2 max-pool / un-pool pairs through ``df_maxpool2x2_idx`` / ``df_maxunpool2x2``.  H and W must be multiples of 32
-(480 x 640 is).  Training this network is not rebuilt: ``train()`` mode forward raises.
+(480 x 640 is).
+
+Training is opt-in: ``SegNet(trainable=True)`` (or ``net.trainable = True``).  The default module keeps its inference-only contract,
+and its ``train()`` forward raises NotImplementedError.  A trainable module's ``train()`` forward runs the reference's graph on the
+tape of segtrain_ops / train_ops: the UNFOLDED parameters (each
+convolution with its bias on the fp32-MFMA kernel, weights arranged OHWI and padded like the eval path's), then BatchNorm2d with
+batch statistics fused with the ReLU (and, at the encoder's stage ends, with the max-pool), writing the module's own
+``running_mean`` / ``running_var`` / ``num_batches_tracked``.  It returns a [B,label_nbr,H,W] view of the channels-last logits; the
+segmentation ``Loss`` (loss.py) reads the channels-last tensor behind it directly.
 """
 from __future__ import annotations
 
@@ -18,6 +26,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib, ops
+from ..segtrain_ops import BatchNormReLU, BatchNormReLUMaxPool, MaxUnpool2x2
+from ..train_ops import ConvAct
 
 # (name, Cin, Cout) in forward order; 'P' = pool, 'U' = unpool (segnet.py:73-118)
 _ENC = [("11", None, 64), ("12", 64, 64), "P", ("21", 64, 128), ("22", 128, 128), "P", ("31", 128, 256), ("32", 256, 256), ("33", 256, 256), "P",
@@ -31,9 +41,10 @@ def _pad4(n):
 
 
 class SegNet(nn.Module):
-    def __init__(self, input_nbr=3, label_nbr=22):
+    def __init__(self, input_nbr=3, label_nbr=22, trainable=False):
         super().__init__()
         self.input_nbr, self.label_nbr = input_nbr, label_nbr
+        self.trainable = trainable             # plain attribute: not part of the state dict
         for item in _ENC + _DEC:
             if isinstance(item, str):
                 continue
@@ -66,14 +77,59 @@ class SegNet(nn.Module):
         self._folded[name] = (tag, w, b)
         return w, b
 
+    def _train_forward(self, x):
+        C = x.shape[1]
+        self._folded = {}                     # the BatchNorm buffers are rewritten below, behind torch's version counters
+        a = x.detach().float().permute(0, 2, 3, 1)
+        a = F.pad(a, (0, _pad4(C) - C)).contiguous()
+        seq = _ENC + _DEC
+        indices = []
+        with _lib.device_guard(x.device):
+            for k, item in enumerate(seq):
+                if item == "P":
+                    continue                  # fused into the BatchNorm before it
+                if item == "U":
+                    a = MaxUnpool2x2.apply(a, indices.pop())
+                    continue
+                name = item[0]
+                conv = getattr(self, "conv" + name)
+                cout, cin = conv.weight.shape[0], conv.weight.shape[1]
+                w = conv.weight.permute(0, 2, 3, 1)                                   # OIHW -> OHWI
+                b = conv.bias
+                # the classifier's outputs are padded to a power of two: its data gradient runs the flipped convolution, whose
+                # input channels (these) the MFMA kernel takes in powers of two only (22 classes -> 32)
+                cpad = 1 << (cout - 1).bit_length() if name == "11d" else _pad4(cout)
+                if _pad4(cin) != cin or cpad != cout:
+                    w = F.pad(w, (0, _pad4(cin) - cin, 0, 0, 0, 0, 0, cpad - cout))
+                    b = F.pad(b, (0, cpad - cout))
+                z = ConvAct.apply(a, w.contiguous(), b.contiguous(), None, None, 1, 1, 1, 0)
+                bn = getattr(self, "bn" + name, None)
+                if bn is None:
+                    a = z
+                    continue
+                if bn.momentum is None or not bn.track_running_stats:
+                    raise NotImplementedError("SegNet.train(): BatchNorm2d with momentum=None or without running statistics")
+                args = (z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
+                if k + 1 < len(seq) and seq[k + 1] == "P":
+                    a, idx = BatchNormReLUMaxPool.apply(*args)
+                    indices.append(idx)
+                else:
+                    a = BatchNormReLU.apply(*args)
+        out = a[..., :self.label_nbr].permute(0, 3, 1, 2)
+        out._nhwc = a                         # Loss (loss.py) takes the channels-last logits from here
+        return out
+
     def forward(self, x):
-        if self.training:
-            raise NotImplementedError("SegNet: only the eval() forward runs on the HIP path (training this network is not rebuilt)")
+        if self.training and not self.trainable:
+            raise NotImplementedError("SegNet: train() forward needs a module built with SegNet(trainable=True) (or net.trainable = True); "
+                                      "the default module is inference-only")
         if not x.is_cuda:
             raise RuntimeError("densefusion_amd needs device tensors (no CPU path): call .cuda() on the input")
         B, C, H, W = x.shape
         if C != self.input_nbr or H % 32 or W % 32:
             raise RuntimeError(f"SegNet.forward: expected [B,{self.input_nbr},H,W] with H, W multiples of 32, got {tuple(x.shape)}")
+        if self.training:
+            return self._train_forward(x)
         L = _lib.lib()
         with torch.no_grad(), _lib.device_guard(x.device):
             a = x.detach().float().permute(0, 2, 3, 1)

@@ -190,6 +190,34 @@ int df_maxpool3s2_fwd(const float *x, float *y, int B, int H, int W, int C, int 
  * the POOLED size H x W and writes [B][2H][2W][C]. */
 int df_maxpool2x2_idx(const float *x, float *y, unsigned char *idx, int B, int H, int W, int C, df_stream_t stream);
 int df_maxunpool2x2(const float *x, const unsigned char *idx, float *y, int B, int H, int W, int C, df_stream_t stream);
+
+/* Training-mode layers of the SegNet (csrc/segtrain.hip), channels-last fp32, C a multiple of 4 (at most 1024).  Deterministic: no
+ * atomics, fixed-order reductions whose partition depends on the shape only.
+ *
+ * BatchNorm2d (train) + ReLU over z [rows][C]: batch mean / biased variance (fp64 partials of z minus a sample of its channel), invstd =
+ * 1/sqrt(var + eps), y = relu(((z - mean) invstd) gamma + beta); running_mean / running_var (unbiased variance) updated with `momentum`
+ * as nn.BatchNorm2d does and *num_batches_tracked += 1 (either may be NULL: no update).  Outputs: var / invstd [C] and mean [2C], the
+ * batch mean rounded to fp32 followed by its fp32 residual (hi + lo); the backward takes mean in that form.
+ * df_bn_relu_bwd: the adjoint from dy, the saved z, mean, invstd (the ReLU mask recomputed from z): dgamma, dbeta [C] and
+ * dz = gamma invstd (g - mean(g) - xhat mean(g xhat)).  pool_idx != NULL: the layer feeds a 2x2 max-pool and dy is the POOLED gradient
+ * [B][H/2][W/2][C] with that pool's index (df_maxpool2x2_idx), rows = B H W; pool_idx == NULL: dy is [rows][C] (H, W unused).
+ * Both take df_bn_workspace_bytes(rows, C) bytes of device scratch. */
+size_t df_bn_workspace_bytes(int64_t rows, int C);
+int df_bn_relu_fwd_train(const float *z, float *y, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                         int64_t *num_batches_tracked, float *mean, float *var, float *invstd, int64_t rows, int C, float momentum,
+                         float eps, void *ws, size_t ws_bytes, df_stream_t stream);
+int df_bn_relu_bwd(const float *dy, const unsigned char *pool_idx, int H, int W, const float *z, const float *mean, const float *invstd,
+                   const float *gamma, const float *beta, float *dz, float *dgamma, float *dbeta, int64_t rows, int C, void *ws,
+                   size_t ws_bytes, df_stream_t stream);
+/* Adjoint of df_maxunpool2x2: dx [B][H][W][C] (the POOLED size) gathers dy [B][2H][2W][C] at the position idx names. */
+int df_maxunpool2x2_bwd(const float *dy, const unsigned char *idx, float *dx, int B, int H, int W, int C, df_stream_t stream);
+/* nn.CrossEntropyLoss() (mean over rows) of logits [rows][ld] whose first `classes` channels are the classes, target int64 [rows]:
+ * *loss (device) and dlogits [rows][ld] = (softmax - onehot) / rows, zero in the channels >= classes, in one pass plus an ordered
+ * finish.  A label outside [0, classes) sets *bad_label (device int, cleared by the call) and its row gets zero gradient.
+ * ws: df_cross_entropy_workspace_bytes(rows) bytes. */
+size_t df_cross_entropy_workspace_bytes(int64_t rows);
+int df_cross_entropy_nhwc(const float *logits, const int64_t *target, float *dlogits, int64_t rows, int ld, int classes, float *loss,
+                          int *bad_label, void *ws, size_t ws_bytes, df_stream_t stream);
 int df_maxpool3s2_bwd(const float *x, const float *dy, float *dx, int B, int H, int W, int C, int OH, int OW, df_stream_t stream);
 int df_adaptive_avgpool(const float *in, float *out, int B, int H, int W, int C, int s, int backward, df_stream_t stream);
 int df_bilinear(const float *in, float *out, int B, int H, int W, int C, int OH, int OW, int align_corners, int backward,
