@@ -109,6 +109,8 @@ SIGNATURES = {
     "df_net_debug_tap_read": (_i, [_vp, ctypes.c_char_p, _vp, _i64, ctypes.POINTER(_i64)]),
     "df_net_profile": (_i, [_vp, _i]),
     "df_net_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(_i)]),
+    "df_net_profile_read_split": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i)]),
+    "df_gemm_route": (_i, [_i, _i, _i]),
 }
 
 

@@ -43,7 +43,14 @@ struct Net {
   std::vector<hipEvent_t> ev;
   std::vector<double> ev_flops, ev_bytes, ev_useful;
   std::vector<std::string> ev_desc;
+  std::vector<char> ev_bf16;           // per launch: 1 = the bf16 x 6 kernel (df_net_profile_read_split), 0 = fp32 (df_net_profile_read)
   size_t ev_used = 0;
+  // bf16 x 6 weight planes (csrc/split_gemm.hip) of every buffer a routed layer reads, by the buffer's address: term p of w[i] at
+  // ptr[p * stride + i].  Allocated by the first ensure_derived, cut again by the first one after any parameter load (after the PSP fold;
+  // the Winograd-domain U and the tap-major copies are made at load), freed by df_net_destroy: the launch path only looks them up
+  struct Planes { long elems = 0, stride = 0; void *ptr = nullptr; };
+  std::map<const float *, Planes> planes;
+  bool planes_dirty = true;
   // debug taps (df_net_debug_taps): copies of named intermediates of the last single-bucket forward, channels-last
   bool psp_dirty = false;               // a psp.* weight changed since the folded matrices were built
   // parameter uploads are enqueued on the null stream WITHOUT host synchronisation (one staging buffer, no per-tensor malloc /
@@ -284,9 +291,100 @@ static int load_param(Net &n, const std::string &key, const float *src, int64_t 
   return DF_OK;
 }
 
-// (re)build what is derived from several parameters: the PSP fold (bottleneck x stage weights, fp64 accumulation)
+// The engine's plain-GEMM weights: every buffer a 1x1 / per-point / Winograd-domain launch reads, with the launches' (N, K, epilogue kind).
+// Those of layers split_route takes get bf16 planes; the launch path (Ctx::conv) finds them by address and fails on a routed launch
+// whose buffer has none, so this table and the launches cannot drift apart silently.
+struct GemmWeight { std::string name; int N, K, epi; };
+static std::vector<GemmWeight> gemm_weights(const Net &n) {
+  std::vector<GemmWeight> v;
+  const std::string P = CNN;
+  if (n.kind == 0) {
+    v.push_back({"psp.fold.w", 1024, 512, GEMM_EPI_PLAIN});
+    v.push_back({"psp.fold.wfeat", 1024, 512, GEMM_EPI_RESIDUAL});
+    v.push_back({P + "up_1.conv.1.weight.tm", 9 * 256, 1024, GEMM_EPI_PLAIN});
+    v.push_back({P + "up_2.conv.1.weight.tm", 9 * 64, 256, GEMM_EPI_PLAIN});
+    v.push_back({P + "up_3.conv.1.weight", 64, 576, GEMM_EPI_PLAIN});
+    for (const ParamInfo &pi : n.spec)
+      if (pi.key.find("feats.layer") != std::string::npos && pi.ndim == 4) {
+        const int O = (int)pi.shape[0], I = (int)pi.shape[1];
+        if (pi.shape[2] * pi.shape[3] == 1) v.push_back({pi.key, O, I, GEMM_EPI_PLAIN});          // downsample.0 (1x1)
+        else {
+          v.push_back({pi.key + ".wino", O, I, GEMM_EPI_PLAIN});
+          v.push_back({pi.key + ".wino4", O, I, GEMM_EPI_PLAIN});
+        }
+      }
+    v.push_back({"feat.conv5.weight", 512, 256, GEMM_EPI_PLAIN});
+    v.push_back({"head1.wpt", 1920, 384, GEMM_EPI_GROUPS});
+    v.push_back({"head1.wpt", 640, 384, GEMM_EPI_GROUPS});       // (the confidence tower alone: pose selection)
+    v.push_back({"head2.w", 256, 640, GEMM_EPI_PLAIN});
+    v.push_back({"head3.w", 128, 256, GEMM_EPI_PLAIN});
+  } else {
+    v.push_back({"feat.conv5.we", 512, 192, GEMM_EPI_PLAIN});
+    v.push_back({"feat.conv5.wx", 512, 192, GEMM_EPI_RESIDUAL});
+  }
+  v.push_back({"feat.e_conv1.weight", 64, 32, GEMM_EPI_PLAIN});
+  v.push_back({"feat.conv2.weight", 128, 64, GEMM_EPI_PLAIN});
+  v.push_back({"feat.e_conv2.weight", 128, 64, GEMM_EPI_PLAIN});
+  v.push_back({"feat.conv6.weight", 1024, 512, GEMM_EPI_GROUPS});
+  return v;
+}
+
+// element count of a packed buffer (the planes cover it whole: launches read sub-ranges and z batches of it)
+static long buffer_elems(const Net &n, const std::string &name) {
+  const std::string P = CNN;
+  auto spec_of = [&](const std::string &key) -> const ParamInfo * {
+    auto it = n.index.find(key);
+    return it == n.index.end() ? nullptr : &n.spec[it->second];
+  };
+  if (name == "psp.fold.w") return 4L * 1024 * 512;
+  if (name == "psp.fold.wfeat") return 1024L * 512;
+  if (name == "head1.wpt") return 1920L * 384;
+  if (name == "head2.w") return 3L * 256 * 640;
+  if (name == "head3.w") return 3L * 128 * 256;
+  if (name == "feat.conv5.we" || name == "feat.conv5.wx") return 512L * 192;
+  const bool wino = ends_with(name, ".wino"), wino4 = ends_with(name, ".wino4"), tm = ends_with(name, ".tm");
+  const std::string key = wino ? name.substr(0, name.size() - 5) : wino4 ? name.substr(0, name.size() - 6) : tm ? name.substr(0, name.size() - 3) : name;
+  const ParamInfo *pi = spec_of(key);
+  if (!pi) return 0;
+  const long O = pi->shape[0], I = pi->shape[1], HW = pi->ndim == 4 ? pi->shape[2] * pi->shape[3] : 1;
+  if (wino) return 16 * O * I;
+  if (wino4) return 36 * O * I;
+  if (tm) return 9 * O * I;
+  return O * HW * ((I + 3) / 4 * 4);          // packed O (H W) Ipad
+}
+
+// (re)cut the planes of every routed layer's buffer on the null stream (after the uploads and the PSP fold, in stream order)
+static int cut_planes(Net &n) {
+  for (const GemmWeight &g : gemm_weights(n)) {
+    if (!split_route(g.N, g.K, g.epi)) continue;
+    auto it = n.buf.find(g.name);
+    const long elems = buffer_elems(n, g.name);
+    if (it == n.buf.end() || elems <= 0) return set_error(DF_ERR_STATE, "weight planes: no packed buffer '%s'", g.name.c_str());
+    Net::Planes &pl = n.planes[it->second];
+    if (!pl.ptr) {
+      pl.elems = elems;
+      pl.stride = (elems + 63) / 64 * 64;
+      if (hipMalloc(&pl.ptr, (size_t)pl.stride * 3 * 2) != hipSuccess) {
+        pl.ptr = nullptr;
+        return set_error(DF_ERR_LAUNCH, "weight planes of '%s': hipMalloc failed", g.name.c_str());
+      }
+      hipMemset(pl.ptr, 0, (size_t)pl.stride * 3 * 2);
+    }
+    cut_weight_planes(it->second, pl.ptr, pl.elems, pl.stride, 0);
+  }
+  if (check_launch("weight planes") != DF_OK) return DF_ERR_LAUNCH;
+  return DF_OK;
+}
+
+// (re)build what is derived from several parameters: the PSP fold (bottleneck x stage weights, fp64 accumulation), then the bf16 planes
 static int ensure_derived(Net &n) {
   if (!n.psp_dirty) {
+    if (n.planes_dirty) {
+      const int rc = cut_planes(n);
+      if (rc != DF_OK) return rc;
+      n.planes_dirty = false;
+      n.upload_pending = true;
+    }
     if (n.upload_pending) {               // the uploads of df_net_load_param ran on the null stream: one wait per batch of loads
       if (hipStreamSynchronize(0) != hipSuccess) return set_error(DF_ERR_LAUNCH, "parameter upload failed: %s", hipGetErrorString(hipGetLastError()));
       n.upload_pending = false;
@@ -300,10 +398,10 @@ static int ensure_derived(Net &n) {
   hipMemcpy2DAsync(wf, 512 * sizeof(float), wb + 2048, 2560 * sizeof(float), 512 * sizeof(float), 1024, hipMemcpyDeviceToDevice, 0);
   for (int st = 0; st < 4; ++st)
     hipLaunchKernelGGL(psp_fold_kernel, dim3(2, 1024, 1), dim3(256), 0, 0, wb, n.buf[P + "psp.stages." + std::to_string(st) + ".1.weight"], wc, st);
-  if (hipStreamSynchronize(0) != hipSuccess || check_launch("psp fold") != DF_OK) return DF_ERR_LAUNCH;
+  if (check_launch("psp fold") != DF_OK) return DF_ERR_LAUNCH;
   n.psp_dirty = false;
-  n.upload_pending = false;
-  return DF_OK;
+  n.upload_pending = true;
+  return ensure_derived(n);            // the planes (cut from the folded matrices too), then one wait
 }
 
 static int check_ready(const Net &n0) {
@@ -371,13 +469,25 @@ struct Ctx {
       }
       hipEventRecord(n.ev[n.ev_used], st);
     }
-#ifdef DF_DEV
     ConvParams pc = p;
-    pc.wgt_const = true;           // the engine's packed parameters: split_gemm_invalidate() on every load / destroy
-    const int rc = launch_conv(pc, st);
-#else
-    const int rc = launch_conv(p, st);
-#endif
+    if (p.KH * p.KW == 1 && split_route(p.Cout, p.Cin, gemm_epi_kind(p))) {
+      // a routed layer: its weights' bf16 planes, cut at load (ensure_derived); looked up, never made, here
+      const long extent = (long)(p.zcount - 1) * p.z_wgt + (long)p.Cout * p.Cin;
+      auto it = n.planes.upper_bound(p.wgt);
+      const Net::Planes *pl = nullptr;
+      if (it != n.planes.begin()) {
+        --it;
+        if (p.wgt >= it->first && p.wgt + extent <= it->first + it->second.elems && (p.wgt - it->first) % 8 == 0) pl = &it->second;
+      }
+      if (!pl) {
+        if (err == DF_OK) err = set_error(DF_ERR_STATE, "routed GEMM N=%d K=%d: its weights have no bf16 planes", p.Cout, p.Cin);
+        return;
+      }
+      pc.wpl = reinterpret_cast<const char *>(pl->ptr) + (p.wgt - it->first) * 2;
+      pc.wpl_stride = pl->stride;
+    }
+    int on_bf16 = 0;
+    const int rc = launch_conv(pc, st, nullptr, &on_bf16);
     if (n.profiling) {
       hipEventRecord(n.ev[n.ev_used + 1], st);
       n.ev_flops.push_back(conv_flops(p));
@@ -387,6 +497,7 @@ struct Ctx {
       snprintf(d, sizeof(d), "M=%ld N=%d K=%d k%dx%d s%d d%d z%d", (long)p.B * p.OH * p.OW, p.Cout, p.KH * p.KW * p.Cin, p.KH,
                p.KW, p.stride, p.dil, p.zcount);
       n.ev_desc.push_back(d);
+      n.ev_bf16.push_back((char)on_bf16);
       n.ev_used += 2;
     }
     if (rc != DF_OK) err = rc;
@@ -840,9 +951,7 @@ extern "C" df_net *df_refiner_create(int num_points, int num_obj) {
 extern "C" void df_net_destroy(df_net *h) {
   if (!h) return;
   Net *n = as_net(h);
-#ifdef DF_DEV
-  split_gemm_invalidate();
-#endif
+  for (auto &kv : n->planes) hipFree(kv.second.ptr);
   for (auto &kv : n->buf) hipFree(kv.second);
   if (n->stage) hipFree(n->stage);
   for (auto &kv : n->taps) if (kv.second.buf) hipFree(kv.second.buf);
@@ -865,9 +974,7 @@ extern "C" int df_net_param_info(const df_net *h, int i, char *key_out, int key_
 
 extern "C" int df_net_load_param(df_net *h, const char *key, const float *ptr, int64_t numel) {
   if (!h || !key) return set_error(DF_ERR_ARG, "load_param: null handle/key");
-#ifdef DF_DEV
-  split_gemm_invalidate();
-#endif
+  as_net(h)->planes_dirty = true;
   return load_param(*as_net(h), key, ptr, numel);
 }
 
@@ -880,19 +987,26 @@ extern "C" int df_net_profile(df_net *h, int enable) {
   n->ev_bytes.clear();
   n->ev_useful.clear();
   n->ev_desc.clear();
+  n->ev_bf16.clear();
   return DF_OK;
 }
 
-// after a stream sync: sum of GEMM launch durations (ms), their algorithmic FLOPs and count since df_net_profile(1)
+// after a stream sync: sum of the fp32-kernel GEMM launch durations (ms), their algorithmic FLOPs and count since df_net_profile(1)
+// (the bf16 x 6 launches: df_net_profile_read_split, which must come first -- this call re-arms)
 extern "C" int df_net_profile_read(df_net *h, double *gemm_ms, double *gemm_flops, double *gemm_useful_flops, double *gemm_bytes,
                                    int *launches) {
   if (!h) return set_error(DF_ERR_ARG, "profile_read: null handle");
   Net *n = as_net(h);
   double ms = 0, fl = 0, by = 0, us = 0;
+  int cnt = 0;
   static const bool verbose = df::dev_getenv("DF_PROFILE_VERBOSE") != nullptr;
   for (size_t i = 0; i + 1 < n->ev_used; i += 2) {
     float t = 0;
     if (hipEventElapsedTime(&t, n->ev[i], n->ev[i + 1]) != hipSuccess) return set_error(DF_ERR_LAUNCH, "profile_read: events not complete");
+    if (verbose && n->ev_bf16[i / 2])
+      fprintf(stderr, "[df-gemm-bf16] %s  %.1f us  %.1f TFLOP/s\n", n->ev_desc[i / 2].c_str(), t * 1e3, n->ev_flops[i / 2] / t / 1e9);
+    if (n->ev_bf16[i / 2]) continue;
+    ++cnt;
     ms += t;
     fl += n->ev_flops[i / 2];
     by += n->ev_bytes[i / 2];
@@ -904,14 +1018,40 @@ extern "C" int df_net_profile_read(df_net *h, double *gemm_ms, double *gemm_flop
   if (gemm_flops) *gemm_flops = fl;
   if (gemm_useful_flops) *gemm_useful_flops = us;
   if (gemm_bytes) *gemm_bytes = by;
-  if (launches) *launches = (int)(n->ev_used / 2);
+  if (launches) *launches = cnt;
   n->ev_used = 0;
   n->ev_flops.clear();
   n->ev_bytes.clear();
   n->ev_useful.clear();
   n->ev_desc.clear();
+  n->ev_bf16.clear();
   return DF_OK;
 }
+
+// after a stream sync: the same sums over the bf16 x 6 launches since df_net_profile(1); does not re-arm
+extern "C" int df_net_profile_read_split(df_net *h, double *gemm_ms, double *gemm_flops, double *gemm_useful_flops, int *launches) {
+  if (!h) return set_error(DF_ERR_ARG, "profile_read_split: null handle");
+  Net *n = as_net(h);
+  double ms = 0, fl = 0, us = 0;
+  int cnt = 0;
+  for (size_t i = 0; i + 1 < n->ev_used; i += 2) {
+    if (!n->ev_bf16[i / 2]) continue;
+    float t = 0;
+    if (hipEventElapsedTime(&t, n->ev[i], n->ev[i + 1]) != hipSuccess) return set_error(DF_ERR_LAUNCH, "profile_read_split: events not complete");
+    ms += t;
+    fl += n->ev_flops[i / 2];
+    us += n->ev_useful[i / 2];
+    ++cnt;
+  }
+  if (gemm_ms) *gemm_ms = ms;
+  if (gemm_flops) *gemm_flops = fl;
+  if (gemm_useful_flops) *gemm_useful_flops = us;
+  if (launches) *launches = cnt;
+  return DF_OK;
+}
+
+// routing of a plain-GEMM layer of the inference engine (csrc/split_gemm.hip split_route)
+extern "C" int df_gemm_route(int n, int k, int epilogue) { return split_route(n, k, epilogue); }
 
 extern "C" int df_net_debug_taps(df_net *h, int enable) {
   if (!h) return set_error(DF_ERR_ARG, "debug_taps: null handle");

@@ -37,9 +37,10 @@ struct ConvParams {
   // split-K (training path only: opt-in through a caller-provided scratch, df_conv_desc.splitk_ws): launches that would fill less than
   // half the chip cut their reduction into `splitk` ranges (blockIdx.z), partial sums go to the scratch and a fixed-order reduce
   // kernel adds them and applies bias / residual / activation (deterministic).  splitk is set by launch_conv.
-  // development build only (csrc/split_gemm.hip): the weights do not change between split_gemm_invalidate() calls, so their bf16 planes
-  // may be cached (set by the inference engine for its own packed parameters); false: the planes are cut again on every launch
-  bool wgt_const = false;
+  // bf16 weight planes of `wgt` (csrc/split_gemm.hip): term p of wgt[i] at wpl[p * wpl_stride + i] (bf16 elements), cut by the weights'
+  // owner once per parameter load (the inference engine, for the layers split_route takes).  null: fp32 kernels only
+  const void *wpl = nullptr;
+  long wpl_stride = 0;
   float *splitk_ws = nullptr;
   size_t splitk_ws_bytes = 0;
   int splitk = 1;
@@ -58,7 +59,8 @@ int conv_colsum_rows(const ConvParams &p);
 double conv_flops(const ConvParams &p);
 // algorithmic HBM bytes (inputs, weights, outputs and residual touched once)
 double conv_bytes(const ConvParams &p);
-int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used = nullptr);     // splitk_used: the K ranges the launch was cut into
+// splitk_used: the K ranges the launch was cut into; on_bf16: 1 when the bf16 x 6 kernel took it (csrc/split_gemm.hip), 0 on the fp32 kernels
+int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used = nullptr, int *on_bf16 = nullptr);
 
 // One crop-size bucket of a multi-bucket launch: B maps of H x W (outputs OH x OW) whose input / output pixel rows start at
 // in_row0 / out_row0 of the concatenated buffers
@@ -87,11 +89,17 @@ size_t wgrad_multi_workspace_bytes(const ConvParams &p, int nseg, const WgradSeg
 int launch_wgrad_multi(const ConvParams &p, int nseg, const WgradSeg *segs, float *dw, float *db, void *ws, size_t ws_bytes, hipStream_t st,
                        int accumulate = 0);
 
-#ifdef DF_DEV
-// development build only (csrc/split_gemm.hip): DF_GEMM_SPLIT_BF16=1 routes eligible plain-GEMM launches to the bf16 x 6 experiment.
-// 1 when the launch was taken (results in p.out), 0 when not eligible (the caller goes on to the fp32 kernels), or a DF_ERR_* code
+// fp32 GEMM on the bf16 matrix cores (csrc/split_gemm.hip).  Epilogue kinds of a plain-GEMM launch (gemm_epi_kind): bias / activation
+// only, + residual, + per-row-group bias and / or fused column sums; anything else (residual with row groups) is not covered.
+enum GemmEpi { GEMM_EPI_PLAIN = 0, GEMM_EPI_RESIDUAL = 1, GEMM_EPI_GROUPS = 2, GEMM_EPI_OTHER = 3 };
+int gemm_epi_kind(const ConvParams &p);
+// 1: a layer with N output channels, reduction K and this epilogue kind runs on the bf16 x 6 kernel when its weights have planes.  A pure
+// function of the layer (no M, batch, crop size, z count, stream or device state): B objects in one call and B solo calls take the same path
+int split_route(int N, int K, int epi);
+// cut `elems` weights into their three bf16 planes (term p of w[i] at planes[p * stride + i], bf16 elements) on stream st
+void cut_weight_planes(const float *w, void *planes, long elems, long stride, hipStream_t st);
+// launch_conv's first step: 1 when the launch was taken by the bf16 x 6 kernel (p.wpl set and split_route true; development build: also
+// DF_GEMM_SPLIT_BF16), 0 when it goes on to the fp32 kernels, or a DF_ERR_* code
 int try_split_gemm(const ConvParams &p, hipStream_t st);
-void split_gemm_invalidate();      // cached weight planes are cut again at their next use (a parameter was loaded / a network destroyed)
-#endif
 
 }  // namespace df

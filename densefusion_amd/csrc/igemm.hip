@@ -1402,7 +1402,8 @@ double conv_flops(const ConvParams &p) {
   return 2.0 * p.B * p.OH * p.OW * (double)p.Cout * p.KH * p.KW * p.Cin * p.zcount;
 }
 
-int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used) {
+int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used, int *on_bf16) {
+  if (on_bf16) *on_bf16 = 0;
   if (!p.in || !p.wgt || (!p.out && !p.colsum)) return set_error(DF_ERR_ARG, "conv: null pointer");
   if (p.Cin % 4 || p.in_ld % 4 || p.in_coff % 4 || p.z_in_coff % 4 || p.z_wgt % 4)
     return set_error(DF_ERR_ARG, "conv: Cin/in_ld/in_coff must be multiples of 4 (16-B vector loads)");
@@ -1412,16 +1413,15 @@ int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used) {
   if (M <= 0 || p.Cout <= 0) return DF_OK;
   if (M * (long)p.out_ld >= (1L << 40) || (long)p.B * p.H * p.W >= (1L << 31))
     return set_error(DF_ERR_ARG, "conv: tensor too large for 32-bit pixel indexing");
-#ifdef DF_DEV
-  if (!p.splitk_ws) {
+  {
     const int taken = try_split_gemm(p, st);
     if (taken < 0) return taken;
     if (taken) {
       if (splitk_used) *splitk_used = 1;
+      if (on_bf16) *on_bf16 = 1;
       return check_launch("split gemm");
     }
   }
-#endif
   const TileCfg c = pick_cfg(p);
   ConvParams pl = p;       // launch copy: + the column-tile group width and the division magics
   make_fdiv((long)p.OH * p.OW, pl.ohw_magic, pl.ohw_sh);

@@ -1,18 +1,24 @@
-// EXPERIMENT (development build only, -DDF_DEV; never the default path, never the bench's headline): fp32 GEMM on the bf16 matrix cores.
+// fp32 GEMM on the bf16 matrix cores (product and development library): the inference engine's routed plain-GEMM launches.
 //
 // Every fp32 operand is cut into three bf16 terms, a = hi + mid + lo (round-to-nearest at each cut: |mid| <= 2^-9 |a|, |lo| <= 2^-18 |a|),
 // and a product a*b is accumulated in fp32 from the six term pairs whose magnitude is above 2^-27 |a b|:
 //   lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi       (v_mfma_f32_32x32x16_bf16, 16x the fp32 MFMA rate: 16 / 6 = 2.7x at equal efficiency).
-// The weights are cut once per layer (cached planes [3][Cout][K] bf16); the activations are cut while the workgroup stages its tile
-// (global fp32 -> registers -> three bf16 planes in LDS): no extra pass over HBM.
+// The result is inside fp32 rounding of the exact product, not bit-identical to the fp32-MFMA kernel's summation order.  Per output element
+// the order depends only on K: k-steps of 32 in ascending order, two k16 MFMAs per step, the six pairs in the fixed order above -- the same in
+// both tile forms, whatever M, the tile or the form picked.
+// The weights are cut once per parameter load by their owner (the engine: Net planes, cut_weight_planes); the activations are cut while the
+// workgroup stages its tile (global fp32 -> registers -> three bf16 planes in LDS): no extra pass over HBM.
 // Covered: 1x1 / per-point / Winograd-domain launches (plain GEMMs: stride 1, no padding) with Cout % 128 == 0 and K % 32 == 0, bias (per
-// channel or per row group), residual, ReLU / PReLU, fused column sums, blockIdx.z batches; everything else stays on the fp32 kernels.
-// Switch: DF_GEMM_SPLIT_BF16=1 in the environment of a process that loaded libdfusion_hip_dev.so.  Results: profiles/r04_experiments/README.md.
+// channel or per row group), residual, ReLU / PReLU, fused column sums, blockIdx.z batches.  Which launches run here is split_route(N, K,
+// epilogue kind) of a launch whose weights come with planes (ConvParams::wpl); everything else stays on the fp32 kernels.
+// Development build only: DF_GEMM_SPLIT_OFF=1 keeps every launch on fp32; DF_GEMM_SPLIT_BF16=1 also takes eligible launches without planes
+// (their weights are cut per launch into a per-stream scratch).  Measurements: DESIGN.md section 6, profiles/r04_experiments/README.md.
 #include "igemm.h"
 #ifdef DF_DEV
 #include <map>
 #include <mutex>
 #include <tuple>
+#endif
 
 namespace df {
 namespace {
@@ -37,13 +43,14 @@ __device__ __forceinline__ void cut3(float a0, float a1, unsigned &hi, unsigned 
   lo = __builtin_bit_cast(unsigned, l);
 }
 
-__global__ void cut_weights_kernel(const float *__restrict__ w, unsigned *__restrict__ planes, long pairs) {
+// planes[p * stride + i] = term p of w[i]
+__global__ void cut_planes_kernel(const float *__restrict__ w, __bf16 *__restrict__ planes, long elems, long stride) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= pairs) return;
-  const float2 v = reinterpret_cast<const float2 *>(w)[i];
+  if (i >= elems) return;
   unsigned h, m, l;
-  cut3(v.x, v.y, h, m, l);
-  planes[i] = h; planes[pairs + i] = m; planes[2 * pairs + i] = l;
+  cut3(w[i], 0.f, h, m, l);
+  unsigned short *pl = reinterpret_cast<unsigned short *>(planes);
+  pl[i] = (unsigned short)h; pl[stride + i] = (unsigned short)m; pl[2 * stride + i] = (unsigned short)l;
 }
 
 struct SplitArgs {
@@ -365,74 +372,85 @@ __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v2_kernel(const SplitA
   split_epilogue(a, acc, z, row0, wr * 64, n0 + wc * 64, fr, fh, (long)tm * 4 + wr);
 }
 
-struct Planes { __bf16 *ptr; long plane; long epoch; };
+#ifdef DF_DEV
+// development switch DF_GEMM_SPLIT_BF16: planes of weights that come without them, cut per launch into a per-(device, stream) scratch
 std::mutex g_mu;
-long g_epoch = 1;
-std::map<std::tuple<const float *, long, int>, Planes> g_cache;        // (weights, elements, device) -> planes; dev build: never freed
-std::map<std::tuple<int, hipStream_t>, Planes> g_scratch;              // (device, stream) -> planes of weights that may change: cut per launch
+std::map<std::tuple<int, hipStream_t>, std::pair<__bf16 *, long>> g_scratch;
 
-void cut(const float *w, __bf16 *planes, long elems, hipStream_t st) {
-  const long pairs = elems / 2;
-  hipLaunchKernelGGL(cut_weights_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, w, reinterpret_cast<unsigned *>(planes), pairs);
-}
-
-Planes weight_planes(const float *w, long elems, bool constant, hipStream_t st) {
+const __bf16 *scratch_planes(const float *w, long elems, hipStream_t st) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   std::lock_guard<std::mutex> g(g_mu);
-  if (!constant) {
-    Planes &sc = g_scratch[std::make_tuple(dev, st)];
-    if (sc.plane < elems) {
-      if (sc.ptr) (void)hipFree(sc.ptr);          // (synchronises the device: launches reading the old planes have finished)
-      sc = Planes{nullptr, 0, 0};
-      if (hipMalloc(reinterpret_cast<void **>(&sc.ptr), (size_t)elems * 3 * sizeof(__bf16)) != hipSuccess) return Planes{nullptr, 0, 0};
-      sc.plane = elems;
-    }
-    cut(w, sc.ptr, elems, st);                   // plane stride = elems of THIS launch (the buffer may be larger)
-    return Planes{sc.ptr, elems, 0};
+  auto &sc = g_scratch[std::make_tuple(dev, st)];
+  if (sc.second < elems) {
+    if (sc.first) (void)hipFree(sc.first);          // (synchronises the device: launches reading the old planes have finished)
+    sc = {nullptr, 0};
+    if (hipMalloc(reinterpret_cast<void **>(&sc.first), (size_t)elems * 3 * sizeof(__bf16)) != hipSuccess) return nullptr;
+    sc.second = elems;
   }
-  Planes &pl = g_cache[std::make_tuple(w, elems, dev)];
-  if (!pl.ptr) {
-    if (hipMalloc(reinterpret_cast<void **>(&pl.ptr), (size_t)elems * 3 * sizeof(__bf16)) != hipSuccess) return Planes{nullptr, 0, 0};
-    pl.plane = elems;
-    pl.epoch = 0;
-  }
-  if (pl.epoch != g_epoch) {
-    cut(w, pl.ptr, elems, st);
-    pl.epoch = g_epoch;
-  }
-  return pl;
+  cut_weight_planes(w, sc.first, elems, elems, st);
+  return sc.first;
 }
+#endif
 
 }  // namespace
 
-void split_gemm_invalidate() {
-  std::lock_guard<std::mutex> g(g_mu);
-  ++g_epoch;
+int split_route(int N, int K, int epi) {
+  // measured in the bench step (profiles/r04_experiments/README.md): from K = 384 up the 256-row form beats the fp32
+  // kernel on every engine shape (139 000 x 2 304 x 1 024: 189 against 142 TFLOP/s, 286 720 x 1 024 x 512: 175 - 185 against 136 - 141,
+  // Winograd-domain 512 x 512: 158 against 136, 286 720 x 640 x 384: 163 against 134); at K = 192 / 256 it loses or ties (99 - 121 against
+  // 118 - 128), and K <= 64 (the point layers csrc/pointfeat.hip chains) stays fp32 so that the chained and the per-layer launches agree
+  if (N <= 0 || N % SBN != 0 || K % SBK != 0 || K < 384) return 0;
+  return epi == GEMM_EPI_PLAIN || epi == GEMM_EPI_RESIDUAL || epi == GEMM_EPI_GROUPS;
+}
+
+int gemm_epi_kind(const ConvParams &p) {
+  const bool groups = p.rows_per_group > 0 || p.bias_group_ld > 0 || p.colsum;
+  if (p.res) return groups ? GEMM_EPI_OTHER : GEMM_EPI_RESIDUAL;
+  return groups ? GEMM_EPI_GROUPS : GEMM_EPI_PLAIN;
+}
+
+void cut_weight_planes(const float *w, void *planes, long elems, long stride, hipStream_t st) {
+  hipLaunchKernelGGL(cut_planes_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, w, reinterpret_cast<__bf16 *>(planes), elems, stride);
 }
 
 int try_split_gemm(const ConvParams &p, hipStream_t st) {
-  static const bool on = dev_getenv("DF_GEMM_SPLIT_BF16") != nullptr;
+  static const bool off = dev_getenv("DF_GEMM_SPLIT_OFF") != nullptr;
+  static const bool all = dev_getenv("DF_GEMM_SPLIT_BF16") != nullptr;
   static const bool verbose = dev_getenv("DF_GEMM_SPLIT_VERBOSE") != nullptr;
-  if (!on) return 0;
+  if (off || p.splitk_ws || (!p.wpl && !all)) return 0;
   const long M = (long)p.B * p.OH * p.OW;
   const int K = p.Cin;
-  const bool ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.up == 1 && p.H == p.OH && p.W == p.OW && (p.out || p.colsum) && !(p.colsum && p.res) && p.splitk <= 1 &&
-                  p.Cout % SBN == 0 && K % SBK == 0 && K >= SBK && M >= 1 && (p.rows_per_group == 0 ? p.bias_group_ld == 0 : p.rows_per_group % SBM == 0) && (p.z_wgt % 2) == 0;
-  if (verbose) fprintf(stderr, "[df-split] M=%ld N=%d K=%d z%d -> %s\n", M, p.Cout, K, p.zcount, ok ? "bf16 x 6" : "fp32");
-  if (!ok) return 0;
-  const long elems = (long)(p.zcount - 1) * p.z_wgt + (long)p.Cout * K;
-  const Planes pl = weight_planes(p.wgt, elems, p.wgt_const, st);
-  if (!pl.ptr) return 0;
+  // launch geometry the kernels cover (every engine plain GEMM: a property of the layer, not of M)
+  const bool ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.up == 1 && p.H == p.OH && p.W == p.OW && (p.out || p.colsum) &&
+                  p.Cout % SBN == 0 && K % SBK == 0 && K >= SBK && M >= 1 && gemm_epi_kind(p) != GEMM_EPI_OTHER &&
+                  (p.rows_per_group == 0 ? p.bias_group_ld == 0 : p.rows_per_group % SBM == 0) && (p.z_wgt % 8) == 0;
+  const bool take = ok && (all || split_route(p.Cout, K, gemm_epi_kind(p)));
+  if (verbose) fprintf(stderr, "[df-split] M=%ld N=%d K=%d z%d -> %s\n", M, p.Cout, K, p.zcount, take ? "bf16 x 6" : "fp32");
+  if (!take) {
+    // planes come only with routed layers: a routed layer the kernels cannot take is a caller error, not a quiet fp32 launch
+    if (p.wpl && !all) return set_error(DF_ERR_ARG, "split gemm: routed launch M=%ld N=%d K=%d outside the kernels' cover", M, p.Cout, K);
+    return 0;
+  }
+  const __bf16 *wpl = reinterpret_cast<const __bf16 *>(p.wpl);
+  long wplane = p.wpl_stride;
+#ifdef DF_DEV
+  if (!wpl) {
+    wplane = (long)(p.zcount - 1) * p.z_wgt + (long)p.Cout * K;
+    wpl = scratch_planes(p.wgt, wplane, st);
+    if (!wpl) return set_error(DF_ERR_LAUNCH, "split gemm: hipMalloc of the weight-plane scratch failed");
+  }
+#endif
   SplitArgs a{};
-  a.in = p.in; a.wpl = pl.ptr; a.bias = p.bias; a.res = p.res; a.prelu = p.prelu; a.out = p.out; a.colsum = p.colsum;
-  a.M = M; a.wplane = pl.plane; a.N = p.Cout; a.K = K; a.in_ld = p.in_ld; a.in_coff = p.in_coff; a.out_ld = p.out_ld; a.out_coff = p.out_coff;
+  a.in = p.in; a.wpl = wpl; a.bias = p.bias; a.res = p.res; a.prelu = p.prelu; a.out = p.out; a.colsum = p.colsum;
+  a.M = M; a.wplane = wplane; a.N = p.Cout; a.K = K; a.in_ld = p.in_ld; a.in_coff = p.in_coff; a.out_ld = p.out_ld; a.out_coff = p.out_coff;
   a.res_ld = p.res_ld; a.res_coff = p.res_coff; a.act = p.act; a.rows_per_group = p.rows_per_group; a.rows_valid = p.rows_valid; a.bias_group_ld = p.bias_group_ld;
   a.z_in_coff = p.z_in_coff; a.z_wgt = p.z_wgt; a.z_bias = p.z_bias; a.z_out_coff = p.z_out_coff;
   a.cs_rows = ((M + 127) / 128) * 2;
   a.tiles_n = p.Cout / SBN;
   static const int variant = dev_getenv("DF_GEMM_SPLIT_V") ? atoi(dev_getenv("DF_GEMM_SPLIT_V")) : 2;
-  // measured per shape: the 256-row form wins from K = 384 up (189 against 172 TFLOP/s on 139 000 x 2 304 x 1 024), the 128-row form below
+  // measured per shape: the 256-row form wins from K = 384 up (189 against 172 TFLOP/s on 139 000 x 2 304 x 1 024), the 128-row form below.
+  // Both add the same products in the same order per element: the choice (by K and the layer's row groups, never by M) changes no bit
   const bool v2 = variant == 2 && K >= 384 && (p.rows_per_group == 0 || p.rows_per_group % 256 == 0);
   if (v2) {
     const int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm_split_bf16_v2_kernel), 2 * V2_STAGE);
@@ -449,4 +467,3 @@ int try_split_gemm(const ConvParams &p, hipStream_t st) {
 }
 
 }  // namespace df
-#endif

@@ -392,6 +392,17 @@ int df_refiner_train_step(df_trainer *t, const float *flat_param, float *flat_gr
 int df_net_profile(df_net *net, int enable);
 int df_net_profile_read(df_net *net, double *gemm_ms, double *gemm_flops, double *gemm_useful_flops, double *gemm_bytes,
                         int *launches);
+/* df_net_profile_read covers only the launches of the fp32-MFMA kernel.  The launches the bf16 x 6 split-precision kernel took
+ * (df_gemm_route) are summed apart: df_net_profile_read_split returns their duration (ms), FLOPs (2 M N K, fp32-equivalent), useful
+ * FLOPs and count since arming, WITHOUT re-arming; call it before df_net_profile_read. */
+int df_net_profile_read_split(df_net *net, double *gemm_ms, double *gemm_flops, double *gemm_useful_flops, int *launches);
+
+/* Which kernel a plain-GEMM layer (1x1 / per-point / Winograd-domain) of a PoseNet / refiner handle runs on: 1 = fp32 on the bf16 matrix
+ * cores, operands cut into three bf16 terms, six term products (inside fp32 rounding of the exact product, not bit-identical to the fp32-MFMA
+ * summation), 0 = the fp32-MFMA kernel.  n = output channels, k = reduction length, epilogue: 0 bias / activation, 1 + residual, 2 + per-object
+ * bias and / or fused column sums, 3 anything else.  A pure function of these three: it does not depend on the rows, batch, crop size or
+ * stream of a call.  Only the handles' own weights are routed; df_conv2d_nhwc and the trainers always run fp32. */
+int df_gemm_route(int n, int k, int epilogue);
 
 /* Debug taps: with df_net_debug_taps(net, 1) armed, a single-bucket PoseNet forward keeps device copies of its named
  * intermediates (channels-last): "stem" [B][H/2][W/2][64] (conv1 + ReLU, lib/extractors.py:115-117), "layer1".."layer4",
