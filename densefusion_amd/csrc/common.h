@@ -30,5 +30,7 @@ inline const char *dev_getenv(const char *) { return nullptr; }
 
 inline hipStream_t to_stream(df_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+inline int conv_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1; }
 
 }  // namespace df

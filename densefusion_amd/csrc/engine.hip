@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "host_plan.h"
 #include "igemm.h"
 #include "layers.h"
 #include "wino.h"
@@ -23,28 +24,14 @@ namespace df {
 // ------------------------------------------------------------------------------------------------
 // parameter store
 // ------------------------------------------------------------------------------------------------
-struct ParamInfo {
-  std::string key;
-  int64_t shape[4];
-  int ndim;
-  int64_t numel() const { int64_t n = 1; for (int i = 0; i < ndim; ++i) n *= shape[i]; return n; }
-};
-
 struct Net {
   int kind = 0;   // 0 = PoseNet, 1 = PoseRefineNet
   int num_points = 0, num_obj = 0;
-  std::vector<ParamInfo> spec;
-  std::map<std::string, int> index;
+  ParamList params;                     // reference keys and shapes (host_plan.h)
   std::vector<char> loaded;
   std::map<std::string, float *> buf;   // packed device buffers by internal name
   int device = 0;
-  // profiling of GEMM launches (bench.py roofline): event pairs around every launch_conv
-  bool profiling = false;
-  std::vector<hipEvent_t> ev;
-  std::vector<double> ev_flops, ev_bytes, ev_useful;
-  std::vector<std::string> ev_desc;
-  std::vector<char> ev_bf16;           // per launch: 1 = the bf16 x 6 kernel (df_net_profile_read_split), 0 = fp32 (df_net_profile_read)
-  size_t ev_used = 0;
+  LaunchTimer timer;                    // df_net_profile (bench.py roofline): every launch_conv, bf16 x 6 launches flagged
   // bf16 x 6 weight planes (csrc/split_gemm.hip) of every buffer a routed layer reads, by the buffer's address: term p of w[i] at
   // ptr[p * stride + i].  Allocated by the first ensure_derived, cut again by the first one after any parameter load (after the PSP fold;
   // the Winograd-domain U and the tap-major copies are made at load), freed by df_net_destroy: the launch path only looks them up
@@ -62,96 +49,6 @@ struct Net {
   struct Tap { float *buf = nullptr; size_t cap = 0; int64_t shape[4] = {0, 0, 0, 0}; };
   std::map<std::string, Tap> taps;
 };
-
-static void add(Net &n, const std::string &key, std::initializer_list<int64_t> shp) {
-  ParamInfo p;
-  p.key = key;
-  p.ndim = (int)shp.size();
-  int i = 0;
-  for (auto v : shp) p.shape[i++] = v;
-  for (; i < 4; ++i) p.shape[i] = 1;
-  n.index[key] = (int)n.spec.size();
-  n.spec.push_back(p);
-}
-
-static const char *CNN = "cnn.model.module.";
-
-static void build_posenet_spec(Net &n) {
-  const std::string c = CNN;
-  add(n, c + "feats.conv1.weight", {64, 3, 7, 7});
-  int inpl = 64;
-  const int planes_of[4] = {64, 128, 256, 512};
-  for (int li = 1; li <= 4; ++li) {
-    const int planes = planes_of[li - 1];
-    for (int blk = 0; blk < 2; ++blk) {
-      const int cin = blk == 0 ? inpl : planes;
-      const std::string base = c + "feats.layer" + std::to_string(li) + "." + std::to_string(blk) + ".";
-      add(n, base + "conv1.weight", {planes, cin, 3, 3});
-      add(n, base + "conv2.weight", {planes, planes, 3, 3});
-      if (blk == 0 && cin != planes) add(n, base + "downsample.0.weight", {planes, cin, 1, 1});
-    }
-    inpl = planes;
-  }
-  for (int s = 0; s < 4; ++s) add(n, c + "psp.stages." + std::to_string(s) + ".1.weight", {512, 512, 1, 1});
-  add(n, c + "psp.bottleneck.weight", {1024, 2560, 1, 1});
-  add(n, c + "psp.bottleneck.bias", {1024});
-  const char *ups[3] = {"up_1", "up_2", "up_3"};
-  const int up_in[3] = {1024, 256, 64}, up_out[3] = {256, 64, 64};
-  for (int u = 0; u < 3; ++u) {
-    add(n, c + ups[u] + ".conv.1.weight", {up_out[u], up_in[u], 3, 3});
-    add(n, c + ups[u] + ".conv.1.bias", {up_out[u]});
-    add(n, c + ups[u] + ".conv.2.weight", {1});
-  }
-  add(n, c + "final.0.weight", {32, 64, 1, 1});
-  add(n, c + "final.0.bias", {32});
-  add(n, c + "classifier.0.weight", {256, 256});   // dead weights (lib/pspnet.py:58-62): accepted, unused
-  add(n, c + "classifier.0.bias", {256});
-  add(n, c + "classifier.2.weight", {21, 256});
-  add(n, c + "classifier.2.bias", {21});
-  const char *fn[6] = {"conv1", "conv2", "e_conv1", "e_conv2", "conv5", "conv6"};
-  const int fi[6] = {3, 64, 32, 64, 256, 512}, fo[6] = {64, 128, 64, 128, 512, 1024};
-  for (int i = 0; i < 6; ++i) {
-    add(n, std::string("feat.") + fn[i] + ".weight", {fo[i], fi[i], 1});
-    add(n, std::string("feat.") + fn[i] + ".bias", {fo[i]});
-  }
-  const int hin[3] = {1408, 640, 256}, hout[3] = {640, 256, 128};
-  const char *hs[3] = {"r", "t", "c"};
-  for (int l = 0; l < 3; ++l)
-    for (int h = 0; h < 3; ++h) {
-      const std::string nm = "conv" + std::to_string(l + 1) + "_" + hs[h];
-      add(n, nm + ".weight", {hout[l], hin[l], 1});
-      add(n, nm + ".bias", {hout[l]});
-    }
-  const int per[3] = {4, 3, 1};
-  for (int h = 0; h < 3; ++h) {
-    const std::string nm = std::string("conv4_") + hs[h];
-    add(n, nm + ".weight", {(int64_t)n.num_obj * per[h], 128, 1});
-    add(n, nm + ".bias", {(int64_t)n.num_obj * per[h]});
-  }
-}
-
-static void build_refiner_spec(Net &n) {
-  const char *fn[6] = {"conv1", "conv2", "e_conv1", "e_conv2", "conv5", "conv6"};
-  const int fi[6] = {3, 64, 32, 64, 384, 512}, fo[6] = {64, 128, 64, 128, 512, 1024};
-  for (int i = 0; i < 6; ++i) {
-    add(n, std::string("feat.") + fn[i] + ".weight", {fo[i], fi[i], 1});
-    add(n, std::string("feat.") + fn[i] + ".bias", {fo[i]});
-  }
-  const int li[2] = {1024, 512}, lo[2] = {512, 128};
-  const char *hs[2] = {"r", "t"};
-  for (int l = 0; l < 2; ++l)
-    for (int h = 0; h < 2; ++h) {
-      const std::string nm = "conv" + std::to_string(l + 1) + "_" + hs[h];
-      add(n, nm + ".weight", {lo[l], li[l]});
-      add(n, nm + ".bias", {lo[l]});
-    }
-  const int per[2] = {4, 3};
-  for (int h = 0; h < 2; ++h) {
-    const std::string nm = std::string("conv3_") + hs[h];
-    add(n, nm + ".weight", {(int64_t)n.num_obj * per[h], 128});
-    add(n, nm + ".bias", {(int64_t)n.num_obj * per[h]});
-  }
-}
 
 static float *dev_alloc(Net &n, const std::string &name, size_t floats) {
   auto it = n.buf.find(name);
@@ -186,16 +83,11 @@ __global__ void psp_fold_kernel(const float *__restrict__ wb, const float *__res
   wc[((size_t)s * 1024 + m) * 512 + i] = (float)acc;
 }
 
-static bool ends_with(const std::string &s, const char *suf) {
-  const size_t l = strlen(suf);
-  return s.size() >= l && s.compare(s.size() - l, l, suf) == 0;
-}
-
 // copies `src` (device, reference layout) into the packed store
 static int load_param(Net &n, const std::string &key, const float *src, int64_t numel) {
-  auto it = n.index.find(key);
-  if (it == n.index.end()) return set_error(DF_ERR_ARG, "load_param: unexpected key '%s'", key.c_str());
-  const ParamInfo &pi = n.spec[it->second];
+  const int at = n.params.find(key);
+  if (at < 0) return set_error(DF_ERR_ARG, "load_param: unexpected key '%s'", key.c_str());
+  const ParamInfo &pi = n.params.spec[at];
   if (numel != pi.numel())
     return set_error(DF_ERR_ARG, "load_param: size mismatch for %s: got %lld elements, expected %lld", key.c_str(),
                      (long long)numel, (long long)pi.numel());
@@ -285,7 +177,7 @@ static int load_param(Net &n, const std::string &key, const float *src, int64_t 
     if (e == hipSuccess) e = copy2d(we + 64, 192, w5 + 256, 384, 128, 512);
   }
   if (e != hipSuccess) return set_error(DF_ERR_LAUNCH, "load_param(%s): %s", key.c_str(), hipGetErrorString(e));
-  n.loaded[it->second] = 1;
+  n.loaded[at] = 1;
   // the folded PSP matrices depend on five tensors: rebuilt once, by the next forward call (ensure_derived), not per key
   if (n.kind == 0 && key.find(".psp.") != std::string::npos && !ends_with(key, ".bias")) n.psp_dirty = true;
   return DF_OK;
@@ -304,7 +196,7 @@ static std::vector<GemmWeight> gemm_weights(const Net &n) {
     v.push_back({P + "up_1.conv.1.weight.tm", 9 * 256, 1024, GEMM_EPI_PLAIN});
     v.push_back({P + "up_2.conv.1.weight.tm", 9 * 64, 256, GEMM_EPI_PLAIN});
     v.push_back({P + "up_3.conv.1.weight", 64, 576, GEMM_EPI_PLAIN});
-    for (const ParamInfo &pi : n.spec)
+    for (const ParamInfo &pi : n.params.spec)
       if (pi.key.find("feats.layer") != std::string::npos && pi.ndim == 4) {
         const int O = (int)pi.shape[0], I = (int)pi.shape[1];
         if (pi.shape[2] * pi.shape[3] == 1) v.push_back({pi.key, O, I, GEMM_EPI_PLAIN});          // downsample.0 (1x1)
@@ -333,8 +225,8 @@ static std::vector<GemmWeight> gemm_weights(const Net &n) {
 static long buffer_elems(const Net &n, const std::string &name) {
   const std::string P = CNN;
   auto spec_of = [&](const std::string &key) -> const ParamInfo * {
-    auto it = n.index.find(key);
-    return it == n.index.end() ? nullptr : &n.spec[it->second];
+    const int at = n.params.find(key);
+    return at < 0 ? nullptr : &n.params.spec[at];
   };
   if (name == "psp.fold.w") return 4L * 1024 * 512;
   if (name == "psp.fold.wfeat") return 1024L * 512;
@@ -406,32 +298,20 @@ static int ensure_derived(Net &n) {
 
 static int check_ready(const Net &n0) {
   Net &n = const_cast<Net &>(n0);
-  for (size_t i = 0; i < n.spec.size(); ++i)
-    if (!n.loaded[i]) return set_error(DF_ERR_STATE, "parameter '%s' was never loaded", n.spec[i].key.c_str());
+  for (size_t i = 0; i < n.params.spec.size(); ++i)
+    if (!n.loaded[i]) return set_error(DF_ERR_STATE, "parameter '%s' was never loaded", n.params.spec[i].key.c_str());
   return ensure_derived(n);
 }
 
 // ------------------------------------------------------------------------------------------------
 // forward plumbing
 // ------------------------------------------------------------------------------------------------
-struct Ctx {
+// one forward call: the workspace arena (host_plan.h; scratch regions are released and reused, see conv3x3) and the net's launch stream
+struct Ctx : Arena {
   Net *net;
   hipStream_t st;
-  bool dry;          // dry run: only measure the workspace
-  char *base;
-  size_t off = 0, cap = 0, peak = 0;   // peak: high-water mark (scratch regions are released and reused, see wino_conv)
-  int err = DF_OK;
 
-  float *f(size_t floats) { return reinterpret_cast<float *>(bytes(floats * sizeof(float))); }
-  void *bytes(size_t b) {
-    b = (b + 255) & ~size_t(255);
-    void *p = dry ? nullptr : base + off;
-    off += b;
-    if (off > peak) peak = off;
-    if (!dry && off > cap && err == DF_OK) err = set_error(DF_ERR_WORKSPACE, "workspace too small: need > %zu bytes, have %zu", off, cap);
-    return p;
-  }
-  bool live() const { return !dry && err == DF_OK; }
+  Ctx(Net *n, hipStream_t s, Arena a = Arena()) : Arena(a), net(n), st(s) {}
   const float *w(const std::string &name) {
     auto it = net->buf.find(name);
     if (it == net->buf.end()) {
@@ -461,13 +341,9 @@ struct Ctx {
   void conv(const ConvParams &p, double useful = 1.0) {
     if (!live()) return;
     Net &n = *net;
-    if (n.profiling) {
-      if (n.ev_used + 2 > n.ev.size()) {
-        const size_t old = n.ev.size();
-        n.ev.resize(old + 256);
-        for (size_t i = old; i < n.ev.size(); ++i) hipEventCreate(&n.ev[i]);
-      }
-      hipEventRecord(n.ev[n.ev_used], st);
+    if (n.timer.on) {
+      fail(n.timer.begin(st));
+      if (!live()) return;
     }
     ConvParams pc = p;
     if (p.KH * p.KW == 1 && split_route(p.Cout, p.Cin, gemm_epi_kind(p))) {
@@ -488,17 +364,12 @@ struct Ctx {
     }
     int on_bf16 = 0;
     const int rc = launch_conv(pc, st, nullptr, &on_bf16);
-    if (n.profiling) {
-      hipEventRecord(n.ev[n.ev_used + 1], st);
-      n.ev_flops.push_back(conv_flops(p));
-      n.ev_bytes.push_back(conv_bytes(p));
-      n.ev_useful.push_back(conv_flops(p) * useful);
-      char d[160];
-      snprintf(d, sizeof(d), "M=%ld N=%d K=%d k%dx%d s%d d%d z%d", (long)p.B * p.OH * p.OW, p.Cout, p.KH * p.KW * p.Cin, p.KH,
-               p.KW, p.stride, p.dil, p.zcount);
-      n.ev_desc.push_back(d);
-      n.ev_bf16.push_back((char)on_bf16);
-      n.ev_used += 2;
+    if (n.timer.on) {
+      LaunchRecord r = launch_record(0, conv_flops(p), p);
+      r.bytes = conv_bytes(p);
+      r.useful = r.flops * useful;
+      r.bf16 = on_bf16 != 0;
+      n.timer.end(st, r);
     }
     if (rc != DF_OK) err = rc;
   }
@@ -544,8 +415,6 @@ static ConvParams conv2d(const float *in, int B, int H, int W, int cin, int in_l
   return p;
 }
 
-static inline int conv_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1; }
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 struct PoseNetOut {
   float *out_r, *out_t, *out_c, *emb;   // caller buffers
@@ -557,14 +426,6 @@ struct PoseNetOut {
 // per-point part) runs ONCE over the rows of all buckets; only the direct kxk convolutions and the memory-bound glue kernels
 // (transforms, pooling, interpolation) are launched per bucket, writing into / reading from the shared row-concatenated buffers.
 struct Grp { int B, H, W; const float *img; };
-
-// per-bucket map sizes and row offsets of one resolution level of the concatenated activations
-struct Level {
-  std::vector<int> h, w;
-  std::vector<long> off;     // first pixel row of bucket i
-  long rows = 0;
-  void push(int B, int hh, int ww) { h.push_back(hh); w.push_back(ww); off.push_back(rows); rows += (long)B * hh * ww; }
-};
 
 // PSPNet colour branch (lib/pspnet.py:64-77 on top of lib/extractors.py:114-124) up to up_2's output: returns the concatenated
 // half-resolution 64-channel maps and their level
@@ -584,10 +445,10 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
       const Grp &g = gs[i];
       float *img4 = c.f((size_t)g.B * g.H * g.W * 4);
       if (c.live()) launch_nchw3_to_nhwc4(g.img, img4, g.B, g.H, g.W, c.st);
-      float *stem = c.f((size_t)g.B * l0.h[i] * l0.w[i] * 64);
-      c.conv(conv2d(img4, g.B, g.H, g.W, 4, 4, c.w(P + "feats.conv1.weight"), nullptr, stem, l0.h[i], l0.w[i], 64, 64, 0, 7, 2, 3, 1, ACT_RELU));
-      if (c.live()) launch_maxpool3s2(stem, x + l1.off[i] * 64, g.B, l0.h[i], l0.w[i], 64, l1.h[i], l1.w[i], c.st);
-      if (nb == 1) c.tap("stem", stem, g.B, l0.h[i], l0.w[i], 64);
+      float *stem = c.f((size_t)g.B * l0.H[i] * l0.W[i] * 64);
+      c.conv(conv2d(img4, g.B, g.H, g.W, 4, 4, c.w(P + "feats.conv1.weight"), nullptr, stem, l0.H[i], l0.W[i], 64, 64, 0, 7, 2, 3, 1, ACT_RELU));
+      if (c.live()) launch_maxpool3s2(stem, x + l1.off[i] * 64, g.B, l0.H[i], l0.W[i], 64, l1.H[i], l1.W[i], c.st);
+      if (nb == 1) c.tap("stem", stem, g.B, l0.H[i], l0.W[i], 64);
     }
     c.off = mark;
     (void)mark;
@@ -599,9 +460,9 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
                      const float *res) {
     std::vector<int> ws[2];        // buckets on the F(2x2) / F(4x4) route
     for (int i = 0; i < nb; ++i) {
-      const int route = stride == 1 ? wino_route_for(li.h[i], li.w[i], dil, ci, co) : 0;
+      const int route = stride == 1 ? wino_route_for(li.H[i], li.W[i], dil, ci, co) : 0;
       if (route) { ws[route == 4].push_back(i); continue; }
-      ConvParams p = conv2d(in + li.off[i] * ci, gs[i].B, li.h[i], li.w[i], ci, ci, c.w(key), nullptr, out + lo.off[i] * co, lo.h[i], lo.w[i], co,
+      ConvParams p = conv2d(in + li.off[i] * ci, gs[i].B, li.H[i], li.W[i], ci, ci, c.w(key), nullptr, out + lo.off[i] * co, lo.H[i], lo.W[i], co,
                             co, 0, 3, stride, dil, dil, ACT_RELU);
       if (res) { p.res = res + lo.off[i] * co; p.res_ld = co; }
       c.conv(p);
@@ -611,13 +472,13 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
       const int m = r ? 4 : 2, nz = (m + 2) * (m + 2);
       std::vector<long> t0;
       long T = 0;
-      for (int i : ws[r]) { t0.push_back(T); T += wino_geom(gs[i].B, li.h[i], li.w[i], dil, m).T; }
+      for (int i : ws[r]) { t0.push_back(T); T += wino_geom(gs[i].B, li.H[i], li.W[i], dil, m).T; }
       const size_t mark = c.off;       // V / M are scratch: consecutive layers reuse the same region
       float *V = c.f((size_t)nz * T * ci), *M = c.f((size_t)nz * T * co);
       // per-bucket tables of the transforms: F(4x4) runs all buckets of the route in one launch (a workgroup belongs to one bucket)
       std::vector<int> tB, tH, tW;
       std::vector<long> trow;
-      for (int i : ws[r]) { tB.push_back(gs[i].B); tH.push_back(li.h[i]); tW.push_back(li.w[i]); trow.push_back(li.off[i]); }
+      for (int i : ws[r]) { tB.push_back(gs[i].B); tH.push_back(li.H[i]); tW.push_back(li.W[i]); trow.push_back(li.off[i]); }
       const int nw = (int)ws[r].size();
       static const bool per_bucket = df::dev_getenv("DF_WINO_PER_BUCKET") != nullptr;       // dev switch: one transform launch per bucket (A/B)
       if (m == 4 && !per_bucket) {
@@ -625,13 +486,13 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
       } else {
         for (size_t j = 0; j < ws[r].size(); ++j) {
           const int i = ws[r][j];
-          if (c.live()) launch_wino_input(in + li.off[i] * ci, ci, 0, V, gs[i].B, li.h[i], li.w[i], ci, dil, c.st, T, t0[j], m);
+          if (c.live()) launch_wino_input(in + li.off[i] * ci, ci, 0, V, gs[i].B, li.H[i], li.W[i], ci, dil, c.st, T, t0[j], m);
         }
       }
       ConvParams p = point_gemm(V, ci, 0, ci, c.w(key + (r ? ".wino4" : ".wino")), nullptr, M, co, 0, co, (int)T, ACT_NONE);
       p.zcount = nz; p.z_in_coff = T * ci; p.z_wgt = (long)co * ci; p.z_out_coff = T * co;
       double px = 0;        // output pixels the tiles are for: a tile yields m x m of them
-      for (int i : ws[r]) px += (double)gs[i].B * li.h[i] * li.w[i];
+      for (int i : ws[r]) px += (double)gs[i].B * li.H[i] * li.W[i];
       c.conv(p, px / ((double)(m * m) * (double)T));
       if (m == 4 && !per_bucket) {           // (stride-1 layers: input and output levels have the same rows)
         if (c.live()) launch_wino4_output_multi(M, out, co, res, co, ACT_RELU, nw, tB.data(), tH.data(), tW.data(), trow.data(), t0.data(), co, dil, T, c.st);
@@ -639,7 +500,7 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
         for (size_t j = 0; j < ws[r].size(); ++j) {
           const int i = ws[r][j];
           if (c.live())
-            launch_wino_output(M, out + lo.off[i] * co, co, 0, nullptr, res ? res + lo.off[i] * co : nullptr, co, 0, ACT_RELU, gs[i].B, li.h[i], li.w[i],
+            launch_wino_output(M, out + lo.off[i] * co, co, 0, nullptr, res ? res + lo.off[i] * co : nullptr, co, 0, ACT_RELU, gs[i].B, li.H[i], li.W[i],
                                co, dil, c.st, T, t0[j], m);
         }
       }
@@ -654,7 +515,7 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
     const int planes = planes_of[li - 1], s = stride_of[li - 1], d = dil_of[li - 1];
     const std::string base = P + "feats.layer" + std::to_string(li) + ".";
     Level lo;
-    for (int i = 0; i < nb; ++i) lo.push(gs[i].B, conv_out(lx.h[i], 3, s, 1, 1), conv_out(lx.w[i], 3, s, 1, 1));
+    for (int i = 0; i < nb; ++i) lo.push(gs[i].B, conv_out(lx.H[i], 3, s, 1, 1), conv_out(lx.W[i], 3, s, 1, 1));
     // block 0: built without dilation (lib/extractors.py:107); carries the stride and the 1x1 downsample
     float *t = c.f((size_t)lo.rows * planes);
     conv3x3(x, lx, cin, base + "0.conv1.weight", t, lo, planes, s, 1, nullptr);
@@ -665,8 +526,8 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
         c.conv(point_gemm(x, cin, 0, cin, c.w(base + "0.downsample.0.weight"), nullptr, ds, planes, 0, planes, (int)lo.rows, ACT_NONE));
       } else {
         for (int i = 0; i < nb; ++i)
-          c.conv(conv2d(x + lx.off[i] * cin, gs[i].B, lx.h[i], lx.w[i], cin, cin, c.w(base + "0.downsample.0.weight"), nullptr, ds + lo.off[i] * planes,
-                        lo.h[i], lo.w[i], planes, planes, 0, 1, s, 0, 1, ACT_NONE));
+          c.conv(conv2d(x + lx.off[i] * cin, gs[i].B, lx.H[i], lx.W[i], cin, cin, c.w(base + "0.downsample.0.weight"), nullptr, ds + lo.off[i] * planes,
+                        lo.H[i], lo.W[i], planes, planes, 0, 1, s, 0, 1, ACT_NONE));
       }
       res = ds;
     }
@@ -678,7 +539,7 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
     float *o1 = c.f((size_t)lo.rows * planes);
     conv3x3(t1, lo, planes, base + "1.conv2.weight", o1, lo, planes, 1, d, o0);
     x = o1; lx = lo; cin = planes;
-    if (nb == 1) c.tap(("layer" + std::to_string(li)).c_str(), x, gs[0].B, lx.h[0], lx.w[0], planes);
+    if (nb == 1) c.tap(("layer" + std::to_string(li)).c_str(), x, gs[0].B, lx.H[0], lx.W[0], planes);
   }
   // PSP module (lib/pspnet.py:20-24) with the bottleneck folded through the pyramid:
   //   bottleneck(cat(up(W_s pool_s(f)), f)) = W_b[:,2048:] f + sum_s up((W_b[:,512s:512s+512] W_s) pool_s(f)) + b
@@ -689,11 +550,11 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
   for (int i = 0; i < nb; ++i) {
     const int B = gs[i].B;
     float *pooled = c.f((size_t)4 * B * 36 * 512), *zst = c.f((size_t)4 * B * 36 * 1024);
-    if (c.live()) launch_psp_pool(x + lx.off[i] * 512, 512, 0, pooled, B, lx.h[i], lx.w[i], 512, c.st);
+    if (c.live()) launch_psp_pool(x + lx.off[i] * 512, 512, 0, pooled, B, lx.H[i], lx.W[i], 512, c.st);
     ConvParams p = point_gemm(pooled, 512, 0, 512, c.w("psp.fold.w"), nullptr, zst, 1024, 0, 1024, B * 36, ACT_NONE);
     p.zcount = 4; p.z_in_coff = (long)B * 36 * 512; p.z_wgt = 1024 * 512; p.z_out_coff = (long)B * 36 * 1024;
     c.conv(p);
-    if (c.live()) launch_psp_prior_sum(zst, prior + lx.off[i] * 1024, B, lx.h[i], lx.w[i], 1024, c.st);
+    if (c.live()) launch_psp_prior_sum(zst, prior + lx.off[i] * 1024, B, lx.H[i], lx.W[i], 1024, c.st);
   }
   float *psp = c.f((size_t)lx.rows * 1024);
   {
@@ -701,7 +562,7 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
     p.res = prior; p.res_ld = 1024;
     c.conv(p);
   }
-  if (nb == 1) c.tap("psp", psp, gs[0].B, lx.h[0], lx.w[0], 1024);
+  if (nb == 1) c.tap("psp", psp, gs[0].B, lx.H[0], lx.W[0], 1024);
   // PSPUpsample stages up_1, up_2 (lib/pspnet.py:27-37,69-73; dropout = identity in eval), each as a low-resolution
   // GEMM with N = 9*Cout (one launch for all buckets) followed by the per-bucket 9-tap interpolation (layers.hip).  up_3 is NOT run
   // here: its output is read at the chosen pixels only, so the caller evaluates it there from the maps returned: [B][h][w][64].
@@ -716,18 +577,18 @@ static float *cnn_forward(Ctx &c, const std::vector<Grp> &gs, Level &half_lv) {
     c.conv(point_gemm(cur, up_in[u], 0, up_in[u], c.w(P + ups[u] + ".conv.1.weight.tm"), nullptr, y, 9 * up_out[u], 0, 9 * up_out[u], (int)lx.rows,
                       ACT_NONE));
     Level lo;
-    for (int i = 0; i < nb; ++i) lo.push(gs[i].B, 2 * lx.h[i], 2 * lx.w[i]);
+    for (int i = 0; i < nb; ++i) lo.push(gs[i].B, 2 * lx.H[i], 2 * lx.W[i]);
     for (int i = 0; i < nb; ++i)
       if (c.live()) {
         const int rc = launch_upconv_gather(y + lx.off[i] * 9 * up_out[u], c.w(P + ups[u] + ".conv.1.bias"), c.w(P + ups[u] + ".conv.2.weight"),
-                                            o + lo.off[i] * up_out[u], gs[i].B, lx.h[i], lx.w[i], up_out[u], c.st);
+                                            o + lo.off[i] * up_out[u], gs[i].B, lx.H[i], lx.W[i], up_out[u], c.st);
         if (rc != DF_OK) c.err = rc;
       }
     c.off = keep;        // the tap products are dead once interpolated
     (void)mark;
     lx = lo;
     cur = o;
-    if (nb == 1) c.tap(ups[u], cur, gs[0].B, lx.h[0], lx.w[0], up_out[u]);
+    if (nb == 1) c.tap(ups[u], cur, gs[0].B, lx.H[0], lx.W[0], up_out[u]);
   }
   half_lv = lx;
   return cur;
@@ -778,12 +639,12 @@ static void posenet_points(Ctx &c, int B, int N, int Npad, const float *cloud, c
     const float *w1 = c.w("head1.wpt"), *w2 = c.w("head2.w"), *b2 = c.w("head2.bias"), *w3 = c.w("head3.w"), *b3 = c.w("head3.bias");
     if (c.err != DF_OK) return;
     {
-      ConvParams p = point_gemm(pf, 384, 0, 384, c.dry ? nullptr : w1 + (size_t)2 * 640 * 384, c.dry ? nullptr : gbias + 1280, h1c, 640, 0, 640, rows, ACT_RELU);
+      ConvParams p = point_gemm(pf, 384, 0, 384, w1 + (size_t)2 * 640 * 384, gbias + 1280, h1c, 640, 0, 640, rows, ACT_RELU);
       p.rows_per_group = Npad; p.rows_valid = N; p.bias_group_ld = 1920;
       c.pconv(p);
     }
-    c.pconv(point_gemm(h1c, 640, 0, 640, c.dry ? nullptr : w2 + (size_t)2 * 256 * 640, c.dry ? nullptr : b2 + 512, h2c, 256, 0, 256, rows, ACT_RELU));
-    c.pconv(point_gemm(h2c, 256, 0, 256, c.dry ? nullptr : w3 + (size_t)2 * 128 * 256, c.dry ? nullptr : b3 + 256, h3c, 128, 0, 128, rows, ACT_RELU));
+    c.pconv(point_gemm(h1c, 640, 0, 640, w2 + (size_t)2 * 256 * 640, b2 + 512, h2c, 256, 0, 256, rows, ACT_RELU));
+    c.pconv(point_gemm(h2c, 256, 0, 256, w3 + (size_t)2 * 128 * 256, b3 + 256, h3c, 128, 0, 128, rows, ACT_RELU));
     if (c.live())
       launch_head_select(h3c, c.w("conv4_c.weight"), c.w("conv4_c.bias"), pf, gbias, w1, w2, b2, w3, b3, c.w("conv4_r.weight"),
                          c.w("conv4_r.bias"), c.w("conv4_t.weight"), c.w("conv4_t.bias"), obj, n.num_obj, cloud, B, N, Npad, conf, sel->pose_wo,
@@ -828,7 +689,7 @@ static void posenet_forward(Ctx &c, const std::vector<Grp> &gs, const float *clo
     long b0 = 0;
     for (size_t i = 0; i < gs.size(); ++i) {
       if (c.live())
-        launch_up3_patches(half + hl.off[i] * 64, choose + b0 * N, patch + (size_t)b0 * Npad * 576, gs[i].B, hl.h[i], hl.w[i], N, Npad, c.st);
+        launch_up3_patches(half + hl.off[i] * 64, choose + b0 * N, patch + (size_t)b0 * Npad * 576, gs[i].B, hl.H[i], hl.W[i], N, Npad, c.st);
       b0 += gs[i].B;
     }
   }
@@ -933,8 +794,8 @@ extern "C" df_net *df_posenet_create(int num_points, int num_obj) {
   Net *n = new Net();
   n->kind = 0; n->num_points = num_points; n->num_obj = num_obj;
   hipGetDevice(&n->device);
-  build_posenet_spec(*n);
-  n->loaded.assign(n->spec.size(), 0);
+  n->params = reference_params(0, num_obj);
+  n->loaded.assign(n->params.spec.size(), 0);
   return reinterpret_cast<df_net *>(n);
 }
 
@@ -943,8 +804,8 @@ extern "C" df_net *df_refiner_create(int num_points, int num_obj) {
   Net *n = new Net();
   n->kind = 1; n->num_points = num_points; n->num_obj = num_obj;
   hipGetDevice(&n->device);
-  build_refiner_spec(*n);
-  n->loaded.assign(n->spec.size(), 0);
+  n->params = reference_params(1, num_obj);
+  n->loaded.assign(n->params.spec.size(), 0);
   return reinterpret_cast<df_net *>(n);
 }
 
@@ -955,21 +816,14 @@ extern "C" void df_net_destroy(df_net *h) {
   for (auto &kv : n->buf) hipFree(kv.second);
   if (n->stage) hipFree(n->stage);
   for (auto &kv : n->taps) if (kv.second.buf) hipFree(kv.second.buf);
-  for (auto e : n->ev) hipEventDestroy(e);
   delete n;
 }
 
-extern "C" int df_net_num_params(const df_net *h) { return h ? (int)as_net(h)->spec.size() : 0; }
+extern "C" int df_net_num_params(const df_net *h) { return h ? (int)as_net(h)->params.spec.size() : 0; }
 
 extern "C" int df_net_param_info(const df_net *h, int i, char *key_out, int key_cap, int64_t *shape4, int *ndim) {
   if (!h) return set_error(DF_ERR_ARG, "param_info: null handle");
-  const Net *n = as_net(h);
-  if (i < 0 || i >= (int)n->spec.size()) return set_error(DF_ERR_ARG, "param_info: index out of range");
-  const ParamInfo &p = n->spec[i];
-  if (key_out && key_cap > 0) { strncpy(key_out, p.key.c_str(), key_cap - 1); key_out[key_cap - 1] = 0; }
-  if (shape4) for (int d = 0; d < 4; ++d) shape4[d] = p.shape[d];
-  if (ndim) *ndim = p.ndim;
-  return DF_OK;
+  return as_net(h)->params.info(i, key_out, key_cap, shape4, ndim, "param_info");
 }
 
 extern "C" int df_net_load_param(df_net *h, const char *key, const float *ptr, int64_t numel) {
@@ -980,14 +834,7 @@ extern "C" int df_net_load_param(df_net *h, const char *key, const float *ptr, i
 
 extern "C" int df_net_profile(df_net *h, int enable) {
   if (!h) return set_error(DF_ERR_ARG, "profile: null handle");
-  Net *n = as_net(h);
-  n->profiling = enable != 0;
-  n->ev_used = 0;
-  n->ev_flops.clear();
-  n->ev_bytes.clear();
-  n->ev_useful.clear();
-  n->ev_desc.clear();
-  n->ev_bf16.clear();
+  as_net(h)->timer.arm(enable != 0);
   return DF_OK;
 }
 
@@ -996,57 +843,30 @@ extern "C" int df_net_profile(df_net *h, int enable) {
 extern "C" int df_net_profile_read(df_net *h, double *gemm_ms, double *gemm_flops, double *gemm_useful_flops, double *gemm_bytes,
                                    int *launches) {
   if (!h) return set_error(DF_ERR_ARG, "profile_read: null handle");
-  Net *n = as_net(h);
-  double ms = 0, fl = 0, by = 0, us = 0;
-  int cnt = 0;
-  static const bool verbose = df::dev_getenv("DF_PROFILE_VERBOSE") != nullptr;
-  for (size_t i = 0; i + 1 < n->ev_used; i += 2) {
-    float t = 0;
-    if (hipEventElapsedTime(&t, n->ev[i], n->ev[i + 1]) != hipSuccess) return set_error(DF_ERR_LAUNCH, "profile_read: events not complete");
-    if (verbose && n->ev_bf16[i / 2])
-      fprintf(stderr, "[df-gemm-bf16] %s  %.1f us  %.1f TFLOP/s\n", n->ev_desc[i / 2].c_str(), t * 1e3, n->ev_flops[i / 2] / t / 1e9);
-    if (n->ev_bf16[i / 2]) continue;
-    ++cnt;
-    ms += t;
-    fl += n->ev_flops[i / 2];
-    by += n->ev_bytes[i / 2];
-    us += n->ev_useful[i / 2];
-    if (verbose)
-      fprintf(stderr, "[df-gemm] %s  %.1f us  %.1f TFLOP/s\n", n->ev_desc[i / 2].c_str(), t * 1e3, n->ev_flops[i / 2] / t / 1e9);
-  }
-  if (gemm_ms) *gemm_ms = ms;
-  if (gemm_flops) *gemm_flops = fl;
-  if (gemm_useful_flops) *gemm_useful_flops = us;
-  if (gemm_bytes) *gemm_bytes = by;
-  if (launches) *launches = cnt;
-  n->ev_used = 0;
-  n->ev_flops.clear();
-  n->ev_bytes.clear();
-  n->ev_useful.clear();
-  n->ev_desc.clear();
-  n->ev_bf16.clear();
+  LaunchTimer &tm = as_net(h)->timer;
+  LaunchSum s[2];
+  static const char *const tags[2] = {"[df-gemm]", "[df-gemm-bf16]"};
+  const int rc = tm.sum(s, [](const LaunchRecord &r) { return (int)r.bf16; }, tags, "profile_read");
+  if (rc != DF_OK) return rc;
+  if (gemm_ms) *gemm_ms = s[0].ms;
+  if (gemm_flops) *gemm_flops = s[0].flops;
+  if (gemm_useful_flops) *gemm_useful_flops = s[0].useful;
+  if (gemm_bytes) *gemm_bytes = s[0].bytes;
+  if (launches) *launches = s[0].launches;
+  tm.rec.clear();                    // re-arm
   return DF_OK;
 }
 
 // after a stream sync: the same sums over the bf16 x 6 launches since df_net_profile(1); does not re-arm
 extern "C" int df_net_profile_read_split(df_net *h, double *gemm_ms, double *gemm_flops, double *gemm_useful_flops, int *launches) {
   if (!h) return set_error(DF_ERR_ARG, "profile_read_split: null handle");
-  Net *n = as_net(h);
-  double ms = 0, fl = 0, us = 0;
-  int cnt = 0;
-  for (size_t i = 0; i + 1 < n->ev_used; i += 2) {
-    if (!n->ev_bf16[i / 2]) continue;
-    float t = 0;
-    if (hipEventElapsedTime(&t, n->ev[i], n->ev[i + 1]) != hipSuccess) return set_error(DF_ERR_LAUNCH, "profile_read_split: events not complete");
-    ms += t;
-    fl += n->ev_flops[i / 2];
-    us += n->ev_useful[i / 2];
-    ++cnt;
-  }
-  if (gemm_ms) *gemm_ms = ms;
-  if (gemm_flops) *gemm_flops = fl;
-  if (gemm_useful_flops) *gemm_useful_flops = us;
-  if (launches) *launches = cnt;
+  LaunchSum s;
+  const int rc = as_net(h)->timer.sum(&s, [](const LaunchRecord &r) { return r.bf16 ? 0 : -1; }, nullptr, "profile_read_split");
+  if (rc != DF_OK) return rc;
+  if (gemm_ms) *gemm_ms = s.ms;
+  if (gemm_flops) *gemm_flops = s.flops;
+  if (gemm_useful_flops) *gemm_useful_flops = s.useful;
+  if (launches) *launches = s.launches;
   return DF_OK;
 }
 
@@ -1106,7 +926,7 @@ static int make_groups(const Net *n, int nb, const int *B, const int *H, const i
 
 extern "C" size_t df_posenet_workspace_bytes(const df_net *h, int B, int H, int W) {
   if (posenet_args_ok(as_net(h), B, H, W) != DF_OK) return 0;
-  Ctx c{const_cast<Net *>(as_net(h)), nullptr, true, nullptr};
+  Ctx c(const_cast<Net *>(as_net(h)), nullptr);
   PoseNetOut o{};
   posenet_forward(c, {Grp{B, H, W, nullptr}}, nullptr, nullptr, nullptr, o);
   return c.peak;
@@ -1119,8 +939,7 @@ extern "C" int df_posenet_forward(df_net *h, int B, int H, int W, const float *i
   if (rc != DF_OK) return rc;
   if ((rc = check_ready(*as_net(h))) != DF_OK) return rc;
   if (!img || !cloud || !choose || !obj || !out_r || !out_t || !out_c || !emb || !ws) return set_error(DF_ERR_ARG, "posenet_forward: null pointer");
-  Ctx c{as_net(h), to_stream(stream), false, static_cast<char *>(ws)};
-  c.cap = ws_bytes;
+  Ctx c(as_net(h), to_stream(stream), Arena(ws, ws_bytes));
   if (df_posenet_workspace_bytes(h, B, H, W) > ws_bytes) return set_error(DF_ERR_WORKSPACE, "posenet_forward: workspace too small");
   PoseNetOut o{out_r, out_t, out_c, emb};
   posenet_forward(c, {Grp{B, H, W, img}}, cloud, choose, obj, o);
@@ -1132,7 +951,7 @@ extern "C" int df_posenet_forward(df_net *h, int B, int H, int W, const float *i
 extern "C" size_t df_posenet_multi_workspace_bytes(const df_net *h, int nb, const int *B, const int *H, const int *W) {
   std::vector<Grp> gs;
   if (!h || as_net(h)->kind != 0 || make_groups(as_net(h), nb, B, H, W, nullptr, gs) != DF_OK) return 0;
-  Ctx c{const_cast<Net *>(as_net(h)), nullptr, true, nullptr};
+  Ctx c(const_cast<Net *>(as_net(h)), nullptr);
   PoseNetOut o{};
   posenet_forward(c, gs, nullptr, nullptr, nullptr, o);
   return c.peak;
@@ -1149,8 +968,7 @@ extern "C" int df_posenet_forward_multi(df_net *h, int nb, const int *B, const i
   if ((rc = check_ready(*as_net(h))) != DF_OK) return rc;
   if (!cloud || !choose || !obj || !out_r || !out_t || !out_c || !emb || !ws) return set_error(DF_ERR_ARG, "posenet_forward_multi: null pointer");
   if (df_posenet_multi_workspace_bytes(h, nb, B, H, W) > ws_bytes) return set_error(DF_ERR_WORKSPACE, "posenet_forward_multi: workspace too small");
-  Ctx c{as_net(h), to_stream(stream), false, static_cast<char *>(ws)};
-  c.cap = ws_bytes;
+  Ctx c(as_net(h), to_stream(stream), Arena(ws, ws_bytes));
   PoseNetOut o{out_r, out_t, out_c, emb};
   posenet_forward(c, gs, cloud, choose, obj, o);
   return finish(c, "posenet_forward_multi");
@@ -1167,7 +985,7 @@ static void refiner_standalone(Ctx &c, int B, const float *x, const float *emb, 
 
 extern "C" size_t df_refiner_workspace_bytes(const df_net *h, int B) {
   if (!h || as_net(h)->kind != 1 || B <= 0) return 0;
-  Ctx c{const_cast<Net *>(as_net(h)), nullptr, true, nullptr};
+  Ctx c(const_cast<Net *>(as_net(h)), nullptr);
   refiner_standalone(c, B, nullptr, nullptr, nullptr, nullptr, nullptr);
   return c.peak;
 }
@@ -1180,8 +998,7 @@ extern "C" int df_refiner_forward(df_net *h, int B, const float *x, const float 
   if (rc != DF_OK) return rc;
   if (!x || !emb || !obj || !out_r || !out_t || !ws) return set_error(DF_ERR_ARG, "refiner_forward: null pointer");
   if (df_refiner_workspace_bytes(h, B) > ws_bytes) return set_error(DF_ERR_WORKSPACE, "refiner_forward: workspace too small");
-  Ctx c{as_net(h), to_stream(stream), false, static_cast<char *>(ws)};
-  c.cap = ws_bytes;
+  Ctx c(as_net(h), to_stream(stream), Arena(ws, ws_bytes));
   refiner_standalone(c, B, x, emb, obj, out_r, out_t);
   return finish(c, "refiner_forward");
 }
@@ -1221,7 +1038,7 @@ static int estimate_handles_ok(const df_net *pn, const df_net *rf) {
 extern "C" size_t df_estimate_multi_workspace_bytes(const df_net *pn, const df_net *rf, int nb, const int *B, const int *H, const int *W) {
   std::vector<Grp> gs;
   if (estimate_handles_ok(pn, rf) != DF_OK || make_groups(as_net(pn), nb, B, H, W, nullptr, gs) != DF_OK) return 0;
-  Ctx cp{const_cast<Net *>(as_net(pn)), nullptr, true, nullptr}, cr{const_cast<Net *>(as_net(rf)), nullptr, true, nullptr};
+  Ctx cp(const_cast<Net *>(as_net(pn)), nullptr), cr(const_cast<Net *>(as_net(rf)), nullptr);
   estimate(cp, cr, gs, nullptr, nullptr, nullptr, 1, nullptr, nullptr);
   return cr.peak;
 }
@@ -1238,8 +1055,7 @@ extern "C" int df_estimate_poses_multi(df_net *pn, df_net *rf, int nb, const int
   if ((rc = check_ready(*as_net(pn))) != DF_OK || (rc = check_ready(*as_net(rf))) != DF_OK) return rc;
   if (!cloud || !choose || !obj || !pose || !ws) return set_error(DF_ERR_ARG, "estimate_poses: null pointer");
   if (df_estimate_multi_workspace_bytes(pn, rf, nb, B, H, W) > ws_bytes) return set_error(DF_ERR_WORKSPACE, "estimate_poses: workspace too small");
-  Ctx cp{as_net(pn), to_stream(stream), false, static_cast<char *>(ws)}, cr{as_net(rf), to_stream(stream), false, static_cast<char *>(ws)};
-  cp.cap = cr.cap = ws_bytes;
+  Ctx cp(as_net(pn), to_stream(stream), Arena(ws, ws_bytes)), cr(as_net(rf), to_stream(stream), Arena(ws, ws_bytes));
   estimate(cp, cr, gs, cloud, choose, obj, iters, pose_wo, pose);
   if (cp.err != DF_OK) return cp.err;
   return finish(cr, "estimate_poses");

@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "host_plan.h"
 #include "igemm.h"
 #include "loss.h"
 #include "layers.h"
@@ -37,8 +38,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TB = 256;
 inline unsigned nblk(long n, long cap = 16384) { long b = (n + TB - 1) / TB; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
 #define GRID_STRIDE(i, n) for (long i = blockIdx.x * (long)TB + threadIdx.x; i < (n); i += (long)gridDim.x * TB)
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline int conv_out(int in, int k, int stride, int pad, int dil) { return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1; }
 
 // ------------------------------------------------------------------------------------------------
 // kernels (the glue between the MFMA launches; every sum in a fixed order)
@@ -784,47 +783,11 @@ __global__ __launch_bounds__(128) void refiner_tail_bwd_kernel(const float *__re
   }
 }
 
-// wt[z][c][tap'][n] = w[z][n][tap][c], tap' = the tap mirrored through the kernel centre (what the data gradient convolves with)
-__global__ __launch_bounds__(TB) void flip_kernel(const float *__restrict__ w, float *__restrict__ wt, int O, int T, int I, int KH, int KW, int Z) {
-  const long per = (long)O * T * I;
-  GRID_STRIDE(i, per * Z) {
-    const long z = i / per, l = i - z * per;
-    const int n = (int)(l % O);
-    const long r = l / O;
-    const int t = (int)(r % T);
-    const long c = r / T;
-    const int ky = t / KW, kx = t - ky * KW;
-    const int tf = (KH - 1 - ky) * KW + (KW - 1 - kx);
-    wt[i] = w[z * per + ((size_t)n * T + tf) * I + c];
-  }
-}
-
-// every flip of a trainer in ONE launch: segment table in device memory (begin = first element of the segment in the launch's index space)
-struct FlipSeg { long off, begin; int O, T, I, KH, KW, Z; };
-__global__ __launch_bounds__(TB) void flip_all_kernel(const float *__restrict__ P, float *__restrict__ wf, const FlipSeg *__restrict__ segs, int nseg,
-                                                      long total) {
-  GRID_STRIDE(g, total) {
-    int lo = 0, hi = nseg - 1;
-    while (lo < hi) {                               // last segment whose begin <= g
-      const int mid = (lo + hi + 1) >> 1;
-      if (segs[mid].begin <= g) lo = mid; else hi = mid - 1;
-    }
-    const FlipSeg sg = segs[lo];
-    const long i = g - sg.begin, per = (long)sg.O * sg.T * sg.I;
-    const long z = i / per, l = i - z * per;
-    const int n = (int)(l % sg.O);
-    const long r = l / sg.O;
-    const int t = (int)(r % sg.T);
-    const long c = r / sg.T;
-    const int ky = t / sg.KW, kx = t - ky * sg.KW;
-    const int tf = (sg.KH - 1 - ky) * sg.KW + (sg.KW - 1 - kx);
-    wf[sg.off + i] = P[sg.off + z * per + ((size_t)n * sg.T + tf) * sg.I + c];
-  }
-}
-
-// The same copies as 32 x 32 (output channel, input channel) tiles through LDS: reads run along c (the source's fastest axis), writes along n
-// (the destination's) -- the element-wise form read with a stride of T * I floats (167 us per optimizer step for PoseNet's 86 MB; this one is
-// bound by the copy).  Tile list: `tbegin` = first tile of the segment in the launch's tile space; a tile = (z, tap, n block, c block).
+// Every flip of a trainer in ONE launch: wf[z][c][tap'][n] = P[z][n][tap][c], tap' = the tap mirrored through the kernel centre (what the
+// data gradient convolves with).  32 x 32 (output channel, input channel) tiles through LDS: reads run along c (the source's fastest axis),
+// writes along n (the destination's) -- an element-wise form reads with a stride of T * I floats (167 us per optimizer step for PoseNet's
+// 86 MB; this one is bound by the copy).  Tile list: `tbegin` = first tile of the segment in the launch's tile space; a tile = (z, tap,
+// n block, c block).
 struct FlipTile { long off; int tbegin; int O, T, I, KH, KW, Z, nb_n, nb_c; };
 __global__ __launch_bounds__(256) void flip_tiles_kernel(const float *__restrict__ P, float *__restrict__ wf, const FlipTile *__restrict__ segs, int nseg) {
   __shared__ float s_t[32][33];
@@ -882,22 +845,18 @@ __global__ __launch_bounds__(TB) void copy2d_kernel(const float *__restrict__ sr
 // ------------------------------------------------------------------------------------------------
 // trainer handle: parameter spec (reference keys / shapes) and where every tensor lives in the flat buffer
 // ------------------------------------------------------------------------------------------------
-struct PSpec {
-  std::string key;
-  int64_t shape[4] = {1, 1, 1, 1};
-  int ndim = 0;
-  // kernel-layout placement: up to two pieces (head layer 1's weight splits into the per-point and the global-feature block)
-  int mode = 2;             // 0 OIHW->O(T)Ipad, 1 OIHW->tap-major, 2 plain copy, 3 head-1 weight split, 4 rows of a stacked tensor
+// where a reference tensor lives in the flat buffer (kernel layout): up to two pieces (head layer 1's weight splits into the per-point and
+// the global-feature block)
+struct Place {
+  int mode = 2;             // 0 OIHW->O(T)Ipad, 1 OIHW->tap-major, 2 plain copy, 3 head-1 weight split
   size_t off = 0, off2 = 0; // flat offsets (floats); off2: second piece of mode 3
-  size_t kfloats = 0;       // floats this tensor occupies in the flat buffer
-  int64_t numel() const { int64_t n = 1; for (int i = 0; i < ndim; ++i) n *= shape[i]; return n; }
 };
 
 struct Trainer {
   int kind = 0, N = 0, K = 0, device = 0;
   std::map<std::vector<int>, size_t> ws_cache;      // (B, H, W, M) -> workspace bytes (the sizing pass walks the whole step)
-  std::vector<PSpec> spec;
-  std::map<std::string, int> index;
+  ParamList params;                          // reference keys and shapes (host_plan.h)
+  std::vector<Place> place;                  // per entry of params
   std::map<std::string, size_t> slot;        // internal name -> flat offset
   size_t flat = 0;
   // flipped / transposed weights for the data gradients, rebuilt when the caller's parameter version changes
@@ -912,20 +871,11 @@ struct Trainer {
   std::map<std::string, Wino> wino;
   float *wino_buf = nullptr;
   size_t wino_floats = 0;
-  FlipSeg *flip_tab = nullptr;     // device copy of `flips` for the one-launch flip
-  long flip_total = 0;
-#ifdef DF_DEV
-  std::vector<std::string> ev_desc;      // shape of every profiled launch (DF_PROFILE_VERBOSE)
-#endif
-  FlipTile *flip_tiles = nullptr;  // the tiled form's segment table
+  FlipTile *flip_tiles = nullptr;  // device copy of `flips` as the tiled flip's segment table
   int flip_ntiles = 0;
   bool splitk = true;             // df_trainer_set_splitk
-  // df_trainer_profile: HIP event pairs around every MFMA launch of a step, executed FLOPs per kind (0 fwd, 1 dgrad, 2 wgrad)
-  bool profiling = false;
-  std::vector<hipEvent_t> ev;
-  size_t ev_used = 0;
-  std::vector<int> ev_kind;
-  std::vector<double> ev_flops;
+  // df_trainer_profile: every MFMA launch of a step, executed FLOPs per kind (0 fwd, 1 dgrad, 2 wgrad)
+  LaunchTimer timer;
 };
 
 size_t take(Trainer &t, const std::string &name, size_t floats) {
@@ -935,25 +885,16 @@ size_t take(Trainer &t, const std::string &name, size_t floats) {
   return o;
 }
 
-void add_spec(Trainer &t, const std::string &key, std::initializer_list<int64_t> shp, int mode, size_t off, size_t kfloats, size_t off2 = 0) {
-  PSpec p;
-  p.key = key;
-  p.ndim = (int)shp.size();
-  int i = 0;
-  for (auto v : shp) p.shape[i++] = v;
-  p.mode = mode; p.off = off; p.off2 = off2; p.kfloats = kfloats;
-  t.index[key] = (int)t.spec.size();
-  t.spec.push_back(p);
-}
-
-// as_gemm: the step uses the packed [O][(ky,kx,c)] rows as a plain GEMM operand (up_3 on chosen-pixel patches): its data gradient
-// needs the plain transpose, not the tap-mirrored one
-void add_conv(Trainer &t, const std::string &key, int O, int I, int k, bool tapmajor = false, bool as_gemm = false) {
+// a convolution weight in O(T)Ipad, or tap-major (up_1 / up_2: the low-resolution product is a 1x1 conv with 9*O outputs).  as_gemm: the
+// step uses the packed [O][(ky,kx,c)] rows as a plain GEMM operand (up_3 on chosen-pixel patches; the strided layer2.0.conv1, whose data
+// gradient goes through per-tap products + a gather): its data gradient needs the plain transpose, not the tap-mirrored one
+void add_conv(Trainer &t, const ParamInfo &p, bool tapmajor, bool as_gemm) {
+  const std::string &key = p.key;
+  const int O = (int)p.shape[0], I = (int)p.shape[1], k = (int)p.shape[2];
   const int Ipad = (I + 3) / 4 * 4, T = k * k;
-  const size_t fl = (size_t)O * T * Ipad;
-  const size_t off = take(t, key, fl);
-  add_spec(t, key, {O, I, k, k}, tapmajor ? 1 : 0, off, fl);
-  if (tapmajor) t.flips.push_back({off, 9 * O, 1, I, 1, 1, 1});        // the low-resolution product is a 1x1 conv with 9*O outputs
+  const size_t off = take(t, key, (size_t)O * T * Ipad);
+  t.place.push_back({tapmajor ? 1 : 0, off});
+  if (tapmajor) t.flips.push_back({off, 9 * O, 1, I, 1, 1, 1});
   else if (as_gemm) t.flips.push_back({off, O, 1, T * Ipad, 1, 1, 1});
   else t.flips.push_back({off, O, T, Ipad, k, k, 1});
   if (k == 3 && !tapmajor && !as_gemm && I >= 128 && I % 4 == 0 && O % 4 == 0 && key.find("feats.layer") != std::string::npos) {
@@ -962,115 +903,48 @@ void add_conv(Trainer &t, const std::string &key, int O, int I, int k, bool tapm
     t.wino_floats += 2 * n;
   }
 }
-void add_plain(Trainer &t, const std::string &key, std::initializer_list<int64_t> shp) {
-  size_t n = 1;
-  for (auto v : shp) n *= (size_t)v;
-  add_spec(t, key, shp, 2, take(t, key, n), n);
-}
-// Conv1d(k=1) / Linear weight [O][I] used as a GEMM operand (needs its transpose for the data gradient)
-void add_gemm(Trainer &t, const std::string &key, int O, int I, bool conv1d) {
-  const size_t off = take(t, key, (size_t)O * I);
-  if (conv1d) add_spec(t, key, {O, I, 1}, 2, off, (size_t)O * I);
-  else add_spec(t, key, {O, I}, 2, off, (size_t)O * I);
-  t.flips.push_back({off, O, 1, I, 1, 1, 1});
-}
 
-const char *CNN = "cnn.model.module.";
-
-void build_posenet(Trainer &t) {
-  const std::string c = CNN;
-  add_conv(t, c + "feats.conv1.weight", 64, 3, 7);
-  int inpl = 64;
-  const int planes_of[4] = {64, 128, 256, 512};
-  for (int li = 1; li <= 4; ++li) {
-    const int planes = planes_of[li - 1];
-    for (int blk = 0; blk < 2; ++blk) {
-      const int cin = blk == 0 ? inpl : planes;
-      const std::string base = c + "feats.layer" + std::to_string(li) + "." + std::to_string(blk) + ".";
-      // (a strided convolution's data gradient goes through per-tap products + a gather: it multiplies with the plain transpose)
-      add_conv(t, base + "conv1.weight", planes, cin, 3, false, blk == 0 && li == 2);
-      add_conv(t, base + "conv2.weight", planes, planes, 3);
-      if (blk == 0 && cin != planes) add_conv(t, base + "downsample.0.weight", planes, cin, 1);
-    }
-    inpl = planes;
-  }
-  for (int s = 0; s < 4; ++s) add_conv(t, c + "psp.stages." + std::to_string(s) + ".1.weight", 512, 512, 1);
-  add_conv(t, c + "psp.bottleneck.weight", 1024, 2560, 1);
-  add_plain(t, c + "psp.bottleneck.bias", {1024});
-  const char *ups[3] = {"up_1", "up_2", "up_3"};
-  const int up_in[3] = {1024, 256, 64}, up_out[3] = {256, 64, 64};
-  for (int u = 0; u < 3; ++u) {
-    add_conv(t, c + ups[u] + ".conv.1.weight", up_out[u], up_in[u], 3, u < 2, u == 2);
-    add_plain(t, c + ups[u] + ".conv.1.bias", {up_out[u]});
-    add_plain(t, c + ups[u] + ".conv.2.weight", {1});
-  }
-  add_conv(t, c + "final.0.weight", 32, 64, 1);
-  add_plain(t, c + "final.0.bias", {32});
-  add_plain(t, c + "classifier.0.weight", {256, 256});     // dead weights (lib/pspnet.py:58-62): carried, never touched
-  add_plain(t, c + "classifier.0.bias", {256});
-  add_plain(t, c + "classifier.2.weight", {21, 256});
-  add_plain(t, c + "classifier.2.bias", {21});
-  add_plain(t, "feat.conv1.weight", {64, 3, 1});
-  add_plain(t, "feat.conv1.bias", {64});
-  const char *fn[5] = {"conv2", "e_conv1", "e_conv2", "conv5", "conv6"};
-  const int fi[5] = {64, 32, 64, 256, 512}, fo[5] = {128, 64, 128, 512, 1024};
-  // reference order of the keys: conv1, conv2, e_conv1, e_conv2, conv5, conv6 (weights then biases per layer)
-  for (int i = 0; i < 5; ++i) {
-    add_gemm(t, std::string("feat.") + fn[i] + ".weight", fo[i], fi[i], true);
-    add_plain(t, std::string("feat.") + fn[i] + ".bias", {fo[i]});
-  }
-  // head layer 1: towers stacked r, t, c; per-point block [1920][384], global-feature block [1920][1024], bias [1920]
-  const size_t wpt = take(t, "head1.wpt", (size_t)1920 * 384), wg = take(t, "head1.wg", (size_t)1920 * 1024), b1 = take(t, "head1.bias", 1920);
-  t.flips.push_back({wpt, 1920, 1, 384, 1, 1, 1});
-  t.flips.push_back({wg, 1920, 1, 1024, 1, 1, 1});
-  const size_t w2 = take(t, "head2.w", (size_t)3 * 256 * 640), b2 = take(t, "head2.bias", 768);
-  t.flips.push_back({w2, 256, 1, 640, 1, 1, 3});
-  const size_t w3 = take(t, "head3.w", (size_t)3 * 128 * 256), b3 = take(t, "head3.bias", 384);
-  t.flips.push_back({w3, 128, 1, 256, 1, 1, 3});
-  const char *hs[3] = {"r", "t", "c"};
-  const int hin[3] = {1408, 640, 256}, hout[3] = {640, 256, 128};
-  for (int l = 0; l < 3; ++l)
-    for (int h = 0; h < 3; ++h) {
-      const std::string nm = "conv" + std::to_string(l + 1) + "_" + hs[h];
-      if (l == 0) {
-        add_spec(t, nm + ".weight", {640, 1408, 1}, 3, wpt + (size_t)h * 640 * 384, (size_t)640 * 1408, wg + (size_t)h * 640 * 1024);
-        add_spec(t, nm + ".bias", {640}, 2, b1 + (size_t)h * 640, 640);
-      } else {
-        const size_t w = l == 1 ? w2 : w3, b = l == 1 ? b2 : b3;
-        add_spec(t, nm + ".weight", {hout[l], hin[l], 1}, 2, w + (size_t)h * hout[l] * hin[l], (size_t)hout[l] * hin[l]);
-        add_spec(t, nm + ".bias", {hout[l]}, 2, b + (size_t)h * hout[l], hout[l]);
+// Lays the reference tensors out in the flat buffer, in reference order (the slots are taken in that order):
+//   * 4-d convolution weights: add_conv;
+//   * PoseNet head layers 1 - 3: the three towers stacked r, t, c ([1920][384] per-point block, [1920][1024] global-feature block and
+//     [1920] bias of layer 1; [3][256][640], [768]; [3][128][256], [384]);
+//   * the Conv1d(k=1) / Linear weights the step uses as GEMM operands (feat.conv2 .. conv6, the refiner's FC towers): plain, with a transpose;
+//   * the rest -- biases, PReLU slopes, the cloud's first conv, the object-indexed last head layer, the dead classifier -- as plain copies.
+void lay_out(Trainer &t) {
+  const size_t npos = std::string::npos;
+  size_t wpt = 0, wg = 0, hw[4] = {}, hb[4] = {};      // the stacked head layers' slots, taken at the first of them
+  for (const ParamInfo &p : t.params.spec) {
+    const std::string &k = p.key;
+    const size_t n = (size_t)p.numel();
+    const bool weight = ends_with(k, ".weight");
+    const bool head = k.rfind("conv", 0) == 0;               // the towers: conv<l>_<r|t|c>
+    const int l = head ? k[4] - '0' : 0, h = head ? (k[6] == 'r' ? 0 : k[6] == 't' ? 1 : 2) : 0;
+    const bool last = head && l == (t.kind == 0 ? 4 : 3);
+    if (p.ndim == 4) {
+      add_conv(t, p, k.find(".up_1.") != npos || k.find(".up_2.") != npos, k.find(".up_3.") != npos || k.find("feats.layer2.0.conv1.") != npos);
+    } else if (t.kind == 0 && head && !last) {
+      if (!wpt) {
+        wpt = take(t, "head1.wpt", (size_t)1920 * 384);
+        wg = take(t, "head1.wg", (size_t)1920 * 1024);
+        hb[1] = take(t, "head1.bias", 1920);
+        hw[2] = take(t, "head2.w", (size_t)3 * 256 * 640);
+        hb[2] = take(t, "head2.bias", 768);
+        hw[3] = take(t, "head3.w", (size_t)3 * 128 * 256);
+        hb[3] = take(t, "head3.bias", 384);
+        t.flips.push_back({wpt, 1920, 1, 384, 1, 1, 1});
+        t.flips.push_back({wg, 1920, 1, 1024, 1, 1, 1});
+        t.flips.push_back({hw[2], 256, 1, 640, 1, 1, 3});
+        t.flips.push_back({hw[3], 128, 1, 256, 1, 1, 3});
       }
+      if (l == 1 && weight) t.place.push_back({3, wpt + (size_t)h * 640 * 384, wg + (size_t)h * 640 * 1024});
+      else t.place.push_back({2, (weight ? hw[l] : hb[l]) + h * n});
+    } else if (weight && p.ndim >= 2 && !last && k != "feat.conv1.weight" && k.find("classifier") == npos) {
+      const size_t off = take(t, k, n);
+      t.place.push_back({2, off});
+      t.flips.push_back({off, (int)p.shape[0], 1, (int)p.shape[1], 1, 1, 1});
+    } else {
+      t.place.push_back({2, take(t, k, n)});
     }
-  const int per[3] = {4, 3, 1};
-  for (int h = 0; h < 3; ++h) {
-    const std::string nm = std::string("conv4_") + hs[h];
-    add_plain(t, nm + ".weight", {(int64_t)t.K * per[h], 128, 1});
-    add_plain(t, nm + ".bias", {(int64_t)t.K * per[h]});
-  }
-}
-
-void build_refiner(Trainer &t) {
-  add_plain(t, "feat.conv1.weight", {64, 3, 1});
-  add_plain(t, "feat.conv1.bias", {64});
-  const char *fn[5] = {"conv2", "e_conv1", "e_conv2", "conv5", "conv6"};
-  const int fi[5] = {64, 32, 64, 384, 512}, fo[5] = {128, 64, 128, 512, 1024};
-  for (int i = 0; i < 5; ++i) {
-    add_gemm(t, std::string("feat.") + fn[i] + ".weight", fo[i], fi[i], true);
-    add_plain(t, std::string("feat.") + fn[i] + ".bias", {fo[i]});
-  }
-  const int li[2] = {1024, 512}, lo[2] = {512, 128};
-  const char *hs[2] = {"r", "t"};
-  for (int l = 0; l < 2; ++l)
-    for (int h = 0; h < 2; ++h) {
-      const std::string nm = "conv" + std::to_string(l + 1) + "_" + hs[h];
-      add_gemm(t, nm + ".weight", lo[l], li[l], false);
-      add_plain(t, nm + ".bias", {lo[l]});
-    }
-  const int per[2] = {4, 3};
-  for (int h = 0; h < 2; ++h) {
-    const std::string nm = std::string("conv3_") + hs[h];
-    add_plain(t, nm + ".weight", {(int64_t)t.K * per[h], 128});
-    add_plain(t, nm + ".bias", {(int64_t)t.K * per[h]});
   }
 }
 
@@ -1079,26 +953,9 @@ void build_refiner(Trainer &t) {
 // ------------------------------------------------------------------------------------------------
 struct View { float *d = nullptr; int ld = 0; };           // [rows][C] view: element (r, c) at d[r * ld + c] (d already offset to its channel)
 
-// One resolution level of a pass: the crop-size buckets' [B_i][H_i][W_i] blocks concatenated along the pixel-row axis (the inference
-// engine's scheme, engine.hip `Level`).  Launches whose arithmetic does not depend on the crop geometry (1x1 convolutions, the
-// Winograd-domain products, every weight gradient, the whole per-point part) cover the rows of all buckets at once; direct k x k
-// convolutions and the memory-bound glue run per bucket on row offsets into the same buffers.  Point rows are a single bucket.
-struct Lv {
-  std::vector<int> B, H, W;
-  std::vector<long> off;      // first pixel row of bucket i
-  std::vector<int> b0;        // first frame of bucket i
-  long rows = 0;
-  int frames = 0;
-  int nb() const { return (int)B.size(); }
-  void push(int b, int h, int w) {
-    B.push_back(b); H.push_back(h); W.push_back(w); off.push_back(rows); b0.push_back(frames);
-    rows += (long)b * h * w; frames += b;
-  }
-};
-
 struct Act {
   View v, g;                    // values; gradient (allocated / aliased during the backward pass)
-  const Lv *lv = nullptr;
+  const Level *lv = nullptr;
   int C = 0;
   bool gset = false;
   long rows() const { return lv->rows; }
@@ -1106,33 +963,19 @@ struct Act {
 
 enum GemmKind { GK_FWD = 0, GK_DGRAD = 1, GK_WGRAD = 2 };
 
-struct Step {
+// one training step: the workspace arena (host_plan.h), the handle, the launch stream, the activation records and the backward tape
+struct Step : Arena {
   Trainer *t;
   hipStream_t st;
-  bool dry;
-  char *base;
-  size_t off = 0, cap = 0, peak = 0;
-  int err = DF_OK;
   const float *P = nullptr;      // flat parameters
   float *G = nullptr;            // flat gradients (accumulated)
   float *splitk = nullptr;
   size_t splitk_bytes = 0;
   std::deque<Act> acts;
-  std::deque<Lv> lvs;
+  std::deque<Level> lvs;
   std::vector<std::function<void()>> tape;
 
-  void *bytes(size_t b) {
-    b = (b + 255) & ~size_t(255);
-    // the sizing pass hands out (never dereferenced) non-null addresses too, so that every "is there a buffer yet" decision of the
-    // backward pass comes out as in the real run: both passes allocate the same sequence by construction
-    void *p = (dry ? reinterpret_cast<char *>(4096) : base) + off;
-    off += b;
-    if (off > peak) peak = off;
-    if (!dry && off > cap && err == DF_OK) err = set_error(DF_ERR_WORKSPACE, "train step: workspace too small (need > %zu bytes, have %zu)", off, cap);
-    return p;
-  }
-  float *f(size_t n) { return static_cast<float *>(bytes(n * sizeof(float))); }
-  bool live() const { return !dry && err == DF_OK; }
+  Step(Trainer *tr, hipStream_t s, Arena a = Arena()) : Arena(a), t(tr), st(s) {}
 #ifdef DF_DEV
   // dev build, DF_TRAIN_DEBUG=1: synchronise after every phase and name it on stderr (localises a faulting launch)
   void dbg(const char *what, const std::string &extra = std::string()) {
@@ -1145,46 +988,29 @@ struct Step {
 #else
   void dbg(const char *, const std::string & = std::string()) {}
 #endif
-  void fail(int rc) { if (rc != DF_OK && err == DF_OK) err = rc; }
   // every MFMA launch of the step goes through here: with df_trainer_profile on, HIP events on the launch stream bracket it and its
   // EXECUTED FLOPs are tallied per kind (forward / data gradient / weight gradient)
-  void prof_begin() {
-    if (!t->profiling || !live()) return;
-    if (t->ev_used + 2 > t->ev.size()) {
-      const size_t old = t->ev.size();
-      t->ev.resize(old + 512);
-      for (size_t i = old; i < t->ev.size(); ++i) hipEventCreate(&t->ev[i]);
-    }
-    hipEventRecord(t->ev[t->ev_used], st);
-  }
-  void prof_end(int kind, double flops, const ConvParams *p = nullptr, long M = 0) {
-    if (!t->profiling || !live()) return;
-    hipEventRecord(t->ev[t->ev_used + 1], st);
-    t->ev_kind.push_back(kind);
-    t->ev_flops.push_back(flops);
-#ifdef DF_DEV
-    char d[160] = "";
-    if (p) snprintf(d, sizeof(d), "M=%ld N=%d K=%d k%dx%d s%d d%d z%d", M > 0 ? M : (long)p->B * p->OH * p->OW, p->Cout, p->KH * p->KW * p->Cin, p->KH, p->KW, p->stride, p->dil, p->zcount);
-    t->ev_desc.push_back(d);
-#endif
-    t->ev_used += 2;
+  template <class Launch> void timed(int kind, double flops, const ConvParams &p, long M, Launch launch) {
+    LaunchTimer &tm = t->timer;
+    if (tm.on) fail(tm.begin(st));
+    if (!live()) return;
+    fail(launch());
+    if (tm.on && live()) tm.end(st, launch_record(kind, flops, p, M));
   }
   void gemm(int kind, const ConvParams &p) {
     if (!live()) return;
-    prof_begin();
-    fail(launch_conv(p, st));
-    prof_end(kind, conv_flops(p), &p);
+    timed(kind, conv_flops(p), p, 0, [&] { return launch_conv(p, st); });
   }
   // the same convolution over several buckets: one launch (launch_conv_multi)
   void gemm_multi(int kind, const ConvParams &p, const std::vector<WgradSeg> &segs) {
     if (!live() || segs.empty()) return;
     double fl = 0;
-    for (const WgradSeg &g : segs) fl += 2.0 * g.B * g.OH * g.OW * (double)p.Cout * p.KH * p.KW * p.Cin;
-    prof_begin();
-    fail(launch_conv_multi(p, (int)segs.size(), segs.data(), st));
     long M = 0;
-    for (const WgradSeg &g : segs) M += (long)g.B * g.OH * g.OW;
-    prof_end(kind, fl, &p, M);
+    for (const WgradSeg &g : segs) {
+      fl += 2.0 * g.B * g.OH * g.OW * (double)p.Cout * p.KH * p.KW * p.Cin;
+      M += (long)g.B * g.OH * g.OW;
+    }
+    timed(kind, fl, p, M, [&] { return launch_conv_multi(p, (int)segs.size(), segs.data(), st); });
   }
   size_t slot(const std::string &name) {
     auto it = t->slot.find(name);
@@ -1197,9 +1023,9 @@ struct Step {
   const float *p(const std::string &name, size_t extra = 0) { const size_t o = slot(name); return dry ? nullptr : P + o + extra; }
   float *gr(const std::string &name, size_t extra = 0) { const size_t o = slot(name); return dry ? nullptr : G + o + extra; }
   const float *pf(const std::string &name, size_t extra = 0) { const size_t o = slot(name); return dry ? nullptr : t->wflip + o + extra; }
-  const Lv *level(const Lv &l) { lvs.push_back(l); return &lvs.back(); }
-  const Lv *flat_level(long rows) { Lv l; l.push((int)rows, 1, 1); return level(l); }
-  Act *act(const Lv *lv, int C, float *d = nullptr, int ld = 0) {
+  const Level *level(const Level &l) { lvs.push_back(l); return &lvs.back(); }
+  const Level *flat_level(long rows) { Level l; l.push((int)rows, 1, 1); return level(l); }
+  Act *act(const Level *lv, int C, float *d = nullptr, int ld = 0) {
     acts.emplace_back();
     Act *a = &acts.back();
     a->lv = lv; a->C = C;
@@ -1227,7 +1053,7 @@ ConvParams flat_params(const Act *x, int cin, const float *w, const float *bias,
   return p;
 }
 // bucket tables of a level, TAB_MAX buckets each (aux: a second level whose first rows go into aux0)
-std::vector<BTab> make_tabs(const Lv *lv, const Lv *aux = nullptr) {
+std::vector<BTab> make_tabs(const Level *lv, const Level *aux = nullptr) {
   std::vector<BTab> out;
   for (int g0 = 0; g0 < lv->nb(); g0 += TAB_MAX) {
     BTab t{};
@@ -1248,7 +1074,7 @@ inline int tab_frames(const BTab &t) { return t.b0[t.n - 1] + t.B[t.n - 1] - t.b
 // bucket i of a k x k convolution between two levels
 ConvParams bucket_params(const Act *x, int i, int cin, const float *w, const float *bias, Act *y, int k, int stride, int pad, int dil, int act) {
   ConvParams p;
-  const Lv *li = x->lv, *lo = y->lv;
+  const Level *li = x->lv, *lo = y->lv;
   p.in = x->v.d + li->off[i] * x->v.ld; p.wgt = w; p.bias = bias; p.out = y->v.d + lo->off[i] * y->v.ld;
   p.B = li->B[i]; p.H = li->H[i]; p.W = li->W[i]; p.Cin = cin; p.in_ld = x->v.ld;
   p.OH = lo->H[i]; p.OW = lo->W[i]; p.Cout = y->C; p.out_ld = y->v.ld;
@@ -1278,9 +1104,8 @@ void wgrad(Step &s, ConvParams f, const std::vector<WgradSeg> &segs, View gy, fl
   if (s.live()) {
     double M = 0;
     for (const WgradSeg &g : segs) M += (double)g.B * g.OH * g.OW;
-    s.prof_begin();
-    s.fail(launch_wgrad_multi(f, (int)segs.size(), segs.data(), dw, db, ws, need, s.st, 1));
-    s.prof_end(GK_WGRAD, 2.0 * M * f.Cout * f.KH * f.KW * f.Cin, &f, (long)M);
+    s.timed(GK_WGRAD, 2.0 * M * f.Cout * f.KH * f.KW * f.Cin, f, (long)M,
+            [&] { return launch_wgrad_multi(f, (int)segs.size(), segs.data(), dw, db, ws, need, s.st, 1); });
   }
   s.dbg("wgrad");
   s.off = mark;
@@ -1323,12 +1148,12 @@ View rows_view(View v, long row0) { return View{v.d + row0 * v.ld, v.ld}; }
 // buckets' pixels (launch_wgrad_multi).
 Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride, int pad, int dil, int act, Act *res = nullptr, Act *into = nullptr,
           bool need_dx = true) {
-  const Lv *li = x->lv;
+  const Level *li = x->lv;
   const int nb = li->nb();
   const bool flat = k == 1 && stride == 1 && pad == 0;
-  const Lv *lo = li;
+  const Level *lo = li;
   if (!flat) {
-    Lv o;
+    Level o;
     for (int i = 0; i < nb; ++i) o.push(li->B[i], conv_out(li->H[i], k, stride, pad, dil), conv_out(li->W[i], k, stride, pad, dil));
     lo = s.level(o);
   }
@@ -1476,16 +1301,10 @@ Act *slice(Step &s, Act *a, int c0, int C) {
 }
 
 int check_flips(Trainer &t, const float *P, long version, hipStream_t st) {
-  if (!t.wflip || (t.wino_floats && !t.wino_buf))
-    return set_error(DF_ERR_STATE, "trainer: created without a device (no arena for the data gradients' weight copies)");
+  if (!t.wflip || !t.flip_tiles || (t.wino_floats && !t.wino_buf))
+    return set_error(DF_ERR_STATE, "trainer: created without a device (no arena or tile table for the data gradients' weight copies)");
   if (t.flip_version == version && t.flip_src == P && version >= 0) return DF_OK;
-  if (t.flip_tiles)
-    hipLaunchKernelGGL(flip_tiles_kernel, dim3(t.flip_ntiles), dim3(256), 0, st, P, t.wflip, t.flip_tiles, (int)t.flips.size());
-  else if (t.flip_tab)
-    hipLaunchKernelGGL(flip_all_kernel, dim3(nblk(t.flip_total, 8192)), dim3(TB), 0, st, P, t.wflip, t.flip_tab, (int)t.flips.size(), t.flip_total);
-  else
-    for (const Trainer::Flip &f : t.flips)
-      hipLaunchKernelGGL(flip_kernel, dim3(nblk((long)f.O * f.T * f.I * f.Z, 1024)), dim3(TB), 0, st, P + f.off, t.wflip + f.off, f.O, f.T, f.I, f.KH, f.KW, f.Z);
+  hipLaunchKernelGGL(flip_tiles_kernel, dim3(t.flip_ntiles), dim3(256), 0, st, P, t.wflip, t.flip_tiles, (int)t.flips.size());
   {   // the F(4x4,3x3)-domain copies, forward (of the packed weights) and data gradient (of the flipped ones: [I][9][O]): one launch per 32
     WinoWTab tab;
     tab.n = 0; tab.e0[0] = 0;
@@ -1536,7 +1355,7 @@ Act *basic_block(Step &s, Act *x, int cin, const std::string &base, int planes, 
 // Dropout2d (lib/pspnet.py:46,52): one keep / drop decision per (frame, channel); out of place -- the PReLU gradient upstream needs
 // the un-scaled activation
 Act *dropout2d(Step &s, Act *a, float p, unsigned seed) {
-  const Lv *lv = a->lv;
+  const Level *lv = a->lv;
   float *scale = s.f((size_t)lv->frames * a->C);
   Act *o = s.act(lv, a->C);
   const std::vector<BTab> tabs = make_tabs(lv);
@@ -1559,16 +1378,16 @@ Act *dropout2d(Step &s, Act *a, float p, unsigned seed) {
 // PSPUpsample through the low-resolution per-tap products (layers.hip upconv_gather): x [B][h][w][Cin] -> [B][2h][2w][Cout] per bucket;
 // the product, its weight and data gradients, the activation / bias adjoints are single launches over the rows of all buckets
 Act *upconv(Step &s, Act *x, const std::string &base, int cin, int cout) {
-  const Lv *li = x->lv;
+  const Level *li = x->lv;
   const int nb = li->nb();
   Act *y = s.act(li, 9 * cout);
   const ConvW cw{base + "conv.1.weight"};
   ConvParams p = flat_params(x, cin, s.p(cw.name), nullptr, y, ACT_NONE);
   p.splitk_ws = s.splitk; p.splitk_ws_bytes = s.splitk_bytes;
   s.gemm(GK_FWD, p);
-  Lv up;
+  Level up;
   for (int i = 0; i < nb; ++i) up.push(li->B[i], 2 * li->H[i], 2 * li->W[i]);
-  const Lv *lo = s.level(up);
+  const Level *lo = s.level(up);
   Act *o = s.act(lo, cout);
   if (s.live())
     for (int i = 0; i < nb; ++i)
@@ -1610,17 +1429,17 @@ void posenet_step(Step &s, const PoseNetIO &io) {
   Step *sp = &s;
 
   // ---- colour branch (lib/extractors.py:114-124, lib/pspnet.py:64-77) ----
-  Lv limg;
+  Level limg;
   for (int i = 0; i < nb; ++i) limg.push(io.B[i], io.H[i], io.W[i]);
   Act *img4 = s.act(s.level(limg), 4);
   if (s.live())
     for (int i = 0; i < nb; ++i) launch_nchw3_to_nhwc4(io.img[i], img4->v.d + img4->lv->off[i] * 4, io.B[i], io.H[i], io.W[i], s.st);
   Act *stem = conv(s, img4, 4, ConvW{C + "feats.conv1.weight"}, 64, 7, 2, 3, 1, ACT_RELU, nullptr, nullptr, false);
-  Lv lpool;
+  Level lpool;
   for (int i = 0; i < nb; ++i) lpool.push(io.B[i], conv_out(stem->lv->H[i], 3, 2, 1, 1), conv_out(stem->lv->W[i], 3, 2, 1, 1));
   Act *x = s.act(s.level(lpool), 64);
   {
-    const Lv *ls = stem->lv, *lx = x->lv;
+    const Level *ls = stem->lv, *lx = x->lv;
     if (s.live())
       for (int i = 0; i < nb; ++i)
         launch_maxpool3s2(stem->v.d + ls->off[i] * 64, x->v.d + lx->off[i] * 64, ls->B[i], ls->H[i], ls->W[i], 64, lx->H[i], lx->W[i], s.st);
@@ -1648,7 +1467,7 @@ void posenet_step(Step &s, const PoseNetIO &io) {
     x = basic_block(s, x, planes, base + "1.", planes, 1, dil_of[li - 1], false, into);
     cin = planes;
   }
-  const Lv *l8 = cat->lv;  // the 1/8-resolution level
+  const Level *l8 = cat->lv;  // the 1/8-resolution level
   // PSP module (lib/pspnet.py:20-24): pool -> 1x1 conv -> bilinear (align_corners=False) into the concat slots.  The pooled maps of
   // every frame of every bucket sit in ONE set of stage blocks ([4][B*36][512], frames in bucket order): the four stage convolutions are
   // single GEMMs; pooling and resampling (and their adjoints) run per bucket
@@ -1704,7 +1523,7 @@ void posenet_step(Step &s, const PoseNetIO &io) {
   if (io.dropout) u2 = dropout2d(s, u2, 0.15f, io.seed * 4 + 3);
   // up_3 + final 1x1 + LogSoftmax at the chosen pixels only (lib/network.py:98-102 reads nothing else)
   Act *patch = s.act((long)rows, 576);
-  const Lv *l2 = u2->lv;   // half resolution
+  const Level *l2 = u2->lv;   // half resolution
   if (s.live())
     for (int i = 0; i < nb; ++i)
       launch_up3_patches(u2->v.d + l2->off[i] * 64, io.choose + (size_t)l2->b0[i] * N, patch->v.d + (size_t)l2->b0[i] * Npad * 576, l2->B[i], l2->H[i], l2->W[i], N,
@@ -2021,23 +1840,13 @@ extern "C" df_trainer *df_trainer_create(int kind, int num_points, int num_obj) 
   Trainer *t = new Trainer();
   t->kind = kind; t->N = num_points; t->K = num_obj;
   hipGetDevice(&t->device);
-  if (kind == 0) build_posenet(*t);
-  else build_refiner(*t);
+  t->params = reference_params(kind, num_obj);
+  lay_out(*t);
   // the data gradients' flipped / transposed weight copies; without a device (layout / workspace queries on a CPU-only host) the
   // handle still works for everything that launches nothing, and a step reports the missing arena
   if (hipMalloc(&t->wflip, t->flat * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); t->wflip = nullptr; }
   if (t->wino_floats && hipMalloc(&t->wino_buf, t->wino_floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); t->wino_buf = nullptr; }
   {
-    std::vector<FlipSeg> tab;
-    long begin = 0;
-    for (const Trainer::Flip &f : t->flips) {
-      tab.push_back(FlipSeg{(long)f.off, begin, f.O, f.T, f.I, f.KH, f.KW, f.Z});
-      begin += (long)f.O * f.T * f.I * f.Z;
-    }
-    t->flip_total = begin;
-    if (t->wflip && hipMalloc(&t->flip_tab, tab.size() * sizeof(FlipSeg)) == hipSuccess)
-      hipMemcpy(t->flip_tab, tab.data(), tab.size() * sizeof(FlipSeg), hipMemcpyHostToDevice);
-    else { (void)hipGetLastError(); t->flip_tab = nullptr; }
     std::vector<FlipTile> tiles;
     long tb = 0;
     for (const Trainer::Flip &f : t->flips) {
@@ -2058,47 +1867,40 @@ extern "C" void df_trainer_destroy(df_trainer *h) {
   Trainer *t = as_trainer(h);
   if (t->wflip) hipFree(t->wflip);
   if (t->wino_buf) hipFree(t->wino_buf);
-  if (t->flip_tab) hipFree(t->flip_tab);
   if (t->flip_tiles) hipFree(t->flip_tiles);
-  for (auto e : t->ev) hipEventDestroy(e);
   delete t;
 }
 
 extern "C" int64_t df_trainer_flat_numel(const df_trainer *h) { return h ? (int64_t)as_trainer(h)->flat : 0; }
-extern "C" int df_trainer_num_params(const df_trainer *h) { return h ? (int)as_trainer(h)->spec.size() : 0; }
+extern "C" int df_trainer_num_params(const df_trainer *h) { return h ? (int)as_trainer(h)->params.spec.size() : 0; }
 
 extern "C" int df_trainer_param_info(const df_trainer *h, int i, char *key_out, int key_cap, int64_t *shape4, int *ndim) {
   if (!h) return set_error(DF_ERR_ARG, "trainer_param_info: null handle");
-  const Trainer *t = as_trainer(h);
-  if (i < 0 || i >= (int)t->spec.size()) return set_error(DF_ERR_ARG, "trainer_param_info: index out of range");
-  const PSpec &p = t->spec[i];
-  if (key_out && key_cap > 0) { strncpy(key_out, p.key.c_str(), key_cap - 1); key_out[key_cap - 1] = 0; }
-  if (shape4) for (int d = 0; d < 4; ++d) shape4[d] = p.shape[d];
-  if (ndim) *ndim = p.ndim;
-  return DF_OK;
+  return as_trainer(h)->params.info(i, key_out, key_cap, shape4, ndim, "trainer_param_info");
 }
 
 // dir 0: reference layout (`ref`, device) -> its place in the flat kernel-layout buffer; dir 1: back
 static int relayout(const Trainer &t, const char *key, float *ref, float *flat, int dir, hipStream_t st) {
   if (!key || !ref || !flat) return set_error(DF_ERR_ARG, "trainer pack/unpack: null pointer");
-  auto it = t.index.find(key);
-  if (it == t.index.end()) return set_error(DF_ERR_ARG, "trainer pack/unpack: unexpected key '%s'", key);
-  const PSpec &p = t.spec[it->second];
-  if (p.mode == 0 || p.mode == 1) {
-    const int O = (int)p.shape[0], I = (int)p.shape[1], T = (int)(p.shape[2] * p.shape[3]), Ipad = p.mode == 0 ? (I + 3) / 4 * 4 : I;
-    hipLaunchKernelGGL(relayout_kernel, dim3(nblk((long)O * T * Ipad, 2048)), dim3(TB), 0, st, dir == 0 ? ref : flat + p.off, dir == 0 ? flat + p.off : ref, O, I, T,
-                       Ipad, p.mode, dir);
-  } else if (p.mode == 3) {       // [640][1408] <-> [640][384] + [640][1024]
+  const int at = t.params.find(key);
+  if (at < 0) return set_error(DF_ERR_ARG, "trainer pack/unpack: unexpected key '%s'", key);
+  const ParamInfo &p = t.params.spec[at];
+  const Place &q = t.place[at];
+  if (q.mode == 0 || q.mode == 1) {
+    const int O = (int)p.shape[0], I = (int)p.shape[1], T = (int)(p.shape[2] * p.shape[3]), Ipad = q.mode == 0 ? (I + 3) / 4 * 4 : I;
+    hipLaunchKernelGGL(relayout_kernel, dim3(nblk((long)O * T * Ipad, 2048)), dim3(TB), 0, st, dir == 0 ? ref : flat + q.off, dir == 0 ? flat + q.off : ref, O, I, T,
+                       Ipad, q.mode, dir);
+  } else if (q.mode == 3) {       // [640][1408] <-> [640][384] + [640][1024]
     if (dir == 0) {
-      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 384)), dim3(TB), 0, st, ref, 1408L, flat + p.off, 384L, 640L, 384L);
-      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 1024)), dim3(TB), 0, st, ref + 384, 1408L, flat + p.off2, 1024L, 640L, 1024L);
+      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 384)), dim3(TB), 0, st, ref, 1408L, flat + q.off, 384L, 640L, 384L);
+      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 1024)), dim3(TB), 0, st, ref + 384, 1408L, flat + q.off2, 1024L, 640L, 1024L);
     } else {
-      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 384)), dim3(TB), 0, st, flat + p.off, 384L, ref, 1408L, 640L, 384L);
-      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 1024)), dim3(TB), 0, st, flat + p.off2, 1024L, ref + 384, 1408L, 640L, 1024L);
+      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 384)), dim3(TB), 0, st, flat + q.off, 384L, ref, 1408L, 640L, 384L);
+      hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(640L * 1024)), dim3(TB), 0, st, flat + q.off2, 1024L, ref + 384, 1408L, 640L, 1024L);
     }
   } else {
     const long n = (long)p.numel();
-    hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(n)), dim3(TB), 0, st, dir == 0 ? ref : flat + p.off, n, dir == 0 ? flat + p.off : ref, n, 1L, n);
+    hipLaunchKernelGGL(copy2d_kernel, dim3(nblk(n)), dim3(TB), 0, st, dir == 0 ? ref : flat + q.off, n, dir == 0 ? flat + q.off : ref, n, 1L, n);
   }
   return check_launch("trainer pack/unpack");
 }
@@ -2132,7 +1934,7 @@ extern "C" size_t df_posenet_train_multi_workspace_bytes(const df_trainer *h, in
   for (int i = 0; i < nb; ++i) { key.push_back(B[i]); key.push_back(H[i]); key.push_back(W[i]); }
   auto it = t.ws_cache.find(key);
   if (it != t.ws_cache.end()) return it->second;
-  Step s{&t, nullptr, true, nullptr};
+  Step s(&t, nullptr);
   PoseNetIO io{};
   io.nb = nb; io.B = B; io.H = H; io.W = W; io.M = M; io.dropout = 1;
   posenet_step(s, io);
@@ -2162,8 +1964,8 @@ extern "C" int df_posenet_train_step_multi(df_trainer *h, const float *flat_para
   if (df_posenet_train_multi_workspace_bytes(h, nb, B, H, W, M) > ws_bytes) return set_error(DF_ERR_WORKSPACE, "posenet_train_step: workspace too small");
   rc = check_flips(t, flat_param, (long)param_version, to_stream(stream));
   if (rc != DF_OK) return rc;
-  Step s{&t, to_stream(stream), false, static_cast<char *>(ws)};
-  s.cap = ws_bytes; s.P = flat_param; s.G = flat_grad;
+  Step s(&t, to_stream(stream), Arena(ws, ws_bytes));
+  s.P = flat_param; s.G = flat_grad;
   PoseNetIO io{nb, B, H, W, img, M, cloud, target, model_points, choose, obj, symmetric_host, w, dropout, seed, loss_out, dis_out, new_points, new_target,
                out_r, out_t, out_c, emb};
   posenet_step(s, io);
@@ -2195,37 +1997,20 @@ extern "C" int df_trainer_set_splitk(df_trainer *h, int enable) {
 // low-resolution up-convolutions, folded head layer 1, chosen-pixel up_3, F(4x4,3x3)-domain products), not the reference graph's.
 extern "C" int df_trainer_profile(df_trainer *h, int enable) {
   if (!h) return set_error(DF_ERR_ARG, "trainer_profile: null handle");
-  Trainer *t = as_trainer(h);
-  t->profiling = enable != 0;
-  t->ev_used = 0;
-  t->ev_kind.clear();
-  t->ev_flops.clear();
+  as_trainer(h)->timer.arm(enable != 0);
   return DF_OK;
 }
 
 // after a stream sync: per kind (0 forward, 1 data gradient, 2 weight gradient) the summed launch durations (ms), executed FLOPs, launches
 extern "C" int df_trainer_profile_read(df_trainer *h, double *ms3, double *flops3, int *launches3) {
   if (!h || !ms3 || !flops3 || !launches3) return set_error(DF_ERR_ARG, "trainer_profile_read: null pointer");
-  Trainer *t = as_trainer(h);
-  for (int k = 0; k < 3; ++k) { ms3[k] = 0; flops3[k] = 0; launches3[k] = 0; }
-  for (size_t i = 0; i + 1 < t->ev_used; i += 2) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]) != hipSuccess) return set_error(DF_ERR_LAUNCH, "trainer_profile_read: events not complete");
-    const int k = t->ev_kind[i / 2];
-    ms3[k] += ms; flops3[k] += t->ev_flops[i / 2]; launches3[k] += 1;
-#ifdef DF_DEV
-    static const bool verbose = dev_getenv("DF_PROFILE_VERBOSE") != nullptr;      // dev switch: one line per MFMA launch of the profiled steps
-    if (verbose && i / 2 < t->ev_desc.size())
-      fprintf(stderr, "[df-train-gemm] %s %-44s %9.1f us %7.1f TFLOP/s\n", k == 0 ? "fwd  " : k == 1 ? "dgrad" : "wgrad", t->ev_desc[i / 2].c_str(), ms * 1e3,
-              t->ev_flops[i / 2] / (ms * 1e-3) / 1e12);
-#endif
-  }
-#ifdef DF_DEV
-  t->ev_desc.clear();
-#endif
-  t->ev_used = 0;
-  t->ev_kind.clear();
-  t->ev_flops.clear();
+  LaunchTimer &tm = as_trainer(h)->timer;
+  LaunchSum k3[3];
+  static const char *const tags[3] = {"[df-train-gemm] fwd  ", "[df-train-gemm] dgrad", "[df-train-gemm] wgrad"};   // DF_PROFILE_VERBOSE
+  const int rc = tm.sum(k3, [](const LaunchRecord &r) { return r.kind; }, tags, "trainer_profile_read");
+  for (int k = 0; k < 3; ++k) { ms3[k] = k3[k].ms; flops3[k] = k3[k].flops; launches3[k] = k3[k].launches; }
+  if (rc != DF_OK) return rc;
+  tm.rec.clear();                    // re-arm
   return DF_OK;
 }
 
@@ -2235,7 +2020,7 @@ extern "C" size_t df_refiner_train_workspace_bytes(const df_trainer *h, int B, i
   const std::vector<int> key{B, M};
   auto it = t.ws_cache.find(key);
   if (it != t.ws_cache.end()) return it->second;
-  Step s{&t, nullptr, true, nullptr};
+  Step s(&t, nullptr);
   RefinerIO io{};
   io.B = B; io.M = M;
   refiner_step(s, io);
@@ -2255,8 +2040,8 @@ extern "C" int df_refiner_train_step(df_trainer *h, const float *flat_param, flo
   if (df_refiner_train_workspace_bytes(h, B, M) > ws_bytes) return set_error(DF_ERR_WORKSPACE, "refiner_train_step: workspace too small");
   int rc = check_flips(t, flat_param, (long)param_version, to_stream(stream));
   if (rc != DF_OK) return rc;
-  Step s{&t, to_stream(stream), false, static_cast<char *>(ws)};
-  s.cap = ws_bytes; s.P = flat_param; s.G = flat_grad;
+  Step s(&t, to_stream(stream), Arena(ws, ws_bytes));
+  s.P = flat_param; s.G = flat_grad;
   RefinerIO io{B, M, points, emb, target, model_points, obj, symmetric_host, dis_out, new_points, new_target};
   refiner_step(s, io);
   if (s.err != DF_OK) return s.err;

@@ -35,3 +35,27 @@ def test_trainer_tables_follow_the_reference_state_dicts():
             assert 0 < a < b
         L.df_trainer_destroy(h)
     assert not L.df_trainer_create(2, 10, 10)
+
+
+def _net_spec(h):
+    L = _lib.lib()
+    key, shape, ndim = ctypes.create_string_buffer(256), (ctypes.c_int64 * 4)(), ctypes.c_int()
+    out = []
+    for i in range(L.df_net_num_params(h)):
+        assert L.df_net_param_info(h, i, key, 256, shape, ctypes.byref(ndim)) == 0
+        out.append((key.value.decode(), tuple(int(shape[d]) for d in range(ndim.value))))
+    return out
+
+
+def test_engine_and_trainer_share_one_parameter_list():
+    # a checkpoint written by the trainer (tools/train.py) is loaded by the engine (PoseNet / PoseRefineNet): same keys, shapes, order
+    L = _lib.lib()
+    for kind, create in ((0, L.df_posenet_create), (1, L.df_refiner_create)):
+        for K in (13, 21):
+            n, t = create(1000, K), L.df_trainer_create(kind, 1000, K)
+            assert n and t
+            a, b = _net_spec(n), _spec(t)
+            assert len(a) == (77 if kind == 0 else 24)
+            assert a == b
+            L.df_net_destroy(n)
+            L.df_trainer_destroy(t)
