@@ -617,8 +617,10 @@ static void posenet_points(Ctx &c, int B, int N, int Npad, const float *cloud, c
     c.pconv(point_gemm(pf, 384, 0, 64, c.w("feat.conv2.weight"), c.w("feat.conv2.bias"), pf, 384, 128, 128, rows, ACT_RELU));
     c.pconv(point_gemm(pf, 384, 64, 64, c.w("feat.e_conv2.weight"), c.w("feat.e_conv2.bias"), pf, 384, 256, 128, rows, ACT_RELU));
   }
+  if (!sel) c.tap("pf", pf, B, Npad, 384, 1);
   float *x5 = c.f((size_t)rows * 512);
   c.pconv(point_gemm(pf, 384, 128, 256, c.w("feat.conv5.weight"), c.w("feat.conv5.bias"), x5, 512, 0, 512, rows, ACT_RELU));
+  if (!sel) c.tap("x5", x5, B, Npad, 512, 1);
   // conv6 + ReLU + AvgPool1d(N): the 1024-wide activation is consumed only by the mean, so it never
   // leaves the GEMM's registers -- per-wave column sums, then a tiny deterministic reduction
   ConvParams p6 = point_gemm(x5, 512, 0, 512, c.w("feat.conv6.weight"), c.w("feat.conv6.bias"), nullptr, 1024, 0, 1024, rows, ACT_RELU);
@@ -657,17 +659,20 @@ static void posenet_points(Ctx &c, int B, int N, int Npad, const float *cloud, c
     p.rows_per_group = Npad; p.rows_valid = N; p.bias_group_ld = 1920;
     c.pconv(p);
   }
+  c.tap("h1", h1, B, Npad, 1920, 1);
   float *h2 = c.f((size_t)rows * 768), *h3 = c.f((size_t)rows * 384);
   {
     ConvParams p = point_gemm(h1, 1920, 0, 640, c.w("head2.w"), c.w("head2.bias"), h2, 768, 0, 256, rows, ACT_RELU);
     p.zcount = 3; p.z_in_coff = 640; p.z_wgt = 256 * 640; p.z_bias = 256; p.z_out_coff = 256;
     c.pconv(p);
   }
+  c.tap("h2", h2, B, Npad, 768, 1);
   {
     ConvParams p = point_gemm(h2, 768, 0, 256, c.w("head3.w"), c.w("head3.bias"), h3, 384, 0, 128, rows, ACT_RELU);
     p.zcount = 3; p.z_in_coff = 256; p.z_wgt = 128 * 256; p.z_bias = 128; p.z_out_coff = 128;
     c.pconv(p);
   }
+  c.tap("h3", h3, B, Npad, 384, 1);
   if (c.live())
     launch_head_final(h3, c.w("conv4_r.weight"), c.w("conv4_r.bias"), c.w("conv4_t.weight"), c.w("conv4_t.bias"),
                       c.w("conv4_c.weight"), c.w("conv4_c.bias"), obj, n.num_obj, out_r, out_t, out_c, B, N, Npad, c.st);
@@ -754,20 +759,26 @@ static void refiner_iterate(Ctx &c, const RefinerBufs &r, int B, int N, int Npad
     if (c.live()) launch_cloud_conv1(cloud, rt, c.w("feat.conv1.weight"), c.w("feat.conv1.bias"), r.pf, 384, B, N, Npad, c.st);
     c.pconv(point_gemm(r.pf, 384, 0, 64, c.w("feat.conv2.weight"), c.w("feat.conv2.bias"), r.pf, 384, 64, 128, rows, ACT_RELU));
   }
+  // (taps: every iteration overwrites them, so after a call they hold its last iteration)
+  c.tap("rf_pf", r.pf, B, Npad, 384, 1);
   {
     ConvParams p = point_gemm(r.pf, 384, 0, 192, c.w("feat.conv5.wx"), nullptr, r.x5, 512, 0, 512, rows, ACT_RELU);
     p.res = r.e5; p.res_ld = 512;
     c.pconv(p);
   }
+  c.tap("rf_x5", r.x5, B, Npad, 512, 1);
   ConvParams p6 = point_gemm(r.x5, 512, 0, 512, c.w("feat.conv6.weight"), c.w("feat.conv6.bias"), nullptr, 1024, 0, 1024, rows, ACT_RELU);
   p6.rows_per_group = Npad; p6.rows_valid = N; p6.colsum = r.partial;
   c.pconv(p6);
   if (c.live()) launch_colsum_finish(r.partial, r.prow / B, r.apx, B, 1024, N, c.st);
+  c.tap("rf_apx", r.apx, B, 1024, 1, 1);
   // FC towers 1024 -> 512 -> 128 for r and t (lib/network.py:191-196): one row per object
   if (c.live()) {
     launch_fc_rows(r.apx, 1024, 0, c.w("fc1.w"), c.w("fc1.bias"), r.f1, 1024, B, 1024, 1024, 1, 1, c.st);
     launch_fc_rows(r.f1, 1024, 512, c.w("fc2.w"), c.w("fc2.bias"), r.f2, 256, B, 512, 128, 2, 1, c.st);
   }
+  c.tap("rf_f1", r.f1, B, 1024, 1, 1);
+  c.tap("rf_f2", r.f2, B, 256, 1, 1);
   if (c.live()) {
     launch_refiner_tail(r.f2, c.w("conv3_r.weight"), c.w("conv3_r.bias"), c.w("conv3_t.weight"), c.w("conv3_t.bias"), obj,
                         c.net->num_obj, out_r, out_t, state, rt_next, pose_out, B, c.st);

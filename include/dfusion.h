@@ -407,7 +407,15 @@ int df_gemm_route(int n, int k, int epilogue);
 /* Debug taps: with df_net_debug_taps(net, 1) armed, a single-bucket PoseNet forward keeps device copies of its named
  * intermediates (channels-last): "stem" [B][H/2][W/2][64] (conv1 + ReLU, lib/extractors.py:115-117), "layer1".."layer4",
  * "psp" [B][H/8][W/8][1024] (lib/pspnet.py:20-24), "up_1" [B][H/4][W/4][256], "up_2" [B][H/2][W/2][64], "up_3" [B][Npad][64]
- * (rows of the chosen pixels only, Npad = num_points rounded up to 128), "ap_x" [B][1024] (lib/network.py:65).  It allocates, so
+ * (rows of the chosen pixels only, Npad = num_points rounded up to 128), "ap_x" [B][1024] (lib/network.py:65).  The full PoseNet
+ * forward (not the pose-selection path of df_estimate_poses) also keeps the point layers and heads, point-major [B][Npad][C]:
+ * "pf" [..][384] = x1 64 | e1 64 | x2 128 | e2 128 (pointfeat_1 | pointfeat_2, lib/network.py:57-62), "x5" [..][512] (conv5 + ReLU),
+ * "h1" [..][1920] = conv1_r | conv1_t | conv1_c (640 each, + ReLU), "h2" [..][768] = conv2 r | t | c (256 each), "h3" [..][384] =
+ * conv3 r | t | c (128 each).  A refiner handle keeps its last refine iteration (the only one of df_refiner_forward): "rf_pf"
+ * [B][Npad][384] = x1 64 | x2 128 | e1 64 | e2 128 (NOT PoseNet's order; lib/network.py:160-163 reads x1 | e1 | x2 | e2),
+ * "rf_x5" [B][Npad][512], "rf_apx" [B][1024] (the AvgPool1d of conv6 + ReLU), "rf_f1" [B][1024] = conv1_r | conv1_t (+ ReLU),
+ * "rf_f2" [B][256] = conv2_r | conv2_t (+ ReLU).  Point rows N .. Npad-1 of an object's block are padding, not part of the
+ * contract.  It allocates, so
  * it is for debugging / layer-level parity tests only (not under hipGraph capture).  df_net_debug_tap_read copies a tap to dst
  * (host or device, `cap` floats) after the caller has synchronised the stream and returns its shape; dst == NULL only queries
  * the shape.  df_net_debug_taps(net, 0) frees the copies. */

@@ -1,0 +1,112 @@
+"""Power of the engine's fp64 tests (tests/test_engine_fp64_gpu.py), on the CPU oracle alone (tests/oracle_fwd.py):
+  * every fixture is well conditioned (fp64 and fp32 pick the same most-confident point, by a gap well above their difference), and the
+    fp32 reference holds its own bound, layer-local and end to end;
+  * defects a kernel could carry, emulated in fp64 in the stage they touch, break that stage's bound at least 3x: a split-GEMM term pair
+    left out (mid*mid, in head 1; the other routed stages below), a mean over Npad instead of N (ap_x and the refiner's conv6), the
+    neighbouring object's global-feature bias or the next class's conv4 rows, and the last output row of a Winograd-domain stage lost.
+A GPU result with such a defect fails the GPU test in that stage.
+
+What the rule cannot separate: a mid*mid term pair is at most 2^-18 of a product (|mid| <= 2^-9 of its operand) and about 2^-19 on average,
+with random sign, so leaving it out moves a K = 384 .. 1024 product by 1e-6 .. 3e-6 relative: the same size as the fp32 reference's own
+rounding.  Measured on the 120 x 160 fixture, the defect is 3.4x the bound in head 1 (asserted below), but only 2.8x in head 2, 1.9x in up_1,
+0.6x in the PSP fold and 0.9x / 2.0x in ap_x / the refiner's conv6, whose mean over the points averages the per-point change down to 8e-8
+while the C x fp32 term of the bound stays.  Tightening those floors cannot help (the C x fp32 term binds, not the floor).  The emulation
+is the lower edge: the split kernel itself, built once without its mid*mid pair, failed the GPU test on the MI355X in the PSP fold (2.4e-6
+relative, 1.7x the bound: the kernel also drops it in the pooled-prior product), up_1 (2.2x), head 1 (4.2x), head 2 (3.8x), on the worst
+channels of ap_x and the refiner's conv6, and end to end on emb / r / c.  The product-level test of the split kernel
+(tests/test_split_gemm_engine_gpu.py: within 1.25x the fp32 kernel's error at every routed shape) stays the net for layer4's own bf16 x 6
+product inside a Winograd-domain stage."""
+import functools
+
+import pytest
+import torch
+
+import oracle_fwd as of
+
+F64, F32 = torch.float64, torch.float32
+MIN_BREAK = 3.0
+
+
+@functools.lru_cache(maxsize=None)
+def _chain(name):
+    """(fixture, fp64 / fp32 state dicts of both nets, inputs, fp64 taps of every PoseNet and refiner stage, chained)."""
+    f, sdp, sdr, b = of.fixture(name)
+    sp, sr = (of.to_sd(sdp, F64), of.to_sd(sdp, F32)), (of.to_sd(sdr, F64), of.to_sd(sdr, F32))
+    inputs = {k: torch.from_numpy(b[k]) for k in ("img", "cloud", "choose", "obj")}
+    with torch.no_grad():
+        T = of.forward_taps(sp[0], inputs, of.POSENET_STAGES)
+        # the refiner on the cloud as it is and PoseNet's emb (stand-alone PoseRefineNet.forward)
+        T = of.forward_taps(sr[0], dict(inputs, rf_x=inputs["cloud"], rf_emb=T["emb"]), of.REFINER_STAGES, T)
+    return f, sp, sr, dict(inputs, rf_x=inputs["cloud"], rf_emb=T["emb"]), T
+
+
+def _refs(name, stage):
+    """(ref64, ref32) of one stage on the fp64 chain's own input taps: {output: (r64, r32)}."""
+    f, sp, sr, inputs, T = _chain(name)
+    sd = sr if stage.startswith("rf_") else sp
+    with torch.no_grad():
+        return of.layer_local(sd[0], sd[1], T, inputs, (stage,))
+
+
+def _breaks(name, stage, out, bad):
+    (r64, r32), = [v for k, v in _refs(name, stage).items() if k == out]
+    ratio = of.bound_ratio(out, bad, r64, r32, of.FLOORS[out])[4]
+    print(f"{name}: {stage} -> {out}: the defect is {ratio:.1f}x the bound")
+    assert ratio >= MIN_BREAK, f"{name}: {out}: the emulated defect is only {ratio:.2f}x the bound (floor {of.FLOORS[out]})"
+
+
+@pytest.mark.parametrize("name", list(of.FIXTURES))
+def test_fixture_is_well_conditioned_and_the_fp32_reference_holds_its_bound(name):
+    f, sdp, sdr, b = of.fixture(name)
+    e64, e32, dt = of.oracle_pair(sdp, sdr, b)
+    of.conditioning(e64, e32)
+    for k in ("emb", "r", "t", "c"):
+        of.check("e2e_" + k, of.channel_view(k, e32[k]), of.channel_view(k, e64[k]), of.channel_view(k, e32[k]), floor=of.E2E_FLOORS[k])
+    f, sp, sr, inputs, T = _chain(name)
+    for stage in of.POSENET_STAGES + of.REFINER_STAGES:
+        for k, (r64, r32) in _refs(name, stage).items():
+            of.check(k, of.channel_view(k, r32), of.channel_view(k, r64), of.channel_view(k, r32), floor=of.FLOORS[k])
+    print(f"{name}: oracle end to end {dt:.1f} s")
+
+
+MIDMID = "k21_n1000_120x160_b2"
+# the stages where a lost mid*mid pair exceeds 3x the bound (the module docstring gives the others' measured ratios)
+MIDMID_SEPARABLE = ["h1"]
+
+
+@pytest.mark.parametrize("stage", MIDMID_SEPARABLE)
+def test_a_dropped_mid_mid_term_pair_breaks_the_bound(stage):
+    f, sp, sr, inputs, T = _chain(MIDMID)
+    sd = sp[0]
+    with torch.no_grad():
+        bad = {"h1": lambda: of.stage_h1(sd, T["pf"], T["ap_x"], drop_midmid=True),
+               "h2": lambda: of.stage_h(sd, 2, T["h1"], drop_midmid=True)}[stage]()
+    _breaks(MIDMID, stage, stage, bad)
+
+
+@pytest.mark.parametrize("name", ["k13_n500_80x80_b3", "k21_n129_80x120"])
+@pytest.mark.parametrize("stage", ["ap_x", "rf_apx"])
+def test_a_mean_over_npad_breaks_the_bound(name, stage):
+    f, sp, sr, inputs, T = _chain(name)
+    with torch.no_grad():
+        bad = of.stage_apx((sr if stage == "rf_apx" else sp)[0], T["rf_x5" if stage == "rf_apx" else "x5"], over_npad=True)
+    _breaks(name, stage, stage, bad)
+
+
+def test_the_neighbouring_objects_bias_or_rows_break_the_bound():
+    name = "k13_n500_80x80_b3"
+    f, sp, sr, inputs, T = _chain(name)
+    with torch.no_grad():
+        _breaks(name, "h1", "h1", of.stage_h1(sp[0], T["pf"], T["ap_x"], roll_objects=True))
+        bad = of.stage_out(sp[0], T["h3"], inputs["obj"], obj_shift=1)
+    for k in ("r", "t", "c"):
+        _breaks(name, "out", k, bad[k])
+
+
+@pytest.mark.parametrize("layer", [2, 3, 4])
+def test_a_lost_winograd_edge_row_breaks_the_bound(layer):
+    name = "k21_n1000_240x320"            # layer2 .. layer4 all on F(4x4,3x3) (test_engine_fp64_gpu asserts the route coverage)
+    f, sp, sr, inputs, T = _chain(name)
+    with torch.no_grad():
+        bad = of.stage_layer(sp[0], layer, T[f"layer{layer - 1}"], zero_last_row=True)
+    _breaks(name, f"layer{layer}", f"layer{layer}", bad)
