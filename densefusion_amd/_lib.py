@@ -81,6 +81,7 @@ SIGNATURES = {
     "df_conv2d_wgrad_multi_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc), _i, _vp, _vp, _vp]),
     "df_conv2d_wgrad_nhwc_multi": (_i, [ctypes.POINTER(ConvDesc), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "df_conv_last_splitk": (_i, []),
+    "df_conv_route": (_i, [ctypes.POINTER(ConvDesc), _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "df_conv3x3_winograd_scratch_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "df_conv3x3_winograd_nhwc": (_i, [ctypes.POINTER(ConvDesc), _vp, ctypes.c_size_t, _vp]),
     "df_wino_route": (_i, [_i, _i, _i, _i, _i]),

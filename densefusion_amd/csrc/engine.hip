@@ -362,13 +362,13 @@ struct Ctx : Arena {
       pc.wpl = reinterpret_cast<const char *>(pl->ptr) + (p.wgt - it->first) * 2;
       pc.wpl_stride = pl->stride;
     }
-    int on_bf16 = 0;
-    const int rc = launch_conv(pc, st, nullptr, &on_bf16);
+    ConvRoute taken;
+    const int rc = launch_conv(pc, st, &taken);
     if (n.timer.on) {
       LaunchRecord r = launch_record(0, conv_flops(p), p);
       r.bytes = conv_bytes(p);
       r.useful = r.flops * useful;
-      r.bf16 = on_bf16 != 0;
+      r.bf16 = taken.kernel == CONV_BF16;
       n.timer.end(st, r);
     }
     if (rc != DF_OK) err = rc;
@@ -1083,24 +1083,27 @@ extern "C" int df_estimate_poses(df_net *pn, df_net *rf, int B, int H, int W, co
 }
 
 static int conv_desc_to_params(const df_conv_desc *d, ConvParams &p, const char *what);
-
-static thread_local int t_last_splitk = 1;
-extern "C" int df_conv_last_splitk(void) { return t_last_splitk; }
-
-extern "C" int df_conv2d_nhwc(const df_conv_desc *d, df_stream_t stream) {
-  if (!d) return set_error(DF_ERR_ARG, "conv2d_nhwc: null descriptor");
-  if (d->KH != d->KW) return set_error(DF_ERR_ARG, "conv2d_nhwc: square kernels only");
-  if (d->act == ACT_PRELU && !d->prelu) return set_error(DF_ERR_ARG, "conv2d_nhwc: PReLU needs a slope");
-  ConvParams p;
+static void desc_fields(const df_conv_desc *d, ConvParams &p) {
   p.in = d->in; p.wgt = d->wgt; p.bias = d->bias; p.res = d->res; p.prelu = d->prelu; p.out = d->out;
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_ld = d->in_ld; p.in_coff = d->in_coff;
   p.OH = d->OH; p.OW = d->OW; p.Cout = d->Cout; p.out_ld = d->out_ld; p.out_coff = d->out_coff;
   p.res_ld = d->res_ld; p.res_coff = d->res_coff;
   p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.act = d->act;
-  if (p.OH != conv_out(p.H, p.KH, p.stride, p.pad, p.dil) || p.OW != conv_out(p.W, p.KW, p.stride, p.pad, p.dil))
-    return set_error(DF_ERR_ARG, "conv2d_nhwc: OH/OW do not match the convolution geometry");
+}
+
+static thread_local int t_last_splitk = 1;
+extern "C" int df_conv_last_splitk(void) { return t_last_splitk; }
+
+extern "C" int df_conv2d_nhwc(const df_conv_desc *d, df_stream_t stream) {
+  ConvParams p;
+  int rc = conv_desc_to_params(d, p, "conv2d_nhwc");
+  if (rc != DF_OK) return rc;
+  if (p.act == ACT_PRELU && !p.prelu) return set_error(DF_ERR_ARG, "conv2d_nhwc: PReLU needs a slope");
   p.splitk_ws = static_cast<float *>(d->splitk_ws); p.splitk_ws_bytes = d->splitk_ws ? d->splitk_ws_bytes : 0;
-  return launch_conv(p, to_stream(stream), &t_last_splitk);
+  ConvRoute taken;
+  rc = launch_conv(p, to_stream(stream), &taken);
+  t_last_splitk = taken.splitk;
+  return rc;
 }
 
 // buckets of a multi-bucket convolution / weight-gradient call: pixel rows concatenated in bucket order in both operands
@@ -1126,11 +1129,35 @@ extern "C" int df_conv2d_nhwc_multi(const df_conv_desc *d, int nb, const int *B,
   if (rc != DF_OK) return rc;
   if (d->act == ACT_PRELU && !d->prelu) return set_error(DF_ERR_ARG, "conv2d_nhwc_multi: PReLU needs a slope");
   ConvParams p;
-  p.in = d->in; p.wgt = d->wgt; p.bias = d->bias; p.res = d->res; p.prelu = d->prelu; p.out = d->out;
-  p.Cin = d->Cin; p.in_ld = d->in_ld; p.in_coff = d->in_coff; p.Cout = d->Cout; p.out_ld = d->out_ld; p.out_coff = d->out_coff;
-  p.res_ld = d->res_ld; p.res_coff = d->res_coff;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.act = d->act;
+  desc_fields(d, p);
+  p.B = p.H = p.W = p.OH = p.OW = 1;      // (the buckets carry the geometry)
   return launch_conv_multi(p, nb, segs.data(), to_stream(stream));
+}
+
+// host only: the fp32 route of a df_conv2d_nhwc (nb = 0) / df_conv2d_nhwc_multi launch (see include/dfusion.h)
+extern "C" int df_conv_route(const df_conv_desc *d, int nb, const int *B, const int *H, const int *W, int first, int up, int zcount,
+                             int groups, int *route) {
+  if (!d || !route) return set_error(DF_ERR_ARG, "conv_route: null pointer");
+  std::vector<WgradSeg> segs;
+  if (nb > 0) {
+    const int rc = make_segs(d, nb, B, H, W, segs, "conv_route");
+    if (rc != DF_OK) return rc;
+  }
+  ConvParams p;
+  desc_fields(d, p);
+  if (nb > 0) p.B = p.H = p.W = p.OH = p.OW = 1;      // as df_conv2d_nhwc_multi
+  p.splitk_ws = static_cast<float *>(d->splitk_ws); p.splitk_ws_bytes = d->splitk_ws ? d->splitk_ws_bytes : 0;
+  p.up = up;
+  p.zcount = zcount;
+  if (groups > 0) {          // a column-sum launch over row groups: its partial-sum buffer is never touched here
+    p.rows_per_group = p.rows_valid = groups;
+    p.colsum = p.out;
+  }
+  ConvRoute r;
+  const int rc = conv_route(p, nb, segs.data(), first, r);
+  const int v[7] = {r.kernel, r.bm, r.bn, r.loader, r.splitk, r.wgroup, r.nseg};
+  for (int i = 0; i < 7; ++i) route[i] = v[i];
+  return rc;
 }
 
 extern "C" size_t df_conv2d_wgrad_multi_workspace_bytes(const df_conv_desc *d, int nb, const int *B, const int *H, const int *W) {
@@ -1228,11 +1255,7 @@ __global__ void flip_transpose_kernel(const float *__restrict__ w, float *__rest
 static int conv_desc_to_params(const df_conv_desc *d, ConvParams &p, const char *what) {
   if (!d) return set_error(DF_ERR_ARG, "%s: null descriptor", what);
   if (d->KH != d->KW) return set_error(DF_ERR_ARG, "%s: square kernels only", what);
-  p.in = d->in; p.wgt = d->wgt; p.bias = d->bias; p.res = d->res; p.prelu = d->prelu; p.out = d->out;
-  p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_ld = d->in_ld; p.in_coff = d->in_coff;
-  p.OH = d->OH; p.OW = d->OW; p.Cout = d->Cout; p.out_ld = d->out_ld; p.out_coff = d->out_coff;
-  p.res_ld = d->res_ld; p.res_coff = d->res_coff;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.act = d->act;
+  desc_fields(d, p);
   if (p.OH != conv_out(p.H, p.KH, p.stride, p.pad, p.dil) || p.OW != conv_out(p.W, p.KW, p.stride, p.pad, p.dil))
     return set_error(DF_ERR_ARG, "%s: OH/OW do not match the convolution geometry", what);
   return DF_OK;
@@ -1256,7 +1279,10 @@ extern "C" int df_conv2d_dgrad_nhwc(const df_conv_desc *d, const float *dy, floa
   if (q.pad < 0) return set_error(DF_ERR_ARG, "conv2d_dgrad: padding larger than the kernel reach is not supported");
   if (accumulate) { q.res = dx; q.res_ld = f.in_ld; q.res_coff = f.in_coff; }
   q.splitk_ws = static_cast<float *>(d->splitk_ws); q.splitk_ws_bytes = d->splitk_ws ? d->splitk_ws_bytes : 0;
-  return launch_conv(q, st, &t_last_splitk);
+  ConvRoute taken;
+  rc = launch_conv(q, st, &taken);
+  t_last_splitk = taken.splitk;
+  return rc;
 }
 
 extern "C" size_t df_conv2d_wgrad_workspace_bytes(const df_conv_desc *d) {

@@ -31,42 +31,47 @@ struct ConvParams {
   int rows_per_group = 0, rows_valid = 0, bias_group_ld = 0;
   // blockIdx.z "head" groups (the r/t/c towers): per-z element offsets
   int zcount = 1;
-  int ngroup = 0;   // column tiles per L2-resident weight group (0 = one group); set by launch_conv
   long z_in_coff = 0, z_wgt = 0, z_bias = 0, z_out_coff = 0;
-  // magic pairs for the kernels' divisions by OH*OW and OW (set by the launchers)
-  // split-K (training path only: opt-in through a caller-provided scratch, df_conv_desc.splitk_ws): launches that would fill less than
-  // half the chip cut their reduction into `splitk` ranges (blockIdx.z), partial sums go to the scratch and a fixed-order reduce
-  // kernel adds them and applies bias / residual / activation (deterministic).  splitk is set by launch_conv.
   // bf16 weight planes of `wgt` (csrc/split_gemm.hip): term p of wgt[i] at wpl[p * wpl_stride + i] (bf16 elements), cut by the weights'
   // owner once per parameter load (the inference engine, for the layers split_route takes).  null: fp32 kernels only
   const void *wpl = nullptr;
   long wpl_stride = 0;
+  // split-K (training path only: opt-in through a caller-provided scratch, df_conv_desc.splitk_ws): launches that would fill less than
+  // half the chip cut their reduction into ranges (blockIdx.z), partial sums go to the scratch and a fixed-order reduce kernel adds them
+  // and applies bias / residual / activation (deterministic).  How many ranges: the launch plan (csrc/igemm.hip plan_conv).
   float *splitk_ws = nullptr;
   size_t splitk_ws_bytes = 0;
-  int splitk = 1;
-  // tile decode of the v4 kernel without integer divisions (set by launch_conv): row-tile count, tiles per full weight group, and
-  // division magics (make_fdiv) for the group size, the widths of a full / the last group and rows_per_group
-  int tiles_m = 0, tile_gn = 0, tile_full = 0;
-  unsigned full_magic = 0, gn_magic = 0, gl_magic = 0, rpg_magic = 0;
-  int full_sh = 0, gn_sh = 0, gl_sh = 0, rpg_sh = 0;
-  unsigned ohw_magic = 0, ow_magic = 0;
-  int ohw_sh = 0, ow_sh = 0;
 };
 
-// number of colsum partial rows a launch with these params writes (so callers can size the buffer)
+// number of colsum partial rows a column-sum launch with these params writes (so callers can size the buffer before p.colsum is set)
 int conv_colsum_rows(const ConvParams &p);
 // FLOPs (2*MAC) of the launch, algorithmic (no padding)
 double conv_flops(const ConvParams &p);
 // algorithmic HBM bytes (inputs, weights, outputs and residual touched once)
 double conv_bytes(const ConvParams &p);
-// splitk_used: the K ranges the launch was cut into; on_bf16: 1 when the bf16 x 6 kernel took it (csrc/split_gemm.hip), 0 on the fp32 kernels
-int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used = nullptr, int *on_bf16 = nullptr);
 
 // One crop-size bucket of a multi-bucket launch: B maps of H x W (outputs OH x OW) whose input / output pixel rows start at
 // in_row0 / out_row0 of the concatenated buffers
 struct WgradSeg { int B, H, W, OH, OW; long in_row0, out_row0; };
+
+// What one launch of launch_conv / launch_conv_multi takes (csrc/igemm.hip plan_conv; df_conv_route reports it)
+enum ConvKernel { CONV_NONE = 0, CONV_V1 = 1, CONV_V2 = 2, CONV_V4 = 3, CONV_V4_COLSUM = 4, CONV_V4_MULTI = 5, CONV_BF16 = 6 };
+struct ConvRoute {
+  int kernel = CONV_NONE;   // ConvKernel (CONV_NONE: nothing to compute)
+  int bm = 0, bn = 0;       // workgroup tile
+  int loader = 0;           // v4: 0 general, 1 plain GEMM, 2 tap-uniform
+  int splitk = 1;           // K ranges
+  int wgroup = 0;           // v2 / v4: column tiles per L2-resident weight group
+  int nseg = 1;             // buckets of the call this launch covers
+};
+// The fp32 route of the launch that starts at bucket `first` of a launch_conv_multi call (nseg > 0), or of launch_conv(p) (nseg = 0):
+// DF_OK or the DF_ERR_* code the call fails with.  Host only (no HIP calls).
+int conv_route(const ConvParams &p, int nseg, const WgradSeg *segs, int first, ConvRoute &r);
+// taken: the route of the launch (kernel CONV_BF16 when the bf16 x 6 kernel took it, csrc/split_gemm.hip)
+int launch_conv(const ConvParams &p, hipStream_t st, ConvRoute *taken = nullptr);
+
 // The same convolution over SEVERAL crop-size buckets whose pixel rows are concatenated in p.in / p.out / p.res (p.B / H / W / OH / OW are
-// ignored): ONE launch of the product kernel (a workgroup's tile lies inside one bucket), CONV_MAX_BUCKETS buckets per launch.  Same
+// ignored): ONE launch of the product kernel (a workgroup's tile lies inside one bucket) per CONV_MAX_BUCKETS buckets.  Same
 // sums in the same order per output element as per-bucket launch_conv calls without split-K.  Shapes the multi-bucket instantiations
 // do not cover (input dilation, grouped / column-sum launches) fall back to one launch per bucket.
 constexpr int CONV_MAX_BUCKETS = 16;

@@ -68,6 +68,18 @@ void make_fdiv(long d, unsigned &magic, int &sh) {
   sh = L - 1;
 }
 
+// Kernel arguments of v2 / v4: the caller's descriptor (a split-K launch: output redirected to the scratch, epilogue left to the reduce)
+// and what plan_conv derives from it.  Tile decode without integer divisions: row-tile count, column tiles per L2-resident weight group,
+// tiles per full group, and division magics (make_fdiv) for a full group, the widths of a full / the last group, rows_per_group, OH*OW and OW
+struct ConvArgs : ConvParams {
+  int splitk = 1;
+  int tiles_m = 0, tile_gn = 0, tile_full = 0;
+  unsigned full_magic = 0, gn_magic = 0, gl_magic = 0, rpg_magic = 0;
+  int full_sh = 0, gn_sh = 0, gl_sh = 0, rpg_sh = 0;
+  unsigned ohw_magic = 0, ow_magic = 0;
+  int ohw_sh = 0, ow_sh = 0;
+};
+
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 __global__ __launch_bounds__(256) void igemm_f32_kernel(const ConvParams p) {
   static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
@@ -256,7 +268,7 @@ __global__ __launch_bounds__(256) void igemm_f32_kernel(const ConvParams p) {
 // Same k order and MFMA sequence per output element as v4: which of the two a launch takes never changes a bit of its result.
 // ------------------------------------------------------------------------------------------------
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BKT>
-__global__ __launch_bounds__(256) void igemm_f32_v2_kernel(const ConvParams p) {
+__global__ __launch_bounds__(256) void igemm_f32_v2_kernel(const ConvArgs p) {
   static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
   constexpr int TM = WM / 32, TN = WN / 32;
@@ -287,13 +299,12 @@ __global__ __launch_bounds__(256) void igemm_f32_v2_kernel(const ConvParams p) {
     wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
   }
   // column-tile groups: when the weight operand is too big for an XCD's L2 (4 MB), the tiles are walked group by group
-  // (p.ngroup column tiles, all row blocks, next group ...) so that the group's weight slice stays L2-resident while the
+  // (p.tile_gn column tiles, all row blocks, next group ...) so that the group's weight slice stays L2-resident while the
   // activation rows stream through once per group instead of every column tile missing on both operands
   int n_tile, m_tile;
   {
-    const int GN = p.ngroup > 0 && p.ngroup < tiles_n ? p.ngroup : tiles_n;
-    const int tiles_m = (int)(gridDim.x / tiles_n);
-    const int full = tiles_m * GN;
+    const int GN = p.tile_gn;
+    const int full = p.tile_full;
     const int g = wgid / full, rem = wgid - g * full;
     const int gw = min(GN, tiles_n - g * GN);
     m_tile = rem / gw;
@@ -535,7 +546,7 @@ __global__ __launch_bounds__(256) void igemm_f32_v2_kernel(const ConvParams p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) csum[e] += __shfl_xor(csum[e], d);
     if (lane < LPR && nok)
-      *reinterpret_cast<f32x4 *>(p.colsum + ((size_t)z * (gridDim.x / tiles_n) * WAVES_M + (size_t)m_tile * WAVES_M + wm) * p.Cout + n) = csum;
+      *reinterpret_cast<f32x4 *>(p.colsum + ((size_t)z * p.tiles_m * WAVES_M + (size_t)m_tile * WAVES_M + wm) * p.Cout + n) = csum;
   }
   DF_TRACE(3);
 }
@@ -572,7 +583,7 @@ struct ConvBuckets {
 };
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BKT, int OCC, int LOADER, bool COLSUM, bool MULTI>
-__device__ __forceinline__ void igemm_f32_v4_body(const ConvParams &pk, const ConvBuckets *tab) {
+__device__ __forceinline__ void igemm_f32_v4_body(const ConvArgs &pk, const ConvBuckets *tab) {
   constexpr bool PURE = LOADER == 1, TAPU = LOADER == 2;
   static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;
@@ -598,7 +609,7 @@ __device__ __forceinline__ void igemm_f32_v4_body(const ConvParams &pk, const Co
     const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
     wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
   }
-  ConvParams pl;
+  ConvArgs pl;
   if constexpr (MULTI) {
     pl = pk;
     int g = 0;
@@ -612,12 +623,12 @@ __device__ __forceinline__ void igemm_f32_v4_body(const ConvParams &pk, const Co
     pl.out = pk.out + tab->out_row0[g] * pk.out_ld;
     if (pk.res) pl.res = pk.res + tab->out_row0[g] * pk.res_ld;
   }
-  const ConvParams &p = MULTI ? pl : pk;
+  const ConvArgs &p = MULTI ? pl : pk;
   const int M = p.B * p.OH * p.OW;
   const int K = p.KH * p.KW * p.Cin;
   const int tiles_n = (p.Cout + BN - 1) / BN;
   // column-tile groups: when the weight operand is too big for an XCD's L2 (4 MB), the tiles are walked group by group
-  // (p.ngroup column tiles, all row blocks, next group ...) so that the group's weight slice stays L2-resident while the
+  // (p.tile_gn column tiles, all row blocks, next group ...) so that the group's weight slice stays L2-resident while the
   // activation rows stream through once per group instead of every column tile missing on both operands
   // (divisions by host-made magics: the prologue is issue time the SIMD's other waves lose)
   int n_tile, m_tile;
@@ -945,11 +956,11 @@ __device__ __forceinline__ void igemm_f32_v4_body(const ConvParams &pk, const Co
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BKT, int OCC, int LOADER, bool COLSUM>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void igemm_f32_v4_kernel(const ConvParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void igemm_f32_v4_kernel(const ConvArgs p) {
   igemm_f32_v4_body<BM, BN, WAVES_M, WAVES_N, BKT, OCC, LOADER, COLSUM, false>(p, nullptr);
 }
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BKT, int OCC, int LOADER>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void igemm_f32_v4_multi_kernel(const ConvParams p, const ConvBuckets tab) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void igemm_f32_v4_multi_kernel(const ConvArgs p, const ConvBuckets tab) {
   igemm_f32_v4_body<BM, BN, WAVES_M, WAVES_N, BKT, OCC, LOADER, false, true>(p, &tab);
 }
 
@@ -1343,18 +1354,22 @@ __global__ __launch_bounds__(256) void bias_reduce_kernel(const float *__restric
 
 struct TileCfg { int bm, bn, wmv; };     // workgroup tile and waves along M
 
+bool force_v1() {
+  static const bool f = df::dev_getenv("DF_IGEMM_V1") != nullptr;   // dev switch: A/B against the un-pipelined kernel; read once
+  return f;
+}
+
 // Launches the product kernel (v4) takes; the rest -- input dilation (the data gradient of a strided convolution), operands of
 // 4 GB or more per z slice (a buffer descriptor's reach), channel offsets / strides that are not multiples of 4 -- go to v1.
 bool takes_v4(const ConvParams &p) {
-  static const bool force_v1 = df::dev_getenv("DF_IGEMM_V1") != nullptr;   // dev switch: A/B against the un-pipelined kernel; read once
   const size_t in_bytes = (size_t)p.B * p.H * p.W * p.in_ld * sizeof(float);      // per z slice
   const size_t w_bytes = (size_t)p.Cout * p.KH * p.KW * p.Cin * sizeof(float);
-  return !force_v1 && p.up == 1 && p.H + p.pad < 32768 && p.W + p.pad < 32768 && p.out_ld < (1 << 21) && p.res_ld < (1 << 21) && in_bytes < (1ull << 32) && w_bytes < (1ull << 32) && p.Cout % 4 == 0 && p.out_ld % 4 == 0 &&
+  return !force_v1() && p.up == 1 && p.H + p.pad < 32768 && p.W + p.pad < 32768 && p.out_ld < (1 << 21) && p.res_ld < (1 << 21) && in_bytes < (1ull << 32) && w_bytes < (1ull << 32) && p.Cout % 4 == 0 && p.out_ld % 4 == 0 &&
          p.out_coff % 4 == 0 && p.z_out_coff % 4 == 0 && (!p.res || (p.res_ld % 4 == 0 && p.res_coff % 4 == 0)) &&
          (!p.bias || (p.bias_group_ld % 4 == 0 && p.z_bias % 4 == 0));
 }
 
-TileCfg pick_cfg(const ConvParams &p) {
+TileCfg pick_cfg(const ConvParams &p, bool colsum) {
   const long M = (long)p.B * p.OH * p.OW;
   // (Row-grouped launches -- fused mean / per-object bias -- need BM | rows_per_group; every tile divides the
   // 128-padded groups the engine uses.)  Pick the tile that minimises  ceil(tiles / 256 CUs) * tile_area / efficiency : the chip
@@ -1363,7 +1378,7 @@ TileCfg pick_cfg(const ConvParams &p) {
   // tiles of 128) is cut into 9 columns of 128x64 tiles.
   // The fused column sum adds rows in per-wave groups: keep that grouping independent of the batch size (so
   // a batched call stays bit-identical to solo calls) by always using the 128x128 tile for it.
-  if (p.colsum || !p.out) return {128, 128, 2};     // (!p.out: the same launch while its partial buffer is being sized)
+  if (colsum) return {128, 128, 2};
   const bool v4 = takes_v4(p);                      // v1 has the two square tiles only
   static const char *const tile_env = df::dev_getenv("DF_IGEMM_TILE");      // dev switch for A/B runs; read once
   if (tile_env) {
@@ -1383,10 +1398,240 @@ TileCfg pick_cfg(const ConvParams &p) {
   return {64, 64, 2};
 }
 
+// v4 loader: 1 plain GEMM; 2 several taps, every 32-wide k tile inside one tap, tap mask in 32 bits, offsets below 2^31 (`shifted`: the
+// input's bytes from the tap-uniform descriptor base); 0 the general one.  The multi-bucket kernel has no plain-GEMM instantiation.
+int pick_loader(const ConvParams &p, size_t shifted, bool multi) {
+  static const bool no_pure = df::dev_getenv("DF_IGEMM_NOPURE") != nullptr;      // dev switch: the general loader for every launch; read once
+  const int taps = p.KH * p.KW;
+  if (no_pure) return 0;
+  if (taps == 1) return !multi && p.stride == 1 && p.pad == 0 && p.Cin % 32 == 0 ? 1 : 0;
+  return taps <= 32 && p.Cin >= 32 && shifted < (1ull << 31) ? 2 : 0;     // (Cin is a power of two here)
+}
+
+// Column-tile groups of the v2 / v4 tile walk: when the weights of all column tiles exceed the budget (3 MB of an XCD's 4 MB L2), the
+// tiles are walked a group of column tiles at a time.  Sets the group width (all column tiles: one group) and its division magics.
+void set_weight_groups(ConvArgs &a, int bn) {
+  static const long budget = df::dev_getenv("DF_IGEMM_WGROUP_KB") ? atol(df::dev_getenv("DF_IGEMM_WGROUP_KB")) * 1024L : 3L << 20;   // dev switch; read once
+  const size_t slice = (size_t)bn * a.KH * a.KW * a.Cin * sizeof(float);       // weights of one column tile
+  const int tiles_n = (a.Cout + bn - 1) / bn;
+  const int ngroup = budget > 0 && (size_t)tiles_n * slice > (size_t)budget ? (int)std::max<long>(1, budget / (long)slice) : 0;
+  a.tile_gn = ngroup > 0 && ngroup < tiles_n ? ngroup : tiles_n;
+  const int last = tiles_n % a.tile_gn;
+  make_fdiv(a.tile_gn, a.gn_magic, a.gn_sh);
+  make_fdiv(last ? last : a.tile_gn, a.gl_magic, a.gl_sh);
+}
+
+// Everything one launch needs, decided on the host: the route, the launch's own descriptor (one bucket of a per-bucket fallback), the
+// kernel arguments, the bucket table of a multi-bucket launch, the grid (tiles x 1 x gz workgroups of 256 threads) and dynamic LDS bytes
+struct ConvPlan {
+  ConvRoute r;
+  ConvParams p;
+  ConvArgs a;
+  ConvBuckets tab;
+  unsigned tiles = 0;
+  int gz = 1;
+  size_t lds = 0;
+};
+
+constexpr size_t LDS_ROW = 36 * sizeof(float);      // one padded k-tile row (BKT = 32)
+
+// one launch_conv call
+int plan_single(const ConvParams &p, ConvPlan &pl) {
+  if (!p.in || !p.wgt || (!p.out && !p.colsum)) return set_error(DF_ERR_ARG, "conv: null pointer");
+  if (p.Cin % 4 || p.in_ld % 4 || p.in_coff % 4 || p.z_in_coff % 4 || p.z_wgt % 4)
+    return set_error(DF_ERR_ARG, "conv: Cin/in_ld/in_coff must be multiples of 4 (16-B vector loads)");
+  if (p.KH * p.KW > 1 && (p.Cin & (p.Cin - 1)))
+    return set_error(DF_ERR_ARG, "conv: multi-tap convolutions need a power-of-two Cin (got %d)", p.Cin);
+  pl.p = p;
+  const long M = (long)p.B * p.OH * p.OW;
+  if (M <= 0 || p.Cout <= 0) return DF_OK;      // nothing to compute: CONV_NONE
+  if (M * (long)p.out_ld >= (1L << 40) || (long)p.B * p.H * p.W >= (1L << 31))
+    return set_error(DF_ERR_ARG, "conv: tensor too large for 32-bit pixel indexing");
+  const TileCfg c = pick_cfg(p, p.colsum != nullptr);
+  if (p.rows_per_group > 0 && (p.rows_per_group % c.bm))
+    return set_error(DF_ERR_ARG, "conv: rows_per_group must be a multiple of %d", c.bm);
+  ConvArgs &a = pl.a;
+  static_cast<ConvParams &>(a) = p;
+  const int tiles_n = (p.Cout + c.bn - 1) / c.bn;
+  a.tiles_m = (int)((M + c.bm - 1) / c.bm);
+  set_weight_groups(a, c.bn);
+  a.tile_full = a.tiles_m * a.tile_gn;
+  make_fdiv(a.tile_full, a.full_magic, a.full_sh);
+  make_fdiv(p.rows_per_group > 0 ? p.rows_per_group : 1, a.rpg_magic, a.rpg_sh);
+  make_fdiv((long)p.OH * p.OW, a.ohw_magic, a.ohw_sh);
+  make_fdiv(p.OW, a.ow_magic, a.ow_sh);
+  const long tiles = (long)a.tiles_m * tiles_n;
+  pl.tiles = (unsigned)tiles;
+  pl.gz = p.zcount;
+  pl.r.bm = c.bm;
+  pl.r.bn = c.bn;
+  if (!takes_v4(p)) {
+    pl.r.kernel = CONV_V1;
+    pl.lds = 2 * (c.bm + c.bn) * LDK * sizeof(float);
+    return DF_OK;
+  }
+  const size_t shifted = ((size_t)p.B * p.H * p.W + (size_t)p.pad * p.W + p.pad) * p.in_ld * sizeof(float);
+  const int loader = pick_loader(p, shifted, false);
+  // split-K (opt-in scratch; training): a grid under one workgroup per CU with a long reduction
+  int S = 1;
+  if (p.splitk_ws && !p.colsum && p.zcount == 1 && loader != 0 && tiles < 256 && p.bias_group_ld == 0 && p.rows_per_group == 0) {
+    const int nkt = (p.KH * p.KW * p.Cin) / 32;
+    S = (int)std::min<long>(8, (1024 + tiles - 1) / tiles);          // one round of workgroups at 4 per CU (512: -1.2 % on the 8-frame training step)
+    S = std::min(S, nkt / 4);
+    while (S > 1 && (size_t)S * M * p.Cout * sizeof(float) > p.splitk_ws_bytes) --S;
+    if ((long)S * M * p.Cout >= (1L << 31)) S = 1;
+    if (S < 1) S = 1;
+  }
+  pl.r.splitk = S;
+  pl.r.wgroup = a.tile_gn;
+  if (S > 1) {      // partial sums to the scratch, one plane per K range; the reduce applies the epilogue
+    a.splitk = S;
+    a.out = p.splitk_ws; a.out_ld = p.Cout; a.out_coff = 0; a.z_out_coff = M * p.Cout;
+    a.bias = nullptr; a.res = nullptr; a.act = ACT_NONE;
+    pl.gz = S;
+  }
+  // grids under two workgroups per CU: the software-pipelined kernel (training, 1 / 8 frames per pass: 142 -> 154 / 670 -> 696 frames/s)
+  static const long lowocc = df::dev_getenv("DF_IGEMM_LOWOCC") ? atol(df::dev_getenv("DF_IGEMM_LOWOCC")) : 512;    // dev switch; read once
+  if (S == 1 && tiles * p.zcount < lowocc && c.bn == c.bm) {
+    pl.r.kernel = CONV_V2;
+    pl.lds = 2 * (c.bm + c.bn) * LDS_ROW;
+    return DF_OK;
+  }
+  if (p.colsum && p.res) return set_error(DF_ERR_ARG, "conv: a column-sum launch cannot take a residual");
+  pl.r.kernel = p.colsum ? CONV_V4_COLSUM : CONV_V4;
+  pl.r.loader = p.colsum && loader == 2 ? 0 : loader;      // (the column-sum launches are plain GEMMs: no tap-uniform instantiation)
+  pl.lds = (c.bm + c.bn) * LDS_ROW;
+  return DF_OK;
+}
+
+// The launch of a launch_conv call (nseg = 0) or the one that starts at bucket `first` of a launch_conv_multi call, into a fresh plan
+int plan_conv(const ConvParams &p, int nseg, const WgradSeg *segs, int first, ConvPlan &pl) {
+  if (nseg == 0) return plan_single(p, pl);
+  if (!p.in || !p.wgt || !p.out || nseg < 0 || !segs || first < 0 || first >= nseg) return set_error(DF_ERR_ARG, "conv_multi: null pointer");
+  const int taps = p.KH * p.KW;
+  // what the multi-bucket instantiations cover: the product kernel's general and tap-uniform loaders, no grouping, no fused sums
+  const bool ok = !force_v1() && p.up == 1 && p.zcount == 1 && !p.colsum && p.rows_per_group == 0 && p.bias_group_ld == 0 && p.Cin % 4 == 0 &&
+                  p.in_ld % 4 == 0 && p.in_coff % 4 == 0 && p.Cout > 0 && p.Cout % 4 == 0 && p.out_ld % 4 == 0 && p.out_coff % 4 == 0 &&
+                  (!p.res || (p.res_ld % 4 == 0 && p.res_coff % 4 == 0)) && (taps == 1 || !(p.Cin & (p.Cin - 1))) && p.out_ld < (1 << 21) &&
+                  p.res_ld < (1 << 21);
+  if (!ok || nseg == 1) {          // anything else: one launch_conv per bucket
+    const WgradSeg &sg = segs[first];
+    ConvParams q = p;
+    q.B = sg.B; q.H = sg.H; q.W = sg.W; q.OH = sg.OH; q.OW = sg.OW;
+    q.in = p.in + sg.in_row0 * p.in_ld; q.out = p.out + sg.out_row0 * p.out_ld;
+    if (p.res) q.res = p.res + sg.out_row0 * p.res_ld;
+    return plan_single(q, pl);
+  }
+  const int n = std::min(CONV_MAX_BUCKETS, nseg - first);
+  long Mtot = 0;
+  size_t shifted = 0;
+  bool small_ok = true;
+  for (int g = first; g < first + n; ++g) {
+    const WgradSeg &sg = segs[g];
+    if (sg.B <= 0 || sg.H <= 0 || sg.W <= 0 || sg.OH <= 0 || sg.OW <= 0) return set_error(DF_ERR_ARG, "conv_multi: empty bucket");
+    Mtot += (long)sg.B * sg.OH * sg.OW;
+    const size_t in_bytes = (size_t)sg.B * sg.H * sg.W * p.in_ld * sizeof(float);
+    const size_t sh = ((size_t)sg.B * sg.H * sg.W + (size_t)p.pad * sg.W + p.pad) * p.in_ld * sizeof(float);
+    shifted = std::max(shifted, sh);
+    small_ok = small_ok && in_bytes < (1ull << 32) && sh < (1ull << 31) && sg.H + p.pad < 32768 && sg.W + p.pad < 32768 &&
+               (size_t)sg.B * sg.OH * sg.OW * p.out_ld < (1ull << 40);
+  }
+  if (!small_ok) return set_error(DF_ERR_ARG, "conv_multi: a bucket is too large for the multi-bucket kernel");
+  ConvParams pt = p;             // tile choice on the whole launch's rows
+  pt.B = (int)std::min<long>(Mtot, 1L << 30); pt.OH = pt.OW = 1;
+  const TileCfg c = pick_cfg(pt, false);
+  pl.p = p;
+  ConvArgs &a = pl.a;
+  static_cast<ConvParams &>(a) = p;
+  set_weight_groups(a, c.bn);
+  const int tiles_n = (p.Cout + c.bn - 1) / c.bn;
+  ConvBuckets &tab = pl.tab;
+  tab.n = n;
+  tab.tile0[0] = 0;
+  for (int i = 0; i < n; ++i) {      // per bucket: its map, row offsets and tile decode (the launch-wide fields stay unset)
+    const WgradSeg &sg = segs[first + i];
+    const long M = (long)sg.B * sg.OH * sg.OW;
+    tab.B[i] = sg.B; tab.H[i] = sg.H; tab.W[i] = sg.W; tab.OH[i] = sg.OH; tab.OW[i] = sg.OW;
+    tab.tiles_m[i] = (int)((M + c.bm - 1) / c.bm);
+    tab.tile_full[i] = tab.tiles_m[i] * a.tile_gn;
+    make_fdiv(tab.tile_full[i], tab.full_magic[i], tab.full_sh[i]);
+    make_fdiv((long)sg.OH * sg.OW, tab.ohw_magic[i], tab.ohw_sh[i]);
+    make_fdiv(sg.OW, tab.ow_magic[i], tab.ow_sh[i]);
+    tab.in_row0[i] = sg.in_row0; tab.out_row0[i] = sg.out_row0;
+    tab.tile0[i + 1] = tab.tile0[i] + tab.tiles_m[i] * tiles_n;
+  }
+  pl.r = ConvRoute{CONV_V4_MULTI, c.bm, c.bn, pick_loader(p, shifted, true), 1, a.tile_gn, n};
+  pl.tiles = (unsigned)tab.tile0[n];
+  pl.lds = (c.bm + c.bn) * LDS_ROW;
+  return DF_OK;
+}
+
+template <int BM, int BN, int OCC>
+void launch_v4(const ConvPlan &pl, hipStream_t st) {
+  const dim3 grid(pl.tiles, 1, pl.gz);
+  if (pl.r.kernel == CONV_V4_MULTI) {
+    if (pl.r.loader == 2) hipLaunchKernelGGL((igemm_f32_v4_multi_kernel<BM, BN, 2, 2, 32, OCC, 2>), grid, dim3(256), pl.lds, st, pl.a, pl.tab);
+    else hipLaunchKernelGGL((igemm_f32_v4_multi_kernel<BM, BN, 2, 2, 32, OCC, 0>), grid, dim3(256), pl.lds, st, pl.a, pl.tab);
+  } else if (pl.r.loader == 1) hipLaunchKernelGGL((igemm_f32_v4_kernel<BM, BN, 2, 2, 32, OCC, 1, false>), grid, dim3(256), pl.lds, st, pl.a);
+  else if (pl.r.loader == 2) hipLaunchKernelGGL((igemm_f32_v4_kernel<BM, BN, 2, 2, 32, OCC, 2, false>), grid, dim3(256), pl.lds, st, pl.a);
+  else hipLaunchKernelGGL((igemm_f32_v4_kernel<BM, BN, 2, 2, 32, OCC, 0, false>), grid, dim3(256), pl.lds, st, pl.a);
+}
+
+// plan -> instantiation.  v1's and v2's 128x128 tiles double-buffer 72 KiB of dynamic LDS: above the 64 KiB default cap, raised just
+// before their launches (the 64x64 tiles take 36 KiB, v4's single k-tile buffer 36 KiB at most).  Non-multi launches go to the bf16 x 6
+// kernel first where try_split_gemm takes them (pl.r then says so).
+int launch_plan(ConvPlan &pl, hipStream_t st) {
+  if (pl.r.kernel == CONV_NONE) return DF_OK;
+  if (pl.r.kernel != CONV_V4_MULTI) {
+    const int taken = try_split_gemm(pl.p, st);
+    if (taken < 0) return taken;
+    if (taken) {
+      pl.r = ConvRoute{};
+      pl.r.kernel = CONV_BF16;
+      return check_launch("split gemm");
+    }
+  }
+  const dim3 grid(pl.tiles, 1, pl.gz);
+  const bool big = pl.r.bm == 128 && pl.r.bn == 128;
+  switch (pl.r.kernel) {
+    case CONV_V1:
+      if (big) {
+        const int rc = raise_lds_limit(reinterpret_cast<const void *>(&igemm_f32_kernel<128, 128, 2, 2>), (int)pl.lds);
+        if (rc != DF_OK) return rc;
+        hipLaunchKernelGGL((igemm_f32_kernel<128, 128, 2, 2>), grid, dim3(256), pl.lds, st, pl.p);
+      } else
+        hipLaunchKernelGGL((igemm_f32_kernel<64, 64, 2, 2>), grid, dim3(256), pl.lds, st, pl.p);
+      break;
+    case CONV_V2:
+      if (big) {
+        const int rc = raise_lds_limit(reinterpret_cast<const void *>(&igemm_f32_v2_kernel<128, 128, 2, 2, 32>), (int)pl.lds);
+        if (rc != DF_OK) return rc;
+        hipLaunchKernelGGL((igemm_f32_v2_kernel<128, 128, 2, 2, 32>), grid, dim3(256), pl.lds, st, pl.a);
+      } else
+        hipLaunchKernelGGL((igemm_f32_v2_kernel<64, 64, 2, 2, 32>), grid, dim3(256), pl.lds, st, pl.a);
+      break;
+    case CONV_V4_COLSUM:      // always the 128x128 tile (pick_cfg)
+      if (pl.r.loader == 1) hipLaunchKernelGGL((igemm_f32_v4_kernel<128, 128, 2, 2, 32, 4, 1, true>), grid, dim3(256), pl.lds, st, pl.a);
+      else hipLaunchKernelGGL((igemm_f32_v4_kernel<128, 128, 2, 2, 32, 4, 0, true>), grid, dim3(256), pl.lds, st, pl.a);
+      break;
+    default:                  // v4, single map or over buckets: 4 / 5 / 6 workgroups per CU (the register budget amdgpu_waves_per_eu leaves each)
+      if (big) launch_v4<128, 128, 4>(pl, st);
+      else if (pl.r.bm == 128) launch_v4<128, 64, 5>(pl, st);
+      else launch_v4<64, 64, 6>(pl, st);      // (a BK = 64 form of the small tile was measured: 0.85-1.0x, dropped)
+  }
+  if (pl.r.splitk > 1) {
+    const ConvParams &p = pl.p;
+    const long M = (long)p.B * p.OH * p.OW, vecs = M * (p.Cout / 4);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((vecs + 255) / 256, 65535L * 8)), dim3(256), 0, st, p.splitk_ws, pl.r.splitk, M,
+                       p.Cout, p.out, p.out_ld, p.out_coff, p.bias, p.res, p.res_ld, p.res_coff, p.act, p.prelu);
+  }
+  return check_launch(pl.r.kernel == CONV_V4_MULTI ? "igemm (multi-bucket)" : "igemm");
+}
+
 }  // namespace
 
 int conv_colsum_rows(const ConvParams &p) {
-  const TileCfg c = pick_cfg(p);
+  const TileCfg c = pick_cfg(p, true);      // the column-sum launch's tile, whether or not p.out / p.colsum are set yet
   const long M = (long)p.B * p.OH * p.OW;
   return (int)(((M + c.bm - 1) / c.bm) * c.wmv) * p.zcount;
 }
@@ -1402,201 +1647,32 @@ double conv_flops(const ConvParams &p) {
   return 2.0 * p.B * p.OH * p.OW * (double)p.Cout * p.KH * p.KW * p.Cin * p.zcount;
 }
 
-int launch_conv(const ConvParams &p, hipStream_t st, int *splitk_used, int *on_bf16) {
-  if (on_bf16) *on_bf16 = 0;
-  if (!p.in || !p.wgt || (!p.out && !p.colsum)) return set_error(DF_ERR_ARG, "conv: null pointer");
-  if (p.Cin % 4 || p.in_ld % 4 || p.in_coff % 4 || p.z_in_coff % 4 || p.z_wgt % 4)
-    return set_error(DF_ERR_ARG, "conv: Cin/in_ld/in_coff must be multiples of 4 (16-B vector loads)");
-  if (p.KH * p.KW > 1 && (p.Cin & (p.Cin - 1)))
-    return set_error(DF_ERR_ARG, "conv: multi-tap convolutions need a power-of-two Cin (got %d)", p.Cin);
-  const long M = (long)p.B * p.OH * p.OW;
-  if (M <= 0 || p.Cout <= 0) return DF_OK;
-  if (M * (long)p.out_ld >= (1L << 40) || (long)p.B * p.H * p.W >= (1L << 31))
-    return set_error(DF_ERR_ARG, "conv: tensor too large for 32-bit pixel indexing");
-  {
-    const int taken = try_split_gemm(p, st);
-    if (taken < 0) return taken;
-    if (taken) {
-      if (splitk_used) *splitk_used = 1;
-      if (on_bf16) *on_bf16 = 1;
-      return check_launch("split gemm");
-    }
-  }
-  const TileCfg c = pick_cfg(p);
-  ConvParams pl = p;       // launch copy: + the column-tile group width and the division magics
-  make_fdiv((long)p.OH * p.OW, pl.ohw_magic, pl.ohw_sh);
-  make_fdiv(p.OW, pl.ow_magic, pl.ow_sh);
-  auto set_tile_decode = [&]() {      // after ngroup is known
-    const int tiles_n = (p.Cout + c.bn - 1) / c.bn;
-    pl.tiles_m = (int)((M + c.bm - 1) / c.bm);
-    pl.tile_gn = pl.ngroup > 0 && pl.ngroup < tiles_n ? pl.ngroup : tiles_n;
-    pl.tile_full = pl.tiles_m * pl.tile_gn;
-    const int last = tiles_n % pl.tile_gn;
-    make_fdiv(pl.tile_full, pl.full_magic, pl.full_sh);
-    make_fdiv(pl.tile_gn, pl.gn_magic, pl.gn_sh);
-    make_fdiv(last ? last : pl.tile_gn, pl.gl_magic, pl.gl_sh);
-    make_fdiv(p.rows_per_group > 0 ? p.rows_per_group : 1, pl.rpg_magic, pl.rpg_sh);
-  };
-  {
-    const size_t slice = (size_t)c.bn * p.KH * p.KW * p.Cin * sizeof(float);       // weights of one column tile
-    const long tn = (p.Cout + c.bn - 1) / c.bn;
-    static const long budget = df::dev_getenv("DF_IGEMM_WGROUP_KB") ? atol(df::dev_getenv("DF_IGEMM_WGROUP_KB")) * 1024L : 3L << 20;
-    if (budget > 0 && (size_t)tn * slice > (size_t)budget) pl.ngroup = (int)std::max<long>(1, budget / (long)slice);
-  }
-  set_tile_decode();
-  if (p.rows_per_group > 0 && (p.rows_per_group % c.bm))
-    return set_error(DF_ERR_ARG, "conv: rows_per_group must be a multiple of %d", c.bm);
-  const long tiles = ((M + c.bm - 1) / c.bm) * ((p.Cout + c.bn - 1) / c.bn);
-  dim3 grid((unsigned)tiles, 1, p.zcount);
-  // v1's and v2's 128x128 tiles double-buffer 72 KiB of dynamic LDS: above the 64 KiB default cap, raised just before their launches.
-  // (The 64x64 tiles take 36 KiB, v4's single k-tile buffer 36 KiB at most.)
-  constexpr size_t ROW = 36 * sizeof(float);      // one padded k-tile row (BKT = 32)
-  // workgroups per CU of the v4 kernel: 4 / 5 / 6 (the register budget amdgpu_waves_per_eu leaves each: 128 / 102 / 85 VGPRs + AGPRs)
-  static const bool no_pure = df::dev_getenv("DF_IGEMM_NOPURE") != nullptr;      // dev switch: the general loader for every launch; read once
-  const bool v4 = takes_v4(p);
-  const int taps = p.KH * p.KW;
-  const size_t shifted = ((size_t)p.B * p.H * p.W + (size_t)p.pad * p.W + p.pad) * p.in_ld * sizeof(float);
-  // loader 1: plain GEMM; loader 2: several taps, every 32-wide k tile inside one tap, tap mask in 32 bits, offsets below 2^31
-  const int loader = no_pure ? 0
-                     : taps == 1 && p.stride == 1 && p.pad == 0 && p.Cin % 32 == 0 ? 1
-                     : taps > 1 && taps <= 32 && p.Cin >= 32 && shifted < (1ull << 31) ? 2 : 0;     // (Cin is a power of two here)
-  // split-K (opt-in scratch; training): a grid under one workgroup per CU with a long reduction
-  int S = 1;
-  if (v4 && p.splitk_ws && !p.colsum && p.zcount == 1 && loader != 0 && tiles < 256 && p.bias_group_ld == 0 && p.rows_per_group == 0) {
-    const int nkt = (p.KH * p.KW * p.Cin) / 32;
-    S = (int)std::min<long>(8, (1024 + tiles - 1) / tiles);          // one round of workgroups at 4 per CU (512: -1.2 % on the 8-frame training step)
-    S = std::min(S, nkt / 4);
-    while (S > 1 && (size_t)S * M * p.Cout * sizeof(float) > p.splitk_ws_bytes) --S;
-    if ((long)S * M * p.Cout >= (1L << 31)) S = 1;
-    if (S < 1) S = 1;
-  }
-  if (splitk_used) *splitk_used = S;
-  if (S > 1) {
-    pl.splitk = S;
-    pl.out = p.splitk_ws; pl.out_ld = p.Cout; pl.out_coff = 0; pl.z_out_coff = M * p.Cout;
-    pl.bias = nullptr; pl.res = nullptr; pl.act = ACT_NONE;
-    grid.z = S;
-  }
-  // grids under two workgroups per CU: the software-pipelined kernel (training, 1 / 8 frames per pass: 142 -> 154 / 670 -> 696 frames/s)
-  static const long lowocc = df::dev_getenv("DF_IGEMM_LOWOCC") ? atol(df::dev_getenv("DF_IGEMM_LOWOCC")) : 512;    // dev switch; read once
-  if (v4 && S == 1 && tiles * p.zcount < lowocc && c.bn == c.bm) {
-    if (c.bm == 128) {
-      constexpr int lds = 2 * 256 * 36 * (int)sizeof(float);
-      const int rc = raise_lds_limit(reinterpret_cast<const void *>(&igemm_f32_v2_kernel<128, 128, 2, 2, 32>), lds);
-      if (rc != DF_OK) return rc;
-      hipLaunchKernelGGL((igemm_f32_v2_kernel<128, 128, 2, 2, 32>), grid, dim3(256), (size_t)lds, st, pl);
-    } else
-      hipLaunchKernelGGL((igemm_f32_v2_kernel<64, 64, 2, 2, 32>), grid, dim3(256), (size_t)2 * 128 * 36 * sizeof(float), st, pl);
-  } else if (v4) {
-    auto launch = [&](auto bm, auto bn, auto occ, size_t rows) {
-      constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value, OCC_ = decltype(occ)::value;
-      if (loader == 1) hipLaunchKernelGGL((igemm_f32_v4_kernel<BM_, BN_, 2, 2, 32, OCC_, 1, false>), grid, dim3(256), rows * ROW, st, pl);
-      else if (loader == 2) hipLaunchKernelGGL((igemm_f32_v4_kernel<BM_, BN_, 2, 2, 32, OCC_, 2, false>), grid, dim3(256), rows * ROW, st, pl);
-      else hipLaunchKernelGGL((igemm_f32_v4_kernel<BM_, BN_, 2, 2, 32, OCC_, 0, false>), grid, dim3(256), rows * ROW, st, pl);
-    };
-    using std::integral_constant;
-    if (p.colsum && p.res) return set_error(DF_ERR_ARG, "conv: a column-sum launch cannot take a residual");
-    if (p.colsum) {      // always the 128x128 tile (pick_cfg); the per-point launches that use it are plain GEMMs
-      if (loader == 1) hipLaunchKernelGGL((igemm_f32_v4_kernel<128, 128, 2, 2, 32, 4, 1, true>), grid, dim3(256), 256 * ROW, st, pl);
-      else hipLaunchKernelGGL((igemm_f32_v4_kernel<128, 128, 2, 2, 32, 4, 0, true>), grid, dim3(256), 256 * ROW, st, pl);
-    } else if (c.bm == 128 && c.bn == 128) launch(integral_constant<int, 128>{}, integral_constant<int, 128>{}, integral_constant<int, 4>{}, 256);
-    else if (c.bm == 128) launch(integral_constant<int, 128>{}, integral_constant<int, 64>{}, integral_constant<int, 5>{}, 192);
-    else launch(integral_constant<int, 64>{}, integral_constant<int, 64>{}, integral_constant<int, 6>{}, 128);      // (a BK = 64 form of the small tile was measured: 0.85-1.0x, dropped)
-    if (S > 1) {
-      const long vecs = M * (p.Cout / 4);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<long>((vecs + 255) / 256, 65535L * 8)), dim3(256), 0, st, p.splitk_ws, S, M, p.Cout,
-                         p.out, p.out_ld, p.out_coff, p.bias, p.res, p.res_ld, p.res_coff, p.act, p.prelu);
-    }
-  } else if (c.bm == 128) {
-    constexpr int lds = 2 * 256 * LDK * (int)sizeof(float);
-    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&igemm_f32_kernel<128, 128, 2, 2>), lds);
-    if (rc != DF_OK) return rc;
-    hipLaunchKernelGGL((igemm_f32_kernel<128, 128, 2, 2>), grid, dim3(256), (size_t)lds, st, p);
-  } else {
-    hipLaunchKernelGGL((igemm_f32_kernel<64, 64, 2, 2>), grid, dim3(256), (size_t)2 * 128 * LDK * sizeof(float), st, p);
-  }
-  return check_launch("igemm");
+int conv_route(const ConvParams &p, int nseg, const WgradSeg *segs, int first, ConvRoute &r) {
+  ConvPlan pl;
+  const int rc = plan_conv(p, nseg, segs, first, pl);
+  r = pl.r;
+  return rc;
 }
 
-// Direct k x k convolution over several crop-size buckets in one launch (igemm_f32_v4_multi_kernel); see igemm.h.
+int launch_conv(const ConvParams &p, hipStream_t st, ConvRoute *taken) {
+  ConvPlan pl;
+  int rc = plan_conv(p, 0, nullptr, 0, pl);
+  if (rc == DF_OK) rc = launch_plan(pl, st);
+  if (taken) *taken = pl.r;
+  return rc;
+}
+
+// Direct k x k convolution over several crop-size buckets, CONV_MAX_BUCKETS per launch of igemm_f32_v4_multi_kernel; see igemm.h.
 int launch_conv_multi(const ConvParams &p, int nseg, const WgradSeg *segs, hipStream_t st) {
-  if (!p.in || !p.wgt || !p.out || nseg <= 0 || !segs) return set_error(DF_ERR_ARG, "conv_multi: null pointer");
-  const int taps = p.KH * p.KW;
-  // what the multi-bucket instantiations cover: the product kernel's general and tap-uniform loaders, no grouping, no fused sums
-  const bool ok = p.up == 1 && p.zcount == 1 && !p.colsum && p.rows_per_group == 0 && p.bias_group_ld == 0 && p.Cin % 4 == 0 && p.in_ld % 4 == 0 &&
-                  p.in_coff % 4 == 0 && p.Cout % 4 == 0 && p.out_ld % 4 == 0 && p.out_coff % 4 == 0 && (!p.res || (p.res_ld % 4 == 0 && p.res_coff % 4 == 0)) &&
-                  (taps == 1 || !(p.Cin & (p.Cin - 1))) && p.out_ld < (1 << 21) && p.res_ld < (1 << 21);
-  if (!ok || nseg == 1) {          // anything else: one launch per bucket
-    for (int g = 0; g < nseg; ++g) {
-      ConvParams q = p;
-      q.B = segs[g].B; q.H = segs[g].H; q.W = segs[g].W; q.OH = segs[g].OH; q.OW = segs[g].OW;
-      q.in = p.in + segs[g].in_row0 * p.in_ld; q.out = p.out + segs[g].out_row0 * p.out_ld;
-      if (p.res) q.res = p.res + segs[g].out_row0 * p.res_ld;
-      const int rc = launch_conv(q, st);
-      if (rc != DF_OK) return rc;
-    }
-    return DF_OK;
+  if (nseg <= 0 || !segs) return set_error(DF_ERR_ARG, "conv_multi: null pointer");
+  for (int g = 0; g < nseg;) {
+    ConvPlan pl;
+    int rc = plan_conv(p, nseg, segs, g, pl);
+    if (rc == DF_OK) rc = launch_plan(pl, st);
+    if (rc != DF_OK) return rc;
+    g += pl.r.nseg;
   }
-  for (int g0 = 0; g0 < nseg; g0 += CONV_MAX_BUCKETS) {
-    const int n = std::min(CONV_MAX_BUCKETS, nseg - g0);
-    long Mtot = 0;
-    bool small_ok = true;
-    for (int g = g0; g < g0 + n; ++g) {
-      const WgradSeg &sg = segs[g];
-      if (sg.B <= 0 || sg.H <= 0 || sg.W <= 0 || sg.OH <= 0 || sg.OW <= 0) return set_error(DF_ERR_ARG, "conv_multi: empty bucket");
-      Mtot += (long)sg.B * sg.OH * sg.OW;
-      const size_t in_bytes = (size_t)sg.B * sg.H * sg.W * p.in_ld * sizeof(float);
-      const size_t shifted = ((size_t)sg.B * sg.H * sg.W + (size_t)p.pad * sg.W + p.pad) * p.in_ld * sizeof(float);
-      small_ok = small_ok && in_bytes < (1ull << 32) && shifted < (1ull << 31) && sg.H + p.pad < 32768 && sg.W + p.pad < 32768 &&
-                 (size_t)sg.B * sg.OH * sg.OW * p.out_ld < (1ull << 40);
-    }
-    if (!small_ok) return set_error(DF_ERR_ARG, "conv_multi: a bucket is too large for the multi-bucket kernel");
-    ConvParams pt = p;             // tile choice on the whole launch's rows
-    pt.B = (int)std::min<long>(Mtot, 1L << 30); pt.OH = pt.OW = 1;
-    const TileCfg c = pick_cfg(pt);
-    ConvParams pl = p;
-    {
-      const size_t slice = (size_t)c.bn * taps * p.Cin * sizeof(float);
-      const long tn = (p.Cout + c.bn - 1) / c.bn;
-      const long budget = 3L << 20;
-      pl.ngroup = (size_t)tn * slice > (size_t)budget ? (int)std::max<long>(1, budget / (long)slice) : 0;
-    }
-    const int tiles_n = (p.Cout + c.bn - 1) / c.bn;
-    pl.tile_gn = pl.ngroup > 0 && pl.ngroup < tiles_n ? pl.ngroup : tiles_n;
-    const int last = tiles_n % pl.tile_gn;
-    make_fdiv(pl.tile_gn, pl.gn_magic, pl.gn_sh);
-    make_fdiv(last ? last : pl.tile_gn, pl.gl_magic, pl.gl_sh);
-    make_fdiv(1, pl.rpg_magic, pl.rpg_sh);
-    pl.splitk = 1;
-    ConvBuckets tab;
-    tab.n = n;
-    tab.tile0[0] = 0;
-    for (int i = 0; i < n; ++i) {
-      const WgradSeg &sg = segs[g0 + i];
-      const long M = (long)sg.B * sg.OH * sg.OW;
-      tab.B[i] = sg.B; tab.H[i] = sg.H; tab.W[i] = sg.W; tab.OH[i] = sg.OH; tab.OW[i] = sg.OW;
-      tab.tiles_m[i] = (int)((M + c.bm - 1) / c.bm);
-      tab.tile_full[i] = tab.tiles_m[i] * pl.tile_gn;
-      make_fdiv(tab.tile_full[i], tab.full_magic[i], tab.full_sh[i]);
-      make_fdiv((long)sg.OH * sg.OW, tab.ohw_magic[i], tab.ohw_sh[i]);
-      make_fdiv(sg.OW, tab.ow_magic[i], tab.ow_sh[i]);
-      tab.in_row0[i] = sg.in_row0; tab.out_row0[i] = sg.out_row0;
-      tab.tile0[i + 1] = tab.tile0[i] + tab.tiles_m[i] * tiles_n;
-    }
-    const dim3 grid((unsigned)tab.tile0[n], 1, 1);
-    constexpr size_t ROW = 36 * sizeof(float);
-    const int loader = taps > 1 && taps <= 32 && p.Cin >= 32 ? 2 : 0;
-    auto launch = [&](auto bm, auto bn, auto occ, size_t rows) {
-      constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value, OCC_ = decltype(occ)::value;
-      if (loader == 2) hipLaunchKernelGGL((igemm_f32_v4_multi_kernel<BM_, BN_, 2, 2, 32, OCC_, 2>), grid, dim3(256), rows * ROW, st, pl, tab);
-      else hipLaunchKernelGGL((igemm_f32_v4_multi_kernel<BM_, BN_, 2, 2, 32, OCC_, 0>), grid, dim3(256), rows * ROW, st, pl, tab);
-    };
-    using std::integral_constant;
-    if (c.bm == 128 && c.bn == 128) launch(integral_constant<int, 128>{}, integral_constant<int, 128>{}, integral_constant<int, 4>{}, 256);
-    else if (c.bm == 128) launch(integral_constant<int, 128>{}, integral_constant<int, 64>{}, integral_constant<int, 5>{}, 192);
-    else launch(integral_constant<int, 64>{}, integral_constant<int, 64>{}, integral_constant<int, 6>{}, 128);
-  }
-  return check_launch("igemm (multi-bucket)");
+  return DF_OK;
 }
 
 namespace {

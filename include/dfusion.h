@@ -286,6 +286,15 @@ int df_conv2d_nhwc(const df_conv_desc *d, df_stream_t stream);
 int df_conv2d_nhwc_multi(const df_conv_desc *d, int nb, const int *B, const int *H, const int *W, df_stream_t stream);
 /* number of K ranges the calling thread's last df_conv2d_nhwc / df_conv2d_dgrad_nhwc launch was cut into (1 = not split): tests */
 int df_conv_last_splitk(void);
+/* Host only (no GPU): the fp32 kernel a df_conv2d_nhwc call on d (nb = 0; B / H / W unused) or the launch of a df_conv2d_nhwc_multi call
+ * on nb buckets that starts at bucket `first` takes.  up > 1: the input dilation of a data-gradient launch; zcount: blockIdx.z batches;
+ * groups > 0: a column-sum launch over row groups of that many rows (column sums into d->out); a split-K scratch in d counts for both
+ * calls alike (the native trainer hands one to its multi-bucket launches).  route[7] receives the kernel (0 nothing
+ * to compute, 1 v1, 2 v2, 3 v4, 4 v4 with column sums, 5 v4 over buckets), the workgroup tile's rows and columns, the v4 loader (0 general,
+ * 1 plain GEMM, 2 tap-uniform), the split-K ranges, the column tiles per weight group and the buckets the launch covers.  Returns 0 or
+ * the error the call fails with. */
+int df_conv_route(const df_conv_desc *d, int nb, const int *B, const int *H, const int *W, int first, int up, int zcount, int groups,
+                  int *route);
 
 /* The same operator for 3x3 / stride 1 / pad == dil (any dilation) evaluated through the Winograd F(2x2,3x3) domain:
  * 16 multiplies per 2x2 outputs instead of 36 (the path the engine takes for the 256/512-channel convs of the

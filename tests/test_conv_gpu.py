@@ -249,6 +249,25 @@ for i, (B, H, W, Cin, Cout, k, stride, pad, dil) in enumerate([
     w = torch.randn(Cout, k, k, Cin, device=dev) * 0.05
     b = torch.randn(Cout, device=dev)
     outs.append(conv2d_nhwc(x, w, b, stride=stride, pad=pad, dil=dil, act=1).cpu())
+# the multi-bucket kernel (tap-uniform loader) over three crop sizes in one launch
+import ctypes
+from densefusion_amd import _lib
+torch.manual_seed(200)
+sizes = [(2, 20, 20), (1, 40, 30), (3, 12, 16)]
+w = torch.randn(128, 3, 3, 64, device=dev) * 0.05
+b = torch.randn(128, device=dev)
+x = torch.randn(sum(n * h * wd for n, h, wd in sizes), 64, device=dev)
+out = torch.empty(x.shape[0], 128, device=dev)
+d = _lib.ConvDesc()
+d.in_, d.wgt, d.bias, d.out = x.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr()
+d.Cin, d.in_ld, d.Cout, d.out_ld = 64, 64, 128, 128
+d.KH = d.KW = 3
+d.stride, d.pad, d.dil, d.act = 1, 1, 1, 1
+arr = ctypes.c_int * 3
+L = _lib.lib()
+_lib.check(L.df_conv2d_nhwc_multi(ctypes.byref(d), 3, arr(*[s[0] for s in sizes]), arr(*[s[1] for s in sizes]), arr(*[s[2] for s in sizes]),
+                                  _lib.current_stream()), "conv2d_nhwc_multi")
+outs.append(out.cpu())
 torch.save(outs, sys.argv[2])
 """
 
@@ -256,8 +275,8 @@ torch.save(outs, sys.argv[2])
 @pytest.mark.gpu
 def test_specialised_loaders_are_bit_identical_to_the_general_one(tmp_path):
     """The plain-GEMM and tap-uniform loaders only change HOW a k tile's addresses are formed: every output element still adds the
-    same products in the same order, so results must equal the general loader's bit for bit (two child processes: the dev
-    switch DF_IGEMM_NOPURE is read once per process)."""
+    same products in the same order, so results must equal the general loader's bit for bit, on the single-map and the multi-bucket
+    kernels (two child processes: the dev switch DF_IGEMM_NOPURE is read once per process)."""
     import os
     import subprocess
     import sys
@@ -270,7 +289,7 @@ def test_specialised_loaders_are_bit_identical_to_the_general_one(tmp_path):
         subprocess.run([sys.executable, "-c", _LOADER_SCRIPT, root, f], check=True, env=e, timeout=300)
         files.append(f)
     a, b = torch.load(files[0]), torch.load(files[1])
-    assert len(a) == len(b) == 5
+    assert len(a) == len(b) == 6
     for i, (u, v) in enumerate(zip(a, b)):
         assert torch.equal(u, v), f"case {i}: loaders disagree, max diff {float((u - v).abs().max())}"
 

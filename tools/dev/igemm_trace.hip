@@ -74,7 +74,7 @@ int main(int argc, char **argv) {
   {
     // MFMA-pipe occupancy per CU: every 128x128 workgroup needs nkt * 4096 pipe cycles on each SIMD (64 MFMAs of 64 cycles per k tile)
     // -- (a) over the CU's whole span, (b) over its middle (first and last workgroup lifetimes cut off: the steady state)
-    const double need = (double)((K + 31) / 32) * 4096.0 * (pick_cfg(p).bm * pick_cfg(p).bn) / 16384.0;
+    const double need = (double)((K + 31) / 32) * 4096.0 * (pick_cfg(p, p.colsum != nullptr).bm * pick_cfg(p, p.colsum != nullptr).bn) / 16384.0;
     double ua = 0, ub = 0, span_max = 0; int nb = 0;
     for (auto &kv : by_cu) {
       auto &v = kv.second;
