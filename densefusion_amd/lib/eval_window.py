@@ -48,6 +48,11 @@ class WindowEstimator:
         """rgb [F,IH,IW,3] uint8, depth [F,IH,IW] int16/uint16 bits, label [F,IH,IW] int32: HOST tensors (pinned for an
         asynchronous upload).  detections: list of (frame, itemid, roi_row, seed) in result order.  Everything is enqueued
         (no host sync); returns a handle for ``collect``."""
+        return self.run(self.upload(rgb, depth, label), rgb.shape[0], detections)
+
+    def upload(self, rgb, depth, label=None):
+        """The upload half of ``submit``: the window's frames (HOST tensors as there; label may be None when the device fills the
+        slot's label buffer itself) go up into the next slot.  Returns the slot, whose stream orders everything after the upload."""
         F = rgb.shape[0]
         if F > self.max_frames:
             raise RuntimeError(f"window of {F} frames exceeds max_frames={self.max_frames}")
@@ -63,16 +68,24 @@ class WindowEstimator:
         with torch.cuda.stream(up):
             slot["rgb"][:F].copy_(rgb, non_blocking=True)
             slot["depth"][:F].copy_(depth.view(torch.int16) if depth.dtype != torch.int16 else depth, non_blocking=True)
-            slot["label"][:F].copy_(label, non_blocking=True)
+            if label is not None:
+                slot["label"][:F].copy_(label, non_blocking=True)
             slot["ready"].record(up)
         main.wait_event(slot["ready"])
+        return slot
+
+    def run(self, slot, F, detections):
+        """The compute half of ``submit``: the pose stage over the first F frames already resident in `slot` (colour, depth and
+        label map), enqueued on the slot's stream.  detections as for ``submit``; returns a handle for ``collect``."""
+        main = slot["stream"]
+        IH, IW = slot["rgb"].shape[1], slot["rgb"].shape[2]
         n = len(detections)
         lost = np.zeros(n, dtype=bool)
         buckets = {}
         for k, (frame, itemid, roi, seed) in enumerate(detections):
             bb = pp.get_bbox(roi)
             H, W = bb[1] - bb[0], bb[3] - bb[2]
-            if H < 8 or W < 8 or bb[0] < 0 or bb[2] < 0 or bb[1] > rgb.shape[1] or bb[3] > rgb.shape[2]:
+            if H < 8 or W < 8 or bb[0] < 0 or bb[2] < 0 or bb[1] > IH or bb[3] > IW:
                 lost[k] = True          # degenerate PoseCNN box: the reference ends in its "Detector Lost" branch (eval_ycb.py:234-237)
                 continue
             buckets.setdefault((H, W), []).append((k, frame, int(itemid), bb, int(seed)))

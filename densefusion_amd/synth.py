@@ -232,3 +232,56 @@ def make_segnet_state_dict(seed, label_nbr=22):
         else:
             sd[key] = rng.uniform(-0.1, 0.1, shape).astype(np.float32)
     return sd
+
+
+BLOCK_COLOURS = {1: (255, 0, 0), 2: (0, 255, 0), 3: (0, 0, 255)}
+
+
+def make_segnet_block_state_dict(label_nbr=22):
+    """SegNet weights whose masks are known in advance (the SegNet -> pose tests and tools/segment_pose_bench.py).
+
+    Every convolution passes the three colour channels through its centre tap (BatchNorm set to identity, +5 on the first layer so the
+    normalised colours stay above the ReLUs); the other channels stay zero.  On an image of uniform 32 x 32 cells each max-pool keeps the
+    cell's first pixel (ties go to the first position) and each un-pool puts it back there, so the classifier sees the cell's colour at
+    its top-left pixel and zeros elsewhere.  The classifier scores class 1 / 2 / 3 as red / green / blue minus the other two minus 100
+    and gives the background a constant 0.5: a red cell labels one pixel 1, a black one nothing.  (The Winograd-domain layers add
+    rounding noise, which may break the pools' ties differently per channel and move a cell's pixel inside its cell; the threshold of 100
+    keeps a lone channel of a black cell, ~3, in the background, and the tests do not depend on where a cell's pixel lands.)"""
+    sd = {}
+    for key, shape in segnet_spec(label_nbr):
+        if key.endswith("num_batches_tracked"):
+            sd[key] = np.array(0, dtype=np.int64)
+        elif key.startswith("bn"):
+            sd[key] = np.ones(shape, np.float32) if key.endswith(("weight", "running_var")) else np.zeros(shape, np.float32)
+        elif key == "conv11d.weight":
+            w = np.zeros(shape, np.float32)
+            for c in (1, 2, 3):
+                w[c, :3, 1, 1] = -1.0
+                w[c, c - 1, 1, 1] = 1.0
+            sd[key] = w
+        elif key == "conv11d.bias":
+            b = np.full(shape, -100.0, np.float32)
+            b[0] = 0.5
+            sd[key] = b
+        elif key.endswith("weight"):
+            w = np.zeros(shape, np.float32)
+            for k in range(3):
+                w[k, k, 1, 1] = 1.0
+            sd[key] = w
+        else:
+            b = np.zeros(shape, np.float32)
+            if key == "conv11.bias":
+                b[:3] = 5.0
+            sd[key] = b
+    return sd
+
+
+def block_frame(rng, blocks, H=480, W=640):
+    """uint8 RGB [H,W,3]: black, with blocks = [(cls, cell_row, cell_col, cell_rows, cell_cols)] of 32 x 32 cells in that class's
+    colour; and a uint16 depth with ~5 % holes."""
+    rgb = np.zeros((H, W, 3), np.uint8)
+    for cls, r, c, nr, nc in blocks:
+        rgb[32 * r:32 * (r + nr), 32 * c:32 * (c + nc)] = BLOCK_COLOURS[cls]
+    depth = rng.integers(5000, 12000, (H, W)).astype(np.uint16)
+    depth[rng.random((H, W)) < 0.05] = 0
+    return rgb, depth

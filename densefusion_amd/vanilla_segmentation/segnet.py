@@ -77,6 +77,13 @@ class SegNet(nn.Module):
         self._folded[name] = (tag, w, b)
         return w, b
 
+    def fold(self):
+        """Fold every BatchNorm into its convolution now, on the current stream (the eval forward otherwise folds a layer on its
+        first use, on whatever stream that forward runs)."""
+        for item in _ENC + _DEC:
+            if not isinstance(item, str):
+                self._layer(item[0])
+
     def _train_forward(self, x):
         C = x.shape[1]
         self._folded = {}                     # the BatchNorm buffers are rewritten below, behind torch's version counters
@@ -130,10 +137,24 @@ class SegNet(nn.Module):
             raise RuntimeError(f"SegNet.forward: expected [B,{self.input_nbr},H,W] with H, W multiples of 32, got {tuple(x.shape)}")
         if self.training:
             return self._train_forward(x)
-        L = _lib.lib()
-        with torch.no_grad(), _lib.device_guard(x.device):
+        with torch.no_grad():
             a = x.detach().float().permute(0, 2, 3, 1)
             a = F.pad(a, (0, _pad4(C) - C)).contiguous()                  # NHWC, channels padded to 4
+            return self.forward_nhwc(a)[..., :self.label_nbr].permute(0, 3, 1, 2).contiguous()
+
+    def forward_nhwc(self, x):
+        """Eval forward on the channels-last input x [B,H,W,pad4(input_nbr)] fp32 (padding channels zero; what df_segment_input
+        writes) -> the channels-last activation [B,H,W,pad4(label_nbr)] whose first label_nbr channels are the logits."""
+        if self.training:
+            raise NotImplementedError("SegNet.forward_nhwc: eval mode only")
+        if not x.is_cuda:
+            raise RuntimeError("densefusion_amd needs device tensors (no CPU path): call .cuda() on the input")
+        if x.dim() != 4 or x.shape[3] != _pad4(self.input_nbr) or x.shape[1] % 32 or x.shape[2] % 32 or x.dtype != torch.float32:
+            raise RuntimeError(f"SegNet.forward_nhwc: expected fp32 [B,H,W,{_pad4(self.input_nbr)}] with H, W multiples of 32, "
+                               f"got {tuple(x.shape)} {x.dtype}")
+        L = _lib.lib()
+        with torch.no_grad(), _lib.device_guard(x.device):
+            a = x.contiguous()
             indices = []
             for item in _ENC + _DEC:
                 if item == "P":
@@ -157,4 +178,4 @@ class SegNet(nn.Module):
                         a = ops.conv3x3_winograd_nhwc(a, w, b, dil=1, act=act)
                     else:
                         a = ops.conv2d_nhwc(a, w, b, stride=1, pad=1, dil=1, act=act)
-            return a[..., :self.label_nbr].permute(0, 3, 1, 2).contiguous()
+            return a

@@ -256,6 +256,27 @@ int df_preprocess_objects(const unsigned char *rgb, const unsigned short *depth,
                           int64_t *choose_out, int *count_out, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Detections from SegNet's own masks (the RGB-D frame -> SegNet -> per-object mask and box step of the reference's real-robot
+ * setting; densefusion_amd/lib/segment.py).  Deterministic: no atomics, integer statistics, and a frame's results do not depend
+ * on the other frames of the call.
+ *
+ * df_segment_input: rgb [F][H][W][3] u8 (4-byte aligned) -> out [F][H][W][4] fp32 (16-byte aligned), the SegNet eval path's input:
+ *   ((float)v - mean_c) / std_c on the 0..255 values with the ImageNet mean / std (vanilla_segmentation/data_controller.py:79,
+ *   true division), channel 3 = 0.
+ * df_segment_detect: logits [F][H][W][ld] fp32 channels-last (16-byte aligned), the first C channels the classes; depth [F][H][W] u16.
+ *   label [F][H][W] int32 = arg-max over the C classes (first maximum wins, NaN counts as maximal);
+ *   stats [F][C][6] int32 = {pixels, pixels with depth != 0, rmin, rmax_excl, cmin, cmax_excl} of each class's tight box (zeros for
+ *   an absent class);  det [F][C][6] int32: per frame, the classes 1..num_obj with more than min_pixels depth-valid pixels
+ *   (datasets/ycb/dataset.py:87,146), ascending, as rows {cls, rmin, rmax_excl, cmin, cmax_excl, n_valid}, zero rows after them;
+ *   ndet [F] the number of rows.  C <= 64, C <= ld <= 64, ld a multiple of 4, num_obj < C.
+ *   scratch: df_segment_scratch_bytes(F, H, W, C) bytes (host-only query; 0 = bad sizes). */
+size_t df_segment_scratch_bytes(int F, int H, int W, int C);
+int df_segment_input(const unsigned char *rgb, float *out, int F, int H, int W, df_stream_t stream);
+int df_segment_detect(const float *logits, const unsigned short *depth, int F, int H, int W, int ld, int C, int num_obj,
+                      int min_pixels, int *label, int *stats, int *det, int *ndet, void *scratch, size_t scratch_bytes,
+                      df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]

@@ -16,6 +16,11 @@ mask pixels, or with a degenerate box, is reported as lost (zero pose), like the
 runs in ``--workers`` threads one window ahead, a window's frames go up in one copy that overlaps the previous window's
 compute, and ALL detections of the window -- bucketed by snapped crop size across its frames -- run through the network
 in one device call.  The result files do not depend on the window length (tests/test_eval_ycb_tool_gpu.py).
+
+``--segnet_model PATH`` (``--min_pixels``, default 50): no PoseCNN file is read; a ``SegNet(label_nbr=num_obj + 1)`` checkpoint
+gives the masks and ROIs on the device (densefusion_amd.lib.segment_pose: one detection per class with more than ``min_pixels``
+depth-valid pixels), and each result file also holds the detections' ``rois`` [n,7], in the order of ``poses``
+(tools/eval_ycb_auc.py --rois_from_results reads them).
 """
 from __future__ import annotations
 
@@ -32,6 +37,8 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from densefusion_amd.lib.eval_window import WindowEstimator  # noqa: E402
 from densefusion_amd.lib.network import PoseNet, PoseRefineNet  # noqa: E402
+from densefusion_amd.lib.segment_pose import SegmentPoseEstimator  # noqa: E402
+from densefusion_amd.vanilla_segmentation.segnet import SegNet  # noqa: E402
 
 
 def read_lines(path):
@@ -61,6 +68,9 @@ def build_parser():
     ap.add_argument("--window", type=int, default=32, help="keyframes per device call (1 = frame by frame)")
     ap.add_argument("--workers", type=int, default=8, help="PNG / .mat reader threads")
     ap.add_argument("--depth", type=int, default=4, help="windows in flight on the device (own stream and workspace each)")
+    ap.add_argument("--segnet_model", type=str, default="",
+                    help="SegNet checkpoint: detections from its masks (densefusion_amd.lib.segment_pose) instead of PoseCNN's .mat files")
+    ap.add_argument("--min_pixels", type=int, default=50, help="with --segnet_model: depth-valid mask pixels a class needs to be detected")
     return ap
 
 
@@ -93,7 +103,13 @@ def main(argv=None):
         return
     IH, IW = 480, 640
     depth = max(1, opt.depth)
-    we = WindowEstimator(estimator, refiner, opt.num_points, opt.iteration, window, (IH, IW), depth=depth)
+    if opt.segnet_model:
+        segnet = SegNet(label_nbr=opt.num_obj + 1)
+        segnet.load_state_dict(torch.load(opt.segnet_model, map_location="cpu", weights_only=True))
+        segnet.to(dev).eval()
+        we = SegmentPoseEstimator(segnet, estimator, refiner, opt.num_points, opt.iteration, window, depth, opt.min_pixels, (IH, IW))
+    else:
+        we = WindowEstimator(estimator, refiner, opt.num_points, opt.iteration, window, (IH, IW), depth=depth)
     # pinned host slots: `depth` windows whose uploads may still be in flight + the one the reader threads are filling
     NH = depth + 2
     host = [dict(rgb=torch.empty(window, IH, IW, 3, dtype=torch.uint8).pin_memory(),
@@ -106,6 +122,8 @@ def main(argv=None):
         h = host[slot]
         np.copyto(h["rgb"][f].numpy(), np.array(Image.open("{0}/{1}-color.png".format(opt.dataset_root, rel)))[:, :, :3])
         np.copyto(h["depth"][f].numpy(), np.array(Image.open("{0}/{1}-depth.png".format(opt.dataset_root, rel))).astype(np.uint16).view(np.int16))
+        if opt.segnet_model:
+            return None                                   # masks and ROIs come from the SegNet on the device
         meta = scio.loadmat("{0}/results_PoseCNN_RSS2018/{1}.mat".format(opt.ycb_toolbox_dir, "%06d" % now))
         np.copyto(h["label"][f].numpy(), np.array(meta["labels"]).astype(np.int32))
         return np.array(meta["rois"])
@@ -114,6 +132,14 @@ def main(argv=None):
         return [pool.submit(read_frame, wi % NH, f, now) for f, now in enumerate(windows[wi])]
 
     def finish(wi, handle, rois_per_frame):
+        if opt.segnet_model:
+            for now, r in zip(windows[wi], we.collect(handle)):
+                for idx in np.flatnonzero(r["lost"]):
+                    print("SegNet Detector Lost {0} at No.{1} keyframe".format(int(r["cls"][idx]), now))
+                scio.savemat("{0}/{1}.mat".format(opt.result_wo_refine_dir, "%04d" % now), {"poses": r["pose_wo_refine"], "rois": r["rois"]})
+                scio.savemat("{0}/{1}.mat".format(opt.result_refine_dir, "%04d" % now), {"poses": r["pose"], "rois": r["rois"]})
+                print("Finish No.{0} keyframe".format(now))
+            return
         wo, refined, lost = we.collect(handle)
         k = 0
         for now, rois in zip(windows[wi], rois_per_frame):
@@ -137,6 +163,9 @@ def main(argv=None):
             reads[wi + 1] = start_read(wi + 1)            # decoded while this window uploads and computes
         F = len(windows[wi])
         h = host[wi % NH]
+        if opt.segnet_model:
+            pending.append((wi, we.submit(h["rgb"][:F], h["depth"][:F], windows[wi], opt.seed), None))      # enqueued; the host
+            continue                                      # waits on the previous window's detection table only
         dets = [(f, int(rois[idx][1]), rois[idx], opt.seed + now * 64 + idx)
                 for f, (now, rois) in enumerate(zip(windows[wi], rois_per_frame)) for idx in range(rois.shape[0])]
         handle = we.submit(h["rgb"][:F], h["depth"][:F], h["label"][:F], dets)       # enqueued, no host sync

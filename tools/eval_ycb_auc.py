@@ -18,7 +18,8 @@ like MATLAB's KDTreeSearcher); everything else is host bookkeeping.  Output: a t
         --result_refine_dir <...> --result_wo_refine_dir <...>
 
 Expected files: ``<toolbox>/classes.txt``, ``<toolbox>/keyframe.txt`` (``0048/000001`` per line),
-``<toolbox>/results_PoseCNN_RSS2018/%06d.mat`` (``rois``), ``<dataset_root>/models/<class>/points.xyz``,
+``<toolbox>/results_PoseCNN_RSS2018/%06d.mat`` (``rois``; with ``--rois_from_results`` the ``rois`` of the refined result
+file instead, which tools/eval_ycb.py --segnet_model writes), ``<dataset_root>/models/<class>/points.xyz``,
 ``<dataset_root>/data/<seq>/<frame>-meta.mat`` (``cls_indexes``, ``poses`` [3,4,n]), result dirs with ``%04d.mat``
 (``poses`` [n,7]).
 """
@@ -45,6 +46,9 @@ def build_parser():
     ap.add_argument("--result_wo_refine_dir", type=str, default="experiments/eval_result/ycb/Densefusion_wo_refine_result")
     ap.add_argument("--output_dir", type=str, default="experiments/eval_result/ycb")
     ap.add_argument("--max_keyframes", type=int, default=0)
+    ap.add_argument("--rois_from_results", action="store_true",
+                    help="take each keyframe's detections from the `rois` of its refined result file (eval_ycb.py --segnet_model) "
+                         "instead of PoseCNN's")
     return ap
 
 
@@ -63,9 +67,10 @@ def collect(opt):
     recs = []
     for i, name in enumerate(keyframes):
         seq, frame = name.split("/")
-        det = scio.loadmat(os.path.join(opt.ycb_toolbox_dir, "results_PoseCNN_RSS2018", "%06d.mat" % i))
+        ref_mat = scio.loadmat(os.path.join(opt.result_refine_dir, "%04d.mat" % i))
+        det = ref_mat if opt.rois_from_results else scio.loadmat(os.path.join(opt.ycb_toolbox_dir, "results_PoseCNN_RSS2018", "%06d.mat" % i))
         rois = np.asarray(det["rois"], dtype=np.float64).reshape(-1, det["rois"].shape[-1]) if det["rois"].size else np.zeros((0, 7))
-        ref = scio.loadmat(os.path.join(opt.result_refine_dir, "%04d.mat" % i))["poses"]
+        ref = ref_mat["poses"]
         wo = scio.loadmat(os.path.join(opt.result_wo_refine_dir, "%04d.mat" % i))["poses"]
         gt = scio.loadmat(os.path.join(opt.dataset_root, "data", seq, "%s-meta.mat" % frame))
         cls_indexes = np.asarray(gt["cls_indexes"]).reshape(-1)
