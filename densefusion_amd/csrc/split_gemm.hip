@@ -4,8 +4,8 @@
 // and a product a*b is accumulated in fp32 from the six term pairs whose magnitude is above 2^-27 |a b|:
 //   lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi       (v_mfma_f32_32x32x16_bf16, 16x the fp32 MFMA rate: 16 / 6 = 2.7x at equal efficiency).
 // The result is inside fp32 rounding of the exact product, not bit-identical to the fp32-MFMA kernel's summation order.  Per output element
-// the order depends only on K: k-steps of 32 in ascending order, two k16 MFMAs per step, the six pairs in the fixed order above -- the same in
-// both tile forms, whatever M, the tile or the form picked.
+// the order depends only on K: k16 groups in ascending order, the six pairs in the fixed order above -- the same in all three tile forms,
+// whatever M, the tile or the form picked: the forms are bit-identical (tests/test_split_gemm_forms_gpu.py).
 // The weights are cut once per parameter load by their owner (the engine: Net planes, cut_weight_planes); the activations are cut while the
 // workgroup stages its tile (global fp32 -> registers -> three bf16 planes in LDS): no extra pass over HBM.
 // Covered: 1x1 / per-point / Winograd-domain launches (plain GEMMs: stride 1, no padding) with Cout % 128 == 0 and K % 32 == 0, bias (per
@@ -14,6 +14,8 @@
 // Development build only: DF_GEMM_SPLIT_OFF=1 keeps every launch on fp32; DF_GEMM_SPLIT_BF16=1 also takes eligible launches without planes
 // (their weights are cut per launch into a per-stream scratch).  Measurements: DESIGN.md section 6, profiles/r04_experiments/README.md.
 #include "igemm.h"
+#include <atomic>
+#include <cstdint>
 #ifdef DF_DEV
 #include <map>
 #include <mutex>
@@ -114,6 +116,71 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs &a, const f32x16 
       if (fh == 0) a.colsum[((size_t)z * a.cs_rows + (size_t)cs_row) * a.N + n] = csum;
     }
   }
+}
+
+// The same epilogue for the 256-column form, stores row-contiguous: the wave passes its 64 x 64 block through its own 16 KB of LDS (`blk`; the
+// main loop's stages are free by then, and only this wave touches it: no workgroup barrier) and writes 4 rows x 256 bytes per instruction instead
+// of 2 rows x 128; a residual is read the same way.  Per element the arithmetic and its order are split_epilogue's: + bias in the fragment layout
+// (lane = column), then + residual, then the activation.  Column sums are taken in the fragment layout, in split_epilogue's order (launches with
+// column sums have no residual: GEMM_EPI_OTHER is not routed).  Needs 16-byte aligned output / residual rows (try_split_gemm checks)
+__device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f32x16 (&acc)[2][2], int z, long row0, int wrow, int nb, int lane, long cs_row, float *blk) {
+  const int fr = lane & 31, fh = lane >> 5;
+  const float slope = a.act == ACT_PRELU ? a.prelu[0] : 0.f;
+  const float *bias = a.bias ? a.bias + z * a.z_bias : nullptr;
+  const float *gbias = bias && a.bias_group_ld > 0 ? bias + (row0 / a.rows_per_group) * a.bias_group_ld : nullptr;
+  const int grp = a.rows_per_group > 0 ? (int)(row0 / a.rows_per_group) : 0;
+  const long left = a.M - row0;
+  const int valid = a.rows_per_group > 0 ? a.rows_valid - (int)(row0 - (long)grp * a.rows_per_group) : (1 << 30);
+  const int limit = (int)(left < valid ? left : valid);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = nb + j * 32 + fr;
+    const float b1 = gbias ? gbias[n] : bias ? bias[n] : 0.f;
+    float csum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int br = i * 32 + 4 * fh + (e & 3) + 8 * (e >> 2);          // row inside the block
+        float v = acc[i][j][e] + b1;
+        if (!a.res) {
+          if (a.act == ACT_RELU) v = v > 0.f ? v : 0.f;
+          else if (a.act == ACT_PRELU) v = v > 0.f ? v : v * slope;
+        }
+        blk[br * 64 + j * 32 + fr] = v;
+        csum += wrow + br < limit ? v : 0.f;
+      }
+    if (a.colsum && cs_row < a.cs_rows) {
+      csum += __shfl_xor(csum, 32);
+      if (fh == 0) a.colsum[((size_t)z * a.cs_rows + (size_t)cs_row) * a.N + n] = csum;
+    }
+  }
+  if (!a.out) return;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  float *out = a.out + z * a.z_out_coff + a.out_coff;
+  const int c4 = (lane & 15) * 4;
+#pragma unroll 4
+  for (int it = 0; it < 16; ++it) {
+    const int br = it * 4 + (lane >> 4);
+    const long m = row0 + wrow + br;
+    float4 v = *reinterpret_cast<const float4 *>(blk + br * 64 + c4);
+    if (m < a.M) {
+      if (a.res) {
+        const float4 r = *reinterpret_cast<const float4 *>(a.res + m * a.res_ld + a.res_coff + nb + c4);
+        v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+        if (a.act == ACT_RELU) {
+          v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
+        } else if (a.act == ACT_PRELU) {
+          v.x = v.x > 0.f ? v.x : v.x * slope; v.y = v.y > 0.f ? v.y : v.y * slope; v.z = v.z > 0.f ? v.z : v.z * slope; v.w = v.w > 0.f ? v.w : v.w * slope;
+        }
+      }
+      *reinterpret_cast<float4 *>(out + m * a.out_ld + nb + c4) = v;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
 }
 
 __global__ __launch_bounds__(256, 2) void gemm_split_bf16_kernel(const SplitArgs a) {
@@ -372,6 +439,167 @@ __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v2_kernel(const SplitA
   split_epilogue(a, acc, z, row0, wr * 64, n0 + wc * 64, fr, fh, (long)tm * 4 + wr);
 }
 
+// Third form: 256 x 256 x 16 tile, 8 waves (2 x 4) of 128 x 64, two LDS stages of one k16 group each (96 KB: one workgroup per CU) and one barrier
+// per group.  Per MFMA it cuts and loads half the activations of the 256 x 128 form (a row tile is staged N / 256 times instead of N / 128) and
+// reads 18 fragments per 48 MFMAs instead of 24.  Per output element nothing moves: k16 groups in ascending k, the six pairs in the same order,
+// the same epilogue on 64 x 64 blocks (a wave owns two, one column-sum partial row each).
+constexpr int V3_PL = 256 * 32, V3_STAGE = 6 * V3_PL;          // a plane: 256 rows x 16 bf16; a stage: A planes 0..2, B planes 3..5
+constexpr int V3_LDS = 8 * 64 * 64 * 4;                          // the epilogue's eight 64 x 64 fp32 blocks: more than the two stages
+
+// byte offset of the 16-byte half `half` (8 consecutive k) of row `row` inside a k16 plane: 32-byte rows, the half XOR-ed with bit 3 of the row:
+// the 16 rows of a ds_read_b128 lane group ({0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} of a fragment's 32) then cover the 16 slots of the
+// 256-byte bank row once each, and the 8 x 8-lane groups of the staging ds_write_b128 (row = tid / 2) write 128 contiguous bytes
+__device__ __forceinline__ int piece16(int row, int half) { return row * 32 + ((half ^ ((row >> 3) & 1)) << 4); }
+
+__global__ __launch_bounds__(512, 1) void gemm_split_bf16_v3_kernel(const SplitArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds3[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  const int tm = (seq / a.tiles_n) * 8 + xcd, tn = seq % a.tiles_n;
+  if (tm >= a.tiles_m) return;
+  const int z = blockIdx.z;
+  const long row0 = (long)tm * 256;
+  const int n0 = tn * 256;
+  const float *in = a.in + z * a.z_in_coff + a.in_coff;
+  const __bf16 *wpl = a.wpl + z * a.z_wgt;
+
+  // staging roles: piece tid of the 512 (row, 8-k) pieces of the activation tile and of each weight plane's tile
+  const int srow = tid >> 1, shalf = tid & 1;
+  const int soff = piece16(srow, shalf);
+  long r = row0 + srow;
+  r = r < a.M ? r : a.M - 1;                                      // the last row tile re-reads row M - 1 (its results are not stored)
+  const float *ag = in + r * a.in_ld + shalf * 8;
+  const __bf16 *bg = wpl + (long)(n0 + srow) * a.K + shalf * 8;
+  // activations (HBM) two groups ahead in two register sets, weight planes (L2) one group ahead
+  float4 xa0, xa1, ya0, ya1;
+  uint4 b0, b1, b2;
+#define V3_FETCH_A(S, k0)                                                        \
+  do {                                                                           \
+    S##a0 = *reinterpret_cast<const float4 *>(ag + (k0));                        \
+    S##a1 = *reinterpret_cast<const float4 *>(ag + (k0) + 4);                    \
+  } while (0)
+#define V3_FETCH_B(k0)                                                           \
+  do {                                                                           \
+    b0 = *reinterpret_cast<const uint4 *>(bg + (k0));                            \
+    b1 = *reinterpret_cast<const uint4 *>(bg + a.wplane + (k0));                 \
+    b2 = *reinterpret_cast<const uint4 *>(bg + 2 * a.wplane + (k0));             \
+  } while (0)
+  // (the empty asm pins a cut behind the phase boundary in front of it: without it instruction selection may start the cut right behind the
+  // set's loads, and the wave then waits out the whole HBM round trip instead of covering it with a group of MFMAs)
+#define V3_PIN(v) asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w))
+#define V3_CUT0(S) do { V3_PIN(S##a0); cut3(S##a0.x, S##a0.y, ch.x, cm.x, cl.x); cut3(S##a0.z, S##a0.w, ch.y, cm.y, cl.y); } while (0)
+#define V3_CUT1(S) do { V3_PIN(S##a1); cut3(S##a1.x, S##a1.y, ch.z, cm.z, cl.z); cut3(S##a1.z, S##a1.w, ch.w, cm.w, cl.w); } while (0)
+#define V3_WRITE_A(base)                                                         \
+  do {                                                                           \
+    *reinterpret_cast<uint4 *>((base) + soff) = ch;                              \
+    *reinterpret_cast<uint4 *>((base) + V3_PL + soff) = cm;                      \
+    *reinterpret_cast<uint4 *>((base) + 2 * V3_PL + soff) = cl;                  \
+  } while (0)
+#define V3_WRITE_B(base)                                                         \
+  do {                                                                           \
+    *reinterpret_cast<uint4 *>((base) + 3 * V3_PL + soff) = b0;                  \
+    *reinterpret_cast<uint4 *>((base) + 4 * V3_PL + soff) = b1;                  \
+    *reinterpret_cast<uint4 *>((base) + 5 * V3_PL + soff) = b2;                  \
+  } while (0)
+
+  const int wr = wave >> 2, wc = wave & 3, fr = lane & 31, fh = lane >> 5;
+  f32x16 acc[2][2][2];          // [64-row block of the wave][32-row tile][32-column tile]
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[h][i][j][e] = 0.f;
+  // (a tile's 32-row offset leaves bit 3 of the row alone: the four A and two B fragments of a plane are one address plus constants)
+  const int offa = piece16(wr * 128 + fr, fh), offb = 3 * V3_PL + piece16(wc * 64 + fr, fh);
+  // the six pairs in the kernel's fixed order (A plane, B plane): lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi; pair-major as in the second form.
+  // Pairs 0..2 bring a new A and a new B plane each: V3_READ(q) is the six fragments pair q is the first to use
+#define V3_PA(q) ((q) == 0 ? 2 : (q) == 2 || (q) == 3 ? 1 : 0)
+#define V3_PB(q) ((q) == 1 ? 2 : (q) == 2 || (q) == 4 ? 1 : 0)
+#define V3_READ(base, q)                                                                                  \
+  do {                                                                                                    \
+    _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                         \
+      fa[t][V3_PA(q)] = *reinterpret_cast<const bf16x8 *>((base) + V3_PA(q) * V3_PL + offa + t * 1024);   \
+    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                         \
+      fb[t][V3_PB(q)] = *reinterpret_cast<const bf16x8 *>((base) + V3_PB(q) * V3_PL + offb + t * 1024);   \
+  } while (0)
+#define V3_MFMA(q)                                                                                        \
+  do {                                                                                                    \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                         \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                         \
+      acc[i >> 1][i & 1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][V3_PA(q)], fb[j][V3_PB(q)], acc[i >> 1][i & 1][j], 0, 0, 0); \
+  } while (0)
+  // n x (one MFMA, then `cnt` instructions of class `mask`): the filler sits in the MFMA gaps of the SAME wave (a wave issuing MFMAs back to back
+  // blocks the other wave of its SIMD: DESIGN 6a); a full scheduling barrier closes each phase so that nothing drifts across it
+#define V3_WEAVE(n, mask, cnt)                                                   \
+  do {                                                                           \
+    _Pragma("unroll") for (int g = 0; g < (n); ++g) {                            \
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                         \
+      __builtin_amdgcn_sched_group_barrier(mask, cnt, 0);                        \
+    }                                                                            \
+    __builtin_amdgcn_sched_barrier(0);                                           \
+  } while (0)
+  // one k16 group in six phases of 8 MFMAs (one pair each): weight loads of group s + 1 and activation loads of group s + 2 (clamped to the last
+  // group: harmless re-read); pairs 0 and 1 run under the fragment reads of the planes the later pairs need, pairs 2 and 3 under the cut of group
+  // s + 1, pairs 4 and 5 under its LDS stores into the other stage (the weight planes last: their loads are the youngest)
+#define V3_BODY(FS, SS, ka, kb, cur, nxt)                                        \
+  do {                                                                           \
+    bf16x8 fa[4][3], fb[2][3];                                                   \
+    uint4 ch, cm, cl;                                                            \
+    V3_FETCH_B(kb);                                                              \
+    V3_FETCH_A(FS, ka);                                                          \
+    V3_READ(cur, 0);                                                             \
+    __builtin_amdgcn_sched_barrier(0);                                           \
+    V3_READ(cur, 1);                                                             \
+    V3_MFMA(0);                                                                  \
+    V3_WEAVE(6, 0x100, 1);                                                       \
+    V3_READ(cur, 2);                                                             \
+    V3_MFMA(1);                                                                  \
+    V3_WEAVE(6, 0x100, 1);                                                       \
+    V3_CUT0(SS);                                                                 \
+    V3_MFMA(2);                                                                  \
+    V3_WEAVE(8, 0x002, 3);                                                       \
+    V3_CUT1(SS);                                                                 \
+    V3_MFMA(3);                                                                  \
+    V3_WEAVE(8, 0x002, 3);                                                       \
+    V3_WRITE_A(nxt);                                                             \
+    V3_MFMA(4);                                                                  \
+    V3_WEAVE(3, 0x200, 1);                                                       \
+    V3_WRITE_B(nxt);                                                             \
+    V3_MFMA(5);                                                                  \
+    V3_WEAVE(3, 0x200, 1);                                                       \
+    __syncthreads();                                                             \
+  } while (0)
+
+  unsigned char *const st0 = lds3, *const st1 = lds3 + V3_STAGE;
+  const int nk = a.K / 16;          // even: K % 32 == 0
+  const int klast = a.K - 16;
+  V3_FETCH_B(0);
+  V3_FETCH_A(x, 0);
+  V3_FETCH_A(y, 16);
+  {
+    uint4 ch, cm, cl;
+    V3_CUT0(x);
+    V3_CUT1(x);
+    V3_WRITE_A(st0);
+    V3_WRITE_B(st0);
+  }
+  __syncthreads();
+  for (int s = 0; s < nk; s += 2) {
+    // stage 0: group s; set y: group s + 1
+    const int k1 = (s + 1) * 16, k2 = (s + 2) * 16, k3 = (s + 3) * 16;
+    V3_BODY(x, y, k2 < klast ? k2 : klast, k1, st0, st1);
+    // stage 1: group s + 1; set x: group s + 2
+    V3_BODY(y, x, k3 < klast ? k3 : klast, k2 < klast ? k2 : klast, st1, st0);
+  }
+  const int cs0 = tm * 4 + wr * 2;
+  float *const blk = reinterpret_cast<float *>(lds3) + wave * (64 * 64);          // (every wave is past the loop's last barrier: the stages are free)
+  split_epilogue_rows(a, acc[0], z, row0, wr * 128, n0 + wc * 64, lane, (long)cs0, blk);
+  split_epilogue_rows(a, acc[1], z, row0, wr * 128 + 64, n0 + wc * 64, lane, (long)cs0 + 1, blk);
+}
+
 #ifdef DF_DEV
 // development switch DF_GEMM_SPLIT_BF16: planes of weights that come without them, cut per launch into a per-(device, stream) scratch
 std::mutex g_mu;
@@ -414,6 +642,20 @@ void cut_weight_planes(const float *w, void *planes, long elems, long stride, hi
   hipLaunchKernelGGL(cut_planes_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, w, reinterpret_cast<__bf16 *>(planes), elems, stride);
 }
 
+// compute units of the current device (one query per device)
+static int compute_units() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64) return 256;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
 int try_split_gemm(const ConvParams &p, hipStream_t st) {
   static const bool off = dev_getenv("DF_GEMM_SPLIT_OFF") != nullptr;
   static const bool all = dev_getenv("DF_GEMM_SPLIT_BF16") != nullptr;
@@ -448,11 +690,25 @@ int try_split_gemm(const ConvParams &p, hipStream_t st) {
   a.z_in_coff = p.z_in_coff; a.z_wgt = p.z_wgt; a.z_bias = p.z_bias; a.z_out_coff = p.z_out_coff;
   a.cs_rows = ((M + 127) / 128) * 2;
   a.tiles_n = p.Cout / SBN;
-  static const int variant = dev_getenv("DF_GEMM_SPLIT_V") ? atoi(dev_getenv("DF_GEMM_SPLIT_V")) : 2;
-  // measured per shape: the 256-row form wins from K = 384 up (189 against 172 TFLOP/s on 139 000 x 2 304 x 1 024), the 128-row form below.
-  // Both add the same products in the same order per element: the choice (by K and the layer's row groups, never by M) changes no bit
-  const bool v2 = variant == 2 && K >= 384 && (p.rows_per_group == 0 || p.rows_per_group % 256 == 0);
-  if (v2) {
+  static const int variant = dev_getenv("DF_GEMM_SPLIT_V") ? atoi(dev_getenv("DF_GEMM_SPLIT_V")) : 3;
+  // measured per shape: the 256-row forms win from K = 384 up (189 against 172 TFLOP/s on 139 000 x 2 304 x 1 024), the 128-row form below.
+  // All forms add the same products in the same order per element: the choice changes no bit
+  const bool v2 = variant >= 2 && K >= 384 && (p.rows_per_group == 0 || p.rows_per_group % 256 == 0);
+  // the 256-column form where N allows it and its tiles still fill the card (the 1 440-row psp fold has 96 of them: it keeps 128 columns)
+  const long tiles3 = ((M + 255) / 256) * (p.Cout / 256) * p.zcount;
+  // (its epilogue moves whole 16-byte pieces of output and residual rows)
+  const bool rows16 = (!p.out || (reinterpret_cast<uintptr_t>(p.out) % 16 == 0 && p.out_ld % 4 == 0 && p.out_coff % 4 == 0 && p.z_out_coff % 4 == 0)) &&
+                      (!p.res || (reinterpret_cast<uintptr_t>(p.res) % 16 == 0 && p.res_ld % 4 == 0 && p.res_coff % 4 == 0));
+  const bool v3 = v2 && variant >= 3 && p.Cout % 256 == 0 && rows16 && tiles3 >= compute_units();
+  if (verbose) fprintf(stderr, "[df-split]   form %s\n", v3 ? "256x256" : v2 ? "256x128" : "128x128");
+  if (v3) {
+    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm_split_bf16_v3_kernel), V3_LDS);
+    if (rc != DF_OK) return rc;
+    a.tiles_m = (int)((M + 255) / 256);
+    a.tiles_n = p.Cout / 256;
+    const unsigned grid = (unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n);
+    hipLaunchKernelGGL(gemm_split_bf16_v3_kernel, dim3(grid, 1, p.zcount), dim3(512), V3_LDS, st, a);
+  } else if (v2) {
     const int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm_split_bf16_v2_kernel), 2 * V2_STAGE);
     if (rc != DF_OK) return rc;
     a.tiles_m = (int)((M + 255) / 256);
