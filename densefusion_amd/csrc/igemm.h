@@ -43,6 +43,11 @@ struct ConvParams {
   size_t splitk_ws_bytes = 0;
 };
 
+// Fused column sums add a tile's rows in per-wave groups, and that grouping must not depend on the batch size (a batched call stays
+// bit-identical to solo calls): whatever tile a launch takes, a partial row covers COLSUM_ROWS output rows -- COLSUM_WAVES_M of them per
+// COLSUM_BM-row tile, the tile the fp32 kernels keep for such launches (csrc/igemm.hip pick_cfg).  Shared with csrc/split_gemm.hip.
+constexpr int COLSUM_BM = 128, COLSUM_WAVES_M = 2, COLSUM_ROWS = COLSUM_BM / COLSUM_WAVES_M;
+inline long colsum_partial_rows(long M) { return ((M + COLSUM_BM - 1) / COLSUM_BM) * COLSUM_WAVES_M; }      // per z
 // number of colsum partial rows a column-sum launch with these params writes (so callers can size the buffer before p.colsum is set)
 int conv_colsum_rows(const ConvParams &p);
 // FLOPs (2*MAC) of the launch, algorithmic (no padding)
@@ -104,7 +109,8 @@ int split_route(int N, int K, int epi);
 // cut `elems` weights into their three bf16 planes (term p of w[i] at planes[p * stride + i], bf16 elements) on stream st
 void cut_weight_planes(const float *w, void *planes, long elems, long stride, hipStream_t st);
 // launch_conv's first step: 1 when the launch was taken by the bf16 x 6 kernel (p.wpl set and split_route true; development build: also
-// DF_GEMM_SPLIT_BF16), 0 when it goes on to the fp32 kernels, or a DF_ERR_* code
-int try_split_gemm(const ConvParams &p, hipStream_t st);
+// DF_GEMM_SPLIT_BF16) -- r is then its route: CONV_BF16 and the tile of the form it ran on --, 0 when it goes on to the fp32 kernels (r
+// untouched), or a DF_ERR_* code
+int try_split_gemm(const ConvParams &p, hipStream_t st, ConvRoute &r);
 
 }  // namespace df

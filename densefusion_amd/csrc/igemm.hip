@@ -1352,7 +1352,7 @@ __global__ __launch_bounds__(256) void bias_reduce_kernel(const float *__restric
 }
 
 
-struct TileCfg { int bm, bn, wmv; };     // workgroup tile and waves along M
+struct TileCfg { int bm, bn; };     // workgroup tile
 
 bool force_v1() {
   static const bool f = df::dev_getenv("DF_IGEMM_V1") != nullptr;   // dev switch: A/B against the un-pipelined kernel; read once
@@ -1378,13 +1378,13 @@ TileCfg pick_cfg(const ConvParams &p, bool colsum) {
   // tiles of 128) is cut into 9 columns of 128x64 tiles.
   // The fused column sum adds rows in per-wave groups: keep that grouping independent of the batch size (so
   // a batched call stays bit-identical to solo calls) by always using the 128x128 tile for it.
-  if (colsum) return {128, 128, 2};
+  if (colsum) return {COLSUM_BM, 128};
   const bool v4 = takes_v4(p);                      // v1 has the two square tiles only
   static const char *const tile_env = df::dev_getenv("DF_IGEMM_TILE");      // dev switch for A/B runs; read once
   if (tile_env) {
-    if (tile_env[0] == 'a') return {128, 128, 2};
-    if (tile_env[0] == 'b' && v4) return {128, 64, 2};
-    if (tile_env[0] == 'c' || tile_env[0] == 'b') return {64, 64, 2};
+    if (tile_env[0] == 'a') return {128, 128};
+    if (tile_env[0] == 'b' && v4) return {128, 64};
+    if (tile_env[0] == 'c' || tile_env[0] == 'b') return {64, 64};
   }
   auto cost = [&](int bm, int bn, double eff) {
     const long tiles = ((M + bm - 1) / bm) * ((p.Cout + bn - 1) / bn) * p.zcount;
@@ -1393,9 +1393,9 @@ TileCfg pick_cfg(const ConvParams &p, bool colsum) {
   };
   // efficiencies from the per-shape table of a bench step run with each tile forced (tools/dev/gemm_list.sh)
   const double ca = p.Cout >= 128 ? cost(128, 128, 1.0) : 1e300, cb = v4 ? cost(128, 64, 0.99) : 1e300, cc = cost(64, 64, 0.96);
-  if (ca <= cb && ca <= cc) return {128, 128, 2};
-  if (cb <= cc) return {128, 64, 2};
-  return {64, 64, 2};
+  if (ca <= cb && ca <= cc) return {128, 128};
+  if (cb <= cc) return {128, 64};
+  return {64, 64};
 }
 
 // v4 loader: 1 plain GEMM; 2 several taps, every 32-wide k tile inside one tap, tap mask in 32 bits, offsets below 2^31 (`shifted`: the
@@ -1583,13 +1583,9 @@ void launch_v4(const ConvPlan &pl, hipStream_t st) {
 int launch_plan(ConvPlan &pl, hipStream_t st) {
   if (pl.r.kernel == CONV_NONE) return DF_OK;
   if (pl.r.kernel != CONV_V4_MULTI) {
-    const int taken = try_split_gemm(pl.p, st);
+    const int taken = try_split_gemm(pl.p, st, pl.r);
     if (taken < 0) return taken;
-    if (taken) {
-      pl.r = ConvRoute{};
-      pl.r.kernel = CONV_BF16;
-      return check_launch("split gemm");
-    }
+    if (taken) return check_launch("split gemm");
   }
   const dim3 grid(pl.tiles, 1, pl.gz);
   const bool big = pl.r.bm == 128 && pl.r.bn == 128;
@@ -1631,9 +1627,7 @@ int launch_plan(ConvPlan &pl, hipStream_t st) {
 }  // namespace
 
 int conv_colsum_rows(const ConvParams &p) {
-  const TileCfg c = pick_cfg(p, true);      // the column-sum launch's tile, whether or not p.out / p.colsum are set yet
-  const long M = (long)p.B * p.OH * p.OW;
-  return (int)(((M + c.bm - 1) / c.bm) * c.wmv) * p.zcount;
+  return (int)colsum_partial_rows((long)p.B * p.OH * p.OW) * p.zcount;      // (whether or not p.out / p.colsum are set yet)
 }
 
 double conv_bytes(const ConvParams &p) {

@@ -13,6 +13,13 @@
 // epilogue kind) of a launch whose weights come with planes (ConvParams::wpl); everything else stays on the fp32 kernels.
 // Development build only: DF_GEMM_SPLIT_OFF=1 keeps every launch on fp32; DF_GEMM_SPLIT_BF16=1 also takes eligible launches without planes
 // (their weights are cut per launch into a per-stream scratch).  Measurements: DESIGN.md section 6, profiles/r04_experiments/README.md.
+//
+// Layout of this file.  What the three tile forms must agree on is stated once, ahead of the kernels: the order of the six pairs (pair_a /
+// pair_b), the cut of eight floats (cut4 / cut8), the tile walk and z offsets (split_tile), the fragment addresses of the two 128-column
+// forms (SPLIT_FRAG_OFFSETS), and the epilogue's rules (epi_rules, epi_finish, epi_colsum) under its two store paths.  The kernels keep what was
+// tuned per form: the fetch / stage / multiply pipelines and their issue-order pins.  On the host plan_split decides everything about a
+// launch (taken or not, form, grid, LDS bytes, kernel arguments) without a HIP call or an environment read; try_split_gemm reads the
+// development switches, runs the plan and makes the one dispatch through the form table (FORMS / the kernel pointers beside it).
 #include "igemm.h"
 #include <atomic>
 #include <cstdint>
@@ -45,6 +52,29 @@ __device__ __forceinline__ void cut3(float a0, float a1, unsigned &hi, unsigned 
   lo = __builtin_bit_cast(unsigned, l);
 }
 
+// half H (k 0..3 or 4..7) of the (hi, mid, lo) 16-byte pieces of eight consecutive k
+template <int H>
+__device__ __forceinline__ void cut4(const float4 &x, uint4 &h, uint4 &m, uint4 &l) {
+  if (H == 0) { cut3(x.x, x.y, h.x, m.x, l.x); cut3(x.z, x.w, h.y, m.y, l.y); }
+  else { cut3(x.x, x.y, h.z, m.z, l.z); cut3(x.z, x.w, h.w, m.w, l.w); }
+}
+__device__ __forceinline__ void cut8(const float4 &x0, const float4 &x1, uint4 &h, uint4 &m, uint4 &l) { cut4<0>(x0, h, m, l); cut4<1>(x1, h, m, l); }
+
+// The six term pairs in the one order every form multiplies them, small terms first (lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi): the plane
+// (0 hi, 1 mid, 2 lo) of A and of B of pair q
+__host__ __device__ constexpr int pair_a(int q) { constexpr int t[6] = {2, 0, 1, 1, 0, 0}; return t[q]; }
+__host__ __device__ constexpr int pair_b(int q) { constexpr int t[6] = {0, 2, 1, 0, 1, 0}; return t[q]; }
+__device__ __forceinline__ f32x16 mfma_pair(const bf16x8 (&fa)[3], const bf16x8 (&fb)[3], int q, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[pair_a(q)], fb[pair_b(q)], c, 0, 0, 0);
+}
+// (the 256 x 256 form reads a group's fragments in the phases of pairs 0..2: each of them must be the first to use its A and its B plane)
+constexpr bool pair_brings_new_planes(int q) {
+  for (int r = 0; r < q; ++r)
+    if (pair_a(r) == pair_a(q) || pair_b(r) == pair_b(q)) return false;
+  return true;
+}
+static_assert(pair_brings_new_planes(0) && pair_brings_new_planes(1) && pair_brings_new_planes(2), "pairs 0..2 must reach all planes of A and of B");
+
 // planes[p * stride + i] = term p of w[i]
 __global__ void cut_planes_kernel(const float *__restrict__ w, __bf16 *__restrict__ planes, long elems, long stride) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,30 +91,137 @@ struct SplitArgs {
   int N, K, in_ld, in_coff, out_ld, out_coff, res_ld, res_coff, act, rows_per_group, rows_valid, bias_group_ld;
   long z_in_coff, z_wgt, z_bias, z_out_coff;
   int tiles_m, tiles_n;         // of the launched kernel's tile
-  long cs_rows;                 // rows of the column-sum partial buffer per z: 2 per 128 rows (igemm.h conv_colsum_rows)
+  long cs_rows;                 // rows of the column-sum partial buffer per z (igemm.h colsum_partial_rows)
 };
 
 // byte offset of the 16-byte piece `slot` (8 consecutive k) of row `row` inside a plane: 64-byte rows, the slot XOR-ed with bits 2..3 of the
 // row so that the 16 rows a ds_read_b128 lane group touches fall on 16 different 16-byte bank slots
 __device__ __forceinline__ int piece(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
 
-// epilogue of one wave's 64 x 64 block: lane = output channel (col), registers = 16 pixel rows: row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5).
-// row0: first row of the workgroup's tile (inside ONE row group: host-checked), wrow: the wave's row offset in it, nb: its first column,
-// cs_row: its row in the column-sum partial buffer (one per 64 tile rows, the fp32 kernel's layout)
-__device__ __forceinline__ void split_epilogue(const SplitArgs &a, const f32x16 (&acc)[2][2], int z, long row0, int wrow, int nb, int fr, int fh, long cs_row) {
-  const float slope = a.act == ACT_PRELU ? a.prelu[0] : 0.f;
-  float *out = a.out + z * a.z_out_coff + a.out_coff;
+// A workgroup's tile and its z batch.  XCD-aware order: the 8 XCDs take whole row tiles, the column tiles of a row tile run back to back on
+// one XCD (its A rows stay in that L2).  false: a padding workgroup of the grid (no tile)
+struct SplitTile { int tm, tn, z; const float *in; const __bf16 *wpl; };
+__device__ __forceinline__ bool split_tile(const SplitArgs &a, SplitTile &t) {
+  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+  t.tm = (seq / a.tiles_n) * 8 + xcd;
+  t.tn = seq % a.tiles_n;
+  t.z = blockIdx.z;
+  t.in = a.in + t.z * a.z_in_coff + a.in_coff;
+  t.wpl = a.wpl + t.z * a.z_wgt;
+  return t.tm < a.tiles_m;
+}
+
+// Steps the kernels' pipelines share, as macros over the kernels' own names like the pipeline steps they are part of (a, tid, row0, n0, wg,
+// the lane roles wr / wc / fr / fh).  (Tried as an inlined function, SPLIT_FRAG_OFFSETS reordered the second form's main loop.)
+// All forms: the three planes of one 16-byte piece, from the weight planes in memory (g: the piece in plane 0), and into LDS planes `stride` apart
+#define SPLIT_FETCH3(p0, p1, p2, g, k0)                                          \
+  do {                                                                           \
+    p0 = *reinterpret_cast<const uint4 *>((g) + (k0));                           \
+    p1 = *reinterpret_cast<const uint4 *>((g) + a.wplane + (k0));                \
+    p2 = *reinterpret_cast<const uint4 *>((g) + 2 * a.wplane + (k0));            \
+  } while (0)
+#define SPLIT_STORE3(base, stride, off, p0, p1, p2)                              \
+  do {                                                                           \
+    *reinterpret_cast<uint4 *>((base) + (off)) = p0;                             \
+    *reinterpret_cast<uint4 *>((base) + (stride) + (off)) = p1;                  \
+    *reinterpret_cast<uint4 *>((base) + 2 * (stride) + (off)) = p2;              \
+  } while (0)
+// The two 128-column forms (waves of 64 x 64, k-steps of 32).  Fragment addresses, [k16 step][32-row / 32-column tile] (b0: byte offset of B
+// plane 0), and the fragments of k16 step ks, [tile][plane]
+#define SPLIT_FRAG_OFFSETS(b0)                                                   \
+  int offa[2][2], offb[2][2];                                                    \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                               \
+  _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                \
+    offa[ks][t] = piece(wr * 64 + t * 32 + fr, ks * 2 + fh);                     \
+    offb[ks][t] = (b0) + piece(wc * 64 + t * 32 + fr, ks * 2 + fh);              \
+  }
+#define SPLIT_READ_FRAGS(base, apl, bpl)                                                                  \
+  bf16x8 fa[2][3], fb[2][3];                                                                              \
+  _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                           \
+  _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                                         \
+    fa[t][p] = *reinterpret_cast<const bf16x8 *>((base) + p * (apl) + offa[ks][t]);                       \
+    fb[t][p] = *reinterpret_cast<const bf16x8 *>((base) + p * (bpl) + offb[ks][t]);                       \
+  }
+// Their staging: a thread owns two (row, 8-k) pieces of the activation tile, `half` rows (half the tile) apart: the pieces' LDS offsets, their
+// global rows (the last row tile re-reads row M - 1: its results are not stored) and the weight row of the first; the fetch of a register
+// set S (x / y) and its cut into the planes at `base`
+#define SPLIT_STAGE_ROLES(half)                                                  \
+  const int srow0 = tid >> 2, srow1 = srow0 + (half), sslot = tid & 3;           \
+  const int soff0 = piece(srow0, sslot), soff1 = piece(srow1, sslot);            \
+  long r0 = row0 + srow0, r1 = row0 + srow1;                                     \
+  r0 = r0 < a.M ? r0 : a.M - 1;                                                  \
+  r1 = r1 < a.M ? r1 : a.M - 1;                                                  \
+  const float *ag0 = wg.in + r0 * a.in_ld + sslot * 8, *ag1 = wg.in + r1 * a.in_ld + sslot * 8; \
+  const __bf16 *bg0 = wg.wpl + (long)(n0 + srow0) * a.K + sslot * 8
+#define SPLIT_FETCH_A(S, k0)                                                     \
+  do {                                                                           \
+    S##a00 = *reinterpret_cast<const float4 *>(ag0 + (k0));                      \
+    S##a01 = *reinterpret_cast<const float4 *>(ag0 + (k0) + 4);                  \
+    S##a10 = *reinterpret_cast<const float4 *>(ag1 + (k0));                      \
+    S##a11 = *reinterpret_cast<const float4 *>(ag1 + (k0) + 4);                  \
+  } while (0)
+#define SPLIT_CUT_STORE(x0, x1, base, stride, off)                               \
+  do {                                                                           \
+    uint4 h, m, l;                                                               \
+    cut8(x0, x1, h, m, l);                                                       \
+    SPLIT_STORE3(base, stride, off, h, m, l);                                    \
+  } while (0)
+
+// The epilogue's rules for one wave's 64 x 64 block, shared by its two store paths.  row0: first row of the workgroup's tile (inside ONE row
+// group: host-checked), wrow: the block's row offset in it
+struct EpiRules {
+  float slope;            // PReLU
+  const float *bias;      // the block's bias row (per channel, or its row group's), or null
+  int limit;              // tile rows below it are real points: the rows fused column sums cover (igemm.h)
+  long cs_row;            // the block's row in the column-sum partial buffer: one per COLSUM_ROWS rows, the fp32 kernel's layout
+};
+__device__ __forceinline__ EpiRules epi_rules(const SplitArgs &a, int z, long row0, int wrow) {
+  EpiRules r;
+  r.slope = a.act == ACT_PRELU ? a.prelu[0] : 0.f;
   const float *bias = a.bias ? a.bias + z * a.z_bias : nullptr;
-  const float *gbias = bias && a.bias_group_ld > 0 ? bias + (row0 / a.rows_per_group) * a.bias_group_ld : nullptr;
-  // fused column sums (igemm.h): over the rows that are real points
+  r.bias = bias && a.bias_group_ld > 0 ? bias + (row0 / a.rows_per_group) * a.bias_group_ld : bias;
   const int grp = a.rows_per_group > 0 ? (int)(row0 / a.rows_per_group) : 0;
   const long left = a.M - row0;
   const int valid = a.rows_per_group > 0 ? a.rows_valid - (int)(row0 - (long)grp * a.rows_per_group) : (1 << 30);
-  const int limit = (int)(left < valid ? left : valid);
+  r.limit = (int)(left < valid ? left : valid);
+  r.cs_row = (row0 + wrow) / COLSUM_ROWS;
+  return r;
+}
+// N elements (one, or four of a row), each in the one order: + bias, + residual, activation.  A null term is skipped (the row-contiguous
+// path adds the residual in a second call)
+template <int N>
+__device__ __forceinline__ void epi_finish(float (&v)[N], const float *bias, const float *res, int act, float slope) {
+  if (bias)
+    for (int k = 0; k < N; ++k) v[k] += *bias;
+  if (res)
+    for (int k = 0; k < N; ++k) v[k] += res[k];
+  if (act == ACT_RELU)
+    for (int k = 0; k < N; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
+  else if (act == ACT_PRELU)
+    for (int k = 0; k < N; ++k) v[k] = v[k] > 0.f ? v[k] : v[k] * slope;
+}
+__device__ __forceinline__ float epi_finish(float x, const float *bias, const float *res, int act, float slope) {
+  float v[1] = {x};
+  epi_finish(v, bias, res, act, slope);
+  return v[0];
+}
+// a lane pair's column sum over the block's 64 rows -> the partial buffer (every partial row the buffer has is written: the finish kernel sums them all)
+__device__ __forceinline__ void epi_colsum(const SplitArgs &a, const EpiRules &r, int z, int n, int fh, float csum) {
+  if (a.colsum && r.cs_row < a.cs_rows) {
+    csum += __shfl_xor(csum, 32);
+    if (fh == 0) a.colsum[((size_t)z * a.cs_rows + (size_t)r.cs_row) * a.N + n] = csum;
+  }
+}
+
+// epilogue of one wave's 64 x 64 block: lane = output channel (col), registers = 16 pixel rows: row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5).
+// nb: the block's first column
+__device__ __forceinline__ void split_epilogue(const SplitArgs &a, const f32x16 (&acc)[2][2], int z, long row0, int wrow, int nb, int fr, int fh) {
+  const EpiRules ru = epi_rules(a, z, row0, wrow);
+  float *out = a.out + z * a.z_out_coff + a.out_coff;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int n = nb + j * 32 + fr;
-    const float b1 = gbias ? gbias[n] : bias ? bias[n] : 0.f;
+    const float b1 = ru.bias ? ru.bias[n] : 0.f;
     float csum = 0.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -103,57 +240,38 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs &a, const f32x16 
       for (int e = 0; e < 16; ++e) {
         const int tr = tb + (e & 3) + 8 * (e >> 2);
         const long m = row0 + tr;
-        float v = acc[i][j][e] + b1;
-        if (a.res) v += r[e];
-        if (a.act == ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (a.act == ACT_PRELU) v = v > 0.f ? v : v * slope;
+        const float v = epi_finish(acc[i][j][e], &b1, a.res ? &r[e] : nullptr, a.act, ru.slope);
         if (a.out && m < a.M) out[m * a.out_ld + n] = v;
-        csum += tr < limit ? v : 0.f;
+        csum += tr < ru.limit ? v : 0.f;
       }
     }
-    if (a.colsum && cs_row < a.cs_rows) {      // (every partial row the buffer has is written: the finish kernel sums them all)
-      csum += __shfl_xor(csum, 32);
-      if (fh == 0) a.colsum[((size_t)z * a.cs_rows + (size_t)cs_row) * a.N + n] = csum;
-    }
+    epi_colsum(a, ru, z, n, fh, csum);
   }
 }
 
 // The same epilogue for the 256-column form, stores row-contiguous: the wave passes its 64 x 64 block through its own 16 KB of LDS (`blk`; the
 // main loop's stages are free by then, and only this wave touches it: no workgroup barrier) and writes 4 rows x 256 bytes per instruction instead
-// of 2 rows x 128; a residual is read the same way.  Per element the arithmetic and its order are split_epilogue's: + bias in the fragment layout
-// (lane = column), then + residual, then the activation.  Column sums are taken in the fragment layout, in split_epilogue's order (launches with
-// column sums have no residual: GEMM_EPI_OTHER is not routed).  Needs 16-byte aligned output / residual rows (try_split_gemm checks)
-__device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f32x16 (&acc)[2][2], int z, long row0, int wrow, int nb, int lane, long cs_row, float *blk) {
+// of 2 rows x 128; a residual is read the same way, and added (with the activation behind it) on the way out.  Column sums are taken in the
+// fragment layout, in split_epilogue's order (launches with column sums have no residual: GEMM_EPI_OTHER is not routed).  Needs 16-byte aligned
+// output / residual rows (plan_split checks)
+__device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f32x16 (&acc)[2][2], int z, long row0, int wrow, int nb, int lane, float *blk) {
   const int fr = lane & 31, fh = lane >> 5;
-  const float slope = a.act == ACT_PRELU ? a.prelu[0] : 0.f;
-  const float *bias = a.bias ? a.bias + z * a.z_bias : nullptr;
-  const float *gbias = bias && a.bias_group_ld > 0 ? bias + (row0 / a.rows_per_group) * a.bias_group_ld : nullptr;
-  const int grp = a.rows_per_group > 0 ? (int)(row0 / a.rows_per_group) : 0;
-  const long left = a.M - row0;
-  const int valid = a.rows_per_group > 0 ? a.rows_valid - (int)(row0 - (long)grp * a.rows_per_group) : (1 << 30);
-  const int limit = (int)(left < valid ? left : valid);
+  const EpiRules ru = epi_rules(a, z, row0, wrow);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int n = nb + j * 32 + fr;
-    const float b1 = gbias ? gbias[n] : bias ? bias[n] : 0.f;
+    const float b1 = ru.bias ? ru.bias[n] : 0.f;
     float csum = 0.f;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int br = i * 32 + 4 * fh + (e & 3) + 8 * (e >> 2);          // row inside the block
-        float v = acc[i][j][e] + b1;
-        if (!a.res) {
-          if (a.act == ACT_RELU) v = v > 0.f ? v : 0.f;
-          else if (a.act == ACT_PRELU) v = v > 0.f ? v : v * slope;
-        }
+        const float v = a.res ? epi_finish(acc[i][j][e], &b1, nullptr, ACT_NONE, 0.f) : epi_finish(acc[i][j][e], &b1, nullptr, a.act, ru.slope);
         blk[br * 64 + j * 32 + fr] = v;
-        csum += wrow + br < limit ? v : 0.f;
+        csum += wrow + br < ru.limit ? v : 0.f;
       }
-    if (a.colsum && cs_row < a.cs_rows) {
-      csum += __shfl_xor(csum, 32);
-      if (fh == 0) a.colsum[((size_t)z * a.cs_rows + (size_t)cs_row) * a.N + n] = csum;
-    }
+    epi_colsum(a, ru, z, n, fh, csum);
   }
   if (!a.out) return;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -169,12 +287,7 @@ __device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f3
     if (m < a.M) {
       if (a.res) {
         const float4 r = *reinterpret_cast<const float4 *>(a.res + m * a.res_ld + a.res_coff + nb + c4);
-        v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
-        if (a.act == ACT_RELU) {
-          v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        } else if (a.act == ACT_PRELU) {
-          v.x = v.x > 0.f ? v.x : v.x * slope; v.y = v.y > 0.f ? v.y : v.y * slope; v.z = v.z > 0.f ? v.z : v.z * slope; v.w = v.w > 0.f ? v.w : v.w * slope;
-        }
+        epi_finish(reinterpret_cast<float (&)[4]>(v), nullptr, &r.x, a.act, ru.slope);
       }
       *reinterpret_cast<float4 *>(out + m * a.out_ld + nb + c4) = v;
     }
@@ -186,101 +299,42 @@ __device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f3
 __global__ __launch_bounds__(256, 2) void gemm_split_bf16_kernel(const SplitArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[6 * PLANE_BYTES];       // A planes 0..2, B planes 3..5
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware order: the 8 XCDs take whole row tiles, the column tiles of a row tile run back to back on one XCD (its A rows stay in that L2)
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int tm = (seq / a.tiles_n) * 8 + xcd, tn = seq % a.tiles_n;
-  if (tm >= a.tiles_m) return;
-  const int z = blockIdx.z;
-  const long row0 = (long)tm * SBM;
-  const int n0 = tn * SBN;
-  const float *in = a.in + z * a.z_in_coff + a.in_coff;
-  const __bf16 *wpl = a.wpl + z * a.z_wgt;
+  SplitTile wg;
+  if (!split_tile(a, wg)) return;
+  const long row0 = (long)wg.tm * SBM;
+  const int n0 = wg.tn * SBN;
 
-  // staging roles: pieces tid and tid + 256 of the 512 (row, 8-k) pieces of a 128 x 32 tile
-  const int srow0 = tid >> 2, srow1 = srow0 + 64, sslot = tid & 3;
-  const int soff0 = piece(srow0, sslot), soff1 = piece(srow1, sslot);
-  long r0 = row0 + srow0, r1 = row0 + srow1;
-  r0 = r0 < a.M ? r0 : a.M - 1;                                   // the last row tile re-reads row M - 1 (its results are not stored)
-  r1 = r1 < a.M ? r1 : a.M - 1;
-  const float *ag0 = in + r0 * a.in_ld + sslot * 8, *ag1 = in + r1 * a.in_ld + sslot * 8;
-  const __bf16 *bg0 = wpl + (long)(n0 + srow0) * a.K + sslot * 8, *bg1 = wpl + (long)(n0 + srow1) * a.K + sslot * 8;
+  // staging roles: pieces tid and tid + 256 of the 512 (row, 8-k) pieces of a 128 x 32 tile, of the activations and of each weight plane
+  SPLIT_STAGE_ROLES(64);
+  const __bf16 *bg1 = wg.wpl + (long)(n0 + srow1) * a.K + sslot * 8;
   // the activation rows come from HBM: their loads for k-step kt + 2 are in flight while step kt is multiplied and step kt + 1 is cut and
   // written to LDS (two register sets x / y: one step of 48 MFMAs per wave = 0.65 us does not cover a miss to HBM); the weight planes sit
   // in the L2: one step ahead
   float4 xa00, xa01, xa10, xa11, ya00, ya01, ya10, ya11;
   uint4 rb00, rb01, rb02, rb10, rb11, rb12;
-#define SPLIT_FETCH_A(S, k0)                                                     \
-  do {                                                                           \
-    S##a00 = *reinterpret_cast<const float4 *>(ag0 + (k0));                      \
-    S##a01 = *reinterpret_cast<const float4 *>(ag0 + (k0) + 4);                  \
-    S##a10 = *reinterpret_cast<const float4 *>(ag1 + (k0));                      \
-    S##a11 = *reinterpret_cast<const float4 *>(ag1 + (k0) + 4);                  \
-  } while (0)
 #define SPLIT_FETCH_B(k0)                                                        \
   do {                                                                           \
-    rb00 = *reinterpret_cast<const uint4 *>(bg0 + (k0));                         \
-    rb01 = *reinterpret_cast<const uint4 *>(bg0 + a.wplane + (k0));              \
-    rb02 = *reinterpret_cast<const uint4 *>(bg0 + 2 * a.wplane + (k0));          \
-    rb10 = *reinterpret_cast<const uint4 *>(bg1 + (k0));                         \
-    rb11 = *reinterpret_cast<const uint4 *>(bg1 + a.wplane + (k0));              \
-    rb12 = *reinterpret_cast<const uint4 *>(bg1 + 2 * a.wplane + (k0));          \
-  } while (0)
-#define SPLIT_STAGE1(x0, x1, off, b0, b1, b2)                                    \
-  do {                                                                           \
-    uint4 h, m, l;                                                               \
-    cut3(x0.x, x0.y, h.x, m.x, l.x);                                             \
-    cut3(x0.z, x0.w, h.y, m.y, l.y);                                             \
-    cut3(x1.x, x1.y, h.z, m.z, l.z);                                             \
-    cut3(x1.z, x1.w, h.w, m.w, l.w);                                             \
-    *reinterpret_cast<uint4 *>(lds + (off)) = h;                                 \
-    *reinterpret_cast<uint4 *>(lds + PLANE_BYTES + (off)) = m;                   \
-    *reinterpret_cast<uint4 *>(lds + 2 * PLANE_BYTES + (off)) = l;               \
-    *reinterpret_cast<uint4 *>(lds + 3 * PLANE_BYTES + (off)) = b0;              \
-    *reinterpret_cast<uint4 *>(lds + 4 * PLANE_BYTES + (off)) = b1;              \
-    *reinterpret_cast<uint4 *>(lds + 5 * PLANE_BYTES + (off)) = b2;              \
+    SPLIT_FETCH3(rb00, rb01, rb02, bg0, k0);                                     \
+    SPLIT_FETCH3(rb10, rb11, rb12, bg1, k0);                                     \
   } while (0)
 #define SPLIT_STAGE(S)                                                           \
   do {                                                                           \
-    SPLIT_STAGE1(S##a00, S##a01, soff0, rb00, rb01, rb02);                       \
-    SPLIT_STAGE1(S##a10, S##a11, soff1, rb10, rb11, rb12);                       \
+    SPLIT_CUT_STORE(S##a00, S##a01, lds, PLANE_BYTES, soff0);                    \
+    SPLIT_STORE3(lds + 3 * PLANE_BYTES, PLANE_BYTES, soff0, rb00, rb01, rb02);   \
+    SPLIT_CUT_STORE(S##a10, S##a11, lds, PLANE_BYTES, soff1);                    \
+    SPLIT_STORE3(lds + 3 * PLANE_BYTES, PLANE_BYTES, soff1, rb10, rb11, rb12);   \
   } while (0)
 
   const int wr = wave >> 1, wc = wave & 1, fr = lane & 31, fh = lane >> 5;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  int offa[2][2], offb[2][2];          // [k16 step][tile]
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      offa[ks][t] = piece(wr * 64 + t * 32 + fr, ks * 2 + fh);
-      offb[ks][t] = 3 * PLANE_BYTES + piece(wc * 64 + t * 32 + fr, ks * 2 + fh);
-    }
+  f32x16 acc[2][2] = {};
+  SPLIT_FRAG_OFFSETS(3 * PLANE_BYTES);
 
 #define SPLIT_COMPUTE()                                                                                   \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                      \
-    bf16x8 fa[2][3], fb[2][3];                                                                            \
-    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                         \
-    _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                                       \
-      fa[t][p] = *reinterpret_cast<const bf16x8 *>(lds + p * PLANE_BYTES + offa[ks][t]);                  \
-      fb[t][p] = *reinterpret_cast<const bf16x8 *>(lds + p * PLANE_BYTES + offb[ks][t]);                  \
-    }                                                                                                     \
+    SPLIT_READ_FRAGS(lds, PLANE_BYTES, PLANE_BYTES);                                                      \
     _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                         \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                       \
-      f32x16 c = acc[i][j]; /* small terms first */                                                       \
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fb[j][0], c, 0, 0, 0);                        \
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][2], c, 0, 0, 0);                        \
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][1], c, 0, 0, 0);                        \
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fb[j][0], c, 0, 0, 0);                        \
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][1], c, 0, 0, 0);                        \
-      c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fb[j][0], c, 0, 0, 0);                        \
-      acc[i][j] = c;                                                                                      \
-    }                                                                                                     \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                         \
+    _Pragma("unroll") for (int q = 0; q < 6; ++q) acc[i][j] = mfma_pair(fa[i], fb[j], q, acc[i][j]);      \
   }
 
   const int nk = a.K / SBK;
@@ -308,7 +362,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_bf16_kernel(const SplitArgs
     __syncthreads();
   }
 
-  split_epilogue(a, acc, z, row0, wr * 64, n0 + wc * 64, fr, fh, (long)tm * 2 + wr);
+  split_epilogue(a, acc, wg.z, row0, wr * 64, n0 + wc * 64, fr, fh);
 }
 
 // Second form: 256 x 128 x 32 tile, 8 waves (4 x 2) of 64 x 64, TWO LDS stages (144 KB: one workgroup per CU, two waves per SIMD) and ONE barrier
@@ -319,87 +373,38 @@ constexpr int V2_APL = 256 * 64, V2_BPL = 128 * 64, V2_STAGE = 3 * V2_APL + 3 * 
 __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v2_kernel(const SplitArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds2[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int tm = (seq / a.tiles_n) * 8 + xcd, tn = seq % a.tiles_n;
-  if (tm >= a.tiles_m) return;
-  const int z = blockIdx.z;
-  const long row0 = (long)tm * 256;
-  const int n0 = tn * SBN;
-  const float *in = a.in + z * a.z_in_coff + a.in_coff;
-  const __bf16 *wpl = a.wpl + z * a.z_wgt;
+  SplitTile wg;
+  if (!split_tile(a, wg)) return;
+  const long row0 = (long)wg.tm * 256;
+  const int n0 = wg.tn * SBN;
 
   // staging roles: A pieces tid and tid + 512 of the 1024 (row, 8-k) pieces of the 256 x 32 tile; B piece tid of each plane's 512
-  const int srow0 = tid >> 2, srow1 = srow0 + 128, sslot = tid & 3;
-  const int soff0 = piece(srow0, sslot), soff1 = piece(srow1, sslot);
-  long r0 = row0 + srow0, r1 = row0 + srow1;
-  r0 = r0 < a.M ? r0 : a.M - 1;
-  r1 = r1 < a.M ? r1 : a.M - 1;
-  const float *ag0 = in + r0 * a.in_ld + sslot * 8, *ag1 = in + r1 * a.in_ld + sslot * 8;
-  const __bf16 *bg0 = wpl + (long)(n0 + srow0) * a.K + sslot * 8;
+  SPLIT_STAGE_ROLES(128);
   float4 xa00, xa01, xa10, xa11, ya00, ya01, ya10, ya11;
   uint4 xb0, xb1, xb2, yb0, yb1, yb2;
 #define V2_FETCH(S, k0)                                                          \
   do {                                                                           \
-    S##a00 = *reinterpret_cast<const float4 *>(ag0 + (k0));                      \
-    S##a01 = *reinterpret_cast<const float4 *>(ag0 + (k0) + 4);                  \
-    S##a10 = *reinterpret_cast<const float4 *>(ag1 + (k0));                      \
-    S##a11 = *reinterpret_cast<const float4 *>(ag1 + (k0) + 4);                  \
-    S##b0 = *reinterpret_cast<const uint4 *>(bg0 + (k0));                        \
-    S##b1 = *reinterpret_cast<const uint4 *>(bg0 + a.wplane + (k0));             \
-    S##b2 = *reinterpret_cast<const uint4 *>(bg0 + 2 * a.wplane + (k0));         \
-  } while (0)
-#define V2_CUT(x0, x1, base, off)                                                \
-  do {                                                                           \
-    uint4 h, m, l;                                                               \
-    cut3(x0.x, x0.y, h.x, m.x, l.x);                                             \
-    cut3(x0.z, x0.w, h.y, m.y, l.y);                                             \
-    cut3(x1.x, x1.y, h.z, m.z, l.z);                                             \
-    cut3(x1.z, x1.w, h.w, m.w, l.w);                                             \
-    *reinterpret_cast<uint4 *>((base) + (off)) = h;                              \
-    *reinterpret_cast<uint4 *>((base) + V2_APL + (off)) = m;                     \
-    *reinterpret_cast<uint4 *>((base) + 2 * V2_APL + (off)) = l;                 \
+    SPLIT_FETCH_A(S, k0);                                                        \
+    SPLIT_FETCH3(S##b0, S##b1, S##b2, bg0, k0);                                  \
   } while (0)
 #define V2_STAGE_TO(S, base)                                                     \
   do {                                                                           \
-    V2_CUT(S##a00, S##a01, base, soff0);                                         \
-    V2_CUT(S##a10, S##a11, base, soff1);                                         \
-    *reinterpret_cast<uint4 *>((base) + 3 * V2_APL + soff0) = S##b0;             \
-    *reinterpret_cast<uint4 *>((base) + 3 * V2_APL + V2_BPL + soff0) = S##b1;    \
-    *reinterpret_cast<uint4 *>((base) + 3 * V2_APL + 2 * V2_BPL + soff0) = S##b2; \
+    SPLIT_CUT_STORE(S##a00, S##a01, base, V2_APL, soff0);                        \
+    SPLIT_CUT_STORE(S##a10, S##a11, base, V2_APL, soff1);                        \
+    SPLIT_STORE3((base) + 3 * V2_APL, V2_BPL, soff0, S##b0, S##b1, S##b2);       \
   } while (0)
 
   const int wr = wave >> 1, wc = wave & 1, fr = lane & 31, fh = lane >> 5;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  int offa[2][2], offb[2][2];          // [k16 step][tile]
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      offa[ks][t] = piece(wr * 64 + t * 32 + fr, ks * 2 + fh);
-      offb[ks][t] = 3 * V2_APL + piece(wc * 64 + t * 32 + fr, ks * 2 + fh);
-    }
+  f32x16 acc[2][2] = {};
+  SPLIT_FRAG_OFFSETS(3 * V2_APL);
   // pair-major order (every tile's lo*hi, then every tile's hi*lo, ...): per accumulator the order is still small terms first, and the lo / mid
   // fragments die early, which leaves registers for the next k16 step's fragments
 #define V2_COMPUTE(base)                                                                                  \
   _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                      \
-    bf16x8 fa[2][3], fb[2][3];                                                                            \
-    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                         \
-    _Pragma("unroll") for (int p = 0; p < 3; ++p) {                                                       \
-      fa[t][p] = *reinterpret_cast<const bf16x8 *>((base) + p * V2_APL + offa[ks][t]);                    \
-      fb[t][p] = *reinterpret_cast<const bf16x8 *>((base) + p * V2_BPL + offb[ks][t]);                    \
-    }                                                                                                     \
-    _Pragma("unroll") for (int q = 0; q < 6; ++q) {                                                       \
-      constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};                               \
-      _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                       \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                       \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[q]], fb[j][PB[q]], acc[i][j], 0, 0, 0); \
-    }                                                                                                     \
+    SPLIT_READ_FRAGS(base, V2_APL, V2_BPL);                                                               \
+    _Pragma("unroll") for (int q = 0; q < 6; ++q)                                                         \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                         \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] = mfma_pair(fa[i], fb[j], q, acc[i][j]);      \
   }
   // one k-step, branch-free: loads of step kt + 2 (clamped to the last step: harmless re-read), cut of step kt + 1 into the other stage, products
   // of step kt -- ONE basic block, with the issue order pinned so that the cut's vector instructions and the LDS traffic sit in the gaps of the
@@ -436,7 +441,7 @@ __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v2_kernel(const SplitA
     V2_BODY(y, x, k3 < klast ? k3 : klast, st1, st0);
   }
   if (nk & 1) { V2_COMPUTE(st0); }       // the last step of an odd count (cut into stage 0 by the loop's second half)
-  split_epilogue(a, acc, z, row0, wr * 64, n0 + wc * 64, fr, fh, (long)tm * 4 + wr);
+  split_epilogue(a, acc, wg.z, row0, wr * 64, n0 + wc * 64, fr, fh);
 }
 
 // Third form: 256 x 256 x 16 tile, 8 waves (2 x 4) of 128 x 64, two LDS stages of one k16 group each (96 KB: one workgroup per CU) and one barrier
@@ -454,22 +459,18 @@ __device__ __forceinline__ int piece16(int row, int half) { return row * 32 + ((
 __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v3_kernel(const SplitArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds3[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
-  const int tm = (seq / a.tiles_n) * 8 + xcd, tn = seq % a.tiles_n;
-  if (tm >= a.tiles_m) return;
-  const int z = blockIdx.z;
-  const long row0 = (long)tm * 256;
-  const int n0 = tn * 256;
-  const float *in = a.in + z * a.z_in_coff + a.in_coff;
-  const __bf16 *wpl = a.wpl + z * a.z_wgt;
+  SplitTile wg;
+  if (!split_tile(a, wg)) return;
+  const long row0 = (long)wg.tm * 256;
+  const int n0 = wg.tn * 256;
 
   // staging roles: piece tid of the 512 (row, 8-k) pieces of the activation tile and of each weight plane's tile
   const int srow = tid >> 1, shalf = tid & 1;
   const int soff = piece16(srow, shalf);
   long r = row0 + srow;
   r = r < a.M ? r : a.M - 1;                                      // the last row tile re-reads row M - 1 (its results are not stored)
-  const float *ag = in + r * a.in_ld + shalf * 8;
-  const __bf16 *bg = wpl + (long)(n0 + srow) * a.K + shalf * 8;
+  const float *ag = wg.in + r * a.in_ld + shalf * 8;
+  const __bf16 *bg = wg.wpl + (long)(n0 + srow) * a.K + shalf * 8;
   // activations (HBM) two groups ahead in two register sets, weight planes (L2) one group ahead
   float4 xa0, xa1, ya0, ya1;
   uint4 b0, b1, b2;
@@ -478,58 +479,31 @@ __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v3_kernel(const SplitA
     S##a0 = *reinterpret_cast<const float4 *>(ag + (k0));                        \
     S##a1 = *reinterpret_cast<const float4 *>(ag + (k0) + 4);                    \
   } while (0)
-#define V3_FETCH_B(k0)                                                           \
-  do {                                                                           \
-    b0 = *reinterpret_cast<const uint4 *>(bg + (k0));                            \
-    b1 = *reinterpret_cast<const uint4 *>(bg + a.wplane + (k0));                 \
-    b2 = *reinterpret_cast<const uint4 *>(bg + 2 * a.wplane + (k0));             \
-  } while (0)
+#define V3_FETCH_B(k0) SPLIT_FETCH3(b0, b1, b2, bg, k0)
   // (the empty asm pins a cut behind the phase boundary in front of it: without it instruction selection may start the cut right behind the
   // set's loads, and the wave then waits out the whole HBM round trip instead of covering it with a group of MFMAs)
 #define V3_PIN(v) asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w))
-#define V3_CUT0(S) do { V3_PIN(S##a0); cut3(S##a0.x, S##a0.y, ch.x, cm.x, cl.x); cut3(S##a0.z, S##a0.w, ch.y, cm.y, cl.y); } while (0)
-#define V3_CUT1(S) do { V3_PIN(S##a1); cut3(S##a1.x, S##a1.y, ch.z, cm.z, cl.z); cut3(S##a1.z, S##a1.w, ch.w, cm.w, cl.w); } while (0)
-#define V3_WRITE_A(base)                                                         \
-  do {                                                                           \
-    *reinterpret_cast<uint4 *>((base) + soff) = ch;                              \
-    *reinterpret_cast<uint4 *>((base) + V3_PL + soff) = cm;                      \
-    *reinterpret_cast<uint4 *>((base) + 2 * V3_PL + soff) = cl;                  \
-  } while (0)
-#define V3_WRITE_B(base)                                                         \
-  do {                                                                           \
-    *reinterpret_cast<uint4 *>((base) + 3 * V3_PL + soff) = b0;                  \
-    *reinterpret_cast<uint4 *>((base) + 4 * V3_PL + soff) = b1;                  \
-    *reinterpret_cast<uint4 *>((base) + 5 * V3_PL + soff) = b2;                  \
-  } while (0)
+#define V3_CUT0(S) do { V3_PIN(S##a0); cut4<0>(S##a0, ch, cm, cl); } while (0)
+#define V3_CUT1(S) do { V3_PIN(S##a1); cut4<1>(S##a1, ch, cm, cl); } while (0)
+#define V3_WRITE_A(base) SPLIT_STORE3(base, V3_PL, soff, ch, cm, cl)
+#define V3_WRITE_B(base) SPLIT_STORE3((base) + 3 * V3_PL, V3_PL, soff, b0, b1, b2)
 
   const int wr = wave >> 2, wc = wave & 3, fr = lane & 31, fh = lane >> 5;
-  f32x16 acc[2][2][2];          // [64-row block of the wave][32-row tile][32-column tile]
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[h][i][j][e] = 0.f;
+  f32x16 acc[2][2][2] = {};          // [64-row block of the wave][32-row tile][32-column tile]
   // (a tile's 32-row offset leaves bit 3 of the row alone: the four A and two B fragments of a plane are one address plus constants)
   const int offa = piece16(wr * 128 + fr, fh), offb = 3 * V3_PL + piece16(wc * 64 + fr, fh);
-  // the six pairs in the kernel's fixed order (A plane, B plane): lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi; pair-major as in the second form.
-  // Pairs 0..2 bring a new A and a new B plane each: V3_READ(q) is the six fragments pair q is the first to use
-#define V3_PA(q) ((q) == 0 ? 2 : (q) == 2 || (q) == 3 ? 1 : 0)
-#define V3_PB(q) ((q) == 1 ? 2 : (q) == 2 || (q) == 4 ? 1 : 0)
+  // pair-major as in the second form.  V3_READ(q), q = 0..2: the six fragments pair q is the first to use (pair_brings_new_planes)
 #define V3_READ(base, q)                                                                                  \
   do {                                                                                                    \
     _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                         \
-      fa[t][V3_PA(q)] = *reinterpret_cast<const bf16x8 *>((base) + V3_PA(q) * V3_PL + offa + t * 1024);   \
+      fa[t][pair_a(q)] = *reinterpret_cast<const bf16x8 *>((base) + pair_a(q) * V3_PL + offa + t * 1024); \
     _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                         \
-      fb[t][V3_PB(q)] = *reinterpret_cast<const bf16x8 *>((base) + V3_PB(q) * V3_PL + offb + t * 1024);   \
+      fb[t][pair_b(q)] = *reinterpret_cast<const bf16x8 *>((base) + pair_b(q) * V3_PL + offb + t * 1024); \
   } while (0)
 #define V3_MFMA(q)                                                                                        \
   do {                                                                                                    \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                         \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                         \
-      acc[i >> 1][i & 1][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][V3_PA(q)], fb[j][V3_PB(q)], acc[i >> 1][i & 1][j], 0, 0, 0); \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i >> 1][i & 1][j] = mfma_pair(fa[i], fb[j], q, acc[i >> 1][i & 1][j]); \
   } while (0)
   // n x (one MFMA, then `cnt` instructions of class `mask`): the filler sits in the MFMA gaps of the SAME wave (a wave issuing MFMAs back to back
   // blocks the other wave of its SIMD: DESIGN 6a); a full scheduling barrier closes each phase so that nothing drifts across it
@@ -594,10 +568,9 @@ __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v3_kernel(const SplitA
     // stage 1: group s + 1; set x: group s + 2
     V3_BODY(y, x, k3 < klast ? k3 : klast, k2 < klast ? k2 : klast, st1, st0);
   }
-  const int cs0 = tm * 4 + wr * 2;
   float *const blk = reinterpret_cast<float *>(lds3) + wave * (64 * 64);          // (every wave is past the loop's last barrier: the stages are free)
-  split_epilogue_rows(a, acc[0], z, row0, wr * 128, n0 + wc * 64, lane, (long)cs0, blk);
-  split_epilogue_rows(a, acc[1], z, row0, wr * 128 + 64, n0 + wc * 64, lane, (long)cs0 + 1, blk);
+  split_epilogue_rows(a, acc[0], wg.z, row0, wr * 128, n0 + wc * 64, lane, blk);
+  split_epilogue_rows(a, acc[1], wg.z, row0, wr * 128 + 64, n0 + wc * 64, lane, blk);
 }
 
 #ifdef DF_DEV
@@ -620,6 +593,64 @@ const __bf16 *scratch_planes(const float *w, long elems, hipStream_t st) {
   return sc.first;
 }
 #endif
+
+// The tile forms: what a launch of each needs.  256x128 and 256x256 take more dynamic LDS than the 64 KiB a kernel gets by default
+enum SplitForm { FORM_128x128 = 0, FORM_256x128 = 1, FORM_256x256 = 2 };
+struct FormDesc { const char *name; void (*kernel)(SplitArgs); int bm, bn, threads, lds; bool raise; };
+const FormDesc FORMS[3] = {{"128x128", gemm_split_bf16_kernel, SBM, SBN, 256, 0, false},
+                           {"256x128", gemm_split_bf16_v2_kernel, 256, SBN, 512, 2 * V2_STAGE, true},
+                           {"256x256", gemm_split_bf16_v3_kernel, 256, 256, 512, V3_LDS, true}};
+
+// Everything one launch needs, decided on the host (no HIP call, no environment: the switches and the device's compute units come in)
+struct SplitPlan {
+  bool examined = false;          // the launch reached the cover check (DF_GEMM_SPLIT_VERBOSE reports those)
+  int form = FORM_128x128;
+  int threads = 0, lds = 0;       // workgroup size; dynamic LDS bytes
+  dim3 grid;
+  SplitArgs a{};                  // tiles_m / tiles_n: of the form's tile.  (A development-build launch without planes: a.wpl / a.wplane are null / 0)
+};
+
+// 0: not taken (the fp32 kernels' launch), 1: taken, pl filled, DF_ERR_ARG: a routed launch outside the kernels' cover.  variant: the highest
+// form allowed (DF_GEMM_SPLIT_V; 3 = all), all: DF_GEMM_SPLIT_BF16 (DF_GEMM_SPLIT_OFF never gets here)
+int plan_split(const ConvParams &p, int compute_units, int variant, bool all, SplitPlan &pl) {
+  pl = SplitPlan{};
+  if (p.splitk_ws || (!p.wpl && !all)) return 0;
+  pl.examined = true;
+  const long M = (long)p.B * p.OH * p.OW;
+  const int K = p.Cin;
+  SplitArgs &a = pl.a;
+  a.in = p.in; a.wpl = reinterpret_cast<const __bf16 *>(p.wpl); a.bias = p.bias; a.res = p.res; a.prelu = p.prelu; a.out = p.out; a.colsum = p.colsum;
+  a.M = M; a.wplane = p.wpl_stride; a.N = p.Cout; a.K = K; a.in_ld = p.in_ld; a.in_coff = p.in_coff; a.out_ld = p.out_ld; a.out_coff = p.out_coff;
+  a.res_ld = p.res_ld; a.res_coff = p.res_coff; a.act = p.act; a.rows_per_group = p.rows_per_group; a.rows_valid = p.rows_valid; a.bias_group_ld = p.bias_group_ld;
+  a.z_in_coff = p.z_in_coff; a.z_wgt = p.z_wgt; a.z_bias = p.z_bias; a.z_out_coff = p.z_out_coff;
+  a.cs_rows = colsum_partial_rows(M);
+  // launch geometry the kernels cover (every engine plain GEMM: a property of the layer, not of M)
+  const bool ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.up == 1 && p.H == p.OH && p.W == p.OW && (p.out || p.colsum) &&
+                  p.Cout % SBN == 0 && K % SBK == 0 && K >= SBK && M >= 1 && gemm_epi_kind(p) != GEMM_EPI_OTHER &&
+                  (p.rows_per_group == 0 ? p.bias_group_ld == 0 : p.rows_per_group % SBM == 0) && (p.z_wgt % 8) == 0;
+  if (!ok || !(all || split_route(p.Cout, K, gemm_epi_kind(p)))) {
+    // planes come only with routed layers: a routed layer the kernels cannot take is a caller error, not a quiet fp32 launch
+    if (p.wpl && !all) return set_error(DF_ERR_ARG, "split gemm: routed launch M=%ld N=%d K=%d outside the kernels' cover", M, p.Cout, K);
+    return 0;
+  }
+  // measured per shape: the 256-row forms win from K = 384 up (189 against 172 TFLOP/s on 139 000 x 2 304 x 1 024), the 128-row form below.
+  // All forms add the same products in the same order per element: the choice changes no bit
+  const bool v2 = variant >= 2 && K >= 384 && (p.rows_per_group == 0 || p.rows_per_group % 256 == 0);
+  // the 256-column form where N allows it and its tiles still fill the card (the 1 440-row psp fold has 96 of them: it keeps 128 columns)
+  const long tiles3 = ((M + 255) / 256) * (p.Cout / 256) * p.zcount;
+  // (its epilogue moves whole 16-byte pieces of output and residual rows)
+  const bool rows16 = (!p.out || (reinterpret_cast<uintptr_t>(p.out) % 16 == 0 && p.out_ld % 4 == 0 && p.out_coff % 4 == 0 && p.z_out_coff % 4 == 0)) &&
+                      (!p.res || (reinterpret_cast<uintptr_t>(p.res) % 16 == 0 && p.res_ld % 4 == 0 && p.res_coff % 4 == 0));
+  const bool v3 = v2 && variant >= 3 && p.Cout % 256 == 0 && rows16 && tiles3 >= compute_units;
+  pl.form = v3 ? FORM_256x256 : v2 ? FORM_256x128 : FORM_128x128;
+  const FormDesc &f = FORMS[pl.form];
+  a.tiles_m = (int)((M + f.bm - 1) / f.bm);
+  a.tiles_n = p.Cout / f.bn;
+  pl.grid = dim3((unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n), 1, p.zcount);      // (whole groups of 8 row tiles: split_tile)
+  pl.threads = f.threads;
+  pl.lds = f.lds;
+  return 1;
+}
 
 }  // namespace
 
@@ -656,69 +687,34 @@ static int compute_units() {
   return n;
 }
 
-int try_split_gemm(const ConvParams &p, hipStream_t st) {
+int try_split_gemm(const ConvParams &p, hipStream_t st, ConvRoute &r) {
   static const bool off = dev_getenv("DF_GEMM_SPLIT_OFF") != nullptr;
   static const bool all = dev_getenv("DF_GEMM_SPLIT_BF16") != nullptr;
   static const bool verbose = dev_getenv("DF_GEMM_SPLIT_VERBOSE") != nullptr;
-  if (off || p.splitk_ws || (!p.wpl && !all)) return 0;
-  const long M = (long)p.B * p.OH * p.OW;
-  const int K = p.Cin;
-  // launch geometry the kernels cover (every engine plain GEMM: a property of the layer, not of M)
-  const bool ok = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.up == 1 && p.H == p.OH && p.W == p.OW && (p.out || p.colsum) &&
-                  p.Cout % SBN == 0 && K % SBK == 0 && K >= SBK && M >= 1 && gemm_epi_kind(p) != GEMM_EPI_OTHER &&
-                  (p.rows_per_group == 0 ? p.bias_group_ld == 0 : p.rows_per_group % SBM == 0) && (p.z_wgt % 8) == 0;
-  const bool take = ok && (all || split_route(p.Cout, K, gemm_epi_kind(p)));
-  if (verbose) fprintf(stderr, "[df-split] M=%ld N=%d K=%d z%d -> %s\n", M, p.Cout, K, p.zcount, take ? "bf16 x 6" : "fp32");
-  if (!take) {
-    // planes come only with routed layers: a routed layer the kernels cannot take is a caller error, not a quiet fp32 launch
-    if (p.wpl && !all) return set_error(DF_ERR_ARG, "split gemm: routed launch M=%ld N=%d K=%d outside the kernels' cover", M, p.Cout, K);
-    return 0;
-  }
-  const __bf16 *wpl = reinterpret_cast<const __bf16 *>(p.wpl);
-  long wplane = p.wpl_stride;
+  static const int variant = dev_getenv("DF_GEMM_SPLIT_V") ? atoi(dev_getenv("DF_GEMM_SPLIT_V")) : 3;
+  if (off) return 0;
+  SplitPlan pl;
+  const int rc = plan_split(p, compute_units(), variant, all, pl);
+  if (verbose && pl.examined) fprintf(stderr, "[df-split] M=%ld N=%d K=%d z%d -> %s\n", pl.a.M, p.Cout, p.Cin, p.zcount, rc == 1 ? "bf16 x 6" : "fp32");
+  if (rc != 1) return rc;
 #ifdef DF_DEV
-  if (!wpl) {
-    wplane = (long)(p.zcount - 1) * p.z_wgt + (long)p.Cout * K;
-    wpl = scratch_planes(p.wgt, wplane, st);
-    if (!wpl) return set_error(DF_ERR_LAUNCH, "split gemm: hipMalloc of the weight-plane scratch failed");
+  if (!pl.a.wpl) {
+    pl.a.wplane = (long)(p.zcount - 1) * p.z_wgt + (long)p.Cout * p.Cin;
+    pl.a.wpl = scratch_planes(p.wgt, pl.a.wplane, st);
+    if (!pl.a.wpl) return set_error(DF_ERR_LAUNCH, "split gemm: hipMalloc of the weight-plane scratch failed");
   }
 #endif
-  SplitArgs a{};
-  a.in = p.in; a.wpl = wpl; a.bias = p.bias; a.res = p.res; a.prelu = p.prelu; a.out = p.out; a.colsum = p.colsum;
-  a.M = M; a.wplane = wplane; a.N = p.Cout; a.K = K; a.in_ld = p.in_ld; a.in_coff = p.in_coff; a.out_ld = p.out_ld; a.out_coff = p.out_coff;
-  a.res_ld = p.res_ld; a.res_coff = p.res_coff; a.act = p.act; a.rows_per_group = p.rows_per_group; a.rows_valid = p.rows_valid; a.bias_group_ld = p.bias_group_ld;
-  a.z_in_coff = p.z_in_coff; a.z_wgt = p.z_wgt; a.z_bias = p.z_bias; a.z_out_coff = p.z_out_coff;
-  a.cs_rows = ((M + 127) / 128) * 2;
-  a.tiles_n = p.Cout / SBN;
-  static const int variant = dev_getenv("DF_GEMM_SPLIT_V") ? atoi(dev_getenv("DF_GEMM_SPLIT_V")) : 3;
-  // measured per shape: the 256-row forms win from K = 384 up (189 against 172 TFLOP/s on 139 000 x 2 304 x 1 024), the 128-row form below.
-  // All forms add the same products in the same order per element: the choice changes no bit
-  const bool v2 = variant >= 2 && K >= 384 && (p.rows_per_group == 0 || p.rows_per_group % 256 == 0);
-  // the 256-column form where N allows it and its tiles still fill the card (the 1 440-row psp fold has 96 of them: it keeps 128 columns)
-  const long tiles3 = ((M + 255) / 256) * (p.Cout / 256) * p.zcount;
-  // (its epilogue moves whole 16-byte pieces of output and residual rows)
-  const bool rows16 = (!p.out || (reinterpret_cast<uintptr_t>(p.out) % 16 == 0 && p.out_ld % 4 == 0 && p.out_coff % 4 == 0 && p.z_out_coff % 4 == 0)) &&
-                      (!p.res || (reinterpret_cast<uintptr_t>(p.res) % 16 == 0 && p.res_ld % 4 == 0 && p.res_coff % 4 == 0));
-  const bool v3 = v2 && variant >= 3 && p.Cout % 256 == 0 && rows16 && tiles3 >= compute_units();
-  if (verbose) fprintf(stderr, "[df-split]   form %s\n", v3 ? "256x256" : v2 ? "256x128" : "128x128");
-  if (v3) {
-    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm_split_bf16_v3_kernel), V3_LDS);
-    if (rc != DF_OK) return rc;
-    a.tiles_m = (int)((M + 255) / 256);
-    a.tiles_n = p.Cout / 256;
-    const unsigned grid = (unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n);
-    hipLaunchKernelGGL(gemm_split_bf16_v3_kernel, dim3(grid, 1, p.zcount), dim3(512), V3_LDS, st, a);
-  } else if (v2) {
-    const int rc = raise_lds_limit(reinterpret_cast<const void *>(&gemm_split_bf16_v2_kernel), 2 * V2_STAGE);
-    if (rc != DF_OK) return rc;
-    a.tiles_m = (int)((M + 255) / 256);
-    const unsigned grid = (unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n);
-    hipLaunchKernelGGL(gemm_split_bf16_v2_kernel, dim3(grid, 1, p.zcount), dim3(512), 2 * V2_STAGE, st, a);
-  } else {
-    a.tiles_m = (int)((M + SBM - 1) / SBM);
-    const unsigned grid = (unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n);
-    hipLaunchKernelGGL(gemm_split_bf16_kernel, dim3(grid, 1, p.zcount), dim3(256), 0, st, a);
+  const FormDesc &f = FORMS[pl.form];
+  if (verbose) fprintf(stderr, "[df-split]   form %s\n", f.name);
+  if (f.raise) {
+    const int e = raise_lds_limit(reinterpret_cast<const void *>(f.kernel), pl.lds);
+    if (e != DF_OK) return e;
   }
+  hipLaunchKernelGGL(f.kernel, pl.grid, dim3(pl.threads), pl.lds, st, pl.a);
+  r = ConvRoute{};
+  r.kernel = CONV_BF16;
+  r.bm = f.bm;
+  r.bn = f.bn;
   return 1;
 }
 
