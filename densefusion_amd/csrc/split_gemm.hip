@@ -11,6 +11,16 @@
 // Covered: 1x1 / per-point / Winograd-domain launches (plain GEMMs: stride 1, no padding) with Cout % 128 == 0 and K % 32 == 0, bias (per
 // channel or per row group), residual, ReLU / PReLU, fused column sums, blockIdx.z batches.  Which launches run here is split_route(N, K,
 // epilogue kind) of a launch whose weights come with planes (ConvParams::wpl); everything else stays on the fp32 kernels.
+// What the tests pin (tests/test_split_gemm_exact_gpu.py).  On operands s (H + Mi 2^-9 + L 2^-18) with small integers H, Mi, L and at most six
+// nonzero products per output, every partial sum is a multiple of 2^-18 below 2^6, so the arithmetic has one fp32 result whatever the order
+// the matrix core adds in, and each form must EQUAL the sum of the six pairs plus the epilogue: at every k32 step count that takes another exit
+// of a k loop (odd counts: the 256 x 128 form's tail, the clamped prefetches), M below one tile, no bias, channel offsets, the 256 x 256 form's
+// fall-back to 256 x 128 on rows that are not 16-byte aligned.  General-valued tolerances cannot pin the pair set: the error of a dropped
+// 2^-18 pair grows like sqrt(K) while sum|a||b| grows like K, and max|y - ref| / max|ref| without lo*hi / hi*lo / mid*mid is 1.55e-6 / 1.44e-6 /
+// 1.73e-6 at M, N, K = 1000, 1024, 512, 1.66e-6 / 2.06e-6 / 2.08e-6 at 1337, 2304, 1024 and 1.86e-6 / 1.84e-6 / 2.11e-6 at 255, 640, 384 (all six:
+// 5.1e-8, 3.7e-8, 4.0e-8; numpy emulation of the cut, pairs summed in fp64) -- on the 2e-6 line of the product tests, under it at several shapes.
+// Operand domain of the cut: finite values whose magnitude does not round to bf16 infinity.  An infinity, or a magnitude from 2^127 (2 - 2^-8)
+// up, cuts into hi = inf, mid = -inf or NaN, and the product is NaN where the fp32 kernel's is an infinity or a finite number.
 // Development build only: DF_GEMM_SPLIT_OFF=1 keeps every launch on fp32; DF_GEMM_SPLIT_BF16=1 also takes eligible launches without planes
 // (their weights are cut per launch into a per-stream scratch).  Measurements: DESIGN.md section 6, profiles/r04_experiments/README.md.
 //

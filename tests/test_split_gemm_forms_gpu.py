@@ -1,7 +1,9 @@
 """GPU: every tile form of the bf16 x 6 split GEMM (csrc/split_gemm.hip) computes the same bits.
 
 Per output element all forms add the same products in the same order (k16 groups in ascending k, the six term pairs in one fixed order, then
-bias, residual, activation), so whichever form the launcher picks must equal the 128 x 128 first form exactly.  The first form is the witness:
+bias, residual, activation), so whichever form the launcher picks must equal the 128 x 128 first form exactly.  (Equal forms can be equally
+wrong: one entry of the shared pair table moves all three.  WHICH pairs are summed, and the k loops' odd step counts and tails, are pinned by
+tests/test_split_gemm_exact_gpu.py against the exact six-pair sum.)  The first form is the witness:
 DF_GEMM_SPLIT_V=1 (development library) keeps every launch on it.  The switches are read once per process, so each side runs in a child process;
 the children return SHA-256 digests of the raw output bytes (equal digests = equal bits, NaN payloads and signed zeros included).
 
