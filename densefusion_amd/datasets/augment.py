@@ -8,25 +8,61 @@ saturation, hue, the four operations applied in an order given by ``random.shuff
 ``ImageEnhance.Brightness / Contrast / Color``, hue adds ``uint8(hue_factor * 255)`` to the H plane of the HSV image with 8-bit
 wrap-around.  Same draws from the same ``random`` state, same PIL calls; parity with torchvision itself is unpinned (it cannot be
 imported here).  Everything in this file runs on the host, in the loader's worker processes.
+
+``ColorJitter.draw()`` / ``apply()`` cut a jitter into its random draws (a ``JitterPlan``) and the pixel work: the draws stay on the
+host and on Python's ``random`` stream, the pixel work runs either here (``apply``: PIL) or on the device (``df_color_jitter``,
+lib/preprocess.py ``color_jitter``, fed ``plan_row(plan)``) with identical results.
 """
 from __future__ import annotations
 
 import random
+from typing import NamedTuple
 
 import numpy as np
 from PIL import Image, ImageEnhance
 
 
-def adjust_hue(img, hue_factor):
-    if not -0.5 <= hue_factor <= 0.5:
-        raise ValueError("hue_factor is not in [-0.5, 0.5].")
+OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE, OP_NONE = 0, 1, 2, 3, 4      # op codes of a plan row (include/dfusion.h, df_color_jitter)
+
+
+def hue_shift(hue_factor):
+    """The 8-bit amount ``adjust_hue`` adds to the H plane: Python's int() truncates toward zero, so -0.05 -> -12 -> 244."""
+    return int(hue_factor * 255) & 0xFF
+
+
+def shift_hue(img, shift):
     mode = img.mode
     if mode in ("L", "1", "I", "F"):
         return img
     h, s, v = img.convert("HSV").split()
     np_h = np.array(h, dtype=np.uint8)
-    np_h = (np_h.astype(np.int32) + (int(hue_factor * 255) & 0xFF)).astype(np.uint8)      # uint8 addition: wraps across the boundary
+    np_h = (np_h.astype(np.int32) + shift).astype(np.uint8)      # uint8 addition: wraps across the boundary
     return Image.merge("HSV", (Image.fromarray(np_h, "L"), s, v)).convert(mode)
+
+
+def adjust_hue(img, hue_factor):
+    if not -0.5 <= hue_factor <= 0.5:
+        raise ValueError("hue_factor is not in [-0.5, 0.5].")
+    return shift_hue(img, hue_shift(hue_factor))
+
+
+class JitterPlan(NamedTuple):
+    """One jitter's draws.  The alphas are what PIL's blend computes with (its C float); an absent operation has alpha 1 / shift 0
+    and is missing from ``order``."""
+    brightness: np.float32
+    contrast: np.float32
+    saturation: np.float32
+    hue_shift: int
+    order: tuple                  # op codes in application order
+
+
+IDENTITY_PLAN = JitterPlan(np.float32(1.0), np.float32(1.0), np.float32(1.0), 0, ())
+
+
+def plan_row(plan):
+    """The plan as the 8 floats df_color_jitter reads: three alphas, the hue shift, four op codes (OP_NONE fills the unused slots)."""
+    order = list(plan.order) + [OP_NONE] * (4 - len(plan.order))
+    return np.array([plan.brightness, plan.contrast, plan.saturation, plan.hue_shift] + order, dtype=np.float32)
 
 
 class ColorJitter:
@@ -57,6 +93,48 @@ class ColorJitter:
         for op in self.get_params():
             img = op(img)
         return img
+
+    def draw(self):
+        """The draws of ``get_params()`` as a plan: the same ``random.uniform`` calls in the same order, then ``random.shuffle`` on a
+        list of as many op codes (its consumption depends on the length only), so ``random`` is left in the state ``get_params()``
+        leaves it in."""
+        alpha, shift, ops = [np.float32(1.0)] * 3, 0, []
+        for k, rng in enumerate((self.brightness, self.contrast, self.saturation)):
+            if rng is not None:
+                alpha[k] = np.float32(random.uniform(*rng))
+                ops.append(k)
+        if self.hue is not None:
+            shift = hue_shift(random.uniform(*self.hue))
+            ops.append(OP_HUE)
+        random.shuffle(ops)
+        return JitterPlan(alpha[0], alpha[1], alpha[2], shift, tuple(ops))
+
+    @staticmethod
+    def apply(img, plan):
+        """The plan applied on the host with PIL: ``self(img)`` is ``apply(img, self.draw())``."""
+        for op in plan.order:
+            if op == OP_BRIGHTNESS:
+                img = ImageEnhance.Brightness(img).enhance(float(plan.brightness))
+            elif op == OP_CONTRAST:
+                img = ImageEnhance.Contrast(img).enhance(float(plan.contrast))
+            elif op == OP_SATURATION:
+                img = ImageEnhance.Color(img).enhance(float(plan.saturation))
+            elif op == OP_HUE:
+                img = shift_hue(img, plan.hue_shift)
+        return img
+
+
+def defer_jitter(trancolor, img):
+    """The host half of a jitter whose pixel work runs on the device: draws the plan (Python's ``random`` advances exactly as under
+    ``trancolor(img)``) and returns (the image to upload, its plan row).  RGB goes up as it is and RGBA without its alpha plane (the
+    enhancers and the hue shift treat the colour planes of both alike, and the loaders drop alpha anyway); any other mode is jittered
+    here with PIL and goes up with the identity plan."""
+    plan = trancolor.draw()
+    if img.mode == "RGBA":
+        img = img.convert("RGB")
+    if img.mode != "RGB":
+        return trancolor.apply(img, plan), plan_row(IDENTITY_PLAN)
+    return img, plan_row(plan)
 
 
 def occluder_mask(f_label, front_num=2):

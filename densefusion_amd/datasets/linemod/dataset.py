@@ -14,7 +14,8 @@ come back resident on the device (``.cuda()`` on them is a no-op).  The random p
 include/dfusion.h; ``mask_to_bbox`` uses 8-connected components instead of OpenCV contours (same rectangles:
 findContours traces the outer border of exactly those components).  ``add_noise=True`` (:114-115,159-160,178-180): colour
 jitter on the decoded frame (``augment.ColorJitter``, a restatement of the pinned torchvision's) and one random translation
-added to cloud and target.
+added to cloud and target.  ``jitter="device"`` keeps the jitter's draws on the host (``ColorJitter.draw``: the same ``random`` stream) and
+applies them to the uploaded frames with ``df_color_jitter`` -- the same bytes as the host's PIL calls, off the loader's CPUs.
 """
 from __future__ import annotations
 
@@ -85,13 +86,17 @@ def _load_yaml(path):
 
 
 class PoseDataset:
-    def __init__(self, mode, num, add_noise, root, noise_trans, refine, device="cuda", seed=0):
+    def __init__(self, mode, num, add_noise, root, noise_trans, refine, device="cuda", seed=0, jitter="host"):
         if mode not in ("train", "test", "eval"):
             raise ValueError(f"mode must be train / test / eval, got {mode!r}")
+        if jitter not in ("host", "device"):
+            raise ValueError(f"jitter must be host / device, got {jitter!r}")
         self.objlist = list(OBJLIST)
         self.mode, self.num, self.root, self.refine = mode, int(num), root, refine
         self.noise_trans, self.add_noise = noise_trans, bool(add_noise)
         self.trancolor = augment.ColorJitter(0.2, 0.2, 0.2, 0.05)                  # :83
+        self.jitter = jitter
+        self._device_jitter = jitter == "device" and self.add_noise
         self.device = torch.device(device)
         self.seed = int(seed)
         self.list_rgb, self.list_depth, self.list_label, self.list_obj, self.list_rank = [], [], [], [], []
@@ -137,7 +142,10 @@ class PoseDataset:
 
     def _host_frame(self, index):
         img = Image.open(self.list_rgb[index])
-        if self.add_noise:
+        row = None
+        if self._device_jitter:                               # the draws of :114-115 here, their application after the upload
+            img, row = augment.defer_jitter(self.trancolor, img)
+        elif self.add_noise:
             img = self.trancolor(img)                         # :114-115
         rgb = np.asarray(img)[:, :, :3]
         depth = np.asarray(Image.open(self.list_depth[index])).astype(np.uint16)
@@ -150,7 +158,7 @@ class PoseDataset:
         else:
             lab2d = label[:, :, 0] if label.ndim == 3 else label       # :110 keeps channel 0 of the per-channel comparison
             box = get_bbox(meta["obj_bb"])
-        return np.ascontiguousarray(rgb), depth, np.ascontiguousarray(lab2d).astype(np.int32), box, obj, meta
+        return np.ascontiguousarray(rgb), depth, np.ascontiguousarray(lab2d).astype(np.int32), box, obj, meta, row
 
     def _targets(self, obj, meta, add_t=None):
         pts = self.pt[obj] / 1000.0
@@ -170,6 +178,8 @@ class PoseDataset:
         host = [self._host_frame(i) for i in indices]
         dev = self.device
         rgb = torch.from_numpy(np.stack([h[0] for h in host])).to(dev)
+        if self._device_jitter:                               # all frames of the call in one launch pair
+            rgb = pp.color_jitter(rgb, np.stack([h[6] for h in host]), out=rgb)
         depth = torch.from_numpy(np.stack([h[1] for h in host]).view(np.int16)).to(dev)
         label = torch.from_numpy(np.stack([h[2] for h in host])).to(dev)
         groups = {}
@@ -206,26 +216,30 @@ class PoseDataset:
         """CPU half of ``__getitem__`` (never touches the device: runs in the loader's worker processes like the reference's
         DataLoader workers, tools/train.py:106): the decoded frame, the snapped box, the number of mask pixels in it and the
         sampled model / target points, as host tensors."""
-        rgb, depth, lab2d, box, obj, meta = self._host_frame(index)
+        rgb, depth, lab2d, box, obj, meta, row = self._host_frame(index)
         rmin, rmax, cmin, cmax = box
         count = int(np.count_nonzero((depth[rmin:rmax, cmin:cmax] != 0) & (lab2d[rmin:rmax, cmin:cmax] == 255)))
         add_t = np.array([random.uniform(-self.noise_trans, self.noise_trans) for _ in range(3)])      # drawn even when unused (:132)
         target, model_points = self._targets(obj, meta, add_t if self.add_noise else None)
-        return (torch.from_numpy(np.array(rgb)), torch.from_numpy(depth.view(np.int16)), torch.from_numpy(lab2d),
+        item = (torch.from_numpy(np.array(rgb)), torch.from_numpy(depth.view(np.int16)), torch.from_numpy(lab2d),
                 torch.tensor([rmin, rmax, cmin, cmax, count, self.objlist.index(obj)], dtype=torch.int64), target, model_points,
                 torch.from_numpy((add_t if self.add_noise else np.zeros(3)).astype(np.float32)))
+        return item + (torch.from_numpy(row[None]),) if self._device_jitter else item      # jitter="device": the raw frame and its plan row
 
     def device_item(self, index, host, choose=None):
         """Device half: uploads + one preparation launch on the current stream, no read-back.  Same 6-tuple as ``__getitem__``.
         ``choose``: the pixel subset as an input (tests: the reference's own draw) instead of the device-side sampling."""
-        rgb, depth, lab2d, info, target, model_points, add_t = host
+        rgb, depth, lab2d, info, target, model_points, add_t = host[:7]
         rmin, rmax, cmin, cmax, count, oi = (int(v) for v in info.tolist())
         if count == 0:
             cc = torch.LongTensor([0])
             return (cc, cc, cc, cc, cc, cc)
         dev = self.device
         up = lambda t: t.to(dev, non_blocking=True)            # asynchronous when the loader pinned `t`, staged otherwise
-        img, cloud, choose, _ = pp.preprocess_objects(up(rgb)[None], up(depth)[None], up(lab2d)[None],
+        rgb = up(rgb)[None]
+        if self._device_jitter:
+            rgb = pp.color_jitter(rgb, up(host[7]), out=rgb)
+        img, cloud, choose, _ = pp.preprocess_objects(rgb, up(depth)[None], up(lab2d)[None],
                                                       [(0, 255, (rmin, rmax, cmin, cmax), (self.seed * 1000003 + int(index)) & 0xFFFFFFFF)],
                                                       self.num, cam=pp.LINEMOD_CAM, choose_in=choose)
         idx = torch.tensor([oi], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)

@@ -88,3 +88,52 @@ def preprocess_objects(rgb, depth, label, objects, num_points, cam=YCB_CAM, choo
                                               count.data_ptr(), _lib.current_stream())
     _lib.check(st, "preprocess_objects")
     return img, cloud, choose, count
+
+
+def color_jitter(frames_u8, plans, out=None):
+    """The training colour jitter on the device (``df_color_jitter``): frames_u8 [F,H,W,3] uint8 device tensor, plans [F,8] float32
+    (``datasets.augment.plan_row`` rows; host or device).  Returns the jittered uint8 frames, bit-identical to
+    ``augment.ColorJitter.apply`` on each; ``out=frames_u8`` works in place."""
+    if not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+        raise RuntimeError("color_jitter: frames must be a [F,H,W,3] uint8 device tensor (no CPU path)")
+    F, H, W, _ = frames_u8.shape
+    dev = frames_u8.device
+    if not torch.is_tensor(plans):
+        plans = torch.from_numpy(np.ascontiguousarray(plans, dtype=np.float32))
+    if tuple(plans.shape) != (F, 8) or plans.dtype != torch.float32:
+        raise RuntimeError("color_jitter: plans must be [F,8] float32")
+    if not plans.is_cuda:
+        plans = (plans if plans.is_pinned() else plans.pin_memory()).to(dev, non_blocking=True)
+    out = torch.empty_like(frames_u8) if out is None else out
+    if out.shape != frames_u8.shape or out.dtype != torch.uint8 or out.device != dev:
+        raise RuntimeError("color_jitter: out must match the frames")
+    sums = torch.empty(F, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        st = _lib.lib().df_color_jitter(_lib.dptr(frames_u8), _lib.dptr(plans), F, H, W, sums.data_ptr(), _lib.dptr(out), _lib.current_stream())
+    _lib.check(st, "color_jitter")
+    return out
+
+
+def compose_frame(rgb, back=None, mask_back=None, front=None, mask_front=None):
+    """The YCB training composition on the device, IN PLACE on rgb [H,W,3] uint8 (``df_compose_frame``; datasets/ycb/dataset.py):
+    ``rgb += back`` where mask_back (uint8 wrap-around like the reference's), then ``rgb = front`` where not mask_front.  Masks [H,W]
+    uint8 / bool device tensors; a layer and its mask are given together or not at all."""
+    if not rgb.is_cuda or rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise RuntimeError("compose_frame: rgb must be a [H,W,3] uint8 device tensor (no CPU path)")
+    H, W, _ = rgb.shape
+    ptrs = []
+    for layer, mask in ((back, mask_back), (front, mask_front)):
+        if (layer is None) != (mask is None):
+            raise RuntimeError("compose_frame: a layer and its mask come together")
+        if layer is None:
+            ptrs += [None, None]
+            continue
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if layer.shape != rgb.shape or layer.dtype != torch.uint8 or tuple(mask.shape) != (H, W) or mask.dtype != torch.uint8:
+            raise RuntimeError("compose_frame: a layer is [H,W,3] uint8, its mask [H,W] uint8 / bool")
+        ptrs += [_lib.dptr(layer), _lib.dptr(mask)]
+    with _lib.device_guard(rgb.device):
+        st = _lib.lib().df_compose_frame(_lib.dptr(rgb), *ptrs, H, W, _lib.current_stream())
+    _lib.check(st, "compose_frame")
+    return rgb

@@ -256,6 +256,24 @@ int df_preprocess_objects(const unsigned char *rgb, const unsigned short *depth,
                           int64_t *choose_out, int *count_out, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training-time pixel augmentation on whole uint8 frames, bit-identical to the host path (densefusion_amd/datasets/augment.py over PIL;
+ * datasets/ycb/dataset.py).  Same conventions as df_preprocess_objects: no allocation, no synchronisation, the caller's stream.
+ *
+ * df_color_jitter: src [F][H][W][3] u8 -> dst, same layout (dst == src allowed, no other overlap); H*W <= 2^24, F <= 65535.
+ *   plan [F][8] float (device): {brightness alpha, contrast alpha, saturation alpha, hue shift 0..255, op0, op1, op2, op3} -- the
+ *   operations in application order, 0 brightness, 1 contrast, 2 saturation, 3 hue, anything else none (augment.plan_row).
+ *   scratch [F] u32 (device): per-frame sums of L, zeroed on the stream by the call.
+ *   brightness / contrast / saturation = trunc(clamp(d + a*(x - d))) in fp32 without fused multiply-add, d = 0 / the frame's rounded mean
+ *   L at that point of the order / the pixel's L, L = (R*19595 + G*38470 + B*7471 + 0x8000) >> 16; hue = PIL's RGB -> HSV, H += shift
+ *   (mod 256), HSV -> RGB.  Deterministic: the only atomics add integers.
+ * df_compose_frame: rgb [H][W][3] u8 in place, in u8 arithmetic: rgb += back where mask_back != 0 (wraps mod 256), then rgb = front
+ *   where mask_front == 0.  Masks [H][W] u8.  back / mask_back and front / mask_front are NULL together (layer absent). */
+int df_color_jitter(const unsigned char *src, const float *plan, int F, int H, int W, unsigned *scratch, unsigned char *dst,
+                    df_stream_t stream);
+int df_compose_frame(unsigned char *rgb, const unsigned char *back, const unsigned char *mask_back, const unsigned char *front,
+                     const unsigned char *mask_front, int H, int W, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Detections from SegNet's own masks (the RGB-D frame -> SegNet -> per-object mask and box step of the reference's real-robot
  * setting; densefusion_amd/lib/segment.py).  Deterministic: no atomics, integer statistics, and a frame's results do not depend
  * on the other frames of the call.

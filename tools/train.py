@@ -80,6 +80,9 @@ def build_parser():
                          "trainer's process only uploads; threads: --workers threads of the trainer's process do both (always for the synthetic set)")
     ap.add_argument("--reference_loaders", action="store_true",
                     help="import datasets.<name>.dataset.PoseDataset from the PYTHONPATH (the reference's loaders) instead of the built-in ones")
+    ap.add_argument("--jitter", type=str, default="host", choices=["host", "device"],
+                    help="where the built-in loaders apply the training colour jitter (and YCB's frame composition): host = PIL in the loader's "
+                         "workers; device = drawn on the host, applied by df_color_jitter after the upload (the same pixels)")
     ap.add_argument("--lanes", type=int, default=4,
                     help="PoseNet phase, native step: passes of one accumulation window run on this many concurrent lanes (own HIP stream, "
                          "host thread, workspace and gradient buffer each; gradients summed in lane order): bs = 1 passes fill a fraction "
@@ -135,6 +138,8 @@ def make_datasets(opt):
     opt.num_objects, opt.num_points = (21, 1000) if opt.dataset == "ycb" else (13, 500)
     if opt.reference_loaders:        # the reference's own loaders from the PYTHONPATH (host-side preparation, its DataLoader semantics)
         PoseDataset = __import__("datasets.%s.dataset" % opt.dataset, fromlist=["PoseDataset"]).PoseDataset
+        if opt.jitter != "host":
+            logging.getLogger("train").info("--jitter %s ignored: the reference's loaders jitter on the host", opt.jitter)
         return (PoseDataset("train", opt.num_points, True, opt.dataset_root, opt.noise_trans, opt.refine_start),
                 PoseDataset("test", opt.num_points, False, opt.dataset_root, 0.0, opt.refine_start))
     # built-in loaders: the reference's constructor arguments (tools/train.py:57-66: augmentation on for the training set)
@@ -142,9 +147,10 @@ def make_datasets(opt):
         from densefusion_amd.datasets.ycb.dataset import PoseDataset
     else:
         from densefusion_amd.datasets.linemod.dataset import PoseDataset
-    logging.getLogger("train").info("datasets.%s: the built-in loader (device-side preparation; training augmentation on, noise_trans %g)",
-                                    opt.dataset, opt.noise_trans)
+    logging.getLogger("train").info("datasets.%s: the built-in loader (device-side preparation; training augmentation on, noise_trans %g, colour jitter on the %s)",
+                                    opt.dataset, opt.noise_trans, opt.jitter)
     kw = dict(dataset_config_dir=opt.dataset_config_dir) if opt.dataset == "ycb" else {}
+    kw["jitter"] = opt.jitter
     return (PoseDataset("train", opt.num_points, True, opt.dataset_root, opt.noise_trans, opt.refine_start, **kw),
             PoseDataset("test", opt.num_points, False, opt.dataset_root, 0.0, opt.refine_start, **kw))
 
