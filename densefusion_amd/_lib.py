@@ -87,6 +87,8 @@ SIGNATURES = {
     "df_conv3x3_winograd_scratch_bytes": (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     "df_conv3x3_winograd_nhwc": (_i, [ctypes.POINTER(ConvDesc), _vp, ctypes.c_size_t, _vp]),
     "df_wino_route": (_i, [_i, _i, _i, _i, _i]),
+    "df_wino_tiles": (ctypes.c_long, [_i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "df_wino_axis_map": (_i, [_i, _i, _i, _i]),
     "df_trainer_create": (_vp, [_i, _i, _i]),
     "df_trainer_destroy": (None, [_vp]),
     "df_trainer_flat_numel": (_i64, [_vp]),

@@ -1227,6 +1227,22 @@ extern "C" int df_conv3x3_winograd_tile_nhwc(const df_conv_desc *d, int tile, vo
 
 extern "C" int df_wino_route(int H, int W, int dil, int Cin, int Cout) { return wino_route(H, W, dil, Cin, Cout); }
 
+extern "C" long df_wino_tiles(int B, int H, int W, int dil, int tile, int *packed_y, int *packed_x) {
+  if (B <= 0 || H <= 0 || W <= 0 || dil < 1 || (tile != 2 && tile != 4)) { set_error(DF_ERR_ARG, "wino_tiles: bad geometry"); return -1; }
+  const WinoGeom g = wino_geom(B, H, W, dil, tile);
+  if (packed_y) *packed_y = g.ay.packed;
+  if (packed_x) *packed_x = g.ax.packed;
+  return g.T;
+}
+
+extern "C" int df_wino_axis_map(int L, int dil, int tile, int v) {
+  if (L <= 0 || dil < 1 || (tile != 2 && tile != 4)) { set_error(DF_ERR_ARG, "wino_axis_map: bad geometry"); return -2; }
+  const WinoAxis a = wino_axis(L, dil, tile);
+  const int per_strip = tile * a.TT;          // positions 0 .. S * per_strip - 1: the strips one after another
+  if (v < 0 || v >= a.S * per_strip) return -1;
+  return wino_axis_coord(a, dil, v / per_strip, v % per_strip);
+}
+
 extern "C" size_t df_conv3x3_winograd_scratch_bytes(const df_conv_desc *d) { return df_conv3x3_winograd_tile_scratch_bytes(d, 2); }
 
 extern "C" int df_conv3x3_winograd_nhwc(const df_conv_desc *d, void *scratch, size_t scratch_bytes, df_stream_t stream) {

@@ -1203,19 +1203,19 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
     for (int i : *f4) {
       tB.push_back(li->B[i]); tH.push_back(li->H[i]); tW.push_back(li->W[i]); trow.push_back(li->off[i]);
       t0.push_back(T);
-      T += wino_geom(li->B[i], li->H[i], li->W[i], dil, 4).T;
+      T += wino_geom(li->B[i], li->H[i], li->W[i], dil, 4, false).T;       // padded tiles: see wino.h
     }
     const size_t mark = s.off;
     float *V = s.f((size_t)36 * T * ci), *M = s.f((size_t)36 * T * co);
     if (s.live()) {
       const int nw = (int)f4->size();
-      launch_wino4_input_multi(in.d, in.ld, V, nw, tB.data(), tH.data(), tW.data(), trow.data(), t0.data(), ci, dil, T, s.st);
+      launch_wino4_input_multi(in.d, in.ld, V, nw, tB.data(), tH.data(), tW.data(), trow.data(), t0.data(), ci, dil, T, s.st, false);
       ConvParams q;
       q.in = V; q.wgt = U; q.out = M;
       q.B = (int)T; q.Cin = ci; q.in_ld = ci; q.Cout = co; q.out_ld = co;
       q.zcount = 36; q.z_in_coff = T * ci; q.z_wgt = (long)co * ci; q.z_out_coff = T * co;
       s.gemm(kind, q);
-      launch_wino4_output_multi(M, out.d, out.ld, rs, rs_ld, a, nw, tB.data(), tH.data(), tW.data(), trow.data(), t0.data(), co, dil, T, s.st);
+      launch_wino4_output_multi(M, out.d, out.ld, rs, rs_ld, a, nw, tB.data(), tH.data(), tW.data(), trow.data(), t0.data(), co, dil, T, s.st, false);
     }
     s.off = mark;
   };

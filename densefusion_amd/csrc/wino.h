@@ -5,11 +5,24 @@
 namespace df {
 
 constexpr int WINO_MAXB = 16;
+// One axis (rows or columns) of a map under dilation d, cut into strips of TT tiles.  The d residue classes of the axis (positions
+// r, r + d, ...: n = ceil(L/d) points for r < R = L - d (n - 1), n - 1 for the others) are convolved independently of each other.
+//   padded: S = d strips, strip r = residue r alone, TT = ceil(n / m): every residue pays its own round-up to whole tiles
+//   packed: S = 1 strip of V = L + k - 1 virtual positions: the k non-empty residues in order, ONE zero position (separator)
+//           between neighbours, which is the convolution's zero padding of both; TT = ceil(V / m).  Virtual position v: R slots of
+//           width n + 1, then slots of width n; a slot's last position is its separator (the last slot has none: it ends at V).
+// Packed is taken for m = 4 and d > 1 only, and only where it has strictly fewer tiles; a function of (L, d, m), never the batch.
+struct WinoAxis { int L, n, S, TT, packed; };
+WinoAxis wino_axis(int L, int d, int m);
+// the point of the axis at virtual position v of a strip (padded: its v-th point), or -1: separator / outside.  Closed form.
+int wino_axis_coord(const WinoAxis &a, int d, int strip, int v);
 // per-bucket table of a multi-bucket transform launch (kernel argument, by value)
-struct WinoTab { int n; int H[WINO_MAXB], W[WINO_MAXB], TH[WINO_MAXB], TW[WINO_MAXB], blocks[WINO_MAXB + 1]; long T[WINO_MAXB], row0[WINO_MAXB], t0[WINO_MAXB]; };
-struct WinoGeom { int TH, TW; long T; };                 // tiles per sub-lattice (rows, columns), tiles in total
-// m = 2: F(2x2,3x3) (16 planes), m = 4: F(4x4,3x3) (36 planes)
-WinoGeom wino_geom(int B, int H, int W, int dil, int m = 2);
+struct WinoTab { int n; WinoAxis ay[WINO_MAXB], ax[WINO_MAXB]; int blocks[WINO_MAXB + 1]; long T[WINO_MAXB], row0[WINO_MAXB], t0[WINO_MAXB]; };
+// the two axes (strips, tiles per strip = TH / TW, layout) and the tiles in total, T = B * ay.S * ax.S * TH * TW
+struct WinoGeom { int TH, TW; long T; WinoAxis ay, ax; };
+// m = 2: F(2x2,3x3) (16 planes), m = 4: F(4x4,3x3) (36 planes).  packed = false keeps every axis padded: the native trainer's choice
+// (its gradients are held to the direct-convolution tape within a bound that the padded tiles' rounding meets)
+WinoGeom wino_geom(int B, int H, int W, int dil, int m = 2, bool packed = true);
 // layer-geometry-only decision (never batch dependent): 0 = direct implicit GEMM, 2 / 4 = the transform-domain product with that tile
 int wino_route(int H, int W, int dil, int Cin, int Cout);
 void launch_wino_weight(const float *w_packed /*[O][3][3][C]*/, float *U /*[(m+2)^2][O][C]*/, int O, int C, hipStream_t st, int m = 2);
@@ -26,10 +39,11 @@ void launch_wino_output(const float *M /*[(m+2)^2][Ttot][C]*/, float *out, int o
                         int res_ld, int res_coff, int act, int B, int H, int W, int C, int dil, hipStream_t st, long Ttot = 0, long t0 = 0,
                         int m = 2);
 
-// F(4x4,3x3) transforms of nb crop-size buckets in one launch per 16 buckets (B / H / W / first pixel row / first tile per bucket)
+// F(4x4,3x3) transforms of nb crop-size buckets in one launch per 16 buckets (B / H / W / first pixel row / first tile per bucket);
+// packed as in the wino_geom call that counted the tiles
 void launch_wino4_input_multi(const float *x, int in_ld, float *V, int nb, const int *B, const int *H, const int *W, const long *row0, const long *t0,
-                              int C, int dil, long Ttot, hipStream_t st);
+                              int C, int dil, long Ttot, hipStream_t st, bool packed = true);
 void launch_wino4_output_multi(const float *M, float *out, int out_ld, const float *res, int res_ld, int act, int nb, const int *B, const int *H,
-                               const int *W, const long *row0, const long *t0, int C, int dil, long Ttot, hipStream_t st);
+                               const int *W, const long *row0, const long *t0, int C, int dil, long Ttot, hipStream_t st, bool packed = true);
 
 }  // namespace df

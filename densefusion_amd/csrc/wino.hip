@@ -9,7 +9,12 @@
 // Exact in real arithmetic; in fp32 it re-associates sums (measured ~2x the rounding error of the direct sum,
 // tests/test_conv_gpu.py), weights are transformed once at load time in fp64.
 //
-// Tile numbering: t = ((b*dil + ry)*dil + rx)*TH*TW + ty*TW + tx,  TH = ceil(ceil(H/dil)/m) (same for all sub-lattices).
+// Tile numbering: t = (((b*Sy + sy)*Sx + sx)*TH + ty)*TW + tx over Sy x Sx strips of TH x TW tiles.  An axis is either padded --
+// one strip per sub-lattice (S = dil, strip = residue), TH = ceil(ceil(H/dil)/m), the same for all sub-lattices -- or, F(4x4) only,
+// packed: ONE strip that holds the sub-lattices one after another in residue order with one zero position between neighbours
+// (wino.h).  The dilated convolution is exactly the dense 3x3 convolution of that rearranged axis (a point's neighbours +-dil sit
+// at +-1, and the separator is the zero padding of both sub-lattices it parts; outputs at separators are not written), so tiles run
+// across sub-lattice boundaries and the axis pays one round-up to m instead of dil of them.  F(2x2) is always padded.
 //
 // F(4x4, 3x3) (m = 4): 6x6 input patches -> 4x4 outputs, 36 multiplies per 16 outputs (2.25 per output against 4 for F(2x2) and 9
 // for the direct sum), V / M are 2.25x the activation instead of 4x.  Interpolation points {0, 1, -1, 1/2, -2, inf}: the mixed
@@ -34,6 +39,40 @@ __device__ __forceinline__ TileId tile_of(int t, int d, int TH, int TW) {
   r.b = t / d;
   return r;
 }
+
+// F(4x4): strips per axis and the padded / packed layouts
+struct Tile4 { int b, sy, sx, ty, tx; };
+
+__device__ __forceinline__ Tile4 tile4_of(int t, const WinoAxis &ay, const WinoAxis &ax) {
+  Tile4 r;
+  r.tx = t % ax.TT; t /= ax.TT;
+  r.ty = t % ay.TT; t /= ay.TT;
+  r.sx = t % ax.S; t /= ax.S;
+  r.sy = t % ay.S;
+  r.b = t / ay.S;
+  return r;
+}
+
+// A virtual position of a strip as (residue r, index i within it, points cnt of that residue); i == cnt is the separator behind the
+// residue.  axis_begin is the closed form (v >= -1), axis_next the step to v + 1 that spares the divisions.
+struct AxisPos { int r, i, cnt; };
+
+__host__ __device__ __forceinline__ AxisPos axis_begin(const WinoAxis &a, int d, int strip, int v) {
+  const int R = a.L - d * (a.n - 1), head = R * (a.n + 1);
+  AxisPos p;
+  if (!a.packed) { p.r = strip; p.i = v; }
+  else if (v < 0) { p.r = 0; p.i = v; }
+  else if (v < head) { p.r = v / (a.n + 1); p.i = v - p.r * (a.n + 1); }
+  else { const int q = (v - head) / a.n; p.r = R + q; p.i = v - head - q * a.n; }
+  p.cnt = a.n - (p.r >= R);
+  return p;
+}
+__host__ __device__ __forceinline__ void axis_next(AxisPos &p, const WinoAxis &a, int d) {
+  ++p.i;
+  if (a.packed && p.i > p.cnt) { ++p.r; p.i = 0; p.cnt = a.n - (p.r >= a.L - d * (a.n - 1)); }
+}
+// the map coordinate, or -1 for a separator and for positions before / behind the axis
+__host__ __device__ __forceinline__ int axis_coord(const AxisPos &p, int d) { return (p.i >= 0 && p.i < p.cnt && p.r < d) ? p.r + d * p.i : -1; }
 
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
@@ -228,24 +267,31 @@ __global__ __launch_bounds__(WB) void wino4_weight_multi_kernel(const float *__r
 }
 
 // V[z = i*6+j][t][c] = (B^T d B)[i][j]; one thread per (tile, 4 channels): 36 vector loads in flight per thread
-__device__ __forceinline__ void wino4_input_body(const float *__restrict__ x, int in_ld, int in_coff, float *__restrict__ V, int H, int W, int C, int d,
-                                                 int TH, int TW, long T, long Ttot, long t0, long e_begin, long e_step) {
-  const int c4n = C >> 2;
+// the patch's rows and columns are the virtual positions 4 ty - 1 .. 4 ty + 4 of its strips: a map coordinate each, or zero
+__device__ __forceinline__ void wino4_input_body(const float *__restrict__ x, int in_ld, int in_coff, float *__restrict__ V, const WinoAxis &ay,
+                                                 const WinoAxis &ax, int C, int d, long T, long Ttot, long t0, long e_begin, long e_step) {
+  const int c4n = C >> 2, H = ay.L, W = ax.L;
   const long total = T * c4n;
   for (long e = e_begin; e < total; e += e_step) {
     const int c = (int)(e % c4n) << 2;
     const long t = e / c4n;
-    const TileId id = tile_of((int)t, d, TH, TW);
-    const int y0 = id.ry + d * (4 * id.ty - 1), x0 = id.rx + d * (4 * id.tx - 1);
+    const Tile4 id = tile4_of((int)t, ay, ax);
+    int ys[6], xs[6];
+    AxisPos py = axis_begin(ay, d, id.sy, 4 * id.ty - 1), px = axis_begin(ax, d, id.sx, 4 * id.tx - 1);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      ys[i] = axis_coord(py, d); xs[i] = axis_coord(px, d);
+      axis_next(py, ay, d); axis_next(px, ax, d);
+    }
     float4 r[6][6];                  // r[i][j] = (B^T d)[i][j]: column pass as the patch arrives
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-      const int xx = x0 + d * j;
+      const int xx = xs[j];
       float4 p[6];
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        const int y = y0 + d * i;
-        const bool ok = (unsigned)y < (unsigned)H && (unsigned)xx < (unsigned)W;
+        const int y = ys[i];
+        const bool ok = (y | xx) >= 0;
         p[i] = ok ? *reinterpret_cast<const float4 *>(x + ((size_t)(id.b * H + y) * W + xx) * in_ld + in_coff + c)
                   : make_float4(0.f, 0.f, 0.f, 0.f);
       }
@@ -272,9 +318,9 @@ __device__ __forceinline__ void at6(const float4 m0, const float4 m1, const floa
   y[3 * stride] = f4add(f4add(d12, m5), f4add(f4s(0.125f, m3), f4s(-8.f, m4)));
 }
 
-__global__ __launch_bounds__(WB) void wino4_input_kernel(const float *__restrict__ x, int in_ld, int in_coff, float *__restrict__ V, int H,
-                                                         int W, int C, int d, int TH, int TW, long T, long Ttot, long t0) {
-  wino4_input_body(x, in_ld, in_coff, V, H, W, C, d, TH, TW, T, Ttot, t0, (long)blockIdx.x * WB + threadIdx.x, (long)gridDim.x * WB);
+__global__ __launch_bounds__(WB) void wino4_input_kernel(const float *__restrict__ x, int in_ld, int in_coff, float *__restrict__ V,
+                                                         const WinoAxis ay, const WinoAxis ax, int C, int d, long T, long Ttot, long t0) {
+  wino4_input_body(x, in_ld, in_coff, V, ay, ax, C, d, T, Ttot, t0, (long)blockIdx.x * WB + threadIdx.x, (long)gridDim.x * WB);
 }
 // the same for up to WINO_MAXB crop-size buckets in ONE launch: a workgroup belongs to one bucket (blocks[k] .. blocks[k + 1]), found by
 // a wave-uniform scan of the table in the kernel arguments
@@ -282,22 +328,30 @@ __global__ __launch_bounds__(WB) void wino4_input_multi_kernel(const float *__re
                                                                const WinoTab tab) {
   int k = 0;
   while (k + 1 < tab.n && (int)blockIdx.x >= tab.blocks[k + 1]) ++k;
-  wino4_input_body(x + tab.row0[k] * in_ld, in_ld, 0, V, tab.H[k], tab.W[k], C, d, tab.TH[k], tab.TW[k], tab.T[k], Ttot, tab.t0[k],
+  wino4_input_body(x + tab.row0[k] * in_ld, in_ld, 0, V, tab.ay[k], tab.ax[k], C, d, tab.T[k], Ttot, tab.t0[k],
                    (long)((int)blockIdx.x - tab.blocks[k]) * WB + threadIdx.x, (long)(tab.blocks[k + 1] - tab.blocks[k]) * WB);
 }
 
-// out = act( A^T M A + bias + res ); one thread per (tile, 4 output channels)
+// out = act( A^T M A + bias + res ); one thread per (tile, 4 output channels).  The tile's outputs are the virtual positions
+// 4 ty .. 4 ty + 3 of its strips; only those that are map coordinates on both axes are written
 __device__ __forceinline__ void wino4_output_body(const float *__restrict__ Mz, float *__restrict__ out, int out_ld, int out_coff,
-                                                  const float *__restrict__ bias, const float *__restrict__ res, int res_ld, int res_coff, int act, int H,
-                                                  int W, int C, int d, int TH, int TW, long T, long Ttot, long t0, long e_begin, long e_step) {
-  const int c4n = C >> 2;
+                                                  const float *__restrict__ bias, const float *__restrict__ res, int res_ld, int res_coff, int act,
+                                                  const WinoAxis &ay, const WinoAxis &ax, int C, int d, long T, long Ttot, long t0, long e_begin,
+                                                  long e_step) {
+  const int c4n = C >> 2, H = ay.L, W = ax.L;
   const long total = T * c4n;
   for (long e = e_begin; e < total; e += e_step) {
     const int c = (int)(e % c4n) << 2;
     const long t = e / c4n;
-    const TileId id = tile_of((int)t, d, TH, TW);
-    const int oy = id.ry + d * 4 * id.ty, ox = id.rx + d * 4 * id.tx;
-    if (oy >= H || ox >= W) continue;                // padding tile of a short sub-lattice
+    const Tile4 id = tile4_of((int)t, ay, ax);
+    int ys[4], xs[4];
+    AxisPos py = axis_begin(ay, d, id.sy, 4 * id.ty), px = axis_begin(ax, d, id.sx, 4 * id.tx);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      ys[i] = axis_coord(py, d); xs[i] = axis_coord(px, d);
+      axis_next(py, ay, d); axis_next(px, ax, d);
+    }
+    if ((ys[0] & ys[1] & ys[2] & ys[3]) < 0 || (xs[0] & xs[1] & xs[2] & xs[3]) < 0) continue;    // padding tile of a short sub-lattice
     const size_t zs = (size_t)Ttot * C / 4;
     const float4 *src = reinterpret_cast<const float4 *>(Mz + ((size_t)t0 + t) * C + c);
     float4 s[4][6];                   // s = A^T M, one column of M at a time
@@ -309,14 +363,14 @@ __device__ __forceinline__ void wino4_output_body(const float *__restrict__ Mz, 
     if (bias) bv = *reinterpret_cast<const float4 *>(bias + c);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      const int yy = oy + d * a;
-      if (yy >= H) continue;
+      const int yy = ys[a];
+      if (yy < 0) continue;
       float4 y[4];
       at6(s[a][0], s[a][1], s[a][2], s[a][3], s[a][4], s[a][5], y, 1);
 #pragma unroll
       for (int b2 = 0; b2 < 4; ++b2) {
-        const int xx = ox + d * b2;
-        if (xx >= W) continue;
+        const int xx = xs[b2];
+        if (xx < 0) continue;
         const size_t pix = (size_t)(id.b * H + yy) * W + xx;
         float4 v = y[b2];
         if (bias) v = f4add(v, bv);
@@ -330,17 +384,17 @@ __device__ __forceinline__ void wino4_output_body(const float *__restrict__ Mz, 
 
 __global__ __launch_bounds__(WB) void wino4_output_kernel(const float *__restrict__ Mz, float *__restrict__ out, int out_ld, int out_coff,
                                                           const float *__restrict__ bias, const float *__restrict__ res, int res_ld,
-                                                          int res_coff, int act, int H, int W, int C, int d, int TH, int TW, long T,
+                                                          int res_coff, int act, const WinoAxis ay, const WinoAxis ax, int C, int d, long T,
                                                           long Ttot, long t0) {
-  wino4_output_body(Mz, out, out_ld, out_coff, bias, res, res_ld, res_coff, act, H, W, C, d, TH, TW, T, Ttot, t0,
+  wino4_output_body(Mz, out, out_ld, out_coff, bias, res, res_ld, res_coff, act, ay, ax, C, d, T, Ttot, t0,
                     (long)blockIdx.x * WB + threadIdx.x, (long)gridDim.x * WB);
 }
 __global__ __launch_bounds__(WB) void wino4_output_multi_kernel(const float *__restrict__ Mz, float *__restrict__ out, int out_ld, const float *__restrict__ res,
                                                                 int res_ld, int act, int C, int d, long Ttot, const WinoTab tab) {
   int k = 0;
   while (k + 1 < tab.n && (int)blockIdx.x >= tab.blocks[k + 1]) ++k;
-  wino4_output_body(Mz, out + tab.row0[k] * out_ld, out_ld, 0, nullptr, res ? res + tab.row0[k] * res_ld : nullptr, res_ld, 0, act, tab.H[k], tab.W[k], C,
-                    d, tab.TH[k], tab.TW[k], tab.T[k], Ttot, tab.t0[k], (long)((int)blockIdx.x - tab.blocks[k]) * WB + threadIdx.x,
+  wino4_output_body(Mz, out + tab.row0[k] * out_ld, out_ld, 0, nullptr, res ? res + tab.row0[k] * res_ld : nullptr, res_ld, 0, act, tab.ay[k], tab.ax[k], C,
+                    d, tab.T[k], Ttot, tab.t0[k], (long)((int)blockIdx.x - tab.blocks[k]) * WB + threadIdx.x,
                     (long)(tab.blocks[k + 1] - tab.blocks[k]) * WB);
 }
 
@@ -351,13 +405,38 @@ inline unsigned blocks_for(long n) {
 
 }  // namespace
 
-WinoGeom wino_geom(int B, int H, int W, int dil, int m) {
+// dev switch (A/B runs, bit-identity tests): DF_WINO_PADDED = every axis in the padded layout
+static bool packing_allowed() {
+  static const bool on = dev_getenv("DF_WINO_PADDED") == nullptr;
+  return on;
+}
+
+static WinoAxis axis_of(int L, int d, int m, bool allow_packed) {
+  WinoAxis a;
+  a.L = L; a.n = (L + d - 1) / d; a.S = d; a.TT = (a.n + m - 1) / m; a.packed = 0;
+  if (allow_packed && m == 4 && d > 1) {
+    const int R = L - d * (a.n - 1), k = a.n > 1 ? d : R, tiles = (L + k - 1 + m - 1) / m;     // k non-empty residues, V = L + k - 1
+    if (tiles < a.S * a.TT) { a.S = 1; a.TT = tiles; a.packed = 1; }
+  }
+  return a;
+}
+
+static WinoGeom geom_of(int B, int H, int W, int dil, int m, bool allow_packed) {
   WinoGeom g;
-  g.TH = ((H + dil - 1) / dil + m - 1) / m;
-  g.TW = ((W + dil - 1) / dil + m - 1) / m;
-  g.T = (long)B * dil * dil * g.TH * g.TW;
+  g.ay = axis_of(H, dil, m, allow_packed); g.ax = axis_of(W, dil, m, allow_packed);
+  g.TH = g.ay.TT; g.TW = g.ax.TT;
+  g.T = (long)B * g.ay.S * g.ax.S * g.TH * g.TW;
   return g;
 }
+
+WinoAxis wino_axis(int L, int d, int m) { return axis_of(L, d, m, packing_allowed()); }
+
+int wino_axis_coord(const WinoAxis &a, int d, int strip, int v) {
+  if (v < 0 || strip < 0 || strip >= a.S) return -1;
+  return axis_coord(axis_begin(a, d, strip, v), d);
+}
+
+WinoGeom wino_geom(int B, int H, int W, int dil, int m, bool packed) { return geom_of(B, H, W, dil, m, packed && packing_allowed()); }
 
 int wino_route(int H, int W, int dil, int Cin, int Cout) {
   // Estimated time per output pixel of the three routes, from the layer geometry only -- never the batch -- so batched and solo
@@ -371,7 +450,9 @@ int wino_route(int H, int W, int dil, int Cin, int Cout) {
   int route = 0;
   for (int m = 2; m <= 4; m += 2) {
     const double n2 = (double)(m + 2) * (m + 2);
-    const double per_px = n2 * (double)wino_geom(1, H, W, dil, m).T / px;          // transform-domain values per output pixel
+    // transform-domain values per output pixel, counted on the PADDED layout: the decision predates the packed one and fixtures are
+    // built around it (DESIGN 5 says what re-costing on the packed counts would move)
+    const double per_px = n2 * (double)geom_of(1, H, W, dil, m, false).T / px;
     const double t = 2.0 * per_px * cc / rate + 4.0 * ((1.0 + per_px) * Cin + (per_px + 2.0) * Cout) / 4.0e12;
     if (t < 0.9 * best) { best = t / 0.9; route = m; }                           // a route has to win by a margin to replace a simpler one
   }
@@ -393,8 +474,7 @@ void launch_wino_input(const float *x, int in_ld, int in_coff, float *V, int B, 
   const WinoGeom g = wino_geom(B, H, W, dil, m);
   if (Ttot <= 0) { Ttot = g.T; t0 = 0; }
   if (m == 4)
-    hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, x, in_ld, in_coff, V, H, W, C, dil, g.TH, g.TW, g.T,
-                       Ttot, t0);
+    hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, x, in_ld, in_coff, V, g.ay, g.ax, C, dil, g.T, Ttot, t0);
   else
     hipLaunchKernelGGL(wino_input_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, x, in_ld, in_coff, V, H, W, C, dil, g.TH, g.TW, g.T,
                        Ttot, t0);
@@ -406,7 +486,7 @@ void launch_wino_output(const float *M, float *out, int out_ld, int out_coff, co
   if (Ttot <= 0) { Ttot = g.T; t0 = 0; }
   if (m == 4)
     hipLaunchKernelGGL(wino4_output_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, M, out, out_ld, out_coff, bias, res, res_ld,
-                       res_coff, act, H, W, C, dil, g.TH, g.TW, g.T, Ttot, t0);
+                       res_coff, act, g.ay, g.ax, C, dil, g.T, Ttot, t0);
   else
     hipLaunchKernelGGL(wino_output_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, M, out, out_ld, out_coff, bias, res, res_ld,
                        res_coff, act, H, W, C, dil, g.TH, g.TW, g.T, Ttot, t0);
@@ -414,32 +494,32 @@ void launch_wino_output(const float *M, float *out, int out_ld, int out_coff, co
 
 // F(4x4,3x3) transforms of several crop-size buckets in one launch each (chunks of WINO_MAXB buckets): bucket k = B[k] maps of
 // H[k] x W[k] whose pixel rows start at row0[k] of x / out / res, and whose tiles are rows t0[k] .. of the Ttot-row planes
-static WinoTab make_tab(int n, const int *B, const int *H, const int *W, const long *row0, const long *t0, int C, int dil) {
+static WinoTab make_tab(int n, const int *B, const int *H, const int *W, const long *row0, const long *t0, int C, int dil, bool packed) {
   WinoTab tab;
   tab.n = n;
   tab.blocks[0] = 0;
   for (int k = 0; k < n; ++k) {
-    const WinoGeom g = wino_geom(B[k], H[k], W[k], dil, 4);
-    tab.H[k] = H[k]; tab.W[k] = W[k]; tab.TH[k] = g.TH; tab.TW[k] = g.TW; tab.T[k] = g.T; tab.row0[k] = row0[k]; tab.t0[k] = t0[k];
+    const WinoGeom g = wino_geom(B[k], H[k], W[k], dil, 4, packed);
+    tab.ay[k] = g.ay; tab.ax[k] = g.ax; tab.T[k] = g.T; tab.row0[k] = row0[k]; tab.t0[k] = t0[k];
     tab.blocks[k + 1] = tab.blocks[k] + (int)blocks_for(g.T * (C / 4));
   }
   return tab;
 }
 
 void launch_wino4_input_multi(const float *x, int in_ld, float *V, int nb, const int *B, const int *H, const int *W, const long *row0, const long *t0,
-                              int C, int dil, long Ttot, hipStream_t st) {
+                              int C, int dil, long Ttot, hipStream_t st, bool packed) {
   for (int k0 = 0; k0 < nb; k0 += WINO_MAXB) {
     const int n = nb - k0 < WINO_MAXB ? nb - k0 : WINO_MAXB;
-    const WinoTab tab = make_tab(n, B + k0, H + k0, W + k0, row0 + k0, t0 + k0, C, dil);
+    const WinoTab tab = make_tab(n, B + k0, H + k0, W + k0, row0 + k0, t0 + k0, C, dil, packed);
     hipLaunchKernelGGL(wino4_input_multi_kernel, dim3(tab.blocks[n]), dim3(WB), 0, st, x, in_ld, V, C, dil, Ttot, tab);
   }
 }
 
 void launch_wino4_output_multi(const float *M, float *out, int out_ld, const float *res, int res_ld, int act, int nb, const int *B, const int *H,
-                               const int *W, const long *row0, const long *t0, int C, int dil, long Ttot, hipStream_t st) {
+                               const int *W, const long *row0, const long *t0, int C, int dil, long Ttot, hipStream_t st, bool packed) {
   for (int k0 = 0; k0 < nb; k0 += WINO_MAXB) {
     const int n = nb - k0 < WINO_MAXB ? nb - k0 : WINO_MAXB;
-    const WinoTab tab = make_tab(n, B + k0, H + k0, W + k0, row0 + k0, t0 + k0, C, dil);
+    const WinoTab tab = make_tab(n, B + k0, H + k0, W + k0, row0 + k0, t0 + k0, C, dil, packed);
     hipLaunchKernelGGL(wino4_output_multi_kernel, dim3(tab.blocks[n]), dim3(WB), 0, st, M, out, out_ld, res, res_ld, act, C, dil, Ttot, tab);
   }
 }

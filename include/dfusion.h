@@ -347,6 +347,13 @@ int df_conv3x3_winograd_nhwc(const df_conv_desc *d, void *scratch, size_t scratc
  * rounding error ~4x that of tile 2 per layer (tests/test_conv_gpu.py), invisible in the selected pose.  The
  * engine picks direct / 2 / 4 per layer and map size from a cost estimate that depends on the layer geometry only. */
 int df_wino_route(int H, int W, int dil, int Cin, int Cout);   /* the engine's choice for an H x W map: 0 direct, 2, 4 (host only) */
+/* Host only: the tiles a B x H x W call of the given tile runs, and per axis whether it takes the packed layout (F(4x4), dilation > 1:
+ * the sub-lattices of the axis laid one after another with one zero position between neighbours, where that needs fewer tiles than
+ * padding each sub-lattice to whole tiles).  packed_y / packed_x may be NULL.  -1 on bad arguments. */
+long df_wino_tiles(int B, int H, int W, int dil, int tile, int *packed_y, int *packed_x);
+/* Host only: the map coordinate at position v of an axis of L points (the axis' strips one after another, tile * tiles-per-strip
+ * positions each), or -1 for a separator, tile padding and positions outside; -2 on bad arguments. */
+int df_wino_axis_map(int L, int dil, int tile, int v);
 size_t df_conv3x3_winograd_tile_scratch_bytes(const df_conv_desc *d, int tile);
 int df_conv3x3_winograd_tile_nhwc(const df_conv_desc *d, int tile, void *scratch, size_t scratch_bytes, df_stream_t stream);
 /* Gradients of df_conv2d_nhwc (training path; `d` describes the FORWARD convolution, d->wgt = its weights):

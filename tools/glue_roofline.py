@@ -17,8 +17,9 @@ N, NPAD, PER, ITERS = bench.N_PTS, 1024, 40, bench.ITERS
 
 
 def wino_geom(H, W, d, m):
-    TH, TW = ((H + d - 1) // d + m - 1) // m, ((W + d - 1) // d + m - 1) // m
-    return d * d * TH * TW
+    """tiles of one H x W map (csrc/wino.hip wino_geom: padded or packed sub-lattices per axis)"""
+    from densefusion_amd import _lib
+    return _lib.lib().df_wino_tiles(1, H, W, d, m, None, None)
 
 
 def wino_route(H, W, d, cin, cout):
