@@ -1,6 +1,6 @@
 // Host plumbing shared by the inference engine (engine.hip) and the native training step (train.hip): the workspace arena with its
-// sizing pass, the per-launch GEMM timer behind df_net_profile / df_trainer_profile, the reference parameter list of each network and
-// one resolution level of a pass over crop-size buckets.
+// sizing pass, the per-launch GEMM timer behind df_net_profile / df_trainer_profile, the reference parameter list of each network,
+// one resolution level of a pass over crop-size buckets and the Winograd-domain pass over some of a level's buckets.
 #pragma once
 #include <cstring>
 #include <map>
@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "common.h"
-#include "igemm.h"
+#include "wino.h"
 
 // hidden: internal to the library, none of it joins the exported symbols
 namespace df __attribute__((visibility("hidden"))) {
@@ -254,5 +254,34 @@ struct Level {
     rows += (long)b * h * w; frames += b;
   }
 };
+
+// ------------------------------------------------------------------------------------------------
+// the Winograd-domain pass over buckets of a level
+// ------------------------------------------------------------------------------------------------
+// The plan of buckets `idx` of a level (stride-1 layers: input and output levels have the same rows).  The layout is chosen here, once.
+inline WinoPlan wino_plan(const Level &lv, const std::vector<int> &idx, int dil, int m, bool packed) {
+  WinoPlan pl{dil, m, packed};
+  for (int i : idx) pl.add(lv.B[i], lv.H[i], lv.W[i], lv.off[i]);
+  return pl;
+}
+
+// out = act(conv3x3(in) + res) over the plan's buckets: input transform, ONE z-batched GEMM over the concatenation of their tiles against
+// the transformed weights U [nz][co][ci], output transform.  V / M are scratch: the arena is wound back, so consecutive layers reuse the
+// region.  gemm(p) launches (and times) the product; like the arena's owner it does nothing on a pass that is not live.
+template <class Gemm>
+void wino_pass(Arena &a, hipStream_t st, const WinoPlan &pl, const float *in, int in_ld, int ci, const float *U, float *out, int out_ld, int co,
+               const float *res, int res_ld, int act, Gemm gemm) {
+  if (pl.b.empty()) return;
+  const size_t mark = a.off;
+  float *V = a.f((size_t)pl.nz() * pl.T * ci), *M = a.f((size_t)pl.nz() * pl.T * co);
+  if (a.live()) launch_wino_input(pl, in, in_ld, V, ci, st);
+  ConvParams p;
+  p.in = V; p.wgt = U; p.out = M;
+  p.B = (int)pl.T; p.Cin = ci; p.in_ld = ci; p.Cout = co; p.out_ld = co;
+  p.zcount = pl.nz(); p.z_in_coff = pl.T * ci; p.z_wgt = (long)co * ci; p.z_out_coff = pl.T * co;
+  gemm(p);
+  if (a.live()) launch_wino_output(pl, M, out, out_ld, res, res_ld, act, co, st);
+  a.off = mark;
+}
 
 }  // namespace df

@@ -55,6 +55,15 @@ double conv_flops(const ConvParams &p);
 // algorithmic HBM bytes (inputs, weights, outputs and residual touched once)
 double conv_bytes(const ConvParams &p);
 
+// The data gradient of the forward launch `f` as a launch of its own (dY's maps in, dX's out, a forward stride as input dilation), host only.
+// Geometry only: pointers, leading dimensions and channel offsets -- the residual on dX that accumulates among them -- are the caller's.
+inline ConvParams dgrad_params(const ConvParams &f) {
+  ConvParams q;
+  q.B = f.B; q.H = f.OH; q.W = f.OW; q.Cin = f.Cout; q.OH = f.H; q.OW = f.W; q.Cout = f.Cin;
+  q.KH = f.KH; q.KW = f.KW; q.stride = 1; q.up = f.stride; q.dil = f.dil; q.pad = f.dil * (f.KH - 1) - f.pad;
+  return q;
+}
+
 // One crop-size bucket of a multi-bucket launch: B maps of H x W (outputs OH x OW) whose input / output pixel rows start at
 // in_row0 / out_row0 of the concatenated buffers
 struct WgradSeg { int B, H, W, OH, OW; long in_row0, out_row0; };

@@ -1117,11 +1117,10 @@ void wgrad(Step &s, const ConvParams &f, View gy, float *dw, float *db) {
 
 // data gradient of forward conv `f` (cached flipped weights): dx (+)= conv^T(gy)
 void dgrad(Step &s, const ConvParams &f, View gy, View dx, const float *wflip, bool accumulate) {
-  ConvParams q;
-  q.in = gy.d; q.B = f.B; q.H = f.OH; q.W = f.OW; q.Cin = f.Cout; q.in_ld = gy.ld;
+  ConvParams q = dgrad_params(f);
+  q.in = gy.d; q.in_ld = gy.ld;
   q.wgt = wflip;
-  q.out = dx.d; q.OH = f.H; q.OW = f.W; q.Cout = f.Cin; q.out_ld = dx.ld;
-  q.KH = f.KH; q.KW = f.KW; q.stride = 1; q.up = f.stride; q.dil = f.dil; q.pad = f.dil * (f.KH - 1) - f.pad;
+  q.out = dx.d; q.out_ld = dx.ld;
   if (accumulate) { q.res = dx.d; q.res_ld = dx.ld; }
   if (f.zcount > 1) {      // (a split-K launch walks blockIdx.z too: the z strides must stay zero for everything else)
     q.zcount = f.zcount; q.z_in_coff = f.z_out_coff; q.z_out_coff = f.z_in_coff; q.z_wgt = (long)f.Cin * f.Cout * f.KH * f.KW;
@@ -1129,6 +1128,13 @@ void dgrad(Step &s, const ConvParams &f, View gy, View dx, const float *wflip, b
   q.splitk_ws = s.splitk; q.splitk_ws_bytes = s.splitk_bytes;
   s.gemm(GK_DGRAD, q);
   s.dbg("dgrad");
+}
+
+// buckets `idx` of a convolution between two levels as the segments of a multi-bucket launch (its data gradient: the levels exchanged)
+std::vector<WgradSeg> level_segs(const Level *li, const Level *lo, const std::vector<int> &idx) {
+  std::vector<WgradSeg> segs;
+  for (int i : idx) segs.push_back(WgradSeg{li->B[i], li->H[i], li->W[i], lo->H[i], lo->W[i], li->off[i], lo->off[i]});
+  return segs;
 }
 
 struct ConvW {
@@ -1163,9 +1169,13 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
   const float *slope = act == ACT_PRELU ? s.p(cw.slope) : nullptr;
   // the launches of the forward pass, kept for the backward closure
   auto plan = std::make_shared<std::vector<ConvParams>>();
-  auto f4 = std::make_shared<std::vector<int>>();          // buckets on the F(4x4,3x3) route
   const auto wit = s.t->wino.find(cw.name);
   const bool wino_ok = !flat && wit != s.t->wino.end() && k == 3 && stride == 1 && pad == dil && cw.bias.empty() && act != ACT_PRELU;
+  // the buckets by route, split once: `direct` for the direct kernel, `f4` through F(4x4,3x3) (stride 1: input and output levels have the
+  // same rows, so the forward pass and the data gradient share the plan).  Padded tiles: see wino.h
+  std::vector<int> all, direct, f4;
+  for (int i = 0; i < nb; ++i) { all.push_back(i); (wino_ok && wino_route(li->H[i], li->W[i], dil, cin, cout) == 4 ? f4 : direct).push_back(i); }
+  const WinoPlan f4plan = wino_plan(*li, f4, dil, 4, false);
   if (flat) {
     ConvParams p = flat_params(x, cin, wp, bp, y, act);
     if (res) { p.res = res->v.d; p.res_ld = res->v.ld; }
@@ -1174,52 +1184,23 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
     plan->push_back(p);
     s.gemm(GK_FWD, p);
   } else {
-    std::vector<WgradSeg> direct;
-    int first_direct = -1;
     for (int i = 0; i < nb; ++i) {
       ConvParams p = bucket_params(x, i, cin, wp, bp, y, k, stride, pad, dil, act);
       if (res) { p.res = res->v.d + lo->off[i] * res->v.ld; p.res_ld = res->v.ld; }
       p.prelu = slope;
       p.splitk_ws = s.splitk; p.splitk_ws_bytes = s.splitk_bytes;
       plan->push_back(p);
-      if (wino_ok && wino_route(li->H[i], li->W[i], dil, cin, cout) == 4) { f4->push_back(i); continue; }
-      if (first_direct < 0) first_direct = i;
-      direct.push_back(WgradSeg{li->B[i], li->H[i], li->W[i], lo->H[i], lo->W[i], li->off[i], lo->off[i]});
     }
-    if (direct.size() == 1) s.gemm(GK_FWD, (*plan)[first_direct]);
+    if (direct.size() == 1) s.gemm(GK_FWD, (*plan)[direct[0]]);
     else if (!direct.empty()) {      // the direct kernel over all of them in one launch (a workgroup's tile lies inside one bucket)
       ConvParams p = (*plan)[0];
       p.in = x->v.d; p.out = y->v.d;
       if (res) p.res = res->v.d;
-      s.gemm_multi(GK_FWD, p, direct);
+      s.gemm_multi(GK_FWD, p, level_segs(li, lo, direct));
     }
+    wino_pass(s, s.st, f4plan, x->v.d, x->v.ld, cin, s.dry || !wino_ok ? nullptr : s.t->wino_buf + wit->second.fwd, y->v.d, y->v.ld, cout, res ? res->v.d : nullptr,
+              res ? res->v.ld : 0, act, [&](const ConvParams &q) { s.gemm(GK_FWD, q); });
   }
-  // transform-domain pass over the buckets of `f4` (stride 1: input and output levels have the same rows)
-  auto wino_pass = [=](Step &s, View in, int ci, const float *U, View out, int co, const float *rs, int rs_ld, int a, int kind) {
-    if (f4->empty()) return;
-    std::vector<int> tB, tH, tW;
-    std::vector<long> trow, t0;
-    long T = 0;
-    for (int i : *f4) {
-      tB.push_back(li->B[i]); tH.push_back(li->H[i]); tW.push_back(li->W[i]); trow.push_back(li->off[i]);
-      t0.push_back(T);
-      T += wino_geom(li->B[i], li->H[i], li->W[i], dil, 4, false).T;       // padded tiles: see wino.h
-    }
-    const size_t mark = s.off;
-    float *V = s.f((size_t)36 * T * ci), *M = s.f((size_t)36 * T * co);
-    if (s.live()) {
-      const int nw = (int)f4->size();
-      launch_wino4_input_multi(in.d, in.ld, V, nw, tB.data(), tH.data(), tW.data(), trow.data(), t0.data(), ci, dil, T, s.st, false);
-      ConvParams q;
-      q.in = V; q.wgt = U; q.out = M;
-      q.B = (int)T; q.Cin = ci; q.in_ld = ci; q.Cout = co; q.out_ld = co;
-      q.zcount = 36; q.z_in_coff = T * ci; q.z_wgt = (long)co * ci; q.z_out_coff = T * co;
-      s.gemm(kind, q);
-      launch_wino4_output_multi(M, out.d, out.ld, rs, rs_ld, a, nw, tB.data(), tH.data(), tW.data(), trow.data(), t0.data(), co, dil, T, s.st, false);
-    }
-    s.off = mark;
-  };
-  wino_pass(s, x->v, cin, s.dry || !wino_ok ? nullptr : s.t->wino_buf + wit->second.fwd, y->v, cout, res ? res->v.d : nullptr, res ? res->v.ld : 0, act, GK_FWD);
   s.dbg("conv fwd", cw.name);
   Step *sp = &s;
   s.tape.push_back([=]() {
@@ -1227,23 +1208,15 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
     s.dbg("conv bwd begin", cw.name);
     if (act != ACT_NONE) launch_act_bwd(s, y, act, slope, act == ACT_PRELU ? s.gr(cw.slope) : nullptr);
     {   // weight gradient: one contraction over every bucket's pixels
-      std::vector<WgradSeg> segs;
-      if (flat) segs.push_back(WgradSeg{(int)x->rows(), 1, 1, 1, 1, 0, 0});
-      else for (int i = 0; i < nb; ++i) segs.push_back(WgradSeg{li->B[i], li->H[i], li->W[i], lo->H[i], lo->W[i], li->off[i], lo->off[i]});
       ConvParams f = (*plan)[0];
       f.in = x->v.d;
-      wgrad(s, f, segs, y->g, s.gr(cw.name, cw.woff), cw.bias.empty() ? nullptr : s.gr(cw.bias, cw.boff));
+      wgrad(s, f, flat ? std::vector<WgradSeg>{WgradSeg{(int)x->rows(), 1, 1, 1, 1, 0, 0}} : level_segs(li, lo, all), y->g, s.gr(cw.name, cw.woff),
+            cw.bias.empty() ? nullptr : s.gr(cw.bias, cw.boff));
     }
     if (need_dx) {
       const bool acc = s.grad_of(x);
       if (flat) dgrad(s, (*plan)[0], y->g, x->g, s.pf(cw.name, cw.woff), acc);
       else {
-        std::vector<int> direct;
-        for (int i = 0; i < nb; ++i) {
-          bool on_f4 = false;
-          for (int j : *f4) on_f4 |= j == i;
-          if (!on_f4) direct.push_back(i);
-        }
         if (stride != 1) {
           // strided: dcol[m][tap * cin + c] = sum_n dY[m][n] w[n][tap][c] for every OUTPUT pixel m -- one GEMM over the rows of all buckets
           // against the plain transpose of the packed weights -- then every input pixel gathers the (tap, output pixel) pairs that read it
@@ -1265,18 +1238,16 @@ Act *conv(Step &s, Act *x, int cin, const ConvW &cw, int cout, int k, int stride
         } else if (direct.size() == 1)
           for (int i : direct) dgrad(s, (*plan)[i], rows_view(y->g, lo->off[i]), rows_view(x->g, li->off[i]), s.pf(cw.name, cw.woff), acc);
         else if (!direct.empty()) {
-          const ConvParams &f = (*plan)[0];
-          ConvParams q;
-          q.in = y->g.d; q.Cin = f.Cout; q.in_ld = y->g.ld;
+          ConvParams q = dgrad_params((*plan)[0]);
+          q.B = q.H = q.W = q.OH = q.OW = 1;      // (the buckets carry the geometry)
+          q.in = y->g.d; q.in_ld = y->g.ld;
           q.wgt = s.pf(cw.name, cw.woff);
-          q.out = x->g.d; q.Cout = f.Cin; q.out_ld = x->g.ld;
-          q.KH = f.KH; q.KW = f.KW; q.stride = 1; q.dil = f.dil; q.pad = f.dil * (f.KH - 1) - f.pad;
+          q.out = x->g.d; q.out_ld = x->g.ld;
           if (acc) { q.res = x->g.d; q.res_ld = x->g.ld; }
-          std::vector<WgradSeg> segs;
-          for (int i : direct) segs.push_back(WgradSeg{lo->B[i], lo->H[i], lo->W[i], li->H[i], li->W[i], lo->off[i], li->off[i]});
-          s.gemm_multi(GK_DGRAD, q, segs);
+          s.gemm_multi(GK_DGRAD, q, level_segs(lo, li, direct));
         }
-        wino_pass(s, y->g, cout, s.dry || !wino_ok ? nullptr : s.t->wino_buf + wit->second.bwd, x->g, cin, acc ? x->g.d : nullptr, x->g.ld, ACT_NONE, GK_DGRAD);
+        wino_pass(s, s.st, f4plan, y->g.d, y->g.ld, cout, s.dry || !wino_ok ? nullptr : s.t->wino_buf + wit->second.bwd, x->g.d, x->g.ld, cin, acc ? x->g.d : nullptr,
+                  x->g.ld, ACT_NONE, [&](const ConvParams &q) { s.gemm(GK_DGRAD, q); });
       }
     }
     if (res) {

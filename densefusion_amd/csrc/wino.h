@@ -1,5 +1,7 @@
 // Winograd F(2x2, 3x3) / F(4x4, 3x3) companion kernels of the batched GEMM (wino.hip).
 #pragma once
+#include <vector>
+
 #include "igemm.h"
 
 namespace df {
@@ -31,19 +33,33 @@ void launch_wino_weight(const float *w_packed /*[O][3][3][C]*/, float *U /*[(m+2
 constexpr int WINO_WMAX = 32;
 struct WinoWTab { int n; int O[WINO_WMAX], C[WINO_WMAX], from_b[WINO_WMAX]; long src_off[WINO_WMAX], dst_off[WINO_WMAX], e0[WINO_WMAX + 1]; };
 void launch_wino4_weight_multi(const float *src_a, const float *src_b, float *dst, const WinoWTab &tab, hipStream_t st);
-// Ttot / t0: the tiles of this call are rows [t0, t0 + T) of planes that hold Ttot tiles each (several crop-size buckets share
-// one Winograd-domain GEMM); Ttot = 0 means the call owns the planes (Ttot = T, t0 = 0)
-void launch_wino_input(const float *x, int in_ld, int in_coff, float *V /*[(m+2)^2][Ttot][C]*/, int B, int H, int W, int C, int dil,
-                       hipStream_t st, long Ttot = 0, long t0 = 0, int m = 2);
-void launch_wino_output(const float *M /*[(m+2)^2][Ttot][C]*/, float *out, int out_ld, int out_coff, const float *bias, const float *res,
-                        int res_ld, int res_coff, int act, int B, int H, int W, int C, int dil, hipStream_t st, long Ttot = 0, long t0 = 0,
-                        int m = 2);
+// one bucket that owns its planes, with a bias and channel offsets (the stand-alone C API)
+void launch_wino_input(const float *x, int in_ld, int in_coff, float *V /*[(m+2)^2][T][C]*/, int B, int H, int W, int C, int dil, hipStream_t st,
+                       int m = 2);
+void launch_wino_output(const float *M /*[(m+2)^2][T][C]*/, float *out, int out_ld, int out_coff, const float *bias, const float *res, int res_ld,
+                        int res_coff, int act, int B, int H, int W, int C, int dil, hipStream_t st, int m = 2);
 
-// F(4x4,3x3) transforms of nb crop-size buckets in one launch per 16 buckets (B / H / W / first pixel row / first tile per bucket);
-// packed as in the wino_geom call that counted the tiles
-void launch_wino4_input_multi(const float *x, int in_ld, float *V, int nb, const int *B, const int *H, const int *W, const long *row0, const long *t0,
-                              int C, int dil, long Ttot, hipStream_t st, bool packed = true);
-void launch_wino4_output_multi(const float *M, float *out, int out_ld, const float *res, int res_ld, int act, int nb, const int *B, const int *H,
-                               const int *W, const long *row0, const long *t0, int C, int dil, long Ttot, hipStream_t st, bool packed = true);
+// The Winograd-domain pass of a list of crop-size buckets, planned once: tile m, dilation and layout are fixed when the plan is made, and the
+// sizes of V / M and the transforms on both sides of the GEMM all read the same geometry from it.  Bucket k = B maps of H x W whose pixel
+// rows start at row0 of the row-concatenated x / out / res and whose tiles are rows [t0, t0 + g.T) of the T-row planes.
+struct WinoBucket { WinoGeom g; long row0, t0; };
+struct WinoPlan {
+  int dil, m;
+  bool packed;
+  long T = 0;          // tiles of all buckets
+  double px = 0;       // output pixels the tiles are for
+  std::vector<WinoBucket> b;
+  void add(int B, int H, int W, long row0) {
+    b.push_back(WinoBucket{wino_geom(B, H, W, dil, m, packed), row0, T});
+    T += b.back().g.T;
+    px += (double)B * H * W;
+  }
+  int nz() const { return (m + 2) * (m + 2); }                     // planes of V / M
+  double useful() const { return px / ((double)(m * m) * (double)T); }     // a tile yields m x m pixels
+};
+// the transforms of every bucket of the plan: m = 4 one launch per WINO_MAXB buckets, m = 2 one launch per bucket
+void launch_wino_input(const WinoPlan &pl, const float *x, int in_ld, float *V /*[nz][T][C]*/, int C, hipStream_t st);
+void launch_wino_output(const WinoPlan &pl, const float *M /*[nz][T][C]*/, float *out, int out_ld, const float *res, int res_ld, int act, int C,
+                        hipStream_t st);
 
 }  // namespace df

@@ -469,59 +469,62 @@ void launch_wino4_weight_multi(const float *src_a, const float *src_b, float *ds
   hipLaunchKernelGGL(wino4_weight_multi_kernel, dim3(blocks_for(tab.e0[tab.n])), dim3(WB), 0, st, src_a, src_b, dst, tab);
 }
 
-void launch_wino_input(const float *x, int in_ld, int in_coff, float *V, int B, int H, int W, int C, int dil, hipStream_t st, long Ttot,
-                       long t0, int m) {
+void launch_wino_input(const float *x, int in_ld, int in_coff, float *V, int B, int H, int W, int C, int dil, hipStream_t st, int m) {
   const WinoGeom g = wino_geom(B, H, W, dil, m);
-  if (Ttot <= 0) { Ttot = g.T; t0 = 0; }
   if (m == 4)
-    hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, x, in_ld, in_coff, V, g.ay, g.ax, C, dil, g.T, Ttot, t0);
+    hipLaunchKernelGGL(wino4_input_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, x, in_ld, in_coff, V, g.ay, g.ax, C, dil, g.T, g.T, 0L);
   else
     hipLaunchKernelGGL(wino_input_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, x, in_ld, in_coff, V, H, W, C, dil, g.TH, g.TW, g.T,
-                       Ttot, t0);
+                       g.T, 0L);
 }
 
 void launch_wino_output(const float *M, float *out, int out_ld, int out_coff, const float *bias, const float *res, int res_ld, int res_coff,
-                        int act, int B, int H, int W, int C, int dil, hipStream_t st, long Ttot, long t0, int m) {
+                        int act, int B, int H, int W, int C, int dil, hipStream_t st, int m) {
   const WinoGeom g = wino_geom(B, H, W, dil, m);
-  if (Ttot <= 0) { Ttot = g.T; t0 = 0; }
   if (m == 4)
     hipLaunchKernelGGL(wino4_output_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, M, out, out_ld, out_coff, bias, res, res_ld,
-                       res_coff, act, g.ay, g.ax, C, dil, g.T, Ttot, t0);
+                       res_coff, act, g.ay, g.ax, C, dil, g.T, g.T, 0L);
   else
     hipLaunchKernelGGL(wino_output_kernel, dim3(blocks_for(g.T * (C / 4))), dim3(WB), 0, st, M, out, out_ld, out_coff, bias, res, res_ld,
-                       res_coff, act, H, W, C, dil, g.TH, g.TW, g.T, Ttot, t0);
+                       res_coff, act, H, W, C, dil, g.TH, g.TW, g.T, g.T, 0L);
 }
 
-// F(4x4,3x3) transforms of several crop-size buckets in one launch each (chunks of WINO_MAXB buckets): bucket k = B[k] maps of
-// H[k] x W[k] whose pixel rows start at row0[k] of x / out / res, and whose tiles are rows t0[k] .. of the Ttot-row planes
-static WinoTab make_tab(int n, const int *B, const int *H, const int *W, const long *row0, const long *t0, int C, int dil, bool packed) {
-  WinoTab tab;
-  tab.n = n;
-  tab.blocks[0] = 0;
-  for (int k = 0; k < n; ++k) {
-    const WinoGeom g = wino_geom(B[k], H[k], W[k], dil, 4, packed);
-    tab.ay[k] = g.ay; tab.ax[k] = g.ax; tab.T[k] = g.T; tab.row0[k] = row0[k]; tab.t0[k] = t0[k];
-    tab.blocks[k + 1] = tab.blocks[k] + (int)blocks_for(g.T * (C / 4));
-  }
-  return tab;
-}
-
-void launch_wino4_input_multi(const float *x, int in_ld, float *V, int nb, const int *B, const int *H, const int *W, const long *row0, const long *t0,
-                              int C, int dil, long Ttot, hipStream_t st, bool packed) {
-  for (int k0 = 0; k0 < nb; k0 += WINO_MAXB) {
-    const int n = nb - k0 < WINO_MAXB ? nb - k0 : WINO_MAXB;
-    const WinoTab tab = make_tab(n, B + k0, H + k0, W + k0, row0 + k0, t0 + k0, C, dil, packed);
-    hipLaunchKernelGGL(wino4_input_multi_kernel, dim3(tab.blocks[n]), dim3(WB), 0, st, x, in_ld, V, C, dil, Ttot, tab);
+// the plan's buckets in chunks of WINO_MAXB, one table and one launch per chunk (F(4x4,3x3))
+template <class Launch> static void for_tabs(const WinoPlan &pl, int C, Launch launch) {
+  for (int k0 = 0, nb = (int)pl.b.size(); k0 < nb; k0 += WINO_MAXB) {
+    WinoTab tab;
+    tab.n = nb - k0 < WINO_MAXB ? nb - k0 : WINO_MAXB;
+    tab.blocks[0] = 0;
+    for (int k = 0; k < tab.n; ++k) {
+      const WinoBucket &b = pl.b[k0 + k];
+      tab.ay[k] = b.g.ay; tab.ax[k] = b.g.ax; tab.T[k] = b.g.T; tab.row0[k] = b.row0; tab.t0[k] = b.t0;
+      tab.blocks[k + 1] = tab.blocks[k] + (int)blocks_for(b.g.T * (C / 4));
+    }
+    launch(tab);
   }
 }
 
-void launch_wino4_output_multi(const float *M, float *out, int out_ld, const float *res, int res_ld, int act, int nb, const int *B, const int *H,
-                               const int *W, const long *row0, const long *t0, int C, int dil, long Ttot, hipStream_t st, bool packed) {
-  for (int k0 = 0; k0 < nb; k0 += WINO_MAXB) {
-    const int n = nb - k0 < WINO_MAXB ? nb - k0 : WINO_MAXB;
-    const WinoTab tab = make_tab(n, B + k0, H + k0, W + k0, row0 + k0, t0 + k0, C, dil, packed);
-    hipLaunchKernelGGL(wino4_output_multi_kernel, dim3(tab.blocks[n]), dim3(WB), 0, st, M, out, out_ld, res, res_ld, act, C, dil, Ttot, tab);
-  }
+void launch_wino_input(const WinoPlan &pl, const float *x, int in_ld, float *V, int C, hipStream_t st) {
+  if (pl.m == 4)
+    for_tabs(pl, C, [&](const WinoTab &tab) {
+      hipLaunchKernelGGL(wino4_input_multi_kernel, dim3(tab.blocks[tab.n]), dim3(WB), 0, st, x, in_ld, V, C, pl.dil, pl.T, tab);
+    });
+  else
+    for (const WinoBucket &b : pl.b)
+      hipLaunchKernelGGL(wino_input_kernel, dim3(blocks_for(b.g.T * (C / 4))), dim3(WB), 0, st, x + b.row0 * in_ld, in_ld, 0, V, b.g.ay.L, b.g.ax.L, C,
+                         pl.dil, b.g.TH, b.g.TW, b.g.T, pl.T, b.t0);
+}
+
+void launch_wino_output(const WinoPlan &pl, const float *M, float *out, int out_ld, const float *res, int res_ld, int act, int C, hipStream_t st) {
+  if (pl.m == 4)
+    for_tabs(pl, C, [&](const WinoTab &tab) {
+      hipLaunchKernelGGL(wino4_output_multi_kernel, dim3(tab.blocks[tab.n]), dim3(WB), 0, st, M, out, out_ld, res, res_ld, act, C, pl.dil, pl.T, tab);
+    });
+  else
+    for (const WinoBucket &b : pl.b)
+      hipLaunchKernelGGL(wino_output_kernel, dim3(blocks_for(b.g.T * (C / 4))), dim3(WB), 0, st, M, out + b.row0 * out_ld, out_ld, 0,
+                         (const float *)nullptr, res ? res + b.row0 * res_ld : nullptr, res_ld, 0, act, b.g.ay.L, b.g.ax.L, C, pl.dil, b.g.TH, b.g.TW,
+                         b.g.T, pl.T, b.t0);
 }
 
 }  // namespace df
