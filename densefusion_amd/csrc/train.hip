@@ -186,12 +186,12 @@ __global__ __launch_bounds__(TB) void pool_bwd_all_kernel(const Ptr4 dy, float *
     for (int si = 0; si < 4; ++si) {
       const int s = si == 0 ? 1 : si == 1 ? 2 : si == 2 ? 3 : 6;
       const float *d = dy.p[si] + (size_t)frame * s * s * C4 * 4;
-      for (int bi = max(0, yy * s / H - 1); bi <= min(s - 1, yy * s / H + 1); ++bi) {
+      // the bins that contain pixel yy are exactly floor(yy*s/H) .. ceil((yy+1)*s/H) - 1: more than three of them where the map is
+      // narrower than s/2 (a 1 x 1 map lies in all 36 bins of the 6-bin stage)
+      for (int bi = yy * s / H; bi <= ((yy + 1) * s + H - 1) / H - 1; ++bi) {
         const int y0 = (bi * H) / s, y1 = ((bi + 1) * H + s - 1) / s;
-        if (yy < y0 || yy >= y1) continue;
-        for (int bj = max(0, xx * s / W - 1); bj <= min(s - 1, xx * s / W + 1); ++bj) {
+        for (int bj = xx * s / W; bj <= ((xx + 1) * s + W - 1) / W - 1; ++bj) {
           const int x0 = (bj * W) / s, x1 = ((bj + 1) * W + s - 1) / s;
-          if (xx < x0 || xx >= x1) continue;
           const f32x4 v = reinterpret_cast<const f32x4 *>(d)[(size_t)(bi * s + bj) * C4 + c4];
           const float cnt = (float)((y1 - y0) * (x1 - x0));
 #pragma unroll

@@ -100,10 +100,28 @@ FIXTURES = {
     "k3_n128_48x48": dict(K=3, N=128, H=48, W=48, objs=[2], wseed=19, iseed=48),
 }
 
+# ---- edge fixtures: the smallest crops the entry points accept (8 <= H, W) and the documented maximum side (DF_MAX_CROP = 3200).  A crop
+# side n gives a trunk map side of ((n - 1) // 2 + 1) three times over: 8 -> 1, 9 .. 16 -> 2, 17 .. 24 -> 3, 25 .. 32 -> 4, 36 -> 5,
+# 3200 -> 400.  On these maps the pooling bins are wider than the map, the bilinear sources collapse onto one pixel, the Winograd axes are
+# shorter than the dilation, the max-pool windows are mostly padding and the up-convolution's staged window is larger than the map.  They
+# stay out of FIXTURES (tests/test_engine_edge_crops_gpu.py runs them); the seeds pass ``conditioning`` (8 x 8 with iseed 508 does not: a
+# top-two confidence gap of 3e-5)
+EDGE_FIXTURES = {
+    "edge_8x8": dict(K=2, N=64, H=8, W=8, objs=[1], wseed=11, iseed=600),            # 1 x 1 trunk map
+    "edge_16x16": dict(K=2, N=64, H=16, W=16, objs=[1], wseed=11, iseed=532),        # 2 x 2
+    "edge_12x20": dict(K=2, N=64, H=12, W=20, objs=[1], wseed=11, iseed=532),        # 2 x 3
+    "edge_8x24": dict(K=2, N=64, H=8, W=24, objs=[1], wseed=11, iseed=532),          # 1 x 3
+    "edge_24x8": dict(K=2, N=64, H=24, W=8, objs=[1], wseed=11, iseed=532),          # 3 x 1
+    "edge_32x32": dict(K=2, N=64, H=32, W=32, objs=[1], wseed=11, iseed=532),        # 4 x 4: one F(4x4) tile exactly
+    "edge_36x28": dict(K=2, N=64, H=36, W=28, objs=[1], wseed=11, iseed=532),        # 5 x 4
+    "edge_8x3200": dict(K=2, N=64, H=8, W=3200, objs=[1], wseed=11, iseed=3708),     # 1 x 400: the maximum side, one row
+    "edge_3200x8": dict(K=2, N=64, H=3200, W=8, objs=[1], wseed=11, iseed=3708),     # 400 x 1: one column
+}
+
 
 def fixture(name):
     """-> (fixture dict, PoseNet state dict, refiner state dict, batch) with the batch's obj set to the fixture's objects."""
-    f = FIXTURES[name]
+    f = FIXTURES[name] if name in FIXTURES else EDGE_FIXTURES[name]
     sdp = synth.make_state_dict(synth.posenet_spec(f["K"]), f["wseed"])
     sdr = synth.make_state_dict(synth.refiner_spec(f["K"]), f["wseed"] + 1000)
     b = synth.make_batch(f["iseed"], len(f["objs"]), f["H"], f["W"], f["N"], f["K"])
@@ -392,6 +410,20 @@ def bound_ratio(name, got, r64, r32, floor):
     w_g, w_32 = (worst_channel(g, a), worst_channel(b, a)) if g.shape[0] > 1 else (0.0, 0.0)
     ratio = max(e_g / max(C * e_32, floor[0]), w_g / max(C * w_32, floor[1]))
     return e_g, e_32, w_g, w_32, ratio
+
+
+def one_element_floor(name, r64, r32):
+    """Worst-channel floor of a tap whose channels hold ONE element each (a 1 x 1 map; a per-object tap of a one-object fixture).  There the
+    worst channel is a single number just above a ReLU's zero, and its relative error is one rounding draw over a tiny value: the fp32
+    reference's error at that very element says nothing about what fp32 arithmetic may do to it (its draw may be near zero).  What does is the
+    reference's typical absolute error on the tensor, the same for every element of a layer's output: the floor is C x the reference's RMS
+    absolute error over the tensor, relative to the smallest channel the check looks at (norm above 1e-6 of the largest).  Computed from the two
+    CPU references alone."""
+    a, b = channel_view(name, r64), channel_view(name, r32)
+    assert a.shape[1] == 1, f"{name}: channels of {a.shape[1]} elements"
+    nb = torch.linalg.vector_norm(a, dim=1)
+    live = nb > 1e-6 * float(nb.max())
+    return C * float(((b - a) ** 2).mean().sqrt()) / float(nb[live].min())
 
 
 # ---- end to end: the oracle's forward and estimate loop per object ----

@@ -60,12 +60,24 @@ WINDOWS = {
                            (80, 120)]),
     # mixed5: the five-frame window of test_native_train_gpu.py (two 40 x 80 frames in one bucket)
     "mixed5": dict(K=3, N=128, M=60, wseed=23, oseed=900, sizes=[(40, 80), (160, 160), (80, 80), (40, 80), (120, 160)]),
+    # tiny11: the smallest crops the step accepts and the maximum side (DF_MAX_CROP = 3200): trunk maps of 1 x 1 (twice), 2 x 2, 1 x 3,
+    # 3 x 1, 2 x 3, 4 x 4, 5 x 4, 2 x 5, 1 x 400 and 400 x 1.  N = 70 with M = 60: the symmetric loss groups 512 // 60 = 8 poses per
+    # workgroup, so its last workgroup holds 6 (every other fixture has N % 8 == 0 or one pose per workgroup); frames 1, 4, 7, 10 are symmetric
+    "tiny11": dict(K=3, N=70, M=60, wseed=47, oseed=3000,
+                   sizes=[(8, 8), (16, 16), (8, 24), (24, 8), (12, 20), (32, 32), (36, 28), (8, 8), (16, 40), (8, 3200), (3200, 8)]),
 }
+# one-bucket windows (no bucket to lose: tests/test_oracle_grads.py leaves them out).  ones3: three 8 x 8 frames, 1 x 1 trunk maps only, so
+# that a defect of the one-pixel map cannot hide behind larger frames in the summed gradients; frame 1 is symmetric.  The seed keeps
+# ``point_relu_margin`` at 2.0e-5 (oseed 3100 has a conv6 pre-activation at 1.1e-6: a ReLU the GPU's fp32 sum may flip)
+ONE_BUCKET_WINDOWS = {
+    "ones3": dict(K=3, N=70, M=60, wseed=49, oseed=3130, sizes=[(8, 8), (8, 8), (8, 8)]),
+}
+RELU_MARGIN = 1e-5      # 10x the fp32 rounding of a K = 512 sum of values of about 10
 
 
 def window(name):
     """-> (K, N, M, state dict, objects): objects from synth.make_object, object index i % K (index 1 is the symmetric one)."""
-    w = WINDOWS[name]
+    w = WINDOWS[name] if name in WINDOWS else ONE_BUCKET_WINDOWS[name]
     K, N, M = w["K"], w["N"], w["M"]
     sd = synth.make_state_dict(synth.posenet_spec(K), w["wseed"])
     objs = [synth.make_object(w["oseed"] + i, h, wd, N, K, num_points_mesh=M) for i, (h, wd) in enumerate(w["sizes"])]
@@ -175,6 +187,25 @@ def refiner_oracle(sd, frames):
         r32 = refiner_frames(sd, frames, torch.float32)
     _check_conditioning(r64, r32)
     return r64, r32
+
+
+def point_relu_margin(sd, objs, r64):
+    """Smallest |pre-activation| of feat.conv5 / feat.conv6 over the points of all frames, in fp64.  Their fp32 sums (K = 256 / 512,
+    values of about 10) carry an absolute rounding error of about 1e-6; a pre-activation closer to zero than that may land on the other side
+    of the ReLU on the GPU.  One such flip moves the conv6 bias gradient of a three-frame window of 70 points by 3e-4 (one of about 100
+    active entries of one channel in 1024): a window that small must keep its distance from zero, a large one dilutes the flip."""
+    import torch.nn.functional as F
+    w = {k: torch.as_tensor(v).double() for k, v in sd.items() if k.startswith("feat.")}
+    conv = lambda n, x: F.conv1d(x, w[f"feat.{n}.weight"], w[f"feat.{n}.bias"])
+    margin = float("inf")
+    for o, r in zip(objs, r64):
+        x = torch.from_numpy(o["cloud"])[None].double().transpose(2, 1)
+        x1, e1 = F.relu(conv("conv1", x)), F.relu(conv("e_conv1", r["emb"].double()))
+        x2, e2 = F.relu(conv("conv2", x1)), F.relu(conv("e_conv2", e1))
+        z5 = conv("conv5", torch.cat([x2, e2], 1))
+        z6 = conv("conv6", F.relu(z5))
+        margin = min(margin, float(z5.abs().min()), float(z6.abs().min()))
+    return margin
 
 
 def summed_grads(res, skip=()):

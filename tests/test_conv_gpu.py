@@ -86,6 +86,8 @@ def test_conv_argument_errors():
     # (B, H, W, Cin, Cout, dil): trunk shapes (layer3 d1/d2, layer4 d1/d4), odd maps, maps shorter than one tile row
     (2, 20, 20, 256, 256, 1), (2, 20, 20, 256, 256, 2), (1, 20, 20, 512, 512, 4), (2, 15, 20, 256, 512, 1),
     (1, 15, 15, 64, 128, 4), (3, 7, 5, 32, 64, 2), (1, 30, 40, 128, 64, 4), (2, 3, 3, 16, 8, 1), (1, 2, 9, 8, 8, 4),
+    # the trunk maps of 8 .. 16 px crops and of an 8 x 3200 crop: axes shorter than the dilation (sub-lattices of one pixel, some empty)
+    (2, 1, 1, 128, 128, 1), (1, 2, 2, 256, 256, 2), (2, 1, 3, 512, 512, 4), (1, 2, 1, 512, 512, 4), (1, 1, 400, 512, 512, 4),
 ])
 @pytest.mark.parametrize("fused", [False, True])
 @pytest.mark.parametrize("tile", [2, 4])

@@ -16,6 +16,12 @@ GEOMS = [
     (700, 1, 1, 32, 64, 1, 1, 0, 1),      # e_conv1 over many points
     (1, 20, 20, 1024, 256, 3, 1, 1, 1),   # up_1
     (2, 9, 11, 64, 256, 3, 1, 1, 1),      # odd sizes (multi-tap dgrad needs a power-of-two Cout)
+    # the trunk on crops of 8 .. 16 px and on an 8 x 3200 crop: maps smaller than the dilation (only the centre tap lands inside)
+    (2, 1, 1, 256, 256, 3, 1, 2, 2),
+    (1, 2, 2, 512, 512, 3, 1, 4, 4),
+    (3, 2, 1, 64, 128, 3, 2, 1, 1),       # layer2.0.conv1 on a 2 x 1 map -> 1 x 1
+    (2, 4, 4, 4, 64, 7, 2, 3, 1),         # the stem on an 8 px crop (Cin = 4 as the engine pads it; windows mostly padding)
+    (1, 1, 400, 256, 256, 3, 1, 2, 2),    # one row, 400 columns
 ]
 
 

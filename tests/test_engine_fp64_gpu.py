@@ -97,11 +97,12 @@ def fp32_runs(tmp_path_factory):
 
 class _Table:
     def __init__(self, title):
-        self.rows, self.fails, self.title = [], [], title
+        self.rows, self.fails, self.title, self.worst = [], [], title, (0.0, "")
 
     def check(self, stage, route, got, r64, r32, floor):
         e_g, e_32, w_g, w_32, ratio = of.bound_ratio(stage, got, r64, r32, floor)
         self.rows.append(f"{stage:8s} {route:6s} {e_g:10.2e} {e_32:10.2e} {w_g:10.2e} {w_32:10.2e} {ratio:7.3f}")
+        self.worst = max(self.worst, (ratio, f"{stage} ({route})"))
         try:
             of.check(f"{stage} ({route})", of.channel_view(stage, got), of.channel_view(stage, r64), of.channel_view(stage, r32), floor=floor)
         except AssertionError as e:
@@ -110,12 +111,14 @@ class _Table:
     def scalar(self, what, route, e_g, e_32, floor):
         bound = max(of.C * e_32, floor)
         self.rows.append(f"{what:8s} {route:6s} {e_g:10.2e} {e_32:10.2e} {'':10s} {'':10s} {e_g / bound:7.3f}")
+        self.worst = max(self.worst, (e_g / bound, f"{what} ({route})"))
         if e_g > bound:
             self.fails.append(f"{what} ({route}): {e_g:.3e} > max({of.C} x fp32 oracle's {e_32:.3e}, {floor:.0e})")
 
     def finish(self):
         print(f"\n{self.title}\n{'stage':8s} {'route':6s} {'gpu rel':>10s} {'fp32 rel':>10s} {'gpu chan':>10s} {'fp32 chan':>10s} {'ratio':>7s}")
         print("\n".join(self.rows))
+        print(f"{self.title}: worst ratio to the bound {self.worst[0]:.3f} at {self.worst[1]}")
         assert not self.fails, "\n".join(self.fails)
 
 
@@ -123,12 +126,12 @@ def _inputs(b):
     return {k: torch.from_numpy(b[k]) for k in ("img", "cloud", "choose", "obj")}
 
 
-@pytest.mark.parametrize("name", list(of.FIXTURES))
-def test_engine_layer_by_layer_and_end_to_end_against_fp64(name, fp32_runs):
+def check_fixture(name, runs, floor=lambda k, r64, r32: of.FLOORS[k]):
+    """One fixture's table: ``runs`` = {route: run_engine(name) on that route}, layer-local over every tap and end to end; the caller
+    finishes the table.  ``floor``: the layer-local floors of tap k (given its two references)."""
     f, sdp, sdr, b = of.fixture(name)
     e64, e32, t_e2e = of.oracle_pair(sdp, sdr, b)
     of.conditioning(e64, e32)
-    runs = {"split": run_engine(name), "fp32": fp32_runs[name]}
     sp64, sp32, sr64, sr32 = of.to_sd(sdp, torch.float64), of.to_sd(sdp, torch.float32), of.to_sd(sdr, torch.float64), of.to_sd(sdr, torch.float32)
     tab = _Table(f"{name}: K={f['K']} N={f['N']} {f['H']}x{f['W']} objects {f['objs']}")
     t_ll = time.time()
@@ -137,7 +140,7 @@ def test_engine_layer_by_layer_and_end_to_end_against_fp64(name, fp32_runs):
         ll = of.layer_local(sp64, sp32, R, _inputs(b), of.POSENET_STAGES)
         ll.update(of.layer_local(sr64, sr32, R, {"obj": torch.from_numpy(b["obj"])}, ("rf_x5", "rf_apx", "rf_f1", "rf_f2")))
         for k, (r64, r32) in ll.items():
-            tab.check(k, route, R[k], r64, r32, of.FLOORS[k])
+            tab.check(k, route, R[k], r64, r32, floor(k, r64, r32))
     t_ll = time.time() - t_ll
     for route in ROUTES:
         R = runs[route]
@@ -151,7 +154,12 @@ def test_engine_layer_by_layer_and_end_to_end_against_fp64(name, fp32_runs):
                 tab.scalar(f"ang{i}" + ("" if key == "pose" else "_0"), route, of.quat_angle(g[:4], p64[:4]), of.quat_angle(p32[:4], p64[:4]),
                            of.ANGLE_FLOOR)
     print(f"\n{name}: oracle wall time: end to end {t_e2e:.1f} s (fp64 + fp32), layer-local {t_ll:.1f} s (both routes)")
-    tab.finish()
+    return tab
+
+
+@pytest.mark.parametrize("name", list(of.FIXTURES))
+def test_engine_layer_by_layer_and_end_to_end_against_fp64(name, fp32_runs):
+    check_fixture(name, {"split": run_engine(name), "fp32": fp32_runs[name]}).finish()
 
 
 def test_fixtures_cover_every_winograd_route_of_the_trunk():

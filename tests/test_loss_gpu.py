@@ -36,9 +36,16 @@ def test_loss_and_loss_refine_golden_nonsymmetric():
     _close(d2, g["r_dis"]); _close(np2, g["r_new_points"]); _close(nt2, g["r_new_target"])
 
 
-@pytest.mark.parametrize("N,M,refine", [(96, 80, False), (500, 500, False), (64, 2600, False), (200, 500, True)])
+@pytest.mark.parametrize("N,M,refine", [(96, 80, False), (500, 500, False), (64, 2600, False), (200, 500, True),
+                                        # add_dis_sym_kernel groups ppb = 512 // M poses per workgroup (one pose where M > 512, in passes of 512)
+                                        (70, 60, False),      # ppb = 8: the last group holds 6 poses
+                                        (5, 3, False),        # M < 8: no full chunk in the scan of the cached targets; one group of 5
+                                        (1, 40, False),       # N = 1 takes the unfused kernel
+                                        (300, 1, False),      # ppb = 256: a second group of 44
+                                        (3, 600, False)])     # ppb = 1, two passes over the mesh, the second of 88 points
 def test_loss_symmetric_vs_oracle(N, M, refine):
-    """Symmetric objects: fused transform + 1-NN + reduction == oracle (materialise, knn_ref.c, gather)."""
+    """Symmetric objects: fused transform + 1-NN + reduction == oracle (materialise, knn_ref.c, gather).  (70, 60) also holds the kernel's
+    nearest-target choices to KNearestNeighbor(1) on the materialised points, as the N = 1000 test below does."""
     from densefusion_amd.lib.loss import Loss
     from densefusion_amd.lib.loss_refiner import Loss_refine
     rng = np.random.Generator(np.random.PCG64(N * 3 + M))
@@ -59,6 +66,9 @@ def test_loss_symmetric_vs_oracle(N, M, refine):
     gotr = Loss_refine(M, [7, 8])(C(q1).cuda(), C(t1).cuda(), got[3], C(mp).cuda(), idx.cuda(), got[2])
     for a, b in zip(gotr, wantr):
         _close(a, b, 5e-5)
+    if (N, M) == (70, 60):
+        dev = lambda a: torch.from_numpy(a[0]).cuda()
+        _matches_are_df_knn(dev(q), dev(pt), dev(pc).reshape(-1), dev(tgt), dev(mp), dev(pts), N, M)
 
 
 def test_add_metric_vs_oracle_and_ply_fixture():
@@ -138,9 +148,6 @@ def test_symmetric_loss_matches_are_df_knn_bit_for_bit():
     """BASELINE configs[3] size (N = 1000 per-point poses, M = 500 mesh points: 250 M pairs): the nearest-neighbour choice
     inside the fused loss kernel (csrc/loss.hip add_dis_sym_kernel) == KNearestNeighbor(1)(target, pred) on the materialised
     transformed points (lib/loss.py:41-47 as intended), index for index; both run the scan of csrc/knn_core.h."""
-    import ctypes
-    from densefusion_amd import _lib
-    from densefusion_amd.lib.knn import KNearestNeighbor
     N, M = 1000, 500
     rng = np.random.Generator(np.random.PCG64(31))
     o = synth.make_object(9300, 120, 160, N, 21, num_points_mesh=M)
@@ -148,6 +155,16 @@ def test_symmetric_loss_matches_are_df_knn_bit_for_bit():
     pt = torch.from_numpy((rng.standard_normal((N, 3)) * 0.03).astype(np.float32)).cuda()
     pc = torch.from_numpy(rng.uniform(0.05, 0.95, N).astype(np.float32)).cuda()
     tgt, mp, pts = (torch.from_numpy(o[k]).cuda() for k in ("target", "model_points", "cloud"))
+    _matches_are_df_knn(q, pt, pc, tgt, mp, pts, N, M)
+
+
+def _matches_are_df_knn(q, pt, pc, tgt, mp, pts, N, M):
+    """df_loss_forward's nearest-target choice ``sel`` of N per-point poses q [N,4] / pt [N,3] (device tensors) against KNearestNeighbor(1)
+    on the points materialised as the kernel forms them; at most N * M // 100000 matches may differ."""
+    import ctypes
+    from densefusion_amd import _lib
+    from densefusion_amd.lib.knn import KNearestNeighbor
+    q, pt, pc, tgt, mp, pts = (t.contiguous() for t in (q, pt, pc, tgt, mp, pts))
     loss, dis = torch.empty(1).cuda(), torch.empty(1).cuda()
     npts, ntgt, scratch = torch.empty(N, 3).cuda(), torch.empty(M, 3).cuda(), torch.empty(N).cuda()
     sel = torch.empty(N, M, dtype=torch.int32).cuda()

@@ -55,7 +55,7 @@ def _breaks(name, stage, out, bad):
     assert ratio >= MIN_BREAK, f"{name}: {out}: the emulated defect is only {ratio:.2f}x the bound (floor {of.FLOORS[out]})"
 
 
-@pytest.mark.parametrize("name", list(of.FIXTURES))
+@pytest.mark.parametrize("name", list(of.FIXTURES) + list(of.EDGE_FIXTURES))
 def test_fixture_is_well_conditioned_and_the_fp32_reference_holds_its_bound(name):
     f, sdp, sdr, b = of.fixture(name)
     e64, e32, dt = of.oracle_pair(sdp, sdr, b)
@@ -67,6 +67,18 @@ def test_fixture_is_well_conditioned_and_the_fp32_reference_holds_its_bound(name
         for k, (r64, r32) in _refs(name, stage).items():
             of.check(k, of.channel_view(k, r32), of.channel_view(k, r64), of.channel_view(k, r32), floor=of.FLOORS[k])
     print(f"{name}: oracle end to end {dt:.1f} s")
+
+
+def test_edge_fixtures_reach_the_trunk_maps_they_are_for():
+    """The fixtures hold every trunk map side from 1 to 5 on both axes, the one-row and the one-column map of the maximum side."""
+    def trunk(n):
+        for _ in range(3):
+            n = (n - 1) // 2 + 1
+        return n
+
+    maps = {(trunk(f["H"]), trunk(f["W"])) for f in of.EDGE_FIXTURES.values()}
+    assert maps >= {(1, 1), (2, 2), (2, 3), (1, 3), (3, 1), (4, 4), (5, 4), (1, 400), (400, 1)}, maps
+    assert not set(of.EDGE_FIXTURES) & set(of.FIXTURES)
 
 
 MIDMID = "k21_n1000_120x160_b2"

@@ -12,8 +12,10 @@ multi-bucket direct kernel; wino.hip WINO_MAXB: the F(4x4,3x3) transforms), past
     own error, per tensor and per worst channel, and 2e-3 of the tensor's scale);
   * two identical passes are bit-identical.
 The native steps at the YCB and LineMOD training shapes and the refiner at the YCB refine mesh size get the same fp64 anchor beside the
-autograd-tape comparisons of test_native_train_gpu.py.  Each test prints its worst ratio of GPU error to fp32-reference error against
-C = 4; measured on the MI355X: small34 1.65, large18 1.63, mixed5 2.60, YCB 2.14, LineMOD 0.76 (its refiner 2.81), YCB refiner 0.05
+autograd-tape comparisons of test_native_train_gpu.py.  Two windows of the smallest crops the step accepts (tiny11: trunk maps of 1 x 1 .. 5 x 4 and
+the 8 x 3200 / 3200 x 8 crops of the maximum side; ones3: 1 x 1 maps only) run the same three checks; they found the pyramid pooling
+adjoint's missed bins (pool_bwd_all_kernel).  Each test prints its worst ratio of GPU error to fp32-reference error against
+C = 4; measured on the MI355X: tiny11 0.06, small34 1.65, large18 1.63, mixed5 2.60, YCB 2.14, LineMOD 0.76 (its refiner 2.81), YCB refiner 0.05
 (a ratio counts the floor as the reference's error where the floor is larger)."""
 import numpy as np
 import pytest
@@ -116,12 +118,55 @@ def test_window_past_the_bucket_chunk_limits(name):
     tr = _trainer("posenet", N, K, sd)
     _window_equals_its_one_frame_passes(tr, frames)
     _window_against_fp64(name, tr, frames, r64, r32)
+    _two_dropout_passes_are_bit_identical(tr, frames)
+
+
+def _two_dropout_passes_are_bit_identical(tr, frames):
     runs = []
     for _ in range(2):
         tr.zero_grad()
         tr.step_posenet_window(frames, 0.015, dropout=True, seed=5)
         runs.append(tr.grad.clone())
     assert torch.equal(runs[0], runs[1]) and float(runs[0].abs().sum()) > 0
+
+
+def test_window_of_the_smallest_crops_and_the_maximum_side():
+    """tiny11: crops of 8 .. 36 pixels (trunk maps of 1 x 1 .. 5 x 4) and the 8 x 3200 / 3200 x 8 crops of the maximum side in one window,
+    N = 70 poses of M = 60 mesh points (the last workgroup of the symmetric loss holds 6 of its 8 poses).  On these maps the pyramid's
+    pooling bins are wider than the map: a pixel of a 1 x 1 map lies in all 36 bins of the 6-bin stage, one of a 2 x 2 map in 3 per axis.
+    pool_bwd_all_kernel searched three candidate bins per axis, complete only for maps of at least 3 pixels per side, and lost the others'
+    gradients (0.38 .. 0.43 relative L2 on the trunk weight gradients of this window in the fp64 emulation of tests/test_oracle_grads.py, 177x
+    the bound and more).  With the exact bin range it prints, on the MI355X, a worst ratio to the fp32 reference's error (C = 4) of 0.06 on
+    the gradients (feat.conv5.weight) and 0.02 on the outputs (new_points)."""
+    K, N, M, sd, objs = og.window("tiny11")
+    sizes = [(o["img"].shape[1], o["img"].shape[2]) for o in objs]
+    maps = {(_trunk(h), _trunk(w)) for h, w in sizes}
+    assert maps >= {(1, 1), (2, 2), (1, 3), (3, 1), (2, 3), (4, 4), (5, 4), (2, 5), (1, 400), (400, 1)} and sizes.count((8, 8)) == 2, maps
+    assert N % (512 // M) != 0 and 512 // M > 1                 # a ragged last group of poses in the symmetric loss
+    assert [i for i, o in enumerate(objs) if o["symmetric"]] == [1, 4, 7, 10]
+    r64, r32 = og.posenet_oracle(sd, objs)
+    frames = _dev_frames(objs)
+    tr = _trainer("posenet", N, K, sd)
+    _window_equals_its_one_frame_passes(tr, frames)
+    _window_against_fp64("tiny11", tr, frames, r64, r32)
+    _two_dropout_passes_are_bit_identical(tr, frames)
+
+
+def test_window_of_one_pixel_trunk_maps_only():
+    """ones3: three 8 x 8 frames, one of them symmetric: every trunk map is 1 x 1, so a defect of the one-pixel map (the pyramid's pooling
+    adjoint above all) cannot hide behind larger frames in the summed gradients: the three-candidate rule moves every trunk gradient of this
+    window by 415x its bound and more (tests/test_oracle_grads.py).  Three frames do not dilute a single flipped ReLU either: with oseed 3100 a
+    conv6 pre-activation lies 1.1e-6 from zero, and the GPU step missed the 1e-4 floor on feat.conv5 / feat.conv6 (3.6e-4 .. 3.9e-4 relative)
+    while every other tensor passed; the fixture now keeps og.point_relu_margin above og.RELU_MARGIN, asserted here."""
+    K, N, M, sd, objs = og.window("ones3")
+    assert all(o["img"].shape[1:] == (8, 8) for o in objs) and [o["symmetric"] for o in objs] == [False, True, False]
+    r64, r32 = og.posenet_oracle(sd, objs)
+    assert og.point_relu_margin(sd, objs, r64) >= og.RELU_MARGIN, "a point-layer ReLU within fp32 rounding of zero -- ill-conditioned fixture"
+    frames = _dev_frames(objs)
+    tr = _trainer("posenet", N, K, sd)
+    _window_equals_its_one_frame_passes(tr, frames)
+    _window_against_fp64("ones3", tr, frames, r64, r32)
+    _two_dropout_passes_are_bit_identical(tr, frames)
 
 
 def test_mixed_window_at_default_splitk_against_fp64():

@@ -36,7 +36,8 @@ def _pair(fn_native, fn_torch, x, tol=1e-5, exact_fwd=False):
     torch.testing.assert_close(xa.grad, xb.grad, rtol=tol, atol=tol)
 
 
-@pytest.mark.parametrize("shape", [(1, 40, 40, 64), (2, 33, 47, 8)])
+@pytest.mark.parametrize("shape", [(1, 40, 40, 64), (2, 33, 47, 8),
+                                   (1, 1, 1, 8), (2, 2, 3, 8), (1, 4, 4, 64)])      # the stem map of an 8 px crop and below: windows mostly padding
 def test_maxpool(shape):
     from densefusion_amd import train_ops as T
     dev = _dev()
@@ -48,7 +49,8 @@ def test_maxpool(shape):
     _pair(T.MaxPool3s2.apply, lambda t: _nhwc(F.max_pool2d(_nchw(t), 3, 2, 1)), xq, exact_fwd=True)
 
 
-@pytest.mark.parametrize("hw", [(20, 20), (10, 15), (7, 5)])
+@pytest.mark.parametrize("hw", [(20, 20), (10, 15), (7, 5),
+                                (1, 1), (2, 2), (1, 3), (2, 5)])      # maps narrower than the 3- and 6-bin stages: a pixel lies in up to 6 bins per axis
 @pytest.mark.parametrize("s", [1, 2, 3, 6])
 def test_adaptive_avgpool(hw, s):
     from densefusion_amd import train_ops as T
@@ -59,7 +61,9 @@ def test_adaptive_avgpool(hw, s):
 
 
 @pytest.mark.parametrize("case", [((6, 6), (20, 20), False), ((1, 1), (10, 15), False), ((3, 3), (7, 5), False),
-                                  ((10, 10), (20, 20), True), ((5, 8), (10, 16), True)])
+                                  ((10, 10), (20, 20), True), ((5, 8), (10, 16), True),
+                                  # one-pixel sources (align_corners on a side of 1) and pyramid stages wider than the map they are read at
+                                  ((1, 1), (2, 2), True), ((1, 2), (2, 4), True), ((6, 6), (1, 1), False), ((6, 6), (2, 3), False)])
 def test_bilinear(case):
     from densefusion_amd import train_ops as T
     (h, w), (oh, ow), align = case
