@@ -76,6 +76,9 @@ SIGNATURES = {
     "df_sigmoid": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     "df_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _i, _f, _vp]),
     "df_preprocess_objects": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "df_cad_frame_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "df_preprocess_objects_cad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _i, _i, _i, _i, _f,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "df_color_jitter": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "df_compose_frame": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "df_conv2d_nhwc": (_i, [ctypes.POINTER(ConvDesc), _vp]),

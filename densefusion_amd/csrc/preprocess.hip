@@ -4,44 +4,13 @@
 // fewer, eval_ycb.py:155-163), back-projection of the chosen depth pixels to a cloud (:165-173) and the
 // ImageNet-normalised crop of the colour image (:175-181, on 0..255-scale values exactly like the reference).
 //
-// RNG contract (the reference uses np.random.shuffle, whose stream cannot be shared with a GPU): every mask
-// pixel gets the key mix32(seed, flat crop index); the num_points pixels with the smallest keys (ties: lower
-// index) are kept, in increasing index order.  Same distribution (a uniformly random subset, order preserved),
-// reproducible from `seed`; the CPU checker of the test suite implements the same contract.
-#include "common.h"
+// Mask compaction and the `choose` rule (steps 1-2, with the RNG contract) live in choose_core.h, shared with cad.hip.
+#include "choose_core.h"
 
 namespace df {
 namespace {
 
-constexpr int PB = 1024;
-
-__device__ __host__ inline unsigned mix32(unsigned seed, unsigned i) {
-  unsigned x = seed ^ (i * 0x9E3779B9u);
-  x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-  return x;
-}
-
-__device__ inline int block_excl_scan(int v, int *s_buf, int &total) {
-  const int tid = threadIdx.x;
-  s_buf[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < PB; d <<= 1) {
-    const int t = tid >= d ? s_buf[tid - d] : 0;
-    __syncthreads();
-    s_buf[tid] += t;
-    __syncthreads();
-  }
-  total = s_buf[PB - 1];
-  const int r = s_buf[tid] - v;
-  __syncthreads();
-  return r;
-}
-
-struct ObjDesc {   // one object: frame index and snapped bounding box (host side: get_bbox, eval_ycb.py:54-90)
-  int frame, itemid, rmin, rmax, cmin, cmax;
-  unsigned seed;
-  int given;         // != 0: this object's row of `choose` was filled in by the caller (chosen indices as an INPUT): step 2 is skipped
-};
+using namespace prep;
 
 // grid = B objects, block = 1024.  rgb [F][IH][IW][3] u8, depth [F][IH][IW] u16, label [F][IH][IW] i32.
 __global__ __launch_bounds__(PB) void preprocess_kernel(const unsigned char *__restrict__ rgb, const unsigned short *__restrict__ depth,
@@ -50,82 +19,18 @@ __global__ __launch_bounds__(PB) void preprocess_kernel(const unsigned char *__r
                                                         float cam_scale, float cloud_div, int *__restrict__ nz_scratch, float *__restrict__ img,
                                                         float *__restrict__ cloud, int64_t *__restrict__ choose,
                                                         int *__restrict__ count_out) {
-  __shared__ int s_scan[PB];
-  __shared__ unsigned s_hist[256];
-  __shared__ unsigned s_prefix, s_remaining;
+  __shared__ ChooseShared s_choose;
   const int b = blockIdx.x, tid = threadIdx.x;
   const ObjDesc o = objs[b];
   const size_t fbase = (size_t)o.frame * IH * IW;
   const int HW = H * W;
-  int *nz = nz_scratch + (size_t)b * HW;
-  const int chunk = (HW + PB - 1) / PB;
-  const int i0 = tid * chunk, i1 = min(HW, i0 + chunk);
   auto in_mask = [&](int i) {
     const int r = o.rmin + i / W, c = o.cmin + i % W;
     const size_t p = fbase + (size_t)r * IW + c;
     return depth[p] != 0 && label[p] == o.itemid;
   };
-  // 1. ordered compaction of the mask pixels (flat crop indices)
-  int cnt = 0;
-  for (int i = i0; i < i1; ++i) cnt += in_mask(i);
-  int total;
-  int off = block_excl_scan(cnt, s_scan, total);
-  for (int i = i0; i < i1; ++i)
-    if (in_mask(i)) nz[off++] = i;
-  if (tid == 0) count_out[b] = total;
-  __syncthreads();
-  // 2. choose
   int64_t *ch = choose + (size_t)b * N;
-  if (o.given) {
-    // the caller's indices (e.g. the subset the reference's np.random.shuffle drew): clamped into the crop, otherwise taken as they are
-    for (int j = tid; j < N; j += PB) { const int64_t v = ch[j]; ch[j] = v < 0 ? 0 : (v >= HW ? HW - 1 : v); }
-  } else if (total == 0) {
-    for (int j = tid; j < N; j += PB) ch[j] = 0;     // detector lost the object; the caller checks count
-  } else if (total <= N) {
-    for (int j = tid; j < N; j += PB) ch[j] = nz[j % total];        // np.pad(..., 'wrap')
-  } else {
-    // radix select of the N-th smallest key (4 rounds of 8 bits)
-    if (tid == 0) { s_prefix = 0; s_remaining = (unsigned)N; }
-    __syncthreads();
-    for (int shift = 24; shift >= 0; shift -= 8) {
-      if (tid < 256) s_hist[tid] = 0;
-      __syncthreads();
-      const unsigned prefix = s_prefix, hmask = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
-      for (int j = tid; j < total; j += PB) {
-        const unsigned k = mix32(o.seed, (unsigned)nz[j]);
-        if ((k & hmask) == prefix) atomicAdd(&s_hist[(k >> shift) & 255], 1u);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        unsigned rem = s_remaining, bin = 0;
-        while (s_hist[bin] < rem) { rem -= s_hist[bin]; ++bin; }
-        s_prefix = prefix | (bin << shift);
-        s_remaining = rem;          // how many keys equal to the final threshold are still to be taken
-      }
-      __syncthreads();
-    }
-    const unsigned T = s_prefix, ties = s_remaining;
-    // keep keys < T, plus the `ties` lowest-index entries with key == T; ordered compaction into choose
-    const int c2 = (total + PB - 1) / PB;
-    const int j0 = tid * c2, j1 = min(total, j0 + c2);
-    int less = 0, eq = 0;
-    for (int j = j0; j < j1; ++j) {
-      const unsigned k = mix32(o.seed, (unsigned)nz[j]);
-      less += k < T; eq += k == T;
-    }
-    int tot_eq, tot_less;
-    int eq_off = block_excl_scan(eq, s_scan, tot_eq);
-    // number of selected entries before this thread's chunk = less-before + min(eq-before, ties)
-    int less_off = block_excl_scan(less, s_scan, tot_less);
-    int out = less_off + min(eq_off, (int)ties);
-    for (int j = j0; j < j1; ++j) {
-      const unsigned k = mix32(o.seed, (unsigned)nz[j]);
-      bool take = k < T;
-      if (k == T) { take = eq_off < (int)ties; ++eq_off; }
-      if (take) ch[out++] = nz[j];
-    }
-  }
-  __syncthreads();
+  choose_pixels(in_mask, o.seed, o.given, HW, N, nz_scratch + (size_t)b * HW, ch, count_out + b, s_choose);
   // 3. cloud from the chosen depth pixels (eval_ycb.py:165-173; xmap = row index, ymap = column index)
   float *cl = cloud + (size_t)b * N * 3;
   for (int j = tid; j < N; j += PB) {

@@ -90,6 +90,85 @@ def preprocess_objects(rgb, depth, label, objects, num_points, cam=YCB_CAM, choo
     return img, cloud, choose, count
 
 
+def _u16(t, what):
+    if t.dtype not in (torch.int16, torch.uint16):
+        raise RuntimeError(f"{what} must be 16-bit")
+    return t.contiguous()
+
+
+def cad_frame_stats(depth, label, label_value=65535):
+    """customCAD frames (``df_cad_frame_stats``): depth, label [F,IH,IW] 16-bit device tensors -> stats [F,6] int32 on the device,
+    ``{depth_max, n_label, rmin, rmax, cmin, cmax}`` per frame: np.max(depth), the number of label pixels and their INCLUSIVE box
+    (get_bbox of datasets/customCAD/dataset.py:247-249); n_label = 0 and a zero box without the label.  No read-back here."""
+    if not (depth.is_cuda and label.is_cuda):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if depth.dim() != 3 or depth.shape != label.shape:
+        raise RuntimeError("cad_frame_stats: depth and label must both be [F,IH,IW]")
+    depth, label = _u16(depth, "cad_frame_stats: depth"), _u16(label, "cad_frame_stats: label")
+    F, IH, IW = depth.shape
+    stats = torch.empty(F, 6, dtype=torch.int32, device=depth.device)
+    with _lib.device_guard(depth.device):
+        st = _lib.lib().df_cad_frame_stats(depth.data_ptr(), label.data_ptr(), F, IH, IW, int(label_value), stats.data_ptr(), _lib.current_stream())
+    _lib.check(st, "cad_frame_stats")
+    return stats
+
+
+def preprocess_objects_cad(rgb, depth, label, objects, num_points, frame_stats, ray_map, p22, p23, add_t=None, cloud_div=10000.0, choose_in=None):
+    """The customCAD counterpart of ``preprocess_objects`` (``df_preprocess_objects_cad``).  rgb [F,IH,IW,3] uint8, depth and label
+    [F,IH,IW] 16-bit, frame_stats [F,6] int32 (``cad_frame_stats``), ray_map [IH,IW,3] float64 -- device tensors; p22, p23: the
+    projection matrix' [2,2] and [2,3]; objects: list of (frame, label_value, (rmin, rmax, cmin, cmax), seed), all boxes of one size;
+    add_t (optional): [B,3] float64, host or device, added to the float32 points in fp64 before the division by ``cloud_div``.
+    Returns img [B,3,H,W], cloud [B,N,3], choose [B,1,N] int64, count [B] int32 (0 = no mask pixel in the box)."""
+    if not (rgb.is_cuda and depth.is_cuda and label.is_cuda and frame_stats.is_cuda and ray_map.is_cuda):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    F, IH, IW, _ = rgb.shape
+    if tuple(depth.shape) != (F, IH, IW) or tuple(label.shape) != (F, IH, IW):
+        raise RuntimeError("preprocess_objects_cad: depth and label must be [F,IH,IW] like rgb")
+    if tuple(frame_stats.shape) != (F, 6) or frame_stats.dtype != torch.int32:
+        raise RuntimeError("preprocess_objects_cad: frame_stats must be [F,6] int32")
+    if tuple(ray_map.shape) != (IH, IW, 3) or ray_map.dtype != torch.float64:
+        raise RuntimeError("preprocess_objects_cad: ray_map must be [IH,IW,3] float64")
+    B = len(objects)
+    H = objects[0][2][1] - objects[0][2][0]
+    W = objects[0][2][3] - objects[0][2][2]
+    desc = np.zeros((B, 8), dtype=np.int32)
+    for i, (frame, label_value, (rmin, rmax, cmin, cmax), seed) in enumerate(objects):
+        if rmax - rmin != H or cmax - cmin != W:
+            raise RuntimeError("preprocess_objects_cad: all boxes of one call must have the same size")
+        if not (0 <= frame < F and 0 <= rmin and rmax <= IH and 0 <= cmin and cmax <= IW):
+            raise RuntimeError("preprocess_objects_cad: box outside the frame")
+        desc[i, :6] = (frame, label_value, rmin, rmax, cmin, cmax)
+        desc[i, 6] = np.array([seed & 0xFFFFFFFF], dtype=np.uint32).view(np.int32)[0]      # uint32 seed bits
+        desc[i, 7] = 1 if choose_in is not None else 0
+    dev = rgb.device
+    d_desc = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
+    if add_t is not None:
+        if not torch.is_tensor(add_t):
+            add_t = torch.from_numpy(np.ascontiguousarray(add_t, dtype=np.float64))
+        if tuple(add_t.shape) != (B, 3) or add_t.dtype != torch.float64:
+            raise RuntimeError("preprocess_objects_cad: add_t must be [B,3] float64")
+        if not add_t.is_cuda:
+            add_t = (add_t if add_t.is_pinned() else add_t.pin_memory()).to(dev, non_blocking=True)
+        add_t = add_t.contiguous()
+    rgb, depth, label = rgb.contiguous(), _u16(depth, "preprocess_objects_cad: depth"), _u16(label, "preprocess_objects_cad: label")
+    scratch = torch.empty(B * H * W, dtype=torch.int32, device=dev)
+    img = torch.empty(B, 3, H, W, device=dev)
+    cloud = torch.empty(B, num_points, 3, device=dev)
+    if choose_in is not None:
+        choose = choose_in.to(device=dev, dtype=torch.int64).reshape(B, 1, num_points).contiguous().clone()
+    else:
+        choose = torch.empty(B, 1, num_points, dtype=torch.int64, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        st = _lib.lib().df_preprocess_objects_cad(rgb.data_ptr(), depth.data_ptr(), label.data_ptr(), F, IH, IW, d_desc.data_ptr(),
+                                                  frame_stats.contiguous().data_ptr(), _lib.dptr(ray_map), float(p22), float(p23),
+                                                  None if add_t is None else add_t.data_ptr(), B, H, W, num_points, float(cloud_div),
+                                                  scratch.data_ptr(), img.data_ptr(), cloud.data_ptr(), choose.data_ptr(), count.data_ptr(),
+                                                  _lib.current_stream())
+    _lib.check(st, "preprocess_objects_cad")
+    return img, cloud, choose, count
+
+
 def color_jitter(frames_u8, plans, out=None):
     """The training colour jitter on the device (``df_color_jitter``): frames_u8 [F,H,W,3] uint8 device tensor, plans [F,8] float32
     (``datasets.augment.plan_row`` rows; host or device).  Returns the jittered uint8 frames, bit-identical to

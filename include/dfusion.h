@@ -256,6 +256,34 @@ int df_preprocess_objects(const unsigned char *rgb, const unsigned short *depth,
                           int64_t *choose_out, int *count_out, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Input preparation for the customCAD dataset (Unity renders: datasets/customCAD/dataset.py:109-166,205 and
+ * project_unity_depth.py:42-51 of the reference).  Same conventions as df_preprocess_objects: no allocation, no synchronisation,
+ * the caller's stream.
+ *
+ * df_cad_frame_stats: depth, label [F][IH][IW] u16 -> stats [F][6] int32 = {depth_max, n_label, rmin, rmax, cmin, cmax}:
+ *   the frame's largest depth value (np.max(depth), :120,132), the number of pixels with label == label_value and the INCLUSIVE
+ *   smallest / largest row and column of those pixels (get_bbox, :247-249; the loader slices [rmin:rmax, cmin:cmax], leaving
+ *   the last row and column out).  A frame without the label gets n_label = 0 and a zero box.  The call initialises stats on the
+ *   stream; integer reductions only, and a frame's row does not depend on the other frames of the call.  F <= 65535, IH*IW <= 2^30.
+ * df_preprocess_objects_cad: B objects of one crop size (H x W) per call.
+ *   rgb [F][IH][IW][3] u8, depth and label [F][IH][IW] u16;
+ *   obj_desc [B][8] int32 = {frame, label_value, rmin, rmax, cmin, cmax, seed, given} as for df_preprocess_objects (an object
+ *   whose box leaves its frame comes back with count 0); frame_stats [F][6] (device; only depth_max is read, so the two calls
+ *   need no host round trip between them); ray_map [IH][IW][3] double (device): the view ray through every pixel, scaled to
+ *   z = 1; p22, p23: the projection matrix' [2][2] and [2][3]; add_t [B][3] double (device) or NULL; scratch: B*H*W int32.
+ *   mask = (label == label_value) & (depth != depth_max[frame]) (:120-124); choose / count_out: the contract of df_preprocess_objects;
+ *   cloud (all in fp64, one rounding per operation, no fused multiply-add -- bit-equal to numpy):
+ *     z = -p23 / (p22 + (1 - d / 65534)); point = (float)(ray_map[r][c][k] * z); with add_t: point = (float)((double)point + add_t[k]);
+ *     cloud = point / cloud_div in fp32 (the loader passes 10000);
+ *   img: the crop with (130, 130, 130) where depth == depth_max (:97,132), then ((float)px - mean) / std into CHW. */
+int df_cad_frame_stats(const unsigned short *depth, const unsigned short *label, int num_frames, int IH, int IW, int label_value,
+                       int *stats, df_stream_t stream);
+int df_preprocess_objects_cad(const unsigned char *rgb, const unsigned short *depth, const unsigned short *label, int num_frames,
+                              int IH, int IW, const int *obj_desc, const int *frame_stats, const double *ray_map, double p22,
+                              double p23, const double *add_t, int B, int H, int W, int num_points, float cloud_div, int *scratch,
+                              float *img_out, float *cloud_out, int64_t *choose_out, int *count_out, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-time pixel augmentation on whole uint8 frames, bit-identical to the host path (densefusion_amd/datasets/augment.py over PIL;
  * datasets/ycb/dataset.py).  Same conventions as df_preprocess_objects: no allocation, no synchronisation, the caller's stream.
  *

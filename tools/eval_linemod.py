@@ -47,11 +47,12 @@ def build_parser():
     return ap
 
 
-def evaluate(testdataset, estimator, refiner, diameter, opt, fw=None):
+def evaluate(testdataset, estimator, refiner, diameter, opt, fw=None, on_pose=None):
     """The loop of tools/eval_linemod.py:68-139; returns (success_count, num_count) per object.  Frames are taken ``--window`` at
     a time: the crops of a window are bucketed by size and run through PoseNet -> arg-max pose -> refine loop as ONE device
     call (``estimate_multi``), the ADD / ADD-S distances of the window as one ``add_metric`` launch; the log lines come out in
-    frame order and do not depend on the window (per-object results are bit-identical to frame-by-frame calls)."""
+    frame order and do not depend on the window (per-object results are bit-identical to frame-by-frame calls).
+    ``on_pose(i, pose [7], model_points [M,3], target [M,3])``, if given, sees every live frame's refined pose and the clouds it is scored on."""
     num_objects = len(diameter)
     pe = PoseEstimator(estimator, refiner)
     sym_list = testdataset.get_sym_list()
@@ -82,6 +83,9 @@ def evaluate(testdataset, estimator, refiner, diameter, opt, fw=None):
             objs = [int(live[k][1][5].reshape(-1)[0]) for k in order]
             dis = add_metric(pose, model_points, target, [1 if o in sym_list else 0 for o in objs]).cpu().tolist()
             dist = {live[k][0]: (objs[j], dis[j]) for j, k in enumerate(order)}
+            if on_pose is not None:
+                for j, k in enumerate(order):
+                    on_pose(live[k][0], pose[j], model_points[j], target[j])
         for i, it in items:
             if i not in dist:
                 say("No.{0} NOT Pass! Lost detection!".format(i))

@@ -12,7 +12,8 @@ xGMI): every rank trains on its own shard of the frame list, gradients live in O
 (85.8 MB for PoseNet, 7.8 MB for the refiner) that is summed with ONE all-reduce per optimizer step; nothing
 else is communicated.  Launch: ``python -m torch.distributed.run --nproc-per-node N tools/train.py ...``.
 
-``--dataset synthetic`` trains on seeded synthetic frames (no dataset ships offline); ``ycb`` / ``linemod`` use the built-in
+``--dataset synthetic`` trains on seeded synthetic frames (no dataset ships offline); ``ycb`` / ``linemod`` / ``cad`` (the reference
+fork's customCAD set and its own default: 5 objects, 500 points) use the built-in
 loaders (``densefusion_amd.datasets``: the reference's constructor, file layout, 6-tuple and training augmentation -- colour jitter,
 occluders, synthetic frames over real backgrounds, pose-translation noise -- with the crop / sampling / back-projection on the
 device and the decode in worker processes); ``--reference_loaders`` imports ``datasets.<name>.dataset.PoseDataset`` from the
@@ -65,7 +66,7 @@ class SyntheticPoseDataset(torch.utils.data.Dataset):
 
 def build_parser():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dataset", type=str, default="synthetic", help="synthetic | ycb | linemod")
+    ap.add_argument("--dataset", type=str, default="synthetic", help="synthetic | ycb | linemod | cad")
     ap.add_argument("--dataset_root", type=str, default="")
     ap.add_argument("--dataset_config_dir", type=str, default="datasets/ycb/dataset_config",
                     help="ycb: the directory of classes.txt / train_data_list.txt / test_data_list.txt (the reference keeps them in its tree)")
@@ -133,11 +134,11 @@ def make_datasets(opt):
         tr = SyntheticPoseDataset("train", opt.num_points, opt.num_objects, opt.synthetic_train_frames)
         te = SyntheticPoseDataset("test", opt.num_points, opt.num_objects, opt.synthetic_test_frames)
         return tr, te
-    if opt.dataset not in ("ycb", "linemod"):
+    if opt.dataset not in ("ycb", "linemod", "cad"):
         raise SystemExit("Unknown dataset")
-    opt.num_objects, opt.num_points = (21, 1000) if opt.dataset == "ycb" else (13, 500)
+    opt.num_objects, opt.num_points = {"ycb": (21, 1000), "linemod": (13, 500), "cad": (5, 500)}[opt.dataset]      # tools/train.py:57-73 of the reference
     if opt.reference_loaders:        # the reference's own loaders from the PYTHONPATH (host-side preparation, its DataLoader semantics)
-        PoseDataset = __import__("datasets.%s.dataset" % opt.dataset, fromlist=["PoseDataset"]).PoseDataset
+        PoseDataset = __import__("datasets.%s.dataset" % {"cad": "customCAD"}.get(opt.dataset, opt.dataset), fromlist=["PoseDataset"]).PoseDataset
         if opt.jitter != "host":
             logging.getLogger("train").info("--jitter %s ignored: the reference's loaders jitter on the host", opt.jitter)
         return (PoseDataset("train", opt.num_points, True, opt.dataset_root, opt.noise_trans, opt.refine_start),
@@ -145,6 +146,8 @@ def make_datasets(opt):
     # built-in loaders: the reference's constructor arguments (tools/train.py:57-66: augmentation on for the training set)
     if opt.dataset == "ycb":
         from densefusion_amd.datasets.ycb.dataset import PoseDataset
+    elif opt.dataset == "cad":
+        from densefusion_amd.datasets.customCAD.dataset import PoseDataset
     else:
         from densefusion_amd.datasets.linemod.dataset import PoseDataset
     logging.getLogger("train").info("datasets.%s: the built-in loader (device-side preparation; training augmentation on, noise_trans %g, colour jitter on the %s)",
