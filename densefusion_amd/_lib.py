@@ -79,6 +79,9 @@ SIGNATURES = {
     "df_cad_frame_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "df_preprocess_objects_cad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _i, _i, _i, _i, _f,
                                        _vp, _vp, _vp, _vp, _vp, _vp]),
+    "df_cad_render_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "df_cad_render": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_double, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                           ctypes.c_size_t, _vp]),
     "df_color_jitter": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "df_compose_frame": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "df_conv2d_nhwc": (_i, [ctypes.POINTER(ConvDesc), _vp]),

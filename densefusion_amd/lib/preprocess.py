@@ -169,6 +169,62 @@ def preprocess_objects_cad(rgb, depth, label, objects, num_points, frame_stats, 
     return img, cloud, choose, count
 
 
+def cad_render(points, normals, colors, pose, model_scale, proj, image_dims, holes=None, splat=0, mask_mode=0, scratch=None):
+    """F views of a coloured cloud as customCAD frames (``df_cad_render``; the contract is its comment in include/dfusion.h).
+    points [P,3] float32, normals [P,3] float32 or None, colors [P,3] uint8 -- device tensors; pose [F,3,4] / [F,12] float64 [R|t] into
+    camera space, host or device; proj: the 4 x 4 projection matrix (host); image_dims = (rows, columns); holes: None or HOST
+    (hole_idx [F,K] int32 with -1 = none, hole_r [F,K] float64); mask_mode 0 = box, 1 = pixels; scratch: an optional uint8 device
+    tensor of at least ``df_cad_render_scratch_bytes`` to reuse between calls.
+    Returns rgb [F,IH,IW,3] uint8, depth and mask [F,IH,IW] uint16, stats [F,6] int32 on the device; no read-back, no synchronisation."""
+    if not (points.is_cuda and colors.is_cuda and (normals is None or normals.is_cuda)):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise RuntimeError("cad_render: points must be [P,3] float32")
+    P = points.shape[0]
+    if tuple(colors.shape) != (P, 3) or colors.dtype != torch.uint8:
+        raise RuntimeError("cad_render: colors must be [P,3] uint8")
+    if normals is not None and (tuple(normals.shape) != (P, 3) or normals.dtype != torch.float32):
+        raise RuntimeError("cad_render: normals must be [P,3] float32")
+    dev = points.device
+    if not torch.is_tensor(pose):
+        pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
+    if pose.dtype != torch.float64 or pose.dim() not in (2, 3) or pose.numel() != pose.shape[0] * 12:
+        raise RuntimeError("cad_render: pose must be [F,3,4] float64")
+    F = pose.shape[0]
+    if not pose.is_cuda:
+        pose = (pose if pose.is_pinned() else pose.pin_memory()).to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
+    pose = pose.contiguous()
+    IH, IW = int(image_dims[0]), int(image_dims[1])
+    proj = np.ascontiguousarray(proj, dtype=np.float64)
+    if proj.shape != (4, 4):
+        raise RuntimeError("cad_render: proj must be 4 x 4")
+    K, hole_idx, hole_r = 0, None, None
+    if holes is not None:
+        hole_idx, hole_r = np.ascontiguousarray(holes[0], dtype=np.int32), np.ascontiguousarray(holes[1], dtype=np.float64)
+        if hole_idx.ndim != 2 or hole_idx.shape[0] != F or hole_r.shape != hole_idx.shape:
+            raise RuntimeError("cad_render: holes must be (hole_idx [F,K], hole_r [F,K])")
+        K = hole_idx.shape[1]
+    L = _lib.lib()
+    need = L.df_cad_render_scratch_bytes(F, IH, IW)
+    if need == 0:
+        raise RuntimeError(f"cad_render: bad sizes F={F}, IH={IH}, IW={IW}")
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < need:
+        raise RuntimeError(f"cad_render: scratch must be a uint8 device tensor of at least {need} bytes")
+    rgb = torch.empty(F, IH, IW, 3, dtype=torch.uint8, device=dev)
+    depth = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    mask = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    stats = torch.empty(F, 6, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        st = L.df_cad_render(_lib.dptr(points), None if normals is None else _lib.dptr(normals), _lib.dptr(colors), P, pose.data_ptr(),
+                             float(model_scale), hole_idx.ctypes.data if K else None, hole_r.ctypes.data if K else None, K,
+                             proj.ctypes.data, F, IH, IW, int(splat), int(mask_mode), rgb.data_ptr(), depth.data_ptr(), mask.data_ptr(),
+                             stats.data_ptr(), scratch.data_ptr(), scratch.numel(), _lib.current_stream())
+    _lib.check(st, "cad_render")
+    return rgb, depth, mask, stats
+
+
 def color_jitter(frames_u8, plans, out=None):
     """The training colour jitter on the device (``df_color_jitter``): frames_u8 [F,H,W,3] uint8 device tensor, plans [F,8] float32
     (``datasets.augment.plan_row`` rows; host or device).  Returns the jittered uint8 frames, bit-identical to

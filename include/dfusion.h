@@ -284,6 +284,50 @@ int df_preprocess_objects_cad(const unsigned char *rgb, const unsigned short *de
                               float *img_out, float *cloud_out, int64_t *choose_out, int *count_out, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point-cloud renderer for customCAD training sets: F views of a coloured CAD cloud as the frames the customCAD loader reads (8-bit
+ * colour, Unity's 16-bit depth, 16-bit mask) -- the job of datasets/customCAD/cad_to_dataset.py:137-243 and mask_generator.py:20-28 of
+ * the reference without open3d, OpenCV or Unity.  No allocation, no synchronisation, the caller's stream; integer atomics only, so the
+ * outputs are bit-reproducible; a frame's outputs do not depend on the other frames of the call.
+ *
+ * df_cad_render_scratch_bytes: F*IH*IW 64-bit keys; 0 for sizes the call refuses (F 1..65535, IH*IW 1..2^30).
+ * df_cad_render:
+ *   DEVICE: points [P][3] float (model file units), normals [P][3] float or NULL (no facing test), colors [P][3] u8,
+ *   pose [F][12] double, row-major [R|t] into camera space (x right, y up, the camera looks along -z), the outputs, scratch (8-byte
+ *   aligned).  HOST, read during the call: proj, 16 doubles row-major, and hole_idx / hole_r [F][K] (NULL when K == 0, K <= 128; they
+ *   reach the kernel as launch arguments, 128 records a launch).
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer, bad sizes, splat outside 0..3, mask_mode outside 0..1, a
+ *   short scratch, a hole index >= P, and a proj whose row 2 is not (0, 0, p22, p23) or whose row 3 is not (0, 0, -1, 0) -- the
+ *   loader's inverse (project_unity_depth.py:42-51) assumes that form.
+ *   Per frame f and point i, all in fp64, one rounding per operation (no fused multiply-add), in exactly this order:
+ *   1. m = (double)points[i].  The point is removed when for some k with h = hole_idx[f][k] >= 0 and c = (double)points[h],
+ *      r = hole_r[f][k]:  ((mx-cx)^2 + (my-cy)^2) + (mz-cz)^2 <= r*r  (radius 0 removes the centre and its exact duplicates);
+ *      the job of augment_pointcloud, :137-164.
+ *   2. s = m * model_scale;  X_j = ((R[j][0]*s_x + R[j][1]*s_y) + R[j][2]*s_z) + t[j].
+ *   3. With normals: n'_j = (R[j][0]*n_x + R[j][1]*n_y) + R[j][2]*n_z; the point is kept only when
+ *      ((n'_x*(-X_x) + n'_y*(-X_y)) + n'_z*(-X_z)) > 0: the point's own view ray (the reference, :175-176, tests against the direction
+ *      to the cloud's centroid, which would need an order-dependent floating-point reduction).
+ *   4. c_j = ((P[j][0]*X_x + P[j][1]*X_y) + P[j][2]*X_z) + P[j][3] for j = 0, 1, 3; dropped unless c_3 > 0;
+ *      ndc_x = c_0 / c_3, ndc_y = c_1 / c_3.
+ *   5. code = rint(65534 * ((1 + p22) + p23 / X_z)), ties to even; dropped unless 0 <= code <= 65534.  The exact inverse of the
+ *      loader's z = -p23 / (p22 + (1 - d / 65534)); nearer points get smaller codes.
+ *   6. col = floor(((ndc_x + 1) * IW) * 0.5 + 0.5), row = floor(((1 - ndc_y) * IH) * 0.5 + 0.5): the nearest node of the loader's
+ *      ray grid, whose ray for pixel (r, c) passes through ndc (-1 + 2c/IW, 1 - 2r/IH).  The footprint is the (2*splat+1)^2 square
+ *      around it; each of its pixels is tested against the frame on its own.
+ *   7. Every footprint pixel takes atomicMin of key = (uint64)code << 32 | i: the nearest point wins, equal codes go to the lowest
+ *      index, and depth and colour share the winner (the reference's assignment at :223-236 gives the colour to the farthest point).
+ *   Resolve, per pixel: covered -> depth = code, rgb = colors[winner]; uncovered -> depth = 65535 (strictly above every code: the
+ *   loader's `depth != np.max(depth)` and its grey fill see a horizon) and rgb = (130, 130, 130).
+ *   stats [F][6] int32 = {covered pixels, points that reached the z-buffer (each once), rmin, rmax, cmin, cmax}: the INCLUSIVE box of
+ *   the covered pixels; all six zero when nothing is covered.
+ *   mask: mode 0 (box) 65535 on rows rmin..rmax-1 and columns cmin..cmax-1 -- the half-open slice of the inclusive box that
+ *   mask_generator.py:21-28 writes, mirrored as it is; mode 1 (pixels) 65535 on the covered pixels; 0 elsewhere. */
+size_t df_cad_render_scratch_bytes(int F, int IH, int IW);
+int df_cad_render(const float *points, const float *normals, const unsigned char *colors, int P, const double *pose, double model_scale,
+                  const int *hole_idx, const double *hole_r, int K, const double *proj, int F, int IH, int IW, int splat, int mask_mode,
+                  unsigned char *rgb_out, unsigned short *depth_out, unsigned short *mask_out, int *stats_out, void *scratch,
+                  size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-time pixel augmentation on whole uint8 frames, bit-identical to the host path (densefusion_amd/datasets/augment.py over PIL;
  * datasets/ycb/dataset.py).  Same conventions as df_preprocess_objects: no allocation, no synchronisation, the caller's stream.
  *

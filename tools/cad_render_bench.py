@@ -1,0 +1,73 @@
+#!/usr/bin/env python
+"""Device time per frame of ``df_cad_render`` (HIP events, the median of ``--calls`` calls after one warm-up) on a fabricated sphere
+cloud, and with ``--cpu`` the time per frame of the numpy restatement (tests/cad_render_np.py) on this machine's CPU.  One JSON line.
+
+    python tools/cad_render_bench.py --points 1000000 --height 520 --width 1109 --splat 1 --chunk 32 [--cpu]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from densefusion_amd.datasets.customCAD import render as cr  # noqa: E402
+
+PROJ = [[1.16667, 0.0, 0.0, 0.0], [0.0, 2.48814, 0.0, 0.0], [0.0, 0.0, 0.5, 3000.0], [0.0, 0.0, -1.0, 0.0]]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=1000000)
+    ap.add_argument("--height", type=int, default=520)
+    ap.add_argument("--width", type=int, default=1109)
+    ap.add_argument("--splat", type=int, default=1)
+    ap.add_argument("--chunk", type=int, default=32)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--cpu", action="store_true", help="also time the numpy restatement on one frame")
+    opt = ap.parse_args(argv)
+    rng = np.random.default_rng(0)
+    d = rng.normal(size=(opt.points, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    pts, nrm, col = (d * 60.0).astype(np.float32), d.astype(np.float32), rng.integers(0, 256, (opt.points, 3), dtype=np.uint8)
+    poses, holes = [], []
+    for s in range(opt.chunk):
+        axis, angle, xyz, hs = cr.sample_view(s, opt.points, (0.0, 0.0, 4.0), 1.0, hole_mean=30.0, hole_std=10.0)
+        R, t = cr.view_pose(axis, angle, xyz, np.zeros(3), 10.0)
+        poses.append(np.concatenate([R, t[:, None]], axis=1)); holes.append(hs)
+    poses = np.stack(poses)
+    renderer = cr.CadRenderer(pts, nrm, col, PROJ, (opt.height, opt.width))
+    times = []
+    for k in range(opt.calls + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = renderer.render(poses, holes=holes, splat=opt.splat, mask="box")
+        e1.record()
+        torch.cuda.synchronize()
+        if k:
+            times.append(e0.elapsed_time(e1))
+    stats = out[3].cpu().numpy()
+    res = {"points": opt.points, "frame": [opt.height, opt.width], "splat": opt.splat, "chunk": opt.chunk,
+           "device_ms_per_frame_median": float(np.median(times)) / opt.chunk, "device_ms_per_call": [round(t, 3) for t in times],
+           "covered_mean": float(stats[:, 0].mean()), "points_reaching_mean": float(stats[:, 1].mean())}
+    if opt.cpu:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import cad_render_np as rnp
+        idx, rad = cr.CadRenderer.pack_holes(holes, opt.chunk) or (None, None)
+        t0 = time.time()
+        want = rnp.render_frame(pts, nrm, col, poses[0], 10.0, None if idx is None else idx[0], None if rad is None else rad[0], PROJ,
+                                opt.height, opt.width, opt.splat, 0)
+        res["numpy_ms_per_frame"] = (time.time() - t0) * 1e3
+        res["frame0_equal"] = bool(all(np.array_equal(o[0].cpu().numpy(), w) for o, w in zip(out, want[:4])))
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()

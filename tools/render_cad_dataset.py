@@ -1,0 +1,168 @@
+#!/usr/bin/env python
+"""Render a customCAD training set from a coloured CAD cloud on the device -- no Unity, open3d or OpenCV.
+
+    python tools/render_cad_dataset.py --model M.ply --output_root ROOT [--object 1 --frames 2000]
+
+writes the tree ``tools/train.py --dataset cad`` and ``tools/eval_cad.py`` read (datasets/customCAD/dataset.py of the reference):
+``ROOT/data/XX/{train,test}.txt``, ``rgb/FrameBuffer_NNNN.png``, ``depth/Depth_NNNN.png``, ``mask/NNNN.png``, ``meta/transforms.txt``,
+``meta/proj_mat.txt`` and ``ROOT/models/obj_XX.ply``.  It does the jobs of the reference's cad_to_dataset.py (views drawn per seed, :264-276;
+holes, :145-160; views with too few pixels skipped, :219-221), mask_generator.py (:21-28) and train_test_generator.py (:17-28).
+
+Views are drawn seed by seed from ``--seed`` on (``render.sample_view``) and rendered ``--chunk`` at a time by ``df_cad_render``; a view
+with fewer than ``--min_pixels`` covered pixels is skipped and the next seed is tried, accepted frames are numbered consecutively.  Every
+pose is first written as its ``transforms.txt`` record (``repr`` precision) and parsed back, and the frame is rendered from the parsed
+values: images and records agree exactly.  Record k + 1 holds frame k (the loader looks up ``index + 1``); record 0 repeats record 1.
+Hole radii are in model file units (the reference's 0.03 / 0.01 apply to a model scaled by 0.001).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import random
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+from PIL import Image
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from densefusion_amd.datasets.customCAD import render as cr  # noqa: E402
+from densefusion_amd.datasets.customCAD.project_unity_depth import read_proj_mat  # noqa: E402
+
+# the reference's shipped dataset_processed/data/01/meta/proj_mat.txt and its 520 x 1109 frames (dataset.py:99)
+DEFAULT_PROJ = [[1.16667, 0.0, 0.0, 0.0], [0.0, 2.48814, 0.0, 0.0], [0.0, 0.0, 0.5, 3000.0], [0.0, 0.0, -1.0, 0.0]]
+
+
+def build_parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", type=str, required=True, help="PLY with red / green / blue (and optionally nx / ny / nz) vertex properties; cloud or mesh")
+    ap.add_argument("--output_root", type=str, required=True)
+    ap.add_argument("--object", type=int, default=1, help="object directory data/XX and models/obj_XX.ply")
+    ap.add_argument("--frames", type=int, default=2000)
+    ap.add_argument("--proj_mat", type=str, default=None, help="a proj_mat.txt (four tab-separated lines); default: the reference's shipped matrix")
+    ap.add_argument("--height", type=int, default=520)
+    ap.add_argument("--width", type=int, default=1109)
+    ap.add_argument("--center", type=float, nargs=3, default=[0.0, 0.0, 4.0], help="mean position in the units of transforms.txt")
+    ap.add_argument("--scene_scale", type=float, default=1.0)
+    ap.add_argument("--model_scale", type=float, default=10.0, help="the loader's `model * 10`")
+    ap.add_argument("--min_pixels", type=int, default=500)
+    ap.add_argument("--splat", type=int, default=1)
+    ap.add_argument("--mask", type=str, default="box", choices=sorted(cr.MASK_MODES))
+    ap.add_argument("--points", type=int, default=0, help="points to draw from a mesh (default 1 000 000) or to keep of a cloud (default all)")
+    ap.add_argument("--max_holes", type=int, default=3)
+    ap.add_argument("--hole_mean", type=float, default=30.0, help="model file units")
+    ap.add_argument("--hole_std", type=float, default=10.0)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--chunk", type=int, default=32, help="views per device call")
+    ap.add_argument("--max_skipped", type=int, default=100000, help="give up after this many skipped views")
+    return ap
+
+
+def record_text(index, pos, quat):
+    """One ``transforms.txt`` record in the generator's format: index / (x, y, z) / (x, y, z, w)."""
+    return "%d\n(%s)\n(%s)\n" % (index, ", ".join(repr(float(v)) for v in pos), ", ".join(repr(float(v)) for v in quat))
+
+
+def parse_record(text):
+    """(pos, quat) of one record, token by token like the loader's ``parse_transforms``."""
+    lines = text.split("\n")
+    return tuple(np.array([float(x.rstrip()) for x in ln.replace("(", "").replace(")", "").replace(",", "").split(" ")]) for ln in lines[1:3])
+
+
+def write_vertex_ply(path, pts):
+    pts = np.ascontiguousarray(pts, dtype="<f4").reshape(-1, 3)
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\ncomment rendered by densefusion_amd\nelement vertex %d\nproperty float x\n"
+                 "property float y\nproperty float z\nend_header\n" % len(pts)).encode("ascii"))
+        f.write(pts.tobytes())
+
+
+def load_model(path, n_points):
+    pts, nrm, col = cr.read_colored_ply(path, n_points=n_points if n_points > 0 else 1000000)
+    if 0 < n_points < len(pts):                      # a cloud with more vertices than asked for
+        keep = np.sort(np.random.choice(len(pts), n_points, replace=False))
+        pts, col, nrm = pts[keep], col[keep], None if nrm is None else nrm[keep]
+    return pts, nrm, col
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("render_cad_dataset needs a GPU (no CPU path)")
+    np.random.seed(opt.seed)
+    pts, nrm, col = load_model(opt.model, opt.points)
+    proj = read_proj_mat(opt.proj_mat) if opt.proj_mat else np.array(DEFAULT_PROJ)
+    sub = os.path.join(opt.output_root, "data", "%02d" % opt.object)
+    for d in ("rgb", "depth", "mask", "meta"):
+        os.makedirs(os.path.join(sub, d), exist_ok=True)
+    os.makedirs(os.path.join(opt.output_root, "models"), exist_ok=True)
+    write_vertex_ply(os.path.join(opt.output_root, "models", "obj_%02d.ply" % opt.object), pts)
+    with open(os.path.join(sub, "meta", "proj_mat.txt"), "w") as f:
+        f.write("".join("\t".join(repr(float(v)) for v in row) + "\n" for row in proj) + "\n")
+    proj = read_proj_mat(os.path.join(sub, "meta", "proj_mat.txt"))          # what the loader will read
+    renderer = cr.CadRenderer(pts, nrm, col, proj, (opt.height, opt.width), model_scale=opt.model_scale)
+    centroid = pts.astype(np.float64).mean(axis=0)
+
+    def save(n, rgb, depth, mask):
+        Image.fromarray(rgb).save(os.path.join(sub, "rgb", "FrameBuffer_%04d.png" % n))
+        Image.fromarray(depth).save(os.path.join(sub, "depth", "Depth_%04d.png" % n))
+        Image.fromarray(mask).save(os.path.join(sub, "mask", "%04d.png" % n))
+
+    records, written, skipped, seed, device_ms = [], 0, 0, opt.seed, []
+    t_start = time.time()
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        pending = []
+        while written < opt.frames:
+            if skipped > opt.max_skipped:
+                raise SystemExit(f"{skipped} views skipped for fewer than {opt.min_pixels} pixels: check --center, --scene_scale and the camera")
+            texts, poses, holes = [], [], []
+            for s in range(seed, seed + opt.chunk):
+                axis, angle, xyz, hs = cr.sample_view(s, len(pts), opt.center, opt.scene_scale, opt.max_holes, hole_mean=opt.hole_mean,
+                                                      hole_std=opt.hole_std)
+                text = record_text(0, *cr.pose_to_transform(*cr.view_pose(axis, angle, xyz, centroid, opt.model_scale)))
+                R, t = cr.transform_to_pose(*parse_record(text))              # rendered from the record's own values
+                texts.append(text); holes.append(hs)
+                poses.append(np.concatenate([R, t[:, None]], axis=1))
+            seed += opt.chunk
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, splat=opt.splat, mask=opt.mask)
+            ev1.record()
+            rows = stats.cpu().numpy()                                        # the chunk's one read-back before its frames
+            device_ms.append(ev0.elapsed_time(ev1))
+            rgb, depth, mask = rgb.cpu().numpy(), depth.cpu().numpy(), mask.cpu().numpy()
+            for k in range(opt.chunk):
+                if written == opt.frames:
+                    break
+                if rows[k, 0] < opt.min_pixels:
+                    skipped += 1
+                    continue
+                pos, quat = parse_record(texts[k])
+                records.append((pos, quat))
+                pending.append(pool.submit(save, written, rgb[k], depth[k], mask[k]))
+                written += 1
+            for p in pending:
+                p.result()
+            pending = []
+    with open(os.path.join(sub, "meta", "transforms.txt"), "w") as f:
+        for idx, (pos, quat) in enumerate([records[0]] + records):
+            f.write(record_text(idx, pos, quat))
+    nums = list(range(written))
+    random.seed(opt.seed)
+    random.shuffle(nums)
+    cut = int(len(nums) / 100. * 80)
+    for name, part in (("train.txt", nums[:cut]), ("test.txt", nums[cut:])):
+        with open(os.path.join(sub, name), "w") as f:
+            f.write("".join("%d\n" % n for n in part))
+    wall = time.time() - t_start
+    per_view = float(np.median(device_ms)) / opt.chunk            # the median call: the first one also loads the kernels
+    print(f"frames written: {written}, views skipped: {skipped}, device time per rendered view: {per_view:.3f} ms "
+          f"(HIP events, the median of {len(device_ms)} calls; {len(pts)} points, {opt.height} x {opt.width}, splat {opt.splat}, chunk {opt.chunk}); "
+          f"wall {wall / max(written, 1) * 1e3:.1f} ms per frame written")
+    return {"written": written, "skipped": skipped, "device_ms_per_view": per_view}
+
+
+if __name__ == "__main__":
+    main()
