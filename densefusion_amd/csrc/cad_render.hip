@@ -6,32 +6,14 @@
 // Four steps on the caller's stream: the keys are set to all-ones; splat_kernel takes atomicMin of (code << 32 | point index) over every
 // footprint pixel (grid = point blocks x frames); resolve_kernel turns keys into depth / colour and reduces count and box per wave before
 // its integer atomics, like frame_stats_kernel of cad.hip (finish_kernel then decodes the F rows in place); mask_kernel fills the mask.
-#include "common.h"
+#include "cad_frame.h"
 
 namespace df {
 namespace {
 
-constexpr int RB = 256;                 // threads per block, every kernel here
 constexpr int SPLAT_MAX_BLOCKS = 256;   // point blocks per frame: the threads stride over the rest
-constexpr int RESOLVE_MAX_BLOCKS = 64;  // pixel blocks per frame in the resolve pass
-constexpr unsigned long long NO_KEY = ~0ull;
 
-constexpr int MAX_HOLES = 128;          // hole records per splat launch (and the largest K): they travel as kernel arguments
-
-struct Camera {
-  double p0[4], p1[4], p3[4];           // rows 0, 1 and 3 of the projection matrix
-  double p22, p23;
-};
-
-// The holes of the frames of one splat launch, [frame - f0][K]: the host arrays are checked on the host and reach the device by value, so
-// the call neither copies from pageable memory nor allocates.
-struct Holes {
-  double r[MAX_HOLES];
-  int idx[MAX_HOLES];
-};
-
-// While the blocks reduce, stats[f] = {covered, points, max(IH - row), max(row + 1), max(IW - col), max(col + 1)}: maxima only, so that
-// zero means "nothing seen"; finish_kernel decodes the row.
+// stats[f][1] counts the points that reached the z-buffer (the row while the blocks reduce: reduce_frame_stats, cad_frame.h)
 __global__ __launch_bounds__(RB) void splat_kernel(const float *__restrict__ points, const float *__restrict__ normals, int P,
                                                    const double *__restrict__ pose, double model_scale, Holes holes, int K, int f0,
                                                    Camera cam, int IH, int IW, int splat, unsigned long long *__restrict__ keys,
@@ -119,51 +101,8 @@ __global__ __launch_bounds__(RB) void resolve_kernel(const unsigned long long *_
     a_r = max(a_r, IH - r); b_r = max(b_r, r + 1);
     a_c = max(a_c, IW - q); b_c = max(b_c, q + 1);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off, 64);
-    a_r = max(a_r, __shfl_down(a_r, off, 64)); b_r = max(b_r, __shfl_down(b_r, off, 64));
-    a_c = max(a_c, __shfl_down(a_c, off, 64)); b_c = max(b_c, __shfl_down(b_c, off, 64));
-  }
-  if ((threadIdx.x & 63) == 0 && cnt) {
-    int *s = stats + (size_t)f * 6;
-    atomicAdd(&s[0], cnt);
-    atomicMax(&s[2], a_r); atomicMax(&s[3], b_r); atomicMax(&s[4], a_c); atomicMax(&s[5], b_c);
-  }
+  reduce_frame_stats(cnt, a_r, b_r, a_c, b_c, stats + (size_t)f * 6);
 }
-
-// {covered, points, rmin, rmax, cmin, cmax}, the box inclusive; all six zero when nothing is covered (a point that reached the z-buffer
-// covers at least one pixel, so `points` is zero then already)
-__global__ void finish_kernel(int F, int IH, int IW, int *__restrict__ stats) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  int *s = stats + (size_t)f * 6;
-  if (s[0] == 0) { s[1] = s[2] = s[3] = s[4] = s[5] = 0; return; }
-  s[2] = IH - s[2]; s[3] = s[3] - 1; s[4] = IW - s[4]; s[5] = s[5] - 1;
-}
-
-// mode 0: the half-open slice [rmin:rmax, cmin:cmax] of the inclusive box (mask_generator.py:21-28); mode 1: the covered pixels
-__global__ __launch_bounds__(RB) void mask_kernel(const unsigned short *__restrict__ depth, const int *__restrict__ stats, int IH, int IW,
-                                                  int mode, unsigned short *__restrict__ mask) {
-  const int f = blockIdx.y;
-  const int npix = IH * IW;
-  const int *s = stats + (size_t)f * 6;
-  const int rmin = s[2], rmax = s[3], cmin = s[4], cmax = s[5];
-  const unsigned short *df = depth + (size_t)f * npix;
-  unsigned short *mf = mask + (size_t)f * npix;
-  for (int p = blockIdx.x * RB + threadIdx.x; p < npix; p += gridDim.x * RB) {
-    bool on;
-    if (mode == 0) {
-      const int r = p / IW, q = p - r * IW;
-      on = r >= rmin && r < rmax && q >= cmin && q < cmax;
-    } else {
-      on = df[p] != 65535;
-    }
-    mf[p] = on ? 65535 : 0;
-  }
-}
-
-bool sizes_ok(int F, int IH, int IW) { return F > 0 && F <= 65535 && IH > 0 && IW > 0 && (long)IH * IW <= (1L << 30); }
 
 }  // namespace
 }  // namespace df
@@ -187,15 +126,12 @@ extern "C" int df_cad_render(const float *points, const float *normals, const un
   if (mask_mode != 0 && mask_mode != 1) return set_error(DF_ERR_ARG, "cad_render: mask_mode %d is neither 0 (box) nor 1 (pixels)", mask_mode);
   if (scratch_bytes < df_cad_render_scratch_bytes(F, IH, IW) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
     return set_error(DF_ERR_ARG, "cad_render: scratch too small or not 8-byte aligned");
-  // the loader's inverse assumes z' = p22 z + p23 and w' = -z (project_unity_depth.py:42-51)
-  if (!(proj[8] == 0.0 && proj[9] == 0.0 && proj[12] == 0.0 && proj[13] == 0.0 && proj[14] == -1.0 && proj[15] == 0.0))
+  if (!proj_form_ok(proj))
     return set_error(DF_ERR_ARG, "cad_render: the projection matrix needs rows 2 = (0, 0, p22, p23) and 3 = (0, 0, -1, 0)");
   for (long j = 0; j < (long)F * K; ++j)
     if (hole_idx[j] >= P) return set_error(DF_ERR_ARG, "cad_render: hole index %d of frame %ld is not below P = %d", hole_idx[j], j / K, P);
   hipStream_t st = to_stream(stream);
-  Camera cam;
-  for (int k = 0; k < 4; ++k) { cam.p0[k] = proj[k]; cam.p1[k] = proj[4 + k]; cam.p3[k] = proj[12 + k]; }
-  cam.p22 = proj[10]; cam.p23 = proj[11];
+  const Camera cam = make_camera(proj);
   const long npix = (long)IH * IW;
   if (hipMemsetAsync(scratch, 0xff, (size_t)F * npix * sizeof(unsigned long long), st) != hipSuccess ||
       hipMemsetAsync(stats_out, 0, sizeof(int) * 6 * F, st) != hipSuccess)
@@ -205,12 +141,7 @@ extern "C" int df_cad_render(const float *points, const float *normals, const un
   const int per_launch = K > 0 ? MAX_HOLES / K : F;                        // frames per splat launch: their holes fit one Holes
   for (int f0 = 0; f0 < F; f0 += per_launch) {
     const int nf = F - f0 < per_launch ? F - f0 : per_launch;
-    Holes holes;
-    for (int j = 0; j < MAX_HOLES; ++j) {
-      const bool live = j < nf * K;
-      holes.idx[j] = live ? hole_idx[(size_t)f0 * K + j] : -1;
-      holes.r[j] = live ? hole_r[(size_t)f0 * K + j] : 0.0;
-    }
+    const Holes holes = make_holes(hole_idx, hole_r, K, f0, nf);
     hipLaunchKernelGGL(splat_kernel, dim3(pb, nf), dim3(RB), 0, st, points, normals, P, pose, model_scale, holes, K, f0, cam, IH, IW, splat,
                        keys, stats_out);
   }

@@ -1,4 +1,5 @@
-"""Views of a coloured CAD cloud as customCAD training frames, rendered on the device (``df_cad_render``) -- the job of the reference's
+"""Views of a coloured CAD cloud (``df_cad_render``) or triangle mesh (``df_cad_render_mesh``) as customCAD training frames, rendered on
+the device -- the job of the reference's
 unfinished Unity-free generator datasets/customCAD/cad_to_dataset.py (needs open3d and cv2, uses ``np.float`` / ``np.int``, stops after 50
 test images), of mask_generator.py and of train_test_generator.py, for the tree ``dataset.py`` of this directory reads.
 
@@ -108,6 +109,33 @@ def read_colored_ply(path, n_points=None):
             np.ascontiguousarray(np.clip(np.rint(col), 0, 255), dtype=np.uint8))
 
 
+def read_colored_mesh(path):
+    """(vertices float32 [V,3], triangles int32 [T,3], colours uint8 [V,3]) of an ASCII or binary little-endian PLY mesh, for
+    ``CadMeshRenderer``: polygons are cut into fans as ``read_ply`` does, a file without ``red green blue`` comes back mid-grey.
+    A file without faces returns T = 0."""
+    data, tris = _read_ply_elements(path)
+    v = data.get("vertex")
+    if v is None or not all(a in v for a in "xyz"):
+        raise ValueError(f"{path}: no vertex positions")
+    pts = np.stack([v[a].astype(np.float64) for a in "xyz"], axis=1)
+    col = (np.stack([v[a].astype(np.float64) for a in ("red", "green", "blue")], axis=1) if all(a in v for a in ("red", "green", "blue"))
+           else np.full(pts.shape, 128.0))
+    return (np.ascontiguousarray(pts, dtype=np.float32), np.ascontiguousarray(tris, dtype=np.int32),
+            np.ascontiguousarray(np.clip(np.rint(col), 0, 255), dtype=np.uint8))
+
+
+def check_triangles(triangles, n_vertices):
+    """triangles as int32 [T,3] with T >= 1; ``ValueError`` on any other shape or on an index outside 0..n_vertices-1 (host only)."""
+    tri = np.asarray(triangles)
+    if tri.ndim != 2 or tri.shape[1] != 3 or tri.shape[0] == 0 or not np.issubdtype(tri.dtype, np.integer):
+        raise ValueError("triangles must be a non-empty integer array [T,3]")
+    lo, hi = int(tri.min()), int(tri.max())
+    if lo < 0 or hi >= n_vertices:
+        bad = np.argwhere((tri < 0) | (tri >= n_vertices))[0]
+        raise ValueError(f"triangle {bad[0]} names vertex {int(tri[bad[0], bad[1]])}, outside 0..{n_vertices - 1}")
+    return np.ascontiguousarray(tri, dtype=np.int32)
+
+
 def sample_view(seed, n_points, center, scene_scale, max_holes=3, *, hole_mean, hole_std):
     """The draws of one view on ``np.random.seed(seed)``, in the reference's order (cad_to_dataset.py:264-276, then :145-160): three
     ``uniform(-1, 1)`` for the axis (normalised), ``uniform(0, 2 pi)`` for the angle, per axis ``uniform(0, 0.5 | 0.5 | 0.3)`` for the
@@ -189,3 +217,34 @@ class CadRenderer:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         return pp.cad_render(self.points, self.normals, self.colors, poses, self.model_scale, self.proj_mat, self.image_dims,
                              holes=self.pack_holes(holes, F), splat=splat, mask_mode=MASK_MODES[mask], scratch=self._scratch)
+
+
+class CadMeshRenderer:
+    """A coloured triangle mesh on the device and the camera of one object directory (``df_cad_render_mesh``).  The triangle indices
+    are checked on the host before anything is uploaded (``check_triangles``).  ``render(poses, holes, cull, mask)``: as
+    ``CadRenderer.render`` without ``splat``; hole indices name vertices, ``cull`` 1 drops the triangles that face away;
+    stats[:, 1] counts the triangles that reached the z-buffer."""
+
+    def __init__(self, vertices, triangles, colors, proj_mat, image_dims, device="cuda", model_scale=10.0):
+        vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        triangles = check_triangles(triangles, len(vertices))
+        self.device = torch.device(device)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        self.vertices = up(vertices, np.float32)
+        self.triangles = up(triangles, np.int32)
+        self.colors = up(colors, np.uint8)
+        self.proj_mat = np.ascontiguousarray(proj_mat, dtype=np.float64)
+        self.image_dims = (int(image_dims[0]), int(image_dims[1]))
+        self.model_scale = float(model_scale)
+        self._scratch = None
+
+    pack_holes = staticmethod(CadRenderer.pack_holes)
+
+    def render(self, poses, holes=None, cull=1, mask="box"):
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3, 4)
+        F = poses.shape[0]
+        need = F * self.image_dims[0] * self.image_dims[1] * 8
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return pp.cad_render_mesh(self.vertices, self.colors, self.triangles, poses, self.model_scale, self.proj_mat, self.image_dims,
+                                  holes=self.pack_holes(holes, F), cull=cull, mask_mode=MASK_MODES[mask], scratch=self._scratch)

@@ -225,6 +225,62 @@ def cad_render(points, normals, colors, pose, model_scale, proj, image_dims, hol
     return rgb, depth, mask, stats
 
 
+def cad_render_mesh(vertices, colors, triangles, pose, model_scale, proj, image_dims, holes=None, cull=1, mask_mode=0, scratch=None):
+    """F views of a coloured triangle mesh as customCAD frames (``df_cad_render_mesh``; the contract is its comment in include/dfusion.h).
+    vertices [V,3] float32, colors [V,3] uint8, triangles [T,3] int32 -- device tensors; pose, proj, image_dims, holes (indices name
+    vertices), mask_mode and scratch as for ``cad_render`` (scratch: at least ``df_cad_render_mesh_scratch_bytes``); cull 1 drops the
+    triangles that face away.
+    Returns rgb [F,IH,IW,3] uint8, depth and mask [F,IH,IW] uint16, stats [F,6] int32 on the device; no read-back, no synchronisation."""
+    if not (vertices.is_cuda and colors.is_cuda and triangles.is_cuda):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise RuntimeError("cad_render_mesh: vertices must be [V,3] float32")
+    V = vertices.shape[0]
+    if tuple(colors.shape) != (V, 3) or colors.dtype != torch.uint8:
+        raise RuntimeError("cad_render_mesh: colors must be [V,3] uint8")
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
+        raise RuntimeError("cad_render_mesh: triangles must be [T,3] int32")
+    T = triangles.shape[0]
+    dev = vertices.device
+    if not torch.is_tensor(pose):
+        pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
+    if pose.dtype != torch.float64 or pose.dim() not in (2, 3) or pose.numel() != pose.shape[0] * 12:
+        raise RuntimeError("cad_render_mesh: pose must be [F,3,4] float64")
+    F = pose.shape[0]
+    if not pose.is_cuda:
+        pose = (pose if pose.is_pinned() else pose.pin_memory()).to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
+    pose = pose.contiguous()
+    IH, IW = int(image_dims[0]), int(image_dims[1])
+    proj = np.ascontiguousarray(proj, dtype=np.float64)
+    if proj.shape != (4, 4):
+        raise RuntimeError("cad_render_mesh: proj must be 4 x 4")
+    K, hole_idx, hole_r = 0, None, None
+    if holes is not None:
+        hole_idx, hole_r = np.ascontiguousarray(holes[0], dtype=np.int32), np.ascontiguousarray(holes[1], dtype=np.float64)
+        if hole_idx.ndim != 2 or hole_idx.shape[0] != F or hole_r.shape != hole_idx.shape:
+            raise RuntimeError("cad_render_mesh: holes must be (hole_idx [F,K], hole_r [F,K])")
+        K = hole_idx.shape[1]
+    L = _lib.lib()
+    need = L.df_cad_render_mesh_scratch_bytes(F, IH, IW, V, T)
+    if need == 0:
+        raise RuntimeError(f"cad_render_mesh: bad sizes F={F}, IH={IH}, IW={IW}, V={V}, T={T}")
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < need:
+        raise RuntimeError(f"cad_render_mesh: scratch must be a uint8 device tensor of at least {need} bytes")
+    rgb = torch.empty(F, IH, IW, 3, dtype=torch.uint8, device=dev)
+    depth = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    mask = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    stats = torch.empty(F, 6, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        st = L.df_cad_render_mesh(_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, pose.data_ptr(), float(model_scale),
+                                  hole_idx.ctypes.data if K else None, hole_r.ctypes.data if K else None, K, proj.ctypes.data, F, IH, IW,
+                                  int(cull), int(mask_mode), rgb.data_ptr(), depth.data_ptr(), mask.data_ptr(), stats.data_ptr(),
+                                  scratch.data_ptr(), scratch.numel(), _lib.current_stream())
+    _lib.check(st, "cad_render_mesh")
+    return rgb, depth, mask, stats
+
+
 def color_jitter(frames_u8, plans, out=None):
     """The training colour jitter on the device (``df_color_jitter``): frames_u8 [F,H,W,3] uint8 device tensor, plans [F,8] float32
     (``datasets.augment.plan_row`` rows; host or device).  Returns the jittered uint8 frames, bit-identical to

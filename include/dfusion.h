@@ -328,6 +328,56 @@ int df_cad_render(const float *points, const float *normals, const unsigned char
                   size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Triangle rasteriser for customCAD training sets: F views of a coloured CAD mesh as the frames df_cad_render writes from a cloud, drawn
+ * from the triangles themselves (the reference renders meshes in Unity; its own attempt without Unity, cad_to_dataset.py, starts from
+ * read_triangle_mesh).  Watertight, no splat parameter, the depth exact on each facet up to the rounding of the 16-bit code.  The rules of
+ * df_cad_render carry over: no allocation, no synchronisation, the caller's stream; integer atomics only, so the outputs are
+ * bit-reproducible; a frame's outputs do not depend on the other frames of the call.
+ *
+ * df_cad_render_mesh_scratch_bytes: F*IH*IW 64-bit keys (V1..V5 below are recomputed per triangle corner, so nothing is kept per
+ *   vertex); 0 for sizes the call refuses (F, IH, IW as for df_cad_render; V, T 1..2^31-1).
+ * df_cad_render_mesh:
+ *   DEVICE: vertices [V][3] float (model file units), colors [V][3] u8, triangles [T][3] int (vertex indices), pose [F][12] double as for
+ *   df_cad_render, the outputs, scratch (8-byte aligned).  HOST, read during the call: proj and hole_idx / hole_r [F][K], as for
+ *   df_cad_render (K <= 128, 128 records a launch); hole indices name vertices.
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer, bad sizes, cull or mask_mode outside 0..1, a short or
+ *   misaligned scratch, a hole index >= V, and a proj that is not of df_cad_render's form.
+ *   All in fp64, one rounding per operation (no fused multiply-add), in exactly this order.
+ *   Per frame f and vertex v:
+ *   V1. m = (double)vertices[v].  The vertex is removed by a hole by step 1 of df_cad_render (the centres are vertices).
+ *   V2. s = m * model_scale;  X_j = ((R[j][0]*s_x + R[j][1]*s_y) + R[j][2]*s_z) + t[j].
+ *   V3. c_0, c_1, c_3 as in step 4 of df_cad_render.  The vertex is BEHIND unless c_3 > 0.  ndc_x = c_0 / c_3, ndc_y = c_1 / c_3.
+ *   V4. sx = ((ndc_x + 1) * IW) * 0.5, sy = ((1 - ndc_y) * IH) * 0.5.  Pixel (r, q) is the node sy = r, sx = q of the loader's ray
+ *       grid: the grid of step 6 of df_cad_render, whose col is floor(sx + 0.5).
+ *   V5. d = (1 + p22) + p23 / X_z: the depth code before scaling and rounding; affine in 1/z, hence exactly linear over the screen on
+ *       a planar triangle.
+ *   Per triangle t = (i0, i1, i2):
+ *   T1. Dropped when an index is outside 0..V-1 (nothing is read through it), two indices are equal, a vertex is removed by a hole, or
+ *       a vertex is behind.  THERE IS NO CLIPPING: a triangle that crosses the camera plane is dropped whole.
+ *   T2. The edge function of the ordered pair (a, b) at a point p, with lo = min(a, b), hi = max(a, b):
+ *       e = (sx_hi - sx_lo)*(p_y - sy_lo) - (sy_hi - sy_lo)*(p_x - sx_lo);  E(a,b;p) = e when a < b, else -e.  The two triangles that
+ *       share an edge see exactly opposite values, so a node is never lost between them: this canonical order makes the raster watertight.
+ *   T3. A = E(i0,i1; (sx_i2, sy_i2)).  Dropped when A == 0 or A is not finite.  Front-facing when A < 0 (counter-clockwise as the camera
+ *       sees it, y up); cull == 1 drops the others.
+ *   T4. Columns from max(ceil(min sx), 0) to min(floor(max sx), IW-1), rows alike with sy and IH; the bounds are compared as doubles
+ *       before any conversion to integer.  An empty range drops the triangle.
+ *   T5. At node (r, q): w0 = E(i1,i2;(q,r)), w1 = E(i2,i0;(q,r)), w2 = E(i0,i1;(q,r)), each negated when A < 0.  The node is covered
+ *       when w0 >= 0, w1 >= 0, w2 >= 0 and W = (w0 + w1) + w2 > 0.
+ *   T6. code = rint(65534 * (((w0*d_i0 + w1*d_i1) + w2*d_i2) / W)), ties to even; the node is dropped unless 0 <= code <= 65534 (a
+ *       triangle that reaches past a code limit is cut per node).
+ *   T7. atomicMin of key = (uint64)code << 32 | t: the nearest surface wins, equal codes go to the lowest triangle index.
+ *   Resolve, per pixel: uncovered -> depth 65535 and rgb (130, 130, 130) as in df_cad_render.  Covered -> depth = code; the winner's
+ *   w_k are recomputed by T5 (the same operations, hence the same bits); u_k = w_k / c_3(i_k) (perspective-correct);
+ *   U = (u0 + u1) + u2; each channel = rint(((u0*C_i0 + u1*C_i1) + u2*C_i2) / U) clamped to 0..255 (a NaN gives 0).
+ *   stats [F][6] and the two mask modes are those of df_cad_render, except stats[f][1]: the number of triangles that took at least one
+ *   key test in T7. */
+size_t df_cad_render_mesh_scratch_bytes(int F, int IH, int IW, int V, int T);
+int df_cad_render_mesh(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const double *pose,
+                       double model_scale, const int *hole_idx, const double *hole_r, int K, const double *proj, int F, int IH, int IW,
+                       int cull, int mask_mode, unsigned char *rgb_out, unsigned short *depth_out, unsigned short *mask_out,
+                       int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-time pixel augmentation on whole uint8 frames, bit-identical to the host path (densefusion_amd/datasets/augment.py over PIL;
  * datasets/ycb/dataset.py).  Same conventions as df_preprocess_objects: no allocation, no synchronisation, the caller's stream.
  *

@@ -3,6 +3,12 @@
 cloud, and with ``--cpu`` the time per frame of the numpy restatement (tests/cad_render_np.py) on this machine's CPU.  One JSON line.
 
     python tools/cad_render_bench.py --points 1000000 --height 520 --width 1109 --splat 1 --chunk 32 [--cpu]
+
+``--mesh`` times ``df_cad_render_mesh`` instead, in one run and on the same poses (no holes): an icosphere of ``--subdiv`` subdivisions
+(tests/cad_raster_np.py builds it; radius 60 file units), a 12-triangle box of the sphere's size, and for comparison the point path on
+``--points`` points drawn from that icosphere by area with their faces' normals.
+
+    python tools/cad_render_bench.py --mesh --subdiv 7 --points 1000000 --splat 1 --chunk 32
 """
 from __future__ import annotations
 
@@ -22,8 +28,64 @@ from densefusion_amd.datasets.customCAD import render as cr  # noqa: E402
 PROJ = [[1.16667, 0.0, 0.0, 0.0], [0.0, 2.48814, 0.0, 0.0], [0.0, 0.0, 0.5, 3000.0], [0.0, 0.0, -1.0, 0.0]]
 
 
+def timed(render, calls):
+    """(device ms of each call after one warm-up, the last call's outputs)"""
+    times = []
+    for k in range(calls + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = render()
+        e1.record()
+        torch.cuda.synchronize()
+        if k:
+            times.append(e0.elapsed_time(e1))
+    return times, out
+
+
+def mesh_bench(opt):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cad_raster_np as mnp
+    rng = np.random.default_rng(0)
+    sv, sf = mnp.icosphere(opt.subdiv, 60.0)
+    e = 60.0 / np.sqrt(3.0)                                   # the cube inscribed in the sphere
+    bv = np.array([[x, y, z] for z in (-e, e) for y in (-e, e) for x in (-e, e)])
+    bf = np.array([[0, 2, 1], [1, 2, 3], [4, 5, 6], [5, 7, 6], [0, 1, 4], [1, 5, 4], [2, 6, 3], [3, 6, 7], [0, 4, 2], [2, 4, 6], [1, 3, 5], [3, 7, 5]])
+    poses = []
+    for s in range(opt.chunk):
+        axis, angle, xyz, _ = cr.sample_view(s, len(sv), (0.0, 0.0, 4.0), 1.0, hole_mean=30.0, hole_std=10.0)
+        R, t = cr.view_pose(axis, angle, xyz, np.zeros(3), 10.0)
+        poses.append(np.concatenate([R, t[:, None]], axis=1))
+    poses = np.stack(poses)
+    dims = (opt.height, opt.width)
+    res = {"frame": list(dims), "chunk": opt.chunk, "holes": 0}
+    for name, v, f in (("icosphere", sv, sf), ("box", bv, bf)):
+        r = cr.CadMeshRenderer(v, f, rng.integers(0, 256, (len(v), 3), dtype=np.uint8), PROJ, dims)
+        times, out = timed(lambda: r.render(poses, cull=1, mask="box"), opt.calls)
+        stats = out[3].cpu().numpy()
+        res[name] = {"triangles": int(len(f)), "device_ms_per_frame_median": float(np.median(times)) / opt.chunk,
+                     "device_ms_per_call": [round(t, 3) for t in times], "covered_mean": float(stats[:, 0].mean()),
+                     "triangles_reaching_mean": float(stats[:, 1].mean())}
+    a, b, c = sv[sf[:, 0]], sv[sf[:, 1]], sv[sf[:, 2]]      # the point path on the same poses: points by area, each with its face's normal
+    cross = np.cross(b - a, c - a)
+    area = 0.5 * np.linalg.norm(cross, axis=1)
+    t = rng.choice(len(sf), opt.points, p=area / area.sum())
+    r1, r2 = np.sqrt(rng.random(opt.points))[:, None], rng.random(opt.points)[:, None]
+    pts = (1.0 - r1) * a[t] + r1 * (1.0 - r2) * b[t] + r1 * r2 * c[t]
+    nrm = cross[t] / (2.0 * area[t])[:, None]
+    r = cr.CadRenderer(pts, nrm, rng.integers(0, 256, (opt.points, 3), dtype=np.uint8), PROJ, dims)
+    times, out = timed(lambda: r.render(poses, splat=opt.splat, mask="box"), opt.calls)
+    stats = out[3].cpu().numpy()
+    res["points_of_icosphere"] = {"points": opt.points, "splat": opt.splat, "device_ms_per_frame_median": float(np.median(times)) / opt.chunk,
+                                  "device_ms_per_call": [round(t, 3) for t in times], "covered_mean": float(stats[:, 0].mean()),
+                                  "points_reaching_mean": float(stats[:, 1].mean())}
+    print(json.dumps(res))
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mesh", action="store_true", help="time df_cad_render_mesh (icosphere, box) and the point path on points of that icosphere")
+    ap.add_argument("--subdiv", type=int, default=7, help="--mesh: icosphere subdivisions (20 * 4^n triangles)")
     ap.add_argument("--points", type=int, default=1000000)
     ap.add_argument("--height", type=int, default=520)
     ap.add_argument("--width", type=int, default=1109)
@@ -32,6 +94,8 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--cpu", action="store_true", help="also time the numpy restatement on one frame")
     opt = ap.parse_args(argv)
+    if opt.mesh:
+        return mesh_bench(opt)
     rng = np.random.default_rng(0)
     d = rng.normal(size=(opt.points, 3))
     d /= np.linalg.norm(d, axis=1, keepdims=True)

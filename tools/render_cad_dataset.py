@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Render a customCAD training set from a coloured CAD cloud on the device -- no Unity, open3d or OpenCV.
+"""Render a customCAD training set from a coloured CAD cloud or mesh on the device -- no Unity, open3d or OpenCV.
 
-    python tools/render_cad_dataset.py --model M.ply --output_root ROOT [--object 1 --frames 2000]
+    python tools/render_cad_dataset.py --model M.ply --output_root ROOT [--object 1 --frames 2000] [--raster mesh]
 
 writes the tree ``tools/train.py --dataset cad`` and ``tools/eval_cad.py`` read (datasets/customCAD/dataset.py of the reference):
 ``ROOT/data/XX/{train,test}.txt``, ``rgb/FrameBuffer_NNNN.png``, ``depth/Depth_NNNN.png``, ``mask/NNNN.png``, ``meta/transforms.txt``,
@@ -13,6 +13,11 @@ with fewer than ``--min_pixels`` covered pixels is skipped and the next seed is 
 pose is first written as its ``transforms.txt`` record (``repr`` precision) and parsed back, and the frame is rendered from the parsed
 values: images and records agree exactly.  Record k + 1 holds frame k (the loader looks up ``index + 1``); record 0 repeats record 1.
 Hole radii are in model file units (the reference's 0.03 / 0.01 apply to a model scaled by 0.001).
+
+``--raster points`` (the default) samples a mesh into a cloud and splats it (``--points``, ``--splat``).  ``--raster mesh`` draws the
+model's triangles themselves (``df_cad_render_mesh``: watertight, the depth exact on each facet, no splat radius): the model must have
+faces, the hole indices of ``sample_view`` name vertices, ``--cull 1`` drops the triangles that face away, and ``models/obj_XX.ply``
+receives the mesh (vertices and faces), which the loader samples by area.
 """
 from __future__ import annotations
 
@@ -49,6 +54,8 @@ def build_parser():
     ap.add_argument("--model_scale", type=float, default=10.0, help="the loader's `model * 10`")
     ap.add_argument("--min_pixels", type=int, default=500)
     ap.add_argument("--splat", type=int, default=1)
+    ap.add_argument("--raster", type=str, default="points", choices=("points", "mesh"), help="splat a sampled cloud, or rasterise the triangles")
+    ap.add_argument("--cull", type=int, default=1, choices=(0, 1), help="--raster mesh: 1 drops the triangles that face away from the camera")
     ap.add_argument("--mask", type=str, default="box", choices=sorted(cr.MASK_MODES))
     ap.add_argument("--points", type=int, default=0, help="points to draw from a mesh (default 1 000 000) or to keep of a cloud (default all)")
     ap.add_argument("--max_holes", type=int, default=3)
@@ -79,6 +86,17 @@ def write_vertex_ply(path, pts):
         f.write(pts.tobytes())
 
 
+def write_mesh_ply(path, vertices, triangles):
+    vertices = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 3)
+    face = np.zeros(len(triangles), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    face["n"], face["v"] = 3, triangles
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\ncomment rendered by densefusion_amd\nelement vertex %d\nproperty float x\n"
+                 "property float y\nproperty float z\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                 % (len(vertices), len(face))).encode("ascii"))
+        f.write(vertices.tobytes() + face.tobytes())
+
+
 def load_model(path, n_points):
     pts, nrm, col = cr.read_colored_ply(path, n_points=n_points if n_points > 0 else 1000000)
     if 0 < n_points < len(pts):                      # a cloud with more vertices than asked for
@@ -88,21 +106,36 @@ def load_model(path, n_points):
 
 
 def main(argv=None):
-    opt = build_parser().parse_args(argv)
+    ap = build_parser()
+    opt = ap.parse_args(argv)
+    mesh = opt.raster == "mesh"
+    if mesh and (opt.splat != ap.get_default("splat") or opt.points != ap.get_default("points")):
+        ap.error("--splat and --points belong to --raster points; --raster mesh draws the triangles themselves")
     if not torch.cuda.is_available():
         raise SystemExit("render_cad_dataset needs a GPU (no CPU path)")
     np.random.seed(opt.seed)
-    pts, nrm, col = load_model(opt.model, opt.points)
+    if mesh:
+        pts, tris, col = cr.read_colored_mesh(opt.model)
+        if len(tris) == 0:
+            raise SystemExit(f"{opt.model}: --raster mesh needs a model with faces")
+    else:
+        pts, nrm, col = load_model(opt.model, opt.points)
     proj = read_proj_mat(opt.proj_mat) if opt.proj_mat else np.array(DEFAULT_PROJ)
     sub = os.path.join(opt.output_root, "data", "%02d" % opt.object)
     for d in ("rgb", "depth", "mask", "meta"):
         os.makedirs(os.path.join(sub, d), exist_ok=True)
     os.makedirs(os.path.join(opt.output_root, "models"), exist_ok=True)
-    write_vertex_ply(os.path.join(opt.output_root, "models", "obj_%02d.ply" % opt.object), pts)
+    if mesh:
+        write_mesh_ply(os.path.join(opt.output_root, "models", "obj_%02d.ply" % opt.object), pts, tris)
+    else:
+        write_vertex_ply(os.path.join(opt.output_root, "models", "obj_%02d.ply" % opt.object), pts)
     with open(os.path.join(sub, "meta", "proj_mat.txt"), "w") as f:
         f.write("".join("\t".join(repr(float(v)) for v in row) + "\n" for row in proj) + "\n")
     proj = read_proj_mat(os.path.join(sub, "meta", "proj_mat.txt"))          # what the loader will read
-    renderer = cr.CadRenderer(pts, nrm, col, proj, (opt.height, opt.width), model_scale=opt.model_scale)
+    if mesh:
+        renderer = cr.CadMeshRenderer(pts, tris, col, proj, (opt.height, opt.width), model_scale=opt.model_scale)
+    else:
+        renderer = cr.CadRenderer(pts, nrm, col, proj, (opt.height, opt.width), model_scale=opt.model_scale)
     centroid = pts.astype(np.float64).mean(axis=0)
 
     def save(n, rgb, depth, mask):
@@ -128,7 +161,10 @@ def main(argv=None):
             seed += opt.chunk
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-            rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, splat=opt.splat, mask=opt.mask)
+            if mesh:
+                rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, cull=opt.cull, mask=opt.mask)
+            else:
+                rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, splat=opt.splat, mask=opt.mask)
             ev1.record()
             rows = stats.cpu().numpy()                                        # the chunk's one read-back before its frames
             device_ms.append(ev0.elapsed_time(ev1))
@@ -158,8 +194,9 @@ def main(argv=None):
             f.write("".join("%d\n" % n for n in part))
     wall = time.time() - t_start
     per_view = float(np.median(device_ms)) / opt.chunk            # the median call: the first one also loads the kernels
+    what = (f"{len(tris)} triangles", f"cull {opt.cull}") if mesh else (f"{len(pts)} points", f"splat {opt.splat}")
     print(f"frames written: {written}, views skipped: {skipped}, device time per rendered view: {per_view:.3f} ms "
-          f"(HIP events, the median of {len(device_ms)} calls; {len(pts)} points, {opt.height} x {opt.width}, splat {opt.splat}, chunk {opt.chunk}); "
+          f"(HIP events, the median of {len(device_ms)} calls; {what[0]}, {opt.height} x {opt.width}, {what[1]}, chunk {opt.chunk}); "
           f"wall {wall / max(written, 1) * 1e3:.1f} ms per frame written")
     return {"written": written, "skipped": skipped, "device_ms_per_view": per_view}
 
