@@ -1,5 +1,6 @@
-// What the two customCAD renderers share (cad_render.hip: points; cad_raster.hip: triangles): the z-buffer key, the camera and hole
-// records that travel as launch arguments, the per-frame statistics and the mask.  Each translation unit gets its own copy of the kernels.
+// What the customCAD renderers share (cad_render.hip: points; cad_raster.hip: triangles; cad_scene.hip: several meshes with occlusion):
+// the z-buffer key, the camera and hole records that travel as launch arguments, the per-frame statistics and the mask.  Each translation
+// unit gets its own copy of the kernels.
 #pragma once
 #include "common.h"
 

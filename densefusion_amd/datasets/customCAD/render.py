@@ -1,5 +1,5 @@
-"""Views of a coloured CAD cloud (``df_cad_render``) or triangle mesh (``df_cad_render_mesh``) as customCAD training frames, rendered on
-the device -- the job of the reference's
+"""Views of a coloured CAD cloud (``df_cad_render``), a triangle mesh (``df_cad_render_mesh``) or a scene of several meshes that occlude
+each other (``df_cad_render_scene``) as customCAD training frames, rendered on the device -- the job of the reference's
 unfinished Unity-free generator datasets/customCAD/cad_to_dataset.py (needs open3d and cv2, uses ``np.float`` / ``np.int``, stops after 50
 test images), of mask_generator.py and of train_test_generator.py, for the tree ``dataset.py`` of this directory reads.
 
@@ -155,6 +155,32 @@ def sample_view(seed, n_points, center, scene_scale, max_holes=3, *, hole_mean, 
     return axis, float(angle), xyz, holes
 
 
+def sample_scene(seed, n_points, center, scene_scale, n_objects, target=0, max_holes=3, *, hole_mean, hole_std, p_present=0.7,
+                 lateral=0.8, depth=0.8):
+    """One scene of ``n_objects`` objects around object ``target``.  The target's view is exactly ``sample_view(seed, n_points, center,
+    scene_scale, max_holes, hole_mean=, hole_std=)``: seed s shows the target where the single-object tool shows it (its holes are
+    drawn and returned, and not applied: in a scene the occluders play that part).  Everything else comes from
+    ``np.random.default_rng((seed, 1))``, which leaves the global stream alone; per other object, in index order: ``random() < p_present``,
+    three ``uniform(-1, 1)`` for the axis (normalised), ``uniform(0, 2 pi)`` for the angle, then the centre as an offset from the
+    target's: ``uniform(-lateral, lateral)`` for x and for y and ``uniform(-depth, depth)`` for z (nearer or farther), in the units of
+    ``transforms.txt``, times ``scene_scale``.  The draws are made whether or not the object is present.
+    Returns (views: per object (present, axis (3,), angle, xyz (3,)), holes: the target's)."""
+    axis, angle, xyz, holes = sample_view(seed, n_points, center, scene_scale, max_holes, hole_mean=hole_mean, hole_std=hole_std)
+    rng = np.random.default_rng((int(seed), 1))
+    views = []
+    for o in range(n_objects):
+        if o == target:
+            views.append((True, axis, angle, xyz))
+            continue
+        here = bool(rng.random() < p_present)
+        a = rng.uniform(-1, 1, size=3)
+        a /= np.linalg.norm(a)
+        ang = float(rng.uniform(0, np.pi * 2))
+        off = np.array([rng.uniform(-lateral, lateral), rng.uniform(-lateral, lateral), rng.uniform(-depth, depth)]) * scene_scale
+        views.append((here, a, ang, xyz + off))
+    return views, holes
+
+
 def transform_to_pose(pos, quat_xyzw):
     """A ``transforms.txt`` record -> (R_cam [3,3], t_cam (3,)): the loader's own arithmetic (``PoseDataset._targets``: ``convert_quat``,
     ``Rotation.from_quat``, ``@ Y_180``, ``pos * 1000`` with z negated), so that target = R_cam (10 model) + t_cam."""
@@ -248,3 +274,49 @@ class CadMeshRenderer:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         return pp.cad_render_mesh(self.vertices, self.colors, self.triangles, poses, self.model_scale, self.proj_mat, self.image_dims,
                                   holes=self.pack_holes(holes, F), cull=cull, mask_mode=MASK_MODES[mask], scratch=self._scratch)
+
+
+class CadSceneRenderer:
+    """Several coloured triangle meshes on the device and one camera (``df_cad_render_scene``): ``meshes`` is a list of (vertices,
+    triangles, colours), object o being meshes[o] with ``model_scales[o]``.  Each mesh's indices are checked on the host
+    (``check_triangles``); the meshes are concatenated once (indices made global) and uploaded once; the scratch buffer is reused.
+    ``render(poses [F,O,3,4], present, cull)`` -> device tensors (rgb [F,IH,IW,3] uint8, depth and label [F,IH,IW] uint16 with label =
+    object + 1 on the pixels it won, stats [F,O,6] int32 = {pixels won, triangles tested, rmin, rmax, cmin, cmax});
+    ``masks(label, stats, pairs, mask)`` -> the loader's mask [N,IH,IW] uint16 of each (frame, object) pair."""
+
+    def __init__(self, meshes, proj_mat, image_dims, model_scales, device="cuda"):
+        if len(meshes) == 0 or len(meshes) != len(np.atleast_1d(model_scales)):
+            raise ValueError("one model scale per mesh, at least one mesh")
+        verts, tris, cols, begin = [], [], [], [0]
+        for v, t, c in meshes:
+            v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
+            t = check_triangles(t, len(v))
+            c = np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 3)
+            if len(c) != len(v):
+                raise ValueError("one colour per vertex")
+            tris.append(t + np.int32(sum(len(x) for x in verts)))
+            verts.append(v); cols.append(c)
+            begin.append(begin[-1] + len(t))
+        self.device = torch.device(device)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+        self.vertices = up(np.concatenate(verts), np.float32)
+        self.triangles = up(np.concatenate(tris), np.int32)
+        self.colors = up(np.concatenate(cols), np.uint8)
+        self.tri_begin = np.array(begin, dtype=np.int32)
+        self.model_scales = np.ascontiguousarray(model_scales, dtype=np.float64).reshape(-1)
+        self.n_objects = len(meshes)
+        self.proj_mat = np.ascontiguousarray(proj_mat, dtype=np.float64)
+        self.image_dims = (int(image_dims[0]), int(image_dims[1]))
+        self._scratch = None
+
+    def render(self, poses, present=None, cull=1):
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, self.n_objects, 3, 4)
+        F = poses.shape[0]
+        need = F * self.image_dims[0] * self.image_dims[1] * 8
+        if self._scratch is None or self._scratch.numel() < need:
+            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return pp.cad_render_scene(self.vertices, self.colors, self.triangles, self.tri_begin, self.model_scales, poses, self.proj_mat,
+                                   self.image_dims, present=present, cull=cull, scratch=self._scratch)
+
+    def masks(self, label, stats, pairs, mask="box"):
+        return pp.cad_scene_mask(label, stats, pairs, mask_mode=MASK_MODES[mask])

@@ -281,6 +281,98 @@ def cad_render_mesh(vertices, colors, triangles, pose, model_scale, proj, image_
     return rgb, depth, mask, stats
 
 
+def cad_render_scene(vertices, colors, triangles, tri_begin, model_scales, pose, proj, image_dims, present=None, cull=1, scratch=None):
+    """F frames of O objects with occlusion (``df_cad_render_scene``; the contract is its comment in include/dfusion.h).
+    vertices [V,3] float32, colors [V,3] uint8, triangles [T,3] int32 -- device tensors, shared by all objects, the indices global;
+    tri_begin [O+1] and model_scales [O] -- HOST; pose [F,O,3,4] / [F,O,12] float64, host or device; present: None (all) or [F,O]
+    uint8, host or device; proj, image_dims and scratch (at least ``df_cad_render_scene_scratch_bytes``) as for ``cad_render_mesh``.
+    Returns rgb [F,IH,IW,3] uint8, depth and label [F,IH,IW] uint16 (label = owner + 1, 0 = horizon), stats [F,O,6] int32 on the
+    device; no read-back, no synchronisation."""
+    if not (vertices.is_cuda and colors.is_cuda and triangles.is_cuda):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise RuntimeError("cad_render_scene: vertices must be [V,3] float32")
+    V = vertices.shape[0]
+    if tuple(colors.shape) != (V, 3) or colors.dtype != torch.uint8:
+        raise RuntimeError("cad_render_scene: colors must be [V,3] uint8")
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
+        raise RuntimeError("cad_render_scene: triangles must be [T,3] int32")
+    T = triangles.shape[0]
+    dev = vertices.device
+    tri_begin = np.ascontiguousarray(tri_begin, dtype=np.int32).reshape(-1)
+    O = tri_begin.shape[0] - 1
+    model_scales = np.ascontiguousarray(model_scales, dtype=np.float64).reshape(-1)
+    if O < 1 or model_scales.shape[0] != O:
+        raise RuntimeError("cad_render_scene: tri_begin must be [O+1] and model_scales [O], O >= 1")
+    if not torch.is_tensor(pose):
+        pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
+    if pose.dtype != torch.float64 or pose.dim() not in (3, 4) or pose.shape[1] != O or pose.numel() != pose.shape[0] * O * 12:
+        raise RuntimeError("cad_render_scene: pose must be [F,O,3,4] float64")
+    F = pose.shape[0]
+    if not pose.is_cuda:
+        pose = (pose if pose.is_pinned() else pose.pin_memory()).to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
+    pose = pose.contiguous()
+    if present is not None:
+        if not torch.is_tensor(present):
+            present = torch.from_numpy(np.ascontiguousarray(present, dtype=np.uint8))
+        if present.dtype != torch.uint8 or tuple(present.shape) != (F, O):
+            raise RuntimeError("cad_render_scene: present must be [F,O] uint8")
+        if not present.is_cuda:
+            present = (present if present.is_pinned() else present.pin_memory()).to(dev, non_blocking=True)
+        present = present.contiguous()
+    IH, IW = int(image_dims[0]), int(image_dims[1])
+    proj = np.ascontiguousarray(proj, dtype=np.float64)
+    if proj.shape != (4, 4):
+        raise RuntimeError("cad_render_scene: proj must be 4 x 4")
+    L = _lib.lib()
+    need = L.df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O)
+    if need == 0:
+        raise RuntimeError(f"cad_render_scene: bad sizes F={F}, IH={IH}, IW={IW}, V={V}, T={T}, O={O}")
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < need:
+        raise RuntimeError(f"cad_render_scene: scratch must be a uint8 device tensor of at least {need} bytes")
+    rgb = torch.empty(F, IH, IW, 3, dtype=torch.uint8, device=dev)
+    depth = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    label = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    stats = torch.empty(F, O, 6, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        st = L.df_cad_render_scene(_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, tri_begin.ctypes.data,
+                                   model_scales.ctypes.data, O, pose.data_ptr(), None if present is None else present.data_ptr(),
+                                   proj.ctypes.data, F, IH, IW, int(cull), rgb.data_ptr(), depth.data_ptr(), label.data_ptr(),
+                                   stats.data_ptr(), scratch.data_ptr(), scratch.numel(), _lib.current_stream())
+    _lib.check(st, "cad_render_scene")
+    return rgb, depth, label, stats
+
+
+def cad_scene_mask(label, stats, pairs, mask_mode=0):
+    """The loader's mask of each (frame, object) pair of a rendered scene (``df_cad_scene_mask``): label [F,IH,IW] uint16 and
+    stats [F,O,6] int32 as ``cad_render_scene`` returns them, pairs [N,2] int32 (host or device).  mask_mode 0 = the half-open slice of
+    the object's box, 1 = the pixels the object won.  Returns [N,IH,IW] uint16 on the device; a pair outside the scene gives zeros."""
+    if not (label.is_cuda and stats.is_cuda):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if label.dim() != 3 or label.dtype != torch.uint16 or stats.dim() != 3 or stats.shape[0] != label.shape[0] or stats.shape[2] != 6 or \
+            stats.dtype != torch.int32:
+        raise RuntimeError("cad_scene_mask: label must be [F,IH,IW] uint16 and stats [F,O,6] int32")
+    dev = label.device
+    F, IH, IW = label.shape
+    O = stats.shape[1]
+    if not torch.is_tensor(pairs):
+        pairs = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2))
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0:
+        raise RuntimeError("cad_scene_mask: pairs must be a non-empty [N,2] int32")
+    if not pairs.is_cuda:
+        pairs = (pairs if pairs.is_pinned() else pairs.pin_memory()).to(dev, non_blocking=True)
+    pairs = pairs.contiguous()
+    N = pairs.shape[0]
+    mask = torch.empty(N, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    with _lib.device_guard(dev):
+        st = _lib.lib().df_cad_scene_mask(label.contiguous().data_ptr(), stats.contiguous().data_ptr(), F, O, IH, IW, pairs.data_ptr(), N,
+                                          int(mask_mode), mask.data_ptr(), _lib.current_stream())
+    _lib.check(st, "cad_scene_mask")
+    return mask
+
+
 def color_jitter(frames_u8, plans, out=None):
     """The training colour jitter on the device (``df_color_jitter``): frames_u8 [F,H,W,3] uint8 device tensor, plans [F,8] float32
     (``datasets.augment.plan_row`` rows; host or device).  Returns the jittered uint8 frames, bit-identical to

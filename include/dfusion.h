@@ -378,6 +378,54 @@ int df_cad_render_mesh(const float *vertices, const unsigned char *colors, int V
                        int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multi-object customCAD scenes with occlusion: F frames of O meshes, each with its own pose per frame, drawn into one z-buffer, so that
+ * a target can be covered by another object and a frame can hold distractors (the Unity scenes the reference was fed; the YCB path has
+ * df_compose_frame for it).  The rules of df_cad_render_mesh carry over: no allocation, no synchronisation, the caller's stream; integer
+ * atomics only, so the outputs are bit-reproducible; a frame's outputs do not depend on the other frames of the call.  There are no holes
+ * in this call: occluders play that part.
+ *
+ * df_cad_render_scene_scratch_bytes: F*IH*IW 64-bit keys; 0 for sizes the call refuses (F, IH, IW, V, T as for df_cad_render_mesh;
+ *   O 1..DF_CAD_SCENE_MAX_OBJECTS).
+ * df_cad_render_scene:
+ *   DEVICE: vertices [V][3] float, colors [V][3] u8 and triangles [T][3] int as for df_cad_render_mesh: one shared vertex array and one
+ *   shared triangle array, the indices global; pose [F][O][12] double, row-major [R|t] of object o in frame f; present [F][O] u8
+ *   (0 = object o is not in frame f) or NULL = all present; the outputs; scratch (8-byte aligned).
+ *   HOST, read during the call: proj as for df_cad_render; tri_begin [O+1] int: object o owns the triangles tri_begin[o] ..
+ *   tri_begin[o+1]-1 (an empty range is allowed); model_scale [O] double.  Both tables reach the kernels as launch arguments.
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer (present excepted), bad sizes, O outside 1..64, cull outside 0..1,
+ *   a short or misaligned scratch, a proj that is not of df_cad_render's form, tri_begin[0] != 0, tri_begin[o+1] < tri_begin[o] for
+ *   some o, tri_begin[O] != T.
+ *   All in fp64, one rounding per operation (no fused multiply-add), in exactly this order.
+ *   Per frame f and triangle t = (i0, i1, i2), with o the object that owns t (tri_begin[o] <= t < tri_begin[o+1]):
+ *   S1. Dropped when present != NULL and present[f][o] == 0.
+ *   S2. Steps V2..V5 of df_cad_render_mesh for its three vertices, with R, t = pose[f][o] and model_scale[o] (no vertex is removed by a
+ *       hole), then T1..T6 verbatim: indices outside 0..V-1 or equal, a vertex behind (NO CLIPPING), the edge functions evaluated from
+ *       the lower GLOBAL vertex index to the higher, A == 0 or not finite, cull, the node range, coverage, the code and its limits.
+ *   S3. T7 with the GLOBAL triangle index: atomicMin of key = (uint64)code << 32 | t.  The nearest surface of any object wins; equal
+ *       codes go to the lowest global triangle index, hence to the object listed first.
+ *   Resolve, per pixel: uncovered -> depth 65535, rgb (130, 130, 130), label 0.  Covered -> the owner o of the winning triangle is found
+ *   in tri_begin; depth = code and rgb exactly as in the resolve of df_cad_render_mesh with pose[f][o] and model_scale[o];
+ *   label = o + 1.
+ *   stats [F][O][6] int32: stats[f][o] = {pixels o won, triangles of o that took at least one key test in S3, rmin, rmax, cmin, cmax}:
+ *   the INCLUSIVE box of the pixels o won, four zeros when it won none.  Entry 1 stays as counted then: an object hidden behind others
+ *   reads {0, n > 0, 0, 0, 0, 0}, an absent one six zeros.
+ * df_cad_scene_mask: the loader's mask of pair n = (f, o) = pairs[n], pairs DEVICE [N][2] int, N 1..65535; label and stats are the
+ *   outputs of df_cad_render_scene for F, O, IH, IW.  mask_out [N][IH][IW]:
+ *   mode 0 (box): 65535 on rows rmin..rmax-1 and columns cmin..cmax-1 of stats[f][o] -- the half-open slice of the inclusive box that
+ *   mask_generator.py:21-28 writes, mirrored as it is (pixels of an occluder inside the box are marked: the reference's own rule);
+ *   mode 1 (pixels): 65535 where label[f] == o + 1, the pixels the object actually won; 0 elsewhere.  A pair outside 0..F-1 x 0..O-1
+ *   gives an all-zero mask and nothing is read through it.  DF_ERR_ARG: a null pointer, bad sizes, O outside 1..64, mask_mode outside
+ *   0..1.  No allocation, no synchronisation, the caller's stream. */
+#define DF_CAD_SCENE_MAX_OBJECTS 64
+size_t df_cad_render_scene_scratch_bytes(int F, int IH, int IW, int V, int T, int O);
+int df_cad_render_scene(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const int *tri_begin,
+                        const double *model_scale, int O, const double *pose, const unsigned char *present, const double *proj, int F,
+                        int IH, int IW, int cull, unsigned char *rgb_out, unsigned short *depth_out, unsigned short *label_out,
+                        int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
+int df_cad_scene_mask(const unsigned short *label, const int *stats, int F, int O, int IH, int IW, const int *pairs, int N, int mask_mode,
+                      unsigned short *mask_out, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-time pixel augmentation on whole uint8 frames, bit-identical to the host path (densefusion_amd/datasets/augment.py over PIL;
  * datasets/ycb/dataset.py).  Same conventions as df_preprocess_objects: no allocation, no synchronisation, the caller's stream.
  *

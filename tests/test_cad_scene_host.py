@@ -1,0 +1,206 @@
+"""CPU: the host side of the customCAD scene renderer -- the numpy restatement of ``df_cad_render_scene`` (tests/cad_scene_np.py) shows
+that the small fixture of the device tests holds each case it is meant to cover, and agrees with the single-mesh restatement for one
+object; then ``sample_scene`` and the tool's arguments."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import cad_raster_np as mnp
+import cad_scene_np as snp
+from densefusion_amd.datasets.customCAD import render as cr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IH, IW, NODE_PROJ = snp.IH, snp.IW, snp.NODE_PROJ
+
+
+@pytest.fixture(scope="module")
+def scene():
+    s = snp.small_scene()
+    s["out"] = {cull: snp.render(s["vertices"], s["colors"], s["triangles"], s["tri_begin"], s["scales"], s["poses"], s["present"],
+                                 NODE_PROJ, IH, IW, cull) for cull in (0, 1)}
+    return s
+
+
+def test_the_fixture_has_its_cases(scene):
+    """What the bit-equality test on the device is meant to cover is really in the scene (restatement only; no device work)."""
+    s, parts = scene, scene["parts"]
+    begin, tris = s["tri_begin"], s["triangles"]
+    assert begin.tolist() == [0, 82, 82, 163, 208], "an empty range; no boundary on a multiple of 64, so waves mix objects"
+    assert len({int(snp.owners(begin, t)) for t in range(64, 128)}) == 2 and len({int(snp.owners(begin, t)) for t in range(128, 192)}) == 2
+    assert snp.owners(begin, np.array([81, 82, 162, 163])).tolist() == [0, 2, 2, 3], "the empty object owns nothing"
+    assert s["scales"][0] != s["scales"][2], "two objects with different model_scale"
+    pres = s["present"]
+    assert (pres[2:, 2] == 0).all() and (pres[:2, 2] == 1).all(), "object 2 is absent in two frames"
+    assert (pres[3] == 0).all(), "a frame with nothing present"
+    # one triangle per object with exactly one corner behind the camera of frame 0
+    for o, name in ((0, "behind0"), (2, "behind2"), (3, "behind3")):
+        v = mnp.project_vertices(s["vertices"], s["poses"][0, o], s["scales"][o], None, None, NODE_PROJ, IH, IW)
+        assert v["behind"][tris[parts[name][0]]].sum() == 1 and begin[o] <= parts[name][0] < begin[o + 1], name
+    # the twins are identical on the screen, bit for bit, and belong to objects 0 and 3
+    v0 = mnp.project_vertices(s["vertices"], s["poses"][0, 0], s["scales"][0], None, None, NODE_PROJ, IH, IW)
+    v3 = mnp.project_vertices(s["vertices"], s["poses"][0, 3], s["scales"][3], None, None, NODE_PROJ, IH, IW)
+    t0, t3 = tris[parts["twin0"][0]], tris[parts["twin3"][0]]
+    assert all(np.array_equal(v0[k][t0], v3[k][t3]) for k in ("sx", "sy", "d", "c3")) and not np.array_equal(s["colors"][t0], s["colors"][t3])
+    assert snp.owners(begin, parts["twin0"][0]) == 0 and snp.owners(begin, parts["twin3"][0]) == 3
+    # the quad is larger than the frame: each node is covered by one of its two triangles, front-facing
+    q = parts["quad"]
+    area = lambda t: float(mnp.edge(tris[t, 0], tris[t, 1], v3["sx"], v3["sy"], v3["sx"][tris[t, 2]], v3["sy"][tris[t, 2]]))
+    assert all(area(t) < 0 for t in q)
+    assert v3["sx"][tris[q]].min() < 0 and v3["sx"][tris[q]].max() > IW - 1 and v3["sy"][tris[q]].min() < 0 and v3["sy"][tris[q]].max() > IH - 1
+    py, px = np.arange(IH, dtype=np.float64)[:, None], np.arange(IW, dtype=np.float64)[None, :]
+    over = np.zeros((IH, IW), dtype=bool)
+    for t in q:                                                  # both node ranges are the whole frame: the cooperative walk
+        w = mnp.weights(tris[t, 0], tris[t, 1], tris[t, 2], True, v3["sx"], v3["sy"], px, py)
+        over |= (w[0] >= 0) & (w[1] >= 0) & (w[2] >= 0)
+    assert over.all()
+    for cull in (0, 1):
+        rgb, depth, label, stats, winner, cover = s["out"][cull]
+        # frame 0: the quad is behind everything and fills what nothing else covers; the earlier twin wins every pixel of the pair
+        assert (label[0] > 0).all() and np.isin(winner[0], q).sum() >= 100 and depth[0].max() == depth[0][np.isin(winner[0], q)].min()
+        assert (winner[0] == parts["twin0"][0]).sum() >= 20 and not (winner[0] == parts["twin3"][0]).any()
+        for name in ("behind0", "behind2", "behind3"):
+            assert not np.isin(winner[0], parts[name]).any(), name
+        # frame 0: the spheres interpenetrate: where both are seen alone, each owns some pixels, and the owner changes between
+        # 4-neighbours inside that overlap (the intersection curve)
+        both = cover[0, 0] & cover[0, 2] & np.isin(winner[0], parts["sphere0"] + parts["sphere2"])
+        l0 = label[0].astype(int)
+        assert (both & (l0 == 1)).sum() >= 10 and (both & (l0 == 3)).sum() >= 10
+        seam = (both[:, 1:] & both[:, :-1] & (l0[:, 1:] != l0[:, :-1])).sum() + (both[1:] & both[:-1] & (l0[1:] != l0[:-1])).sum()
+        assert seam >= 5, seam
+        # frame 1: object 2 is wholly hidden behind object 0: it tested keys and won nothing
+        assert stats[1, 2, 0] == 0 and stats[1, 2, 1] > 0 and (stats[1, 2, 2:] == 0).all() and cover[1, 2].sum() >= 20
+        assert (label[1][cover[1, 2]] == 1).sum() >= 20 and np.isin(label[1][cover[1, 2]], (1, 4)).all(), "what it would cover is nearer objects'"
+        # frame 2: the absent object has an all-zero row; the others are there
+        assert (stats[2, 2] == 0).all() and stats[2, 0, 0] > 0 and stats[2, 3, 0] > 0 and not (label[2] == 3).any()
+        # frame 3: nothing present
+        assert (stats[3] == 0).all() and (depth[3] == 65535).all() and (label[3] == 0).all() and (rgb[3] == 130).all()
+        assert (stats[:, 1] == 0).all(), "the empty object"
+        # the statistics are those of the label image
+        for f in range(4):
+            for o in range(4):
+                r, c = np.where(label[f] == o + 1)
+                want = [len(r), stats[f, o, 1]] + ([r.min(), r.max(), c.min(), c.max()] if len(r) else [0, 0, 0, 0])
+                assert stats[f, o].tolist() == want, (f, o)
+        # both walks are taken: triangles of at most 16 nodes and larger ones
+        assert (stats[0, :, 1] > 0).sum() == 3
+    assert not np.array_equal(s["out"][0][3], s["out"][1][3]), "culling changes the key-test counts"
+
+
+def test_one_object_is_the_single_mesh_restatement(scene):
+    """O = 1 and all present: rgb, depth and stats are those of tests/cad_raster_np.py; the two masks are its masks."""
+    s = scene
+    b, e = s["tri_begin"][3], s["tri_begin"][4]
+    tris = s["triangles"][b:e]
+    poses = s["poses"][:3, 3]
+    for cull in (0, 1):
+        got = snp.render(s["vertices"], s["colors"], tris, [0, len(tris)], s["scales"][3:], poses[:, None], None, NODE_PROJ, IH, IW, cull)
+        for mode in (0, 1):
+            want = mnp.render(s["vertices"], s["colors"], tris, poses, 10.0, None, NODE_PROJ, IH, IW, cull, mode)
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and np.array_equal(got[3][:, 0], want[3])
+            assert np.array_equal(got[4], want[4])
+            assert np.array_equal(snp.scene_mask(got[2], got[3], [[f, 0] for f in range(3)], mode), want[2])
+    assert (want[3][:, 0] > 0).all()
+
+
+def test_scene_mask_restated():
+    label = np.zeros((2, 6, 7), dtype=np.uint16)
+    label[1, 1:4, 2:6] = 2
+    label[1, 2, 3] = 1
+    stats = np.zeros((2, 2, 6), dtype=np.int32)
+    stats[1, 1] = [11, 3, 1, 3, 2, 5]
+    stats[1, 0] = [1, 1, 2, 2, 3, 3]
+    m0 = snp.scene_mask(label, stats, [[1, 1], [1, 0], [0, 1], [2, 0], [0, -1], [1, 2]], 0)
+    assert m0[0].sum() == 65535 * 2 * 3 and (m0[0, 1:3, 2:5] == 65535).all(), "half-open, as mask_generator.py writes it"
+    assert not m0[1:].any(), "a one-pixel box has an empty half-open slice; nothing won; pairs outside the scene"
+    m1 = snp.scene_mask(label, stats, [[1, 1], [1, 0], [0, 1], [2, 0]], 1)
+    assert np.array_equal(m1[0] == 65535, label[1] == 2) and m1[1].sum() == 65535 and not m1[2:].any()
+
+
+KW = dict(hole_mean=30.0, hole_std=10.0)
+
+
+def test_sample_scene_is_deterministic_and_keeps_the_targets_view():
+    for seed in (0, 1, 7, 123456):
+        for target in (0, 2):
+            want = cr.sample_view(seed, 642, [0.0, 0.0, 4.0], 1.0, 3, **KW)
+            state = np.random.get_state()[1].copy()
+            views, holes = cr.sample_scene(seed, 642, [0.0, 0.0, 4.0], 1.0, 4, target, 3, **KW)
+            assert np.array_equal(np.random.get_state()[1], state), "the other objects are drawn from a generator of their own"
+            here, axis, angle, xyz = views[target]
+            assert here is True and np.array_equal(axis, want[0]) and angle == want[1] and np.array_equal(xyz, want[2]) and holes == want[3]
+            again, _ = cr.sample_scene(seed, 642, [0.0, 0.0, 4.0], 1.0, 4, target, 3, **KW)
+            for a, b in zip(views, again):
+                assert a[0] == b[0] and np.array_equal(a[1], b[1]) and a[2] == b[2] and np.array_equal(a[3], b[3])
+            assert len(views) == 4
+            for o, (here, axis, angle, c) in enumerate(views):
+                assert abs(np.linalg.norm(axis) - 1) < 1e-12 and 0 <= angle < 2 * np.pi
+                if o != target:
+                    off = c - xyz
+                    assert (np.abs(off[:2]) <= 0.8).all() and abs(off[2]) <= 0.8 and np.abs(off).min() > 0
+    a, _ = cr.sample_scene(5, 642, [0.0, 0.0, 4.0], 1.0, 3, 0, 3, **KW)
+    b, _ = cr.sample_scene(6, 642, [0.0, 0.0, 4.0], 1.0, 3, 0, 3, **KW)
+    assert not np.array_equal(a[1][3], b[1][3])
+    # scene_scale scales the offsets; p_present 0 and 1 are honoured; the draws do not depend on presence
+    half, _ = cr.sample_scene(5, 642, [0.0, 0.0, 4.0], 0.5, 3, 0, 3, **KW)
+    base = cr.sample_view(5, 642, [0.0, 0.0, 4.0], 0.5, 3, **KW)[2]
+    assert np.allclose(half[1][3] - base, 0.5 * (a[1][3] - a[0][3]), rtol=0, atol=1e-15)
+    none, _ = cr.sample_scene(5, 642, [0.0, 0.0, 4.0], 1.0, 3, 0, 3, p_present=0.0, **KW)
+    every, _ = cr.sample_scene(5, 642, [0.0, 0.0, 4.0], 1.0, 3, 0, 3, p_present=1.0, **KW)
+    assert [v[0] for v in none] == [True, False, False] and [v[0] for v in every] == [True, True, True]
+    assert np.array_equal(none[2][3], every[2][3])
+
+
+def test_sample_scene_is_pinned():
+    """The stream of the other objects: ``default_rng((seed, 1))``, per object random, 3 x uniform(-1, 1), uniform(0, 2 pi), then the
+    three offsets -- restated here draw by draw."""
+    views, _ = cr.sample_scene(11, 100, [0.1, -0.2, 4.0], 2.0, 3, 1, 3, p_present=0.4, lateral=0.3, depth=0.5, **KW)
+    rng = np.random.default_rng((11, 1))
+    centre = cr.sample_view(11, 100, [0.1, -0.2, 4.0], 2.0, 3, **KW)[2]
+    for o in (0, 2):
+        here = bool(rng.random() < 0.4)
+        axis = rng.uniform(-1, 1, size=3)
+        axis /= np.linalg.norm(axis)
+        angle = float(rng.uniform(0, np.pi * 2))
+        off = np.array([rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3), rng.uniform(-0.5, 0.5)]) * 2.0
+        assert views[o][0] == here and np.array_equal(views[o][1], axis) and views[o][2] == angle and np.array_equal(views[o][3], centre + off)
+
+
+def test_scene_renderer_checks_its_meshes_on_the_host():
+    v, c = np.zeros((4, 3), dtype=np.float32), np.zeros((4, 3), dtype=np.uint8)
+    good = np.array([[0, 1, 2]])
+    with pytest.raises(ValueError, match="outside 0..3"):
+        cr.CadSceneRenderer([(v, good, c), (v, np.array([[0, 1, 4]]), c)], NODE_PROJ, (IH, IW), [10.0, 10.0])
+    with pytest.raises(ValueError):
+        cr.CadSceneRenderer([(v, good, c)], NODE_PROJ, (IH, IW), [10.0, 10.0])
+    with pytest.raises(ValueError):
+        cr.CadSceneRenderer([], NODE_PROJ, (IH, IW), [])
+
+
+def test_tool_arguments(capsys):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        tool = importlib.import_module("render_cad_dataset")
+    finally:
+        sys.path.pop(0)
+    ap = tool.build_parser()
+    opt = ap.parse_args(["--model", "m.ply", "--output_root", "out"])
+    assert opt.model == ["m.ply"] and opt.scene is False and opt.distractor == [] and opt.raster == "points" and opt.cull == 1 and \
+        opt.splat == 1 and opt.points == 0 and opt.mask == "box" and opt.min_pixels == 500, "single-object parsing is unchanged"
+    opt = ap.parse_args(["--scene", "--model", "a.ply", "b.ply", "--distractor", "d.ply", "e.ply", "--output_root", "out", "--min_visible", "0.5",
+                         "--p_present", "0.9", "--mask", "pixels"])
+    assert opt.scene and opt.model == ["a.ply", "b.ply"] and opt.distractor == ["d.ply", "e.ply"] and opt.min_visible == 0.5 and opt.p_present == 0.9
+    assert ap.get_default("min_visible") == 0.3
+    # several models, or a distractor, without --scene: refused before anything is read or written
+    for argv in (["--model", "a.ply", "b.ply", "--output_root", "out"], ["--model", "a.ply", "--distractor", "d.ply", "--output_root", "out"]):
+        with pytest.raises(SystemExit) as e:
+            tool.main(argv)
+        assert e.value.code == 2 and "--scene" in capsys.readouterr().err
+    assert not os.path.exists("out")
+    # the point path's flags do not apply to scenes
+    for extra in (["--splat", "2"], ["--points", "5000"], ["--raster", "mesh"]):
+        with pytest.raises(SystemExit) as e:
+            tool.main(["--scene", "--model", "a.ply", "b.ply", "--output_root", "out"] + extra)
+        assert e.value.code == 2 and "--scene" in capsys.readouterr().err

@@ -9,6 +9,18 @@ cloud, and with ``--cpu`` the time per frame of the numpy restatement (tests/cad
 ``--points`` points drawn from that icosphere by area with their faces' normals.
 
     python tools/cad_render_bench.py --mesh --subdiv 7 --points 1000000 --splat 1 --chunk 32
+
+``--scene`` times ``df_cad_render_scene`` on one icosphere of ``--subdiv`` subdivisions (the target of ``render.sample_scene``), four
+icospheres of subdivision 5 and the 12-triangle box, all present, next to the sum of the six ``df_cad_render_mesh`` calls that draw each
+mesh alone at the same poses (without occlusion: what the single-object path costs for the same work).
+
+    python tools/cad_render_bench.py --scene --subdiv 7 --chunk 32
+
+``--visibility N`` draws the scenes of seeds 0..N-1 as tools/render_cad_dataset.py --scene does for the meshes of its test
+(tests/cad_scene_np.py: two spheres as models, a box as distractor, 96 x 144 frames) and prints the histogram of the visible fractions
+of the models that are present, in ten bins.
+
+    python tools/cad_render_bench.py --visibility 256
 """
 from __future__ import annotations
 
@@ -82,8 +94,72 @@ def mesh_bench(opt):
     return res
 
 
+def scene_bench(opt):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cad_raster_np as mnp
+    rng = np.random.default_rng(0)
+    e = 60.0 / np.sqrt(3.0)                                   # the cube inscribed in the target's sphere
+    bv = np.array([[x, y, z] for z in (-e, e) for y in (-e, e) for x in (-e, e)])
+    bf = np.array([[0, 2, 1], [1, 2, 3], [4, 5, 6], [5, 7, 6], [0, 1, 4], [1, 5, 4], [2, 6, 3], [3, 6, 7], [0, 4, 2], [2, 4, 6], [1, 3, 5], [3, 7, 5]])
+    shapes = [mnp.icosphere(opt.subdiv, 60.0)] + [mnp.icosphere(5, 40.0) for _ in range(4)] + [(bv, bf)]
+    meshes = [(v, f, rng.integers(0, 256, (len(v), 3), dtype=np.uint8)) for v, f in shapes]
+    O = len(meshes)
+    poses = np.zeros((opt.chunk, O, 3, 4))
+    for s in range(opt.chunk):
+        views, _ = cr.sample_scene(s, len(meshes[0][0]), (0.0, 0.0, 4.0), 1.0, O, 0, hole_mean=30.0, hole_std=10.0, p_present=1.0)
+        for o, (_, axis, angle, xyz) in enumerate(views):
+            R, t = cr.view_pose(axis, angle, xyz, np.zeros(3), 10.0)
+            poses[s, o] = np.concatenate([R, t[:, None]], axis=1)
+    dims = (opt.height, opt.width)
+    scene = cr.CadSceneRenderer(meshes, PROJ, dims, [10.0] * O)
+    times, out = timed(lambda: scene.render(poses, cull=1), opt.calls)
+    stats = out[3].cpu().numpy()
+    res = {"frame": list(dims), "chunk": opt.chunk, "objects": O, "triangles": [int(len(m[1])) for m in meshes],
+           "scene": {"device_ms_per_frame_median": float(np.median(times)) / opt.chunk, "device_ms_per_call": [round(t, 3) for t in times],
+                     "pixels_won_mean": [float(x) for x in stats[:, :, 0].mean(axis=0)],
+                     "triangles_tested_mean": [float(x) for x in stats[:, :, 1].mean(axis=0)]},
+           "solo": []}
+    for o, (v, f, c) in enumerate(meshes):
+        r = cr.CadMeshRenderer(v, f, c, PROJ, dims)
+        times, out = timed(lambda: r.render(poses[:, o], cull=1, mask="box"), opt.calls)
+        res["solo"].append({"triangles": int(len(f)), "device_ms_per_frame_median": float(np.median(times)) / opt.chunk,
+                            "covered_mean": float(out[3].cpu().numpy()[:, 0].mean())})
+    res["solo_sum_device_ms_per_frame"] = float(sum(x["device_ms_per_frame_median"] for x in res["solo"]))
+    print(json.dumps(res))
+    return res
+
+
+def visibility(opt):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cad_scene_np as snp
+    meshes = snp.tool_meshes()
+    O, n_targets, dims = len(meshes), 2, (96, 144)
+    centroids = [m[0].astype(np.float64).mean(axis=0) for m in meshes]
+    scene = cr.CadSceneRenderer(meshes, PROJ, dims, [10.0] * O)
+    poses, present = np.zeros((opt.visibility, O, 3, 4)), np.zeros((opt.visibility, O), dtype=np.uint8)
+    for s in range(opt.visibility):
+        views, _ = cr.sample_scene(s, len(meshes[s % n_targets][0]), (0.0, 0.0, 4.0), 1.0, O, s % n_targets, hole_mean=30.0, hole_std=10.0)
+        for o, (here, axis, angle, xyz) in enumerate(views):
+            R, t = cr.view_pose(axis, angle, xyz, centroids[o], 10.0)
+            poses[s, o], present[s, o] = np.concatenate([R, t[:, None]], axis=1), here
+    won = scene.render(poses, present=present)[3].cpu().numpy()[:, :, 0]
+    frac = []
+    for k in range(n_targets):
+        alone = np.zeros_like(present)
+        alone[:, k] = present[:, k]
+        solo = scene.render(poses, present=alone)[3].cpu().numpy()[:, k, 0]
+        frac.extend((won[:, k][solo > 0] / solo[solo > 0]).tolist())
+    hist = np.histogram(frac, bins=10, range=(0.0, 1.0))[0]
+    res = {"seeds": opt.visibility, "frame": list(dims), "views": len(frac), "visible_fraction_histogram_10_bins": hist.tolist(),
+           "wholly_visible": int(sum(1 for x in frac if x == 1.0)), "mean": float(np.mean(frac))}
+    print(json.dumps(res))
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scene", action="store_true", help="time df_cad_render_scene (six objects) next to the sum of the solo df_cad_render_mesh calls")
+    ap.add_argument("--visibility", type=int, default=0, help="histogram of the visible fractions sample_scene gives over this many seeds")
     ap.add_argument("--mesh", action="store_true", help="time df_cad_render_mesh (icosphere, box) and the point path on points of that icosphere")
     ap.add_argument("--subdiv", type=int, default=7, help="--mesh: icosphere subdivisions (20 * 4^n triangles)")
     ap.add_argument("--points", type=int, default=1000000)
@@ -94,6 +170,10 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--cpu", action="store_true", help="also time the numpy restatement on one frame")
     opt = ap.parse_args(argv)
+    if opt.visibility:
+        return visibility(opt)
+    if opt.scene:
+        return scene_bench(opt)
     if opt.mesh:
         return mesh_bench(opt)
     rng = np.random.default_rng(0)

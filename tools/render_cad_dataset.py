@@ -18,6 +18,19 @@ Hole radii are in model file units (the reference's 0.03 / 0.01 apply to a model
 model's triangles themselves (``df_cad_render_mesh``: watertight, the depth exact on each facet, no splat radius): the model must have
 faces, the hole indices of ``sample_view`` name vertices, ``--cull 1`` drops the triangles that face away, and ``models/obj_XX.ply``
 receives the mesh (vertices and faces), which the loader samples by area.
+
+    python tools/render_cad_dataset.py --scene --model A.ply B.ply ... [--distractor D.ply ...] --output_root ROOT [--min_visible 0.3]
+
+renders frames that hold several meshes at once (``df_cad_render_scene``: one z-buffer, so objects cover each other) and writes one tree
+per ``--model``: model k is object k + 1, ``data/%02d`` and ``models/obj_%02d.ply``.  Distractors are drawn and can occlude; they are
+never targets and get no tree.  The view of seed s is ``render.sample_scene``: object s mod (number of models) is shown exactly where the
+single-object tool shows it for that seed, the others are present with ``--p_present`` at a drawn offset from it (``--lateral``,
+``--depth``).  Each chunk takes one scene call plus one call per model with only that model present, which gives its unoccluded pixel
+count at the same poses: visible fraction = pixels won in the scene / pixels won alone.  A frame goes into a model's tree when the model
+is present, won at least ``--min_pixels`` pixels and is visible to at least ``--min_visible``; its rgb and depth files are the shared
+scene's, its mask, record and numbering its own.  No holes are cut in scenes.  ``--mask box`` marks the occluder's pixels inside the box
+as the object -- the reference's own rule (mask_generator.py:21-28) -- so the loader's cloud then holds points of the occluder;
+``--mask pixels`` marks only the pixels the object won and is the mode that keeps them out.
 """
 from __future__ import annotations
 
@@ -42,7 +55,14 @@ DEFAULT_PROJ = [[1.16667, 0.0, 0.0, 0.0], [0.0, 2.48814, 0.0, 0.0], [0.0, 0.0, 0
 
 def build_parser():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", type=str, required=True, help="PLY with red / green / blue (and optionally nx / ny / nz) vertex properties; cloud or mesh")
+    ap.add_argument("--model", type=str, nargs="+", required=True,
+                    help="PLY with red / green / blue (and optionally nx / ny / nz) vertex properties; cloud or mesh.  Several only with --scene")
+    ap.add_argument("--scene", action="store_true", help="render the models together, with occlusion: one tree per model from shared frames")
+    ap.add_argument("--distractor", type=str, nargs="*", default=[], help="--scene: meshes that are drawn and can occlude, never targets")
+    ap.add_argument("--min_visible", type=float, default=0.3, help="--scene: smallest visible fraction of a frame that enters a model's tree")
+    ap.add_argument("--p_present", type=float, default=0.7, help="--scene: probability that an object other than the view's own is in the frame")
+    ap.add_argument("--lateral", type=float, default=0.8, help="--scene: largest sideways offset of the others, units of transforms.txt")
+    ap.add_argument("--depth", type=float, default=0.8, help="--scene: largest offset of the others towards or away from the camera")
     ap.add_argument("--output_root", type=str, required=True)
     ap.add_argument("--object", type=int, default=1, help="object directory data/XX and models/obj_XX.ply")
     ap.add_argument("--frames", type=int, default=2000)
@@ -105,9 +125,132 @@ def load_model(path, n_points):
     return pts, nrm, col
 
 
+def write_split(sub, written, seed):
+    """train_test_generator.py:17-28: the shuffled frame numbers, 80 / 20"""
+    nums = list(range(written))
+    random.seed(seed)
+    random.shuffle(nums)
+    cut = int(len(nums) / 100. * 80)
+    for name, part in (("train.txt", nums[:cut]), ("test.txt", nums[cut:])):
+        with open(os.path.join(sub, name), "w") as f:
+            f.write("".join("%d\n" % n for n in part))
+
+
+def main_scene(opt, ap):
+    """--scene: one tree per model from shared frames of all models and distractors."""
+    if opt.splat != ap.get_default("splat") or opt.points != ap.get_default("points") or opt.raster != ap.get_default("raster"):
+        ap.error("--scene draws the triangles of every model: --raster, --splat and --points do not apply")
+    if not torch.cuda.is_available():
+        raise SystemExit("render_cad_dataset needs a GPU (no CPU path)")
+    n_targets = len(opt.model)
+    meshes = []
+    for path in list(opt.model) + list(opt.distractor):
+        pts, tris, col = cr.read_colored_mesh(path)
+        if len(tris) == 0:
+            raise SystemExit(f"{path}: --scene needs models with faces")
+        meshes.append((pts, tris, col))
+    O = len(meshes)
+    proj = read_proj_mat(opt.proj_mat) if opt.proj_mat else np.array(DEFAULT_PROJ)
+    os.makedirs(os.path.join(opt.output_root, "models"), exist_ok=True)
+    subs = [os.path.join(opt.output_root, "data", "%02d" % (k + 1)) for k in range(n_targets)]
+    for k, sub in enumerate(subs):
+        for d in ("rgb", "depth", "mask", "meta"):
+            os.makedirs(os.path.join(sub, d), exist_ok=True)
+        write_mesh_ply(os.path.join(opt.output_root, "models", "obj_%02d.ply" % (k + 1)), meshes[k][0], meshes[k][1])
+        with open(os.path.join(sub, "meta", "proj_mat.txt"), "w") as f:
+            f.write("".join("\t".join(repr(float(v)) for v in row) + "\n" for row in proj) + "\n")
+    proj = read_proj_mat(os.path.join(subs[0], "meta", "proj_mat.txt"))      # what the loader will read
+    renderer = cr.CadSceneRenderer(meshes, proj, (opt.height, opt.width), [opt.model_scale] * O)
+    centroids = [m[0].astype(np.float64).mean(axis=0) for m in meshes]
+
+    def save(sub, n, rgb, depth, mask):
+        Image.fromarray(rgb).save(os.path.join(sub, "rgb", "FrameBuffer_%04d.png" % n))
+        Image.fromarray(depth).save(os.path.join(sub, "depth", "Depth_%04d.png" % n))
+        Image.fromarray(mask).save(os.path.join(sub, "mask", "%04d.png" % n))
+
+    records = [[] for _ in range(n_targets)]
+    visible = [[] for _ in range(n_targets)]
+    seeds = [[] for _ in range(n_targets)]
+    skipped, seed, device_ms = 0, opt.seed, []
+    t_start = time.time()
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        while any(len(r) < opt.frames for r in records):
+            if skipped > opt.max_skipped:
+                raise SystemExit(f"{skipped} views skipped for fewer than {opt.min_pixels} pixels or less than {opt.min_visible} visible: "
+                                 "check --center, --scene_scale, --lateral, --depth and the camera")
+            texts, poses, present = [], [], np.zeros((opt.chunk, O), dtype=np.uint8)
+            for j, s in enumerate(range(seed, seed + opt.chunk)):
+                primary = s % n_targets
+                views, _ = cr.sample_scene(s, len(meshes[primary][0]), opt.center, opt.scene_scale, O, primary, opt.max_holes,
+                                           hole_mean=opt.hole_mean, hole_std=opt.hole_std, p_present=opt.p_present, lateral=opt.lateral,
+                                           depth=opt.depth)
+                row_t, row_p = [], []
+                for o, (here, axis, angle, xyz) in enumerate(views):
+                    text = record_text(0, *cr.pose_to_transform(*cr.view_pose(axis, angle, xyz, centroids[o], opt.model_scale)))
+                    R, t = cr.transform_to_pose(*parse_record(text))          # rendered from the record's own values
+                    row_t.append(text); row_p.append(np.concatenate([R, t[:, None]], axis=1))
+                    present[j, o] = here
+                texts.append(row_t); poses.append(np.stack(row_p))
+            seed += opt.chunk
+            poses = np.stack(poses)
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            rgb, depth, label, stats = renderer.render(poses, present=present, cull=opt.cull)
+            ev1.record()
+            rows = stats.cpu().numpy()                                        # the chunk's read-backs before its frames
+            device_ms.append(ev0.elapsed_time(ev1))
+            solo = np.zeros((opt.chunk, n_targets), dtype=np.int64)
+            for k in range(n_targets):                                        # the same poses with model k alone: its unoccluded pixels
+                alone = np.zeros_like(present)
+                alone[:, k] = present[:, k]
+                solo[:, k] = renderer.render(poses, present=alone, cull=opt.cull)[3][:, k, 0].cpu().numpy()
+            pairs = []
+            for j in range(opt.chunk):
+                for k in range(n_targets):
+                    if len(records[k]) + sum(1 for p in pairs if p[1] == k) >= opt.frames or not present[j, k]:
+                        continue
+                    frac = rows[j, k, 0] / solo[j, k] if solo[j, k] > 0 else 0.0
+                    if rows[j, k, 0] < opt.min_pixels or frac < opt.min_visible:
+                        skipped += 1
+                        continue
+                    pairs.append((j, k, frac))
+            if not pairs:
+                continue
+            mask = renderer.masks(label, stats, np.array([[j, k] for j, k, _ in pairs], dtype=np.int32), mask=opt.mask).cpu().numpy()
+            rgb, depth = rgb.cpu().numpy(), depth.cpu().numpy()
+            pending = []
+            for n, (j, k, frac) in enumerate(pairs):
+                pending.append(pool.submit(save, subs[k], len(records[k]), rgb[j], depth[j], mask[n]))
+                records[k].append(parse_record(texts[j][k]))
+                visible[k].append(float(frac)); seeds[k].append(seed - opt.chunk + j)
+            for p in pending:
+                p.result()
+    for k, sub in enumerate(subs):
+        with open(os.path.join(sub, "meta", "transforms.txt"), "w") as f:
+            for idx, (pos, quat) in enumerate([records[k][0]] + records[k]):
+                f.write(record_text(idx, pos, quat))
+        write_split(sub, len(records[k]), opt.seed)
+    wall = time.time() - t_start
+    per_view = float(np.median(device_ms)) / opt.chunk
+    summary = {"objects": {}, "skipped": skipped, "device_ms_per_view": per_view}
+    for k in range(n_targets):
+        summary["objects"][k + 1] = {"written": len(records[k]), "mean_visible": float(np.mean(visible[k])), "visible": visible[k],
+                                     "seeds": seeds[k]}
+        print(f"object {k + 1}: frames written: {len(records[k])}, mean visible fraction: {np.mean(visible[k]):.3f}")
+    print(f"views skipped: {skipped}, device time per rendered scene: {per_view:.3f} ms (HIP events, the median of {len(device_ms)} calls; "
+          f"{O} objects, {int(renderer.tri_begin[-1])} triangles, {opt.height} x {opt.width}, cull {opt.cull}, chunk {opt.chunk}); "
+          f"wall {wall / max(sum(len(r) for r in records), 1) * 1e3:.1f} ms per frame written")
+    return summary
+
+
 def main(argv=None):
     ap = build_parser()
     opt = ap.parse_args(argv)
+    if opt.scene:
+        return main_scene(opt, ap)
+    if len(opt.model) != 1 or opt.distractor:
+        ap.error("several --model paths and --distractor need --scene; without it exactly one model is rendered")
+    opt.model = opt.model[0]
     mesh = opt.raster == "mesh"
     if mesh and (opt.splat != ap.get_default("splat") or opt.points != ap.get_default("points")):
         ap.error("--splat and --points belong to --raster points; --raster mesh draws the triangles themselves")
@@ -185,13 +328,7 @@ def main(argv=None):
     with open(os.path.join(sub, "meta", "transforms.txt"), "w") as f:
         for idx, (pos, quat) in enumerate([records[0]] + records):
             f.write(record_text(idx, pos, quat))
-    nums = list(range(written))
-    random.seed(opt.seed)
-    random.shuffle(nums)
-    cut = int(len(nums) / 100. * 80)
-    for name, part in (("train.txt", nums[:cut]), ("test.txt", nums[cut:])):
-        with open(os.path.join(sub, name), "w") as f:
-            f.write("".join("%d\n" % n for n in part))
+    write_split(sub, written, opt.seed)
     wall = time.time() - t_start
     per_view = float(np.median(device_ms)) / opt.chunk            # the median call: the first one also loads the kernels
     what = (f"{len(tris)} triangles", f"cull {opt.cull}") if mesh else (f"{len(pts)} points", f"splat {opt.splat}")
