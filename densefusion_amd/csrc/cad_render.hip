@@ -6,6 +6,7 @@
 // Four steps on the caller's stream: the keys are set to all-ones; splat_kernel takes atomicMin of (code << 32 | point index) over every
 // footprint pixel (grid = point blocks x frames); resolve_kernel turns keys into depth / colour and reduces count and box per wave before
 // its integer atomics, like frame_stats_kernel of cad.hip (finish_kernel then decodes the F rows in place); mask_kernel fills the mask.
+// The pose record, the hole rule, the horizon and the host side of the entry point are those of cad_frame.h, shared with the mesh calls.
 #include "cad_frame.h"
 
 namespace df {
@@ -19,35 +20,21 @@ __global__ __launch_bounds__(RB) void splat_kernel(const float *__restrict__ poi
                                                    Camera cam, int IH, int IW, int splat, unsigned long long *__restrict__ keys,
                                                    int *__restrict__ stats) {
   const int f = f0 + blockIdx.y;
-  const double *T = pose + (size_t)f * 12;
-  double R[3][3], t[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    R[j][0] = T[j * 4]; R[j][1] = T[j * 4 + 1]; R[j][2] = T[j * 4 + 2]; t[j] = T[j * 4 + 3];
-  }
+  const Pose M = load_pose(pose + (size_t)f * 12);
   unsigned long long *kf = keys + (size_t)f * IH * IW;
   int reached = 0;
   for (long i = (long)blockIdx.x * RB + threadIdx.x; i < P; i += (long)gridDim.x * RB) {
+    if (vertex_cut(points, i, holes, blockIdx.y * K, K)) continue;            // 1. holes
     const double mx = (double)points[i * 3], my = (double)points[i * 3 + 1], mz = (double)points[i * 3 + 2];
-    bool cut = false;                                                         // 1. holes
-    for (int k = 0; k < K; ++k) {
-      const int h = holes.idx[blockIdx.y * K + k];
-      if (h < 0) continue;
-      const double cx = (double)points[(size_t)h * 3], cy = (double)points[(size_t)h * 3 + 1], cz = (double)points[(size_t)h * 3 + 2];
-      const double r = holes.r[blockIdx.y * K + k];
-      const double dx = mx - cx, dy = my - cy, dz = mz - cz;
-      cut |= ((dx * dx + dy * dy) + dz * dz) <= r * r;
-    }
-    if (cut) continue;
     const double sx = mx * model_scale, sy = my * model_scale, sz = mz * model_scale;      // 2. camera space
     double X[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) X[j] = ((R[j][0] * sx + R[j][1] * sy) + R[j][2] * sz) + t[j];
+    for (int j = 0; j < 3; ++j) X[j] = ((M.R[j][0] * sx + M.R[j][1] * sy) + M.R[j][2] * sz) + M.t[j];
     if (normals) {                                                            // 3. facing test on the point's own view ray
       const double nx = (double)normals[i * 3], ny = (double)normals[i * 3 + 1], nz = (double)normals[i * 3 + 2];
       double n[3];
 #pragma unroll
-      for (int j = 0; j < 3; ++j) n[j] = (R[j][0] * nx + R[j][1] * ny) + R[j][2] * nz;
+      for (int j = 0; j < 3; ++j) n[j] = (M.R[j][0] * nx + M.R[j][1] * ny) + M.R[j][2] * nz;
       if (!(((n[0] * (-X[0]) + n[1] * (-X[1])) + n[2] * (-X[2])) > 0.0)) continue;
     }
     const double c0 = ((cam.p0[0] * X[0] + cam.p0[1] * X[1]) + cam.p0[2] * X[2]) + cam.p0[3];      // 4. clip space
@@ -89,8 +76,7 @@ __global__ __launch_bounds__(RB) void resolve_kernel(const unsigned long long *_
     const unsigned long long key = kf[p];
     unsigned char *px = cf + (size_t)p * 3;
     if (key == NO_KEY) {
-      df[p] = 65535;                                                          // the horizon: above every code
-      px[0] = 130; px[1] = 130; px[2] = 130;
+      write_horizon(df + p, px);
       continue;
     }
     const unsigned char *c = colors + (size_t)(unsigned)(key & 0xffffffffu) * 3;
@@ -119,33 +105,22 @@ extern "C" int df_cad_render(const float *points, const float *normals, const un
                              int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream) {
   if (!points || !colors || !pose || !proj || !rgb_out || !depth_out || !mask_out || !stats_out || !scratch)
     return set_error(DF_ERR_ARG, "cad_render: null pointer");
-  if (K > 0 && (!hole_idx || !hole_r)) return set_error(DF_ERR_ARG, "cad_render: null pointer (K holes need hole_idx and hole_r)");
-  if (K < 0 || K > MAX_HOLES) return set_error(DF_ERR_ARG, "cad_render: K = %d holes per frame outside 0..%d", K, MAX_HOLES);
+  if (int e = check_hole_args("cad_render", hole_idx, hole_r, K)) return e;
   if (P <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "cad_render: bad sizes");
   if (splat < 0 || splat > 3) return set_error(DF_ERR_ARG, "cad_render: splat %d outside 0..3", splat);
   if (mask_mode != 0 && mask_mode != 1) return set_error(DF_ERR_ARG, "cad_render: mask_mode %d is neither 0 (box) nor 1 (pixels)", mask_mode);
-  if (scratch_bytes < df_cad_render_scratch_bytes(F, IH, IW) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
-    return set_error(DF_ERR_ARG, "cad_render: scratch too small or not 8-byte aligned");
-  if (!proj_form_ok(proj))
-    return set_error(DF_ERR_ARG, "cad_render: the projection matrix needs rows 2 = (0, 0, p22, p23) and 3 = (0, 0, -1, 0)");
-  for (long j = 0; j < (long)F * K; ++j)
-    if (hole_idx[j] >= P) return set_error(DF_ERR_ARG, "cad_render: hole index %d of frame %ld is not below P = %d", hole_idx[j], j / K, P);
+  if (int e = check_scratch_and_proj("cad_render", scratch, scratch_bytes, df_cad_render_scratch_bytes(F, IH, IW), proj)) return e;
+  if (int e = check_hole_indices("cad_render", hole_idx, F, K, 'P', P)) return e;
   hipStream_t st = to_stream(stream);
   const Camera cam = make_camera(proj);
   const long npix = (long)IH * IW;
-  if (hipMemsetAsync(scratch, 0xff, (size_t)F * npix * sizeof(unsigned long long), st) != hipSuccess ||
-      hipMemsetAsync(stats_out, 0, sizeof(int) * 6 * F, st) != hipSuccess)
-    return check_launch("cad_render (clear)");
+  if (!clear_frames(scratch, F, npix, stats_out, F, st)) return check_launch("cad_render (clear)");
   unsigned long long *keys = static_cast<unsigned long long *>(scratch);
-  const int pb = cdiv(P, RB) < SPLAT_MAX_BLOCKS ? cdiv(P, RB) : SPLAT_MAX_BLOCKS;
-  const int per_launch = K > 0 ? MAX_HOLES / K : F;                        // frames per splat launch: their holes fit one Holes
-  for (int f0 = 0; f0 < F; f0 += per_launch) {
-    const int nf = F - f0 < per_launch ? F - f0 : per_launch;
-    const Holes holes = make_holes(hole_idx, hole_r, K, f0, nf);
+  const int pb = grid_blocks(P, SPLAT_MAX_BLOCKS), xb = grid_blocks(npix, RESOLVE_MAX_BLOCKS);
+  for_hole_batches(hole_idx, hole_r, K, F, [&](int f0, int nf, const Holes &holes) {
     hipLaunchKernelGGL(splat_kernel, dim3(pb, nf), dim3(RB), 0, st, points, normals, P, pose, model_scale, holes, K, f0, cam, IH, IW, splat,
                        keys, stats_out);
-  }
-  const int xb = cdiv(npix, RB) < RESOLVE_MAX_BLOCKS ? cdiv(npix, RB) : RESOLVE_MAX_BLOCKS;
+  });
   hipLaunchKernelGGL(resolve_kernel, dim3(xb, F), dim3(RB), 0, st, keys, colors, IH, IW, rgb_out, depth_out, stats_out);
   hipLaunchKernelGGL(finish_kernel, dim3(cdiv(F, RB)), dim3(RB), 0, st, F, IH, IW, stats_out);
   hipLaunchKernelGGL(mask_kernel, dim3(xb, F), dim3(RB), 0, st, depth_out, stats_out, IH, IW, mask_mode, mask_out);

@@ -4,12 +4,13 @@
 // numpy and the outputs are compared bit for bit.  Built with -ffp-contract=off: no fused multiply-add anywhere.
 //
 // Steps on the caller's stream: the keys are set to all-ones and the stats to zero; scene_raster_kernel (grid = triangle blocks x frames)
-// keeps raster_kernel's shape -- one triangle per lane, small node ranges walked by the lane, large ones by the whole wave after a
-// ballot, the plain load before atomicMin -- with the owner looked up in the tri_begin table and the pose and model scale per lane, since
-// the object ranges do not align to waves.  scene_resolve_kernel finds the winner's owner in the same table, writes depth, colour and
-// label, and counts pixels and boxes per owner: a lane gathers for one owner at a time, the wave reduces per distinct owner when a lane
-// meets another one, then one set of integer atomics (the max-encoded scheme of reduce_frame_stats).  scene_finish_kernel decodes the
-// boxes.  The object table (tri_begin, model_scale) is checked on the host and travels as a launch argument.
+// runs the set-up and the walks of cad_raster_core.h as raster_kernel does -- one triangle per lane, small node ranges walked by the
+// lane, large ones by the whole wave -- with the owner looked up in the tri_begin table and the pose and model scale per lane, since
+// the object ranges do not align to waves, and hands its key-test counts over per owner.  scene_resolve_kernel finds the winner's owner
+// in the same table, writes depth and colour (shade_winner, with the owner's pose and scale) and the label, and counts pixels and boxes
+// per owner: a lane gathers for one owner at a time, the wave reduces per distinct owner when a lane meets another one, then one set of
+// integer atomics (the max-encoded scheme of reduce_frame_stats).  scene_finish_kernel decodes the boxes.  The object table (tri_begin,
+// model_scale) is checked on the host and travels as a launch argument.
 #include "cad_raster_core.h"
 
 namespace df {
@@ -82,12 +83,10 @@ __global__ __launch_bounds__(RB) void scene_raster_kernel(const float *__restric
   int *sf = stats + (size_t)f * O * 6;
   const int lane = threadIdx.x & 63;
   int reached = 0, reached_o = 0;                                             // `reached` counts for object `reached_o`
-  // `base` is the same in all lanes of a wave, so the wave stays whole for the ballots and the shuffles below
+  // `base` is the same in all lanes of a wave, so the wave stays whole for the ballots and the shuffles below and in the walks
   for (long base = (long)blockIdx.x * RB + (threadIdx.x - lane); base < T; base += (long)gridDim.x * RB) {
     const long i = base + lane;
-    Tri tri = {};
-    bool neg = false;
-    int r0 = 0, r1 = -1, q0 = 0, q1 = -1;
+    Setup s;
     bool live = i < T;
     int o = reached_o;
     if (live) {
@@ -100,61 +99,9 @@ __global__ __launch_bounds__(RB) void scene_raster_kernel(const float *__restric
       reached = 0;
     }
     reached_o = o;
-    if (live) {                                                               // T1: nothing is read through an index outside 0..V-1
-#pragma unroll
-      for (int k = 0; k < 3; ++k) tri.id[k] = triangles[i * 3 + k];
-      live = tri.id[0] >= 0 && tri.id[0] < V && tri.id[1] >= 0 && tri.id[1] < V && tri.id[2] >= 0 && tri.id[2] < V &&
-             tri.id[0] != tri.id[1] && tri.id[1] != tri.id[2] && tri.id[0] != tri.id[2];
-    }
-    if (live) {
-      const Pose P = load_pose(pose + ((size_t)f * O + o) * 12);
-      const double model_scale = tab.scale[o];
-      const bool f0_ = project_corner<0>(tri, vertices, P, model_scale, cam, IH, IW);
-      const bool f1_ = project_corner<1>(tri, vertices, P, model_scale, cam, IH, IW);
-      const bool f2_ = project_corner<2>(tri, vertices, P, model_scale, cam, IH, IW);
-      live = f0_ && f1_ && f2_;
-    }
-    if (live) {
-      const double A = signed_area(tri);                                      // T3
-      live = A != 0.0 && A - A == 0.0 && !(cull == 1 && A > 0.0);             // A - A == 0: finite
-      neg = A < 0.0;
-    }
-    if (live) {                                                               // T4: compared as doubles, before any conversion
-      const double cq0 = fmax(ceil(fmin(fmin(tri.sx[0], tri.sx[1]), tri.sx[2])), 0.0);
-      const double cq1 = fmin(floor(fmax(fmax(tri.sx[0], tri.sx[1]), tri.sx[2])), (double)(IW - 1));
-      const double cr0 = fmax(ceil(fmin(fmin(tri.sy[0], tri.sy[1]), tri.sy[2])), 0.0);
-      const double cr1 = fmin(floor(fmax(fmax(tri.sy[0], tri.sy[1]), tri.sy[2])), (double)(IH - 1));
-      live = cq0 <= cq1 && cr0 <= cr1;
-      if (live) { q0 = (int)cq0; q1 = (int)cq1; r0 = (int)cr0; r1 = (int)cr1; }
-    }
-    const int n = live ? (r1 - r0 + 1) * (q1 - q0 + 1) : 0;                   // at most IH * IW <= 2^30
-    if (live && n <= SMALL_NODES) {
-      bool hit = false;
-      for (int r = r0; r <= r1; ++r)
-        for (int q = q0; q <= q1; ++q) hit |= raster_node(tri, neg, r, q, (unsigned)i, kf, IW);
-      reached += hit;
-    }
-    unsigned long long big = __ballot(live && n > SMALL_NODES);
-    while (big) {                                                             // the wave's large triangles, one at a time, all lanes
-      const int src = __ffsll((long long)big) - 1;
-      big &= big - 1;
-      Tri b;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        b.id[k] = __shfl(tri.id[k], src, 64);
-        b.sx[k] = __shfl(tri.sx[k], src, 64); b.sy[k] = __shfl(tri.sy[k], src, 64); b.d[k] = __shfl(tri.d[k], src, 64);
-      }
-      const bool bneg = __shfl((int)neg, src, 64) != 0;
-      const int br0 = __shfl(r0, src, 64), br1 = __shfl(r1, src, 64), bq0 = __shfl(q0, src, 64), bq1 = __shfl(q1, src, 64);
-      const int bw = bq1 - bq0 + 1, bn = (br1 - br0 + 1) * bw;
-      const unsigned bt = (unsigned)(base + src);                             // T7: the global triangle index
-      bool hit = false;
-      for (int j = lane; j < bn; j += 64) {
-        const int jr = j / bw;
-        hit |= raster_node(b, bneg, br0 + jr, bq0 + (j - jr * bw), bt, kf, IW);
-      }
-      if (__ballot(hit) && lane == src) ++reached;
-    }
+    live = live && load_triangle(s.tri, triangles, i, V);
+    if (live) live = setup_triangle(s, vertices, load_pose(pose + ((size_t)f * O + o) * 12), tab.scale[o], cam, IH, IW, cull);
+    reached += walk_triangles(s, live, base, kf, IW);                         // T7: the key carries the global triangle index
   }
   flush_reached(reached_o, reached, sf);
 }
@@ -204,32 +151,13 @@ __global__ __launch_bounds__(RB) void scene_resolve_kernel(const unsigned long l
     if (p >= npix) continue;
     unsigned char *px = cf + (size_t)p * 3;
     if (!covered) {
-      df[p] = 65535;                                                          // the horizon: above every code
-      px[0] = 130; px[1] = 130; px[2] = 130;
+      write_horizon(df + p, px);
       lf[p] = 0;
       continue;
     }
     const int r = p / IW, q = p - r * IW;
-    // the winner passed T1..T7 in scene_raster_kernel: its indices are in range and its corners in front of the camera
-    const size_t t = (size_t)(unsigned)(key & 0xffffffffu);
-    const Pose P = load_pose(pose + ((size_t)f * O + o) * 12);
-    const double model_scale = tab.scale[o];
-    Tri tri;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) tri.id[k] = triangles[t * 3 + k];
-    project_corner<0>(tri, vertices, P, model_scale, cam, IH, IW);
-    project_corner<1>(tri, vertices, P, model_scale, cam, IH, IW);
-    project_corner<2>(tri, vertices, P, model_scale, cam, IH, IW);
-    double w[3], W;
-    node_weights(tri, signed_area(tri) < 0.0, r, q, w, W);
-    const double u0 = w[0] / tri.c3[0], u1 = w[1] / tri.c3[1], u2 = w[2] / tri.c3[2];
-    const double U = (u0 + u1) + u2;
-    const unsigned char *c0 = colors + (size_t)tri.id[0] * 3, *c1 = colors + (size_t)tri.id[1] * 3, *c2 = colors + (size_t)tri.id[2] * 3;
-    df[p] = (unsigned short)(key >> 32);
+    shade_winner(key, r, q, vertices, colors, triangles, load_pose(pose + ((size_t)f * O + o) * 12), tab.scale[o], cam, IH, IW, df + p, px);
     lf[p] = (unsigned short)(o + 1);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-      px[ch] = to_channel(rint(((u0 * (double)c0[ch] + u1 * (double)c1[ch]) + u2 * (double)c2[ch]) / U));
     ++g.cnt;
     g.a_r = max(g.a_r, IH - r); g.b_r = max(g.b_r, r + 1);
     g.a_c = max(g.a_c, IW - q); g.b_c = max(g.b_c, q + 1);
@@ -296,10 +224,8 @@ extern "C" int df_cad_render_scene(const float *vertices, const unsigned char *c
   if (!objects_ok(O)) return set_error(DF_ERR_ARG, "cad_render_scene: O = %d objects outside 1..%d", O, MAX_OBJECTS);
   if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "cad_render_scene: bad sizes");
   if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "cad_render_scene: cull %d is neither 0 nor 1", cull);
-  if (scratch_bytes < df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O) || (reinterpret_cast<uintptr_t>(scratch) & 7u))
-    return set_error(DF_ERR_ARG, "cad_render_scene: scratch too small or not 8-byte aligned");
-  if (!proj_form_ok(proj))
-    return set_error(DF_ERR_ARG, "cad_render_scene: the projection matrix needs rows 2 = (0, 0, p22, p23) and 3 = (0, 0, -1, 0)");
+  if (int e = check_scratch_and_proj("cad_render_scene", scratch, scratch_bytes, df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O), proj))
+    return e;
   if (tri_begin[0] != 0) return set_error(DF_ERR_ARG, "cad_render_scene: tri_begin[0] = %d, not 0", tri_begin[0]);
   for (int o = 0; o < O; ++o)
     if (tri_begin[o + 1] < tri_begin[o])
@@ -309,14 +235,11 @@ extern "C" int df_cad_render_scene(const float *vertices, const unsigned char *c
   const Camera cam = make_camera(proj);
   const Objects objects = make_objects(tri_begin, model_scale, O, T);
   const long npix = (long)IH * IW;
-  if (hipMemsetAsync(scratch, 0xff, (size_t)F * npix * sizeof(unsigned long long), st) != hipSuccess ||
-      hipMemsetAsync(stats_out, 0, sizeof(int) * 6 * (size_t)F * O, st) != hipSuccess)
-    return check_launch("cad_render_scene (clear)");
+  if (!clear_frames(scratch, F, npix, stats_out, (size_t)F * O, st)) return check_launch("cad_render_scene (clear)");
   unsigned long long *keys = static_cast<unsigned long long *>(scratch);
-  const int tb = cdiv(T, RB) < RASTER_MAX_BLOCKS ? cdiv(T, RB) : RASTER_MAX_BLOCKS;
+  const int tb = grid_blocks(T, RASTER_MAX_BLOCKS), xb = grid_blocks(npix, RESOLVE_MAX_BLOCKS);
   hipLaunchKernelGGL(scene_raster_kernel, dim3(tb, F), dim3(RB), 0, st, vertices, V, triangles, T, objects, O, pose, present, cam, IH, IW,
                      cull, keys, stats_out);
-  const int xb = cdiv(npix, RB) < RESOLVE_MAX_BLOCKS ? cdiv(npix, RB) : RESOLVE_MAX_BLOCKS;
   hipLaunchKernelGGL(scene_resolve_kernel, dim3(xb, F), dim3(RB), 0, st, keys, vertices, colors, triangles, objects, O, pose, cam, IH, IW,
                      rgb_out, depth_out, label_out, stats_out);
   hipLaunchKernelGGL(scene_finish_kernel, dim3(cdiv((long)F * O, RB)), dim3(RB), 0, st, F * O, IH, IW, stats_out);
@@ -330,8 +253,7 @@ extern "C" int df_cad_scene_mask(const unsigned short *label, const int *stats, 
   if (!sizes_ok(F, IH, IW) || N <= 0 || N > 65535) return set_error(DF_ERR_ARG, "cad_scene_mask: bad sizes");
   if (mask_mode != 0 && mask_mode != 1)
     return set_error(DF_ERR_ARG, "cad_scene_mask: mask_mode %d is neither 0 (box) nor 1 (pixels)", mask_mode);
-  const long npix = (long)IH * IW;
-  const int xb = cdiv(npix, RB) < RESOLVE_MAX_BLOCKS ? cdiv(npix, RB) : RESOLVE_MAX_BLOCKS;
+  const int xb = grid_blocks((long)IH * IW, RESOLVE_MAX_BLOCKS);
   hipLaunchKernelGGL(scene_mask_kernel, dim3(xb, N), dim3(RB), 0, to_stream(stream), label, stats, F, O, IH, IW, pairs, mask_mode, mask_out);
   return check_launch("cad_scene_mask");
 }

@@ -90,6 +90,18 @@ def preprocess_objects(rgb, depth, label, objects, num_points, cam=YCB_CAM, choo
     return img, cloud, choose, count
 
 
+def _on_device(x, np_dtype, dev, ok, error):
+    """A host array, a host tensor or a device tensor -> a contiguous device tensor.  ``ok(tensor)`` checks dtype and shape before
+    anything is uploaded (``RuntimeError(error)`` otherwise); host data goes up from pinned memory: the upload does not wait for the stream."""
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype))
+    if not ok(x):
+        raise RuntimeError(error)
+    if not x.is_cuda:
+        x = (x if x.is_pinned() else x.pin_memory()).to(dev, non_blocking=True)
+    return x.contiguous()
+
+
 def _u16(t, what):
     if t.dtype not in (torch.int16, torch.uint16):
         raise RuntimeError(f"{what} must be 16-bit")
@@ -143,13 +155,8 @@ def preprocess_objects_cad(rgb, depth, label, objects, num_points, frame_stats, 
     dev = rgb.device
     d_desc = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
     if add_t is not None:
-        if not torch.is_tensor(add_t):
-            add_t = torch.from_numpy(np.ascontiguousarray(add_t, dtype=np.float64))
-        if tuple(add_t.shape) != (B, 3) or add_t.dtype != torch.float64:
-            raise RuntimeError("preprocess_objects_cad: add_t must be [B,3] float64")
-        if not add_t.is_cuda:
-            add_t = (add_t if add_t.is_pinned() else add_t.pin_memory()).to(dev, non_blocking=True)
-        add_t = add_t.contiguous()
+        add_t = _on_device(add_t, np.float64, dev, lambda t: tuple(t.shape) == (B, 3) and t.dtype == torch.float64,
+                           "preprocess_objects_cad: add_t must be [B,3] float64")
     rgb, depth, label = rgb.contiguous(), _u16(depth, "preprocess_objects_cad: depth"), _u16(label, "preprocess_objects_cad: label")
     scratch = torch.empty(B * H * W, dtype=torch.int32, device=dev)
     img = torch.empty(B, 3, H, W, device=dev)
@@ -169,6 +176,60 @@ def preprocess_objects_cad(rgb, depth, label, objects, num_points, frame_stats, 
     return img, cloud, choose, count
 
 
+def _cad_pose(pose, dev, name):
+    """pose [F,3,4] / [F,12] float64, host or device -> the device tensor"""
+    return _on_device(pose, np.float64, dev, lambda p: p.dtype == torch.float64 and p.dim() in (2, 3) and p.numel() == p.shape[0] * 12,
+                      f"{name}: pose must be [F,3,4] float64")
+
+
+def _cad_proj(proj, name):
+    proj = np.ascontiguousarray(proj, dtype=np.float64)
+    if proj.shape != (4, 4):
+        raise RuntimeError(f"{name}: proj must be 4 x 4")
+    return proj
+
+
+def _cad_holes(holes, F, name):
+    """None or (hole_idx [F,K], hole_r [F,K]) -> (K, hole_idx int32, hole_r float64), the arrays None without holes"""
+    if holes is None:
+        return 0, None, None
+    hole_idx, hole_r = np.ascontiguousarray(holes[0], dtype=np.int32), np.ascontiguousarray(holes[1], dtype=np.float64)
+    if hole_idx.ndim != 2 or hole_idx.shape[0] != F or hole_r.shape != hole_idx.shape:
+        raise RuntimeError(f"{name}: holes must be (hole_idx [F,K], hole_r [F,K])")
+    return hole_idx.shape[1], hole_idx, hole_r
+
+
+def _cad_scratch(scratch, need, dev, name, sizes):
+    """The caller's scratch, checked against the ``need`` bytes the library asks for (0: it refuses the sizes), or a new one"""
+    if need == 0:
+        raise RuntimeError(f"{name}: bad sizes {sizes}")
+    if scratch is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < need:
+        raise RuntimeError(f"{name}: scratch must be a uint8 device tensor of at least {need} bytes")
+    return scratch
+
+
+def _cad_frames(F, IH, IW, dev):
+    """rgb [F,IH,IW,3] uint8, depth [F,IH,IW] uint16 and a third uint16 image (mask or label), uninitialised"""
+    u16 = lambda: torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    return torch.empty(F, IH, IW, 3, dtype=torch.uint8, device=dev), u16(), u16()
+
+
+def _cad_mesh(vertices, colors, triangles, name):
+    """The checks of a mesh on the device: vertices [V,3] float32, colors [V,3] uint8, triangles [T,3] int32 -> (V, T)"""
+    if not (vertices.is_cuda and colors.is_cuda and triangles.is_cuda):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise RuntimeError(f"{name}: vertices must be [V,3] float32")
+    V = vertices.shape[0]
+    if tuple(colors.shape) != (V, 3) or colors.dtype != torch.uint8:
+        raise RuntimeError(f"{name}: colors must be [V,3] uint8")
+    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
+        raise RuntimeError(f"{name}: triangles must be [T,3] int32")
+    return V, triangles.shape[0]
+
+
 def cad_render(points, normals, colors, pose, model_scale, proj, image_dims, holes=None, splat=0, mask_mode=0, scratch=None):
     """F views of a coloured cloud as customCAD frames (``df_cad_render``; the contract is its comment in include/dfusion.h).
     points [P,3] float32, normals [P,3] float32 or None, colors [P,3] uint8 -- device tensors; pose [F,3,4] / [F,12] float64 [R|t] into
@@ -186,35 +247,13 @@ def cad_render(points, normals, colors, pose, model_scale, proj, image_dims, hol
     if normals is not None and (tuple(normals.shape) != (P, 3) or normals.dtype != torch.float32):
         raise RuntimeError("cad_render: normals must be [P,3] float32")
     dev = points.device
-    if not torch.is_tensor(pose):
-        pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
-    if pose.dtype != torch.float64 or pose.dim() not in (2, 3) or pose.numel() != pose.shape[0] * 12:
-        raise RuntimeError("cad_render: pose must be [F,3,4] float64")
-    F = pose.shape[0]
-    if not pose.is_cuda:
-        pose = (pose if pose.is_pinned() else pose.pin_memory()).to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
-    pose = pose.contiguous()
-    IH, IW = int(image_dims[0]), int(image_dims[1])
-    proj = np.ascontiguousarray(proj, dtype=np.float64)
-    if proj.shape != (4, 4):
-        raise RuntimeError("cad_render: proj must be 4 x 4")
-    K, hole_idx, hole_r = 0, None, None
-    if holes is not None:
-        hole_idx, hole_r = np.ascontiguousarray(holes[0], dtype=np.int32), np.ascontiguousarray(holes[1], dtype=np.float64)
-        if hole_idx.ndim != 2 or hole_idx.shape[0] != F or hole_r.shape != hole_idx.shape:
-            raise RuntimeError("cad_render: holes must be (hole_idx [F,K], hole_r [F,K])")
-        K = hole_idx.shape[1]
+    pose = _cad_pose(pose, dev, "cad_render")
+    F, IH, IW = pose.shape[0], int(image_dims[0]), int(image_dims[1])
+    proj = _cad_proj(proj, "cad_render")
+    K, hole_idx, hole_r = _cad_holes(holes, F, "cad_render")
     L = _lib.lib()
-    need = L.df_cad_render_scratch_bytes(F, IH, IW)
-    if need == 0:
-        raise RuntimeError(f"cad_render: bad sizes F={F}, IH={IH}, IW={IW}")
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < need:
-        raise RuntimeError(f"cad_render: scratch must be a uint8 device tensor of at least {need} bytes")
-    rgb = torch.empty(F, IH, IW, 3, dtype=torch.uint8, device=dev)
-    depth = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
-    mask = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    scratch = _cad_scratch(scratch, L.df_cad_render_scratch_bytes(F, IH, IW), dev, "cad_render", f"F={F}, IH={IH}, IW={IW}")
+    rgb, depth, mask = _cad_frames(F, IH, IW, dev)
     stats = torch.empty(F, 6, dtype=torch.int32, device=dev)
     with _lib.device_guard(dev):
         st = L.df_cad_render(_lib.dptr(points), None if normals is None else _lib.dptr(normals), _lib.dptr(colors), P, pose.data_ptr(),
@@ -231,46 +270,16 @@ def cad_render_mesh(vertices, colors, triangles, pose, model_scale, proj, image_
     vertices), mask_mode and scratch as for ``cad_render`` (scratch: at least ``df_cad_render_mesh_scratch_bytes``); cull 1 drops the
     triangles that face away.
     Returns rgb [F,IH,IW,3] uint8, depth and mask [F,IH,IW] uint16, stats [F,6] int32 on the device; no read-back, no synchronisation."""
-    if not (vertices.is_cuda and colors.is_cuda and triangles.is_cuda):
-        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise RuntimeError("cad_render_mesh: vertices must be [V,3] float32")
-    V = vertices.shape[0]
-    if tuple(colors.shape) != (V, 3) or colors.dtype != torch.uint8:
-        raise RuntimeError("cad_render_mesh: colors must be [V,3] uint8")
-    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
-        raise RuntimeError("cad_render_mesh: triangles must be [T,3] int32")
-    T = triangles.shape[0]
+    V, T = _cad_mesh(vertices, colors, triangles, "cad_render_mesh")
     dev = vertices.device
-    if not torch.is_tensor(pose):
-        pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
-    if pose.dtype != torch.float64 or pose.dim() not in (2, 3) or pose.numel() != pose.shape[0] * 12:
-        raise RuntimeError("cad_render_mesh: pose must be [F,3,4] float64")
-    F = pose.shape[0]
-    if not pose.is_cuda:
-        pose = (pose if pose.is_pinned() else pose.pin_memory()).to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
-    pose = pose.contiguous()
-    IH, IW = int(image_dims[0]), int(image_dims[1])
-    proj = np.ascontiguousarray(proj, dtype=np.float64)
-    if proj.shape != (4, 4):
-        raise RuntimeError("cad_render_mesh: proj must be 4 x 4")
-    K, hole_idx, hole_r = 0, None, None
-    if holes is not None:
-        hole_idx, hole_r = np.ascontiguousarray(holes[0], dtype=np.int32), np.ascontiguousarray(holes[1], dtype=np.float64)
-        if hole_idx.ndim != 2 or hole_idx.shape[0] != F or hole_r.shape != hole_idx.shape:
-            raise RuntimeError("cad_render_mesh: holes must be (hole_idx [F,K], hole_r [F,K])")
-        K = hole_idx.shape[1]
+    pose = _cad_pose(pose, dev, "cad_render_mesh")
+    F, IH, IW = pose.shape[0], int(image_dims[0]), int(image_dims[1])
+    proj = _cad_proj(proj, "cad_render_mesh")
+    K, hole_idx, hole_r = _cad_holes(holes, F, "cad_render_mesh")
     L = _lib.lib()
-    need = L.df_cad_render_mesh_scratch_bytes(F, IH, IW, V, T)
-    if need == 0:
-        raise RuntimeError(f"cad_render_mesh: bad sizes F={F}, IH={IH}, IW={IW}, V={V}, T={T}")
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < need:
-        raise RuntimeError(f"cad_render_mesh: scratch must be a uint8 device tensor of at least {need} bytes")
-    rgb = torch.empty(F, IH, IW, 3, dtype=torch.uint8, device=dev)
-    depth = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
-    mask = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    scratch = _cad_scratch(scratch, L.df_cad_render_mesh_scratch_bytes(F, IH, IW, V, T), dev, "cad_render_mesh",
+                           f"F={F}, IH={IH}, IW={IW}, V={V}, T={T}")
+    rgb, depth, mask = _cad_frames(F, IH, IW, dev)
     stats = torch.empty(F, 6, dtype=torch.int32, device=dev)
     with _lib.device_guard(dev):
         st = L.df_cad_render_mesh(_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, pose.data_ptr(), float(model_scale),
@@ -288,53 +297,24 @@ def cad_render_scene(vertices, colors, triangles, tri_begin, model_scales, pose,
     uint8, host or device; proj, image_dims and scratch (at least ``df_cad_render_scene_scratch_bytes``) as for ``cad_render_mesh``.
     Returns rgb [F,IH,IW,3] uint8, depth and label [F,IH,IW] uint16 (label = owner + 1, 0 = horizon), stats [F,O,6] int32 on the
     device; no read-back, no synchronisation."""
-    if not (vertices.is_cuda and colors.is_cuda and triangles.is_cuda):
-        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise RuntimeError("cad_render_scene: vertices must be [V,3] float32")
-    V = vertices.shape[0]
-    if tuple(colors.shape) != (V, 3) or colors.dtype != torch.uint8:
-        raise RuntimeError("cad_render_scene: colors must be [V,3] uint8")
-    if triangles.dim() != 2 or triangles.shape[1] != 3 or triangles.dtype != torch.int32:
-        raise RuntimeError("cad_render_scene: triangles must be [T,3] int32")
-    T = triangles.shape[0]
+    V, T = _cad_mesh(vertices, colors, triangles, "cad_render_scene")
     dev = vertices.device
     tri_begin = np.ascontiguousarray(tri_begin, dtype=np.int32).reshape(-1)
     O = tri_begin.shape[0] - 1
     model_scales = np.ascontiguousarray(model_scales, dtype=np.float64).reshape(-1)
     if O < 1 or model_scales.shape[0] != O:
         raise RuntimeError("cad_render_scene: tri_begin must be [O+1] and model_scales [O], O >= 1")
-    if not torch.is_tensor(pose):
-        pose = torch.from_numpy(np.ascontiguousarray(pose, dtype=np.float64))
-    if pose.dtype != torch.float64 or pose.dim() not in (3, 4) or pose.shape[1] != O or pose.numel() != pose.shape[0] * O * 12:
-        raise RuntimeError("cad_render_scene: pose must be [F,O,3,4] float64")
-    F = pose.shape[0]
-    if not pose.is_cuda:
-        pose = (pose if pose.is_pinned() else pose.pin_memory()).to(dev, non_blocking=True)      # pinned: the upload does not wait for the stream
-    pose = pose.contiguous()
+    pose = _on_device(pose, np.float64, dev, lambda p: p.dtype == torch.float64 and p.dim() in (3, 4) and p.shape[1] == O and
+                      p.numel() == p.shape[0] * O * 12, "cad_render_scene: pose must be [F,O,3,4] float64")
+    F, IH, IW = pose.shape[0], int(image_dims[0]), int(image_dims[1])
     if present is not None:
-        if not torch.is_tensor(present):
-            present = torch.from_numpy(np.ascontiguousarray(present, dtype=np.uint8))
-        if present.dtype != torch.uint8 or tuple(present.shape) != (F, O):
-            raise RuntimeError("cad_render_scene: present must be [F,O] uint8")
-        if not present.is_cuda:
-            present = (present if present.is_pinned() else present.pin_memory()).to(dev, non_blocking=True)
-        present = present.contiguous()
-    IH, IW = int(image_dims[0]), int(image_dims[1])
-    proj = np.ascontiguousarray(proj, dtype=np.float64)
-    if proj.shape != (4, 4):
-        raise RuntimeError("cad_render_scene: proj must be 4 x 4")
+        present = _on_device(present, np.uint8, dev, lambda p: p.dtype == torch.uint8 and tuple(p.shape) == (F, O),
+                             "cad_render_scene: present must be [F,O] uint8")
+    proj = _cad_proj(proj, "cad_render_scene")
     L = _lib.lib()
-    need = L.df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O)
-    if need == 0:
-        raise RuntimeError(f"cad_render_scene: bad sizes F={F}, IH={IH}, IW={IW}, V={V}, T={T}, O={O}")
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not scratch.is_cuda or scratch.dtype != torch.uint8 or scratch.numel() < need:
-        raise RuntimeError(f"cad_render_scene: scratch must be a uint8 device tensor of at least {need} bytes")
-    rgb = torch.empty(F, IH, IW, 3, dtype=torch.uint8, device=dev)
-    depth = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
-    label = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    scratch = _cad_scratch(scratch, L.df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O), dev, "cad_render_scene",
+                           f"F={F}, IH={IH}, IW={IW}, V={V}, T={T}, O={O}")
+    rgb, depth, label = _cad_frames(F, IH, IW, dev)
     stats = torch.empty(F, O, 6, dtype=torch.int32, device=dev)
     with _lib.device_guard(dev):
         st = L.df_cad_render_scene(_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, tri_begin.ctypes.data,
@@ -358,12 +338,9 @@ def cad_scene_mask(label, stats, pairs, mask_mode=0):
     F, IH, IW = label.shape
     O = stats.shape[1]
     if not torch.is_tensor(pairs):
-        pairs = torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2))
-    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] == 0:
-        raise RuntimeError("cad_scene_mask: pairs must be a non-empty [N,2] int32")
-    if not pairs.is_cuda:
-        pairs = (pairs if pairs.is_pinned() else pairs.pin_memory()).to(dev, non_blocking=True)
-    pairs = pairs.contiguous()
+        pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    pairs = _on_device(pairs, np.int32, dev, lambda p: p.dtype == torch.int32 and p.dim() == 2 and p.shape[1] == 2 and p.shape[0] != 0,
+                       "cad_scene_mask: pairs must be a non-empty [N,2] int32")
     N = pairs.shape[0]
     mask = torch.empty(N, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
     with _lib.device_guard(dev):

@@ -72,6 +72,26 @@ def test_scene_equals_the_restatement_bit_for_bit(scene, cull):
 
 
 @gpu
+@pytest.mark.parametrize("cull", [0, 1])
+def test_large_triangles_of_three_owners_in_one_wave(cull):
+    """The fixture of tests/test_cad_scene_host.py::test_the_large_triangle_fixture_has_its_case: six triangles of three objects, all
+    walked by the first wave as a whole; the count each walk leaves with one lane goes to that lane's owner."""
+    _dev()
+    from densefusion_amd.lib import preprocess as pp
+    from test_cad_scene_host import large_triangle_scene
+    s = large_triangle_scene()
+    want = snp.render(s["vertices"], s["colors"], s["triangles"], s["tri_begin"], s["scales"], s["poses"], s["present"], NODE_PROJ, IH, IW, cull)
+    got = _gpu(s, s["poses"], s["present"], (IH, IW), cull)
+    _same(got, want)
+    pairs = np.array([[f, o] for f in range(2) for o in range(3)], dtype=np.int32)
+    for mode in (0, 1):
+        mask = pp.cad_scene_mask(_up(got[2]), _up(got[3]), pairs, mode).cpu().numpy()
+        wm = snp.scene_mask(want[2], want[3], pairs, mode)
+        assert mask.dtype == wm.dtype and np.array_equal(mask, wm), mode
+    assert wm.any()
+
+
+@gpu
 def test_one_object_equals_the_mesh_rasteriser(scene):
     """O = 1, all present, against ``df_cad_render_mesh`` with K = 0 on the same mesh and poses, on the device: rgb, depth and stats bit
     for bit, and the two masks through ``df_cad_scene_mask`` with one pair per frame."""

@@ -1,5 +1,5 @@
 """CPU: the host side of the customCAD scene renderer -- the numpy restatement of ``df_cad_render_scene`` (tests/cad_scene_np.py) shows
-that the small fixture of the device tests holds each case it is meant to cover, and agrees with the single-mesh restatement for one
+that the fixtures of the device tests hold each case they are meant to cover, and agrees with the single-mesh restatement for one
 object; then ``sample_scene`` and the tool's arguments."""
 import importlib
 import os
@@ -7,6 +7,7 @@ import sys
 
 import numpy as np
 import pytest
+from scipy.spatial.transform import Rotation
 
 import cad_raster_np as mnp
 import cad_scene_np as snp
@@ -22,6 +23,49 @@ def scene():
     s["out"] = {cull: snp.render(s["vertices"], s["colors"], s["triangles"], s["tri_begin"], s["scales"], s["poses"], s["present"],
                                  NODE_PROJ, IH, IW, cull) for cull in (0, 1)}
     return s
+
+
+def large_triangle_scene():
+    """Three objects of two triangles each (a quad), six triangles in all: the first wave holds large triangles of three owners at once,
+    so the count that the cooperative walk leaves with the lane that set a triangle up meets the hand-over per owner.  The quads lie at
+    three depths and overlap on the screen: object 0 nearest, object 2 (model_scale 7.5) farthest.  frame 0: unrotated, where ``on``
+    holds; frame 1: each quad turned in its plane and tilted, object 1 absent.  Same keys as ``small_scene`` without ``parts``."""
+    quad = lambda q0, q1, r0, r1, z, k=1.0: np.array([snp.on(q0, r0, z), snp.on(q1, r0, z), snp.on(q1, r1, z), snp.on(q0, r1, z)]) * k
+    tris = [[0, 2, 1], [0, 3, 2]]
+    verts, tri, begin = snp.concat_meshes([(quad(4.3, 30.6, 3.2, 24.7, 90.0), tris), (quad(19.4, 47.8, 9.6, 33.1, 10.0), tris),
+                                           (quad(9.7, 41.2, 14.4, 31.5, -120.0, 10.0 / 7.5), tris)])
+    col = np.random.default_rng(5).integers(0, 256, (len(verts), 3), dtype=np.uint8)
+    eye, far = np.eye(3), [0.0, 0.0, -4096.0]
+    turn = lambda z, x: Rotation.from_euler("zx", [z, x], degrees=True).as_matrix()
+    poses = np.array([[snp.pose(eye, far)] * 3,
+                      [snp.pose(turn(25.0, 10.0), [60.0, -40.0, -3900.0]), snp.pose(eye, far), snp.pose(turn(-40.0, -15.0), [-30.0, 50.0, -4300.0])]])
+    return dict(vertices=verts, colors=col, triangles=tri, tri_begin=begin, scales=np.array([10.0, 10.0, 7.5]), poses=poses,
+                present=np.array([[1, 1, 1], [1, 0, 1]], dtype=np.uint8))
+
+
+def test_the_large_triangle_fixture_has_its_case():
+    """One wave, six large triangles, three owners: every triangle of a present object is walked by the whole wave and takes a key
+    test, in both frames and with either ``cull`` (restatement only; the device test is test_large_triangles_of_three_owners_in_one_wave)."""
+    s = large_triangle_scene()
+    begin, tris = s["tri_begin"], s["triangles"]
+    assert begin.tolist() == [0, 2, 4, 6] and len(tris) <= 64, "all in the first wave"
+    assert s["present"].tolist() == [[1, 1, 1], [1, 0, 1]]
+    for cull in (0, 1):
+        for f in range(2):
+            for o in range(3):
+                if not s["present"][f, o]:
+                    continue
+                v = mnp.project_vertices(s["vertices"], s["poses"][f, o], s["scales"][o], None, None, NODE_PROJ, IH, IW)
+                idx, _, rng = mnp.setup_triangles(v, tris[begin[o]:begin[o + 1]], IH, IW, cull)
+                assert idx.tolist() == [0, 1] and ((rng[:, 1] - rng[:, 0] + 1) * (rng[:, 3] - rng[:, 2] + 1) > 16).all(), (cull, f, o)
+        rgb, depth, label, stats, winner, cover = snp.render(s["vertices"], s["colors"], tris, begin, s["scales"], s["poses"], s["present"],
+                                                             NODE_PROJ, IH, IW, cull)
+        assert (stats[:, :, 1][s["present"] == 1] == 2).all(), "every triangle of a present object takes a key test"
+        assert (stats[0, :, 0] > 0).sum() >= 2 and (stats[1, 1] == 0).all()
+        # three depths that overlap on the screen: where two objects would be seen alone, the nearer one owns the pixel
+        for f, near, hid in ((0, 0, 1), (0, 1, 2), (0, 0, 2), (1, 0, 2)):
+            both = cover[f, near] & cover[f, hid]
+            assert both.sum() >= 20 and (label[f][both] <= near + 1).all() and (label[f][both] > 0).all(), (f, near, hid)
 
 
 def test_the_fixture_has_its_cases(scene):
