@@ -85,9 +85,13 @@ SIGNATURES = {
     "df_cad_render_mesh_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i]),
     "df_cad_render_mesh": (_i, [_vp, _vp, _i, _vp, _i, _vp, ctypes.c_double, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                 ctypes.c_size_t, _vp]),
+    "df_cad_render_mesh_lit": (_i, [_vp, _vp, _i, _vp, _i, _vp, ctypes.c_double, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, ctypes.c_size_t, _vp]),
     "df_cad_render_scene_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "df_cad_render_scene": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                  ctypes.c_size_t, _vp]),
+    "df_cad_render_scene_lit": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     ctypes.c_size_t, _vp]),
     "df_cad_scene_mask": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "df_color_jitter": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "df_compose_frame": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -7,7 +7,9 @@
 // Steps on the caller's stream: the keys are set to all-ones; raster_kernel (grid = triangle blocks x frames) sets up one triangle per lane,
 // recomputing V1..V5 for its three corners (no per-vertex scratch: see DESIGN), and takes atomicMin of (code << 32 | triangle index) on
 // every covered node: small node ranges by the lane, large ones by the whole wave.  resolve_mesh_kernel recomputes the winner's edge
-// functions (the same device functions, hence the same bits) for the perspective-correct colour.  The set-up, the walks and the shading
+// functions (the same device functions, hence the same bits) for the perspective-correct colour; its LIT instantiation
+// (df_cad_render_mesh_lit with a light) multiplies that colour by the diffuse term of the frame's light record, steps L1..L6.
+// The set-up, the walks and the shading
 // are the device functions of cad_raster_core.h, which cad_scene.hip shares; the kernels here add the pose of the block's frame, the
 // hole test (vertex_cut, cad_frame.h) and the per-wave sum of the key-test counts.  finish_kernel and mask_kernel are those of the point
 // renderer (cad_frame.h).  No clipping: a triangle with a corner behind the camera is dropped whole.
@@ -43,14 +45,19 @@ __global__ __launch_bounds__(RB) void raster_kernel(const float *__restrict__ ve
   if (lane == 0 && reached) atomicAdd(&stats[(size_t)f * 6 + 1], reached);
 }
 
+// LIT: the covered pixels take the diffuse term of light[f] (L1..L6); normals, normal_mode and light are not read otherwise
+template <bool LIT>
 __global__ __launch_bounds__(RB) void resolve_mesh_kernel(const unsigned long long *__restrict__ keys, const float *__restrict__ vertices,
                                                           const unsigned char *__restrict__ colors, const int *__restrict__ triangles,
                                                           const double *__restrict__ pose, double model_scale, Camera cam, int IH, int IW,
-                                                          unsigned char *__restrict__ rgb, unsigned short *__restrict__ depth,
-                                                          int *__restrict__ stats) {
+                                                          const float *__restrict__ normals, int normal_mode,
+                                                          const double *__restrict__ light, unsigned char *__restrict__ rgb,
+                                                          unsigned short *__restrict__ depth, int *__restrict__ stats) {
   const int f = blockIdx.y;
   const int npix = IH * IW;
   const Pose P = load_pose(pose + (size_t)f * 12);
+  Shading sh = {};
+  if constexpr (LIT) sh = load_shading(normals, normal_mode, light + (size_t)f * 8);
   const unsigned long long *kf = keys + (size_t)f * npix;
   unsigned char *cf = rgb + (size_t)f * npix * 3;
   unsigned short *df = depth + (size_t)f * npix;
@@ -63,7 +70,7 @@ __global__ __launch_bounds__(RB) void resolve_mesh_kernel(const unsigned long lo
       continue;
     }
     const int r = p / IW, q = p - r * IW;
-    shade_winner(key, r, q, vertices, colors, triangles, P, model_scale, cam, IH, IW, df + p, px);
+    shade_winner<LIT>(key, r, q, vertices, colors, triangles, P, model_scale, cam, IH, IW, sh, df + p, px);
     ++cnt;
     a_r = max(a_r, IH - r); b_r = max(b_r, r + 1);
     a_c = max(a_c, IW - q); b_c = max(b_c, q + 1);
@@ -81,33 +88,53 @@ extern "C" size_t df_cad_render_mesh_scratch_bytes(int F, int IH, int IW, int V,
   return sizes_ok(F, IH, IW) && V > 0 && T > 0 ? (size_t)F * IH * IW * sizeof(unsigned long long) : 0;
 }
 
-extern "C" int df_cad_render_mesh(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const double *pose,
-                                  double model_scale, const int *hole_idx, const double *hole_r, int K, const double *proj, int F, int IH,
-                                  int IW, int cull, int mask_mode, unsigned char *rgb_out, unsigned short *depth_out,
-                                  unsigned short *mask_out, int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+// df_cad_render_mesh (light == NULL) and df_cad_render_mesh_lit: `name` is the call's name in front of every message
+static int render_mesh(const char *name, const float *vertices, const unsigned char *colors, int V, const int *triangles, int T,
+                       const double *pose, double model_scale, const int *hole_idx, const double *hole_r, int K, const double *proj, int F,
+                       int IH, int IW, int cull, int mask_mode, const float *normals, int normal_mode, const double *light,
+                       unsigned char *rgb_out, unsigned short *depth_out, unsigned short *mask_out, int *stats_out, void *scratch,
+                       size_t scratch_bytes, df_stream_t stream) {
   if (!vertices || !colors || !triangles || !pose || !proj || !rgb_out || !depth_out || !mask_out || !stats_out || !scratch)
-    return set_error(DF_ERR_ARG, "cad_render_mesh: null pointer");
-  if (int e = check_hole_args("cad_render_mesh", hole_idx, hole_r, K)) return e;
-  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "cad_render_mesh: bad sizes");
-  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "cad_render_mesh: cull %d is neither 0 nor 1", cull);
-  if (mask_mode != 0 && mask_mode != 1)
-    return set_error(DF_ERR_ARG, "cad_render_mesh: mask_mode %d is neither 0 (box) nor 1 (pixels)", mask_mode);
-  if (int e = check_scratch_and_proj("cad_render_mesh", scratch, scratch_bytes, df_cad_render_mesh_scratch_bytes(F, IH, IW, V, T), proj))
-    return e;
-  if (int e = check_hole_indices("cad_render_mesh", hole_idx, F, K, 'V', V)) return e;
+    return set_error(DF_ERR_ARG, "%s: null pointer", name);
+  if (light && !normals) return set_error(DF_ERR_ARG, "%s: null pointer (a light needs normals)", name);
+  if (light && normal_mode != 0 && normal_mode != 1)
+    return set_error(DF_ERR_ARG, "%s: normal_mode %d is neither 0 (per triangle) nor 1 (per vertex)", name, normal_mode);
+  if (int e = check_hole_args(name, hole_idx, hole_r, K)) return e;
+  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
+  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
+  if (mask_mode != 0 && mask_mode != 1) return set_error(DF_ERR_ARG, "%s: mask_mode %d is neither 0 (box) nor 1 (pixels)", name, mask_mode);
+  if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, df_cad_render_mesh_scratch_bytes(F, IH, IW, V, T), proj)) return e;
+  if (int e = check_hole_indices(name, hole_idx, F, K, 'V', V)) return e;
   hipStream_t st = to_stream(stream);
   const Camera cam = make_camera(proj);
   const long npix = (long)IH * IW;
-  if (!clear_frames(scratch, F, npix, stats_out, F, st)) return check_launch("cad_render_mesh (clear)");
+  if (!clear_frames(scratch, F, npix, stats_out, F, st)) return check_launch(name);
   unsigned long long *keys = static_cast<unsigned long long *>(scratch);
   const int tb = grid_blocks(T, RASTER_MAX_BLOCKS), xb = grid_blocks(npix, RESOLVE_MAX_BLOCKS);
   for_hole_batches(hole_idx, hole_r, K, F, [&](int f0, int nf, const Holes &holes) {
     hipLaunchKernelGGL(raster_kernel, dim3(tb, nf), dim3(RB), 0, st, vertices, V, triangles, T, pose, model_scale, holes, K, f0, cam, IH, IW,
                        cull, keys, stats_out);
   });
-  hipLaunchKernelGGL(resolve_mesh_kernel, dim3(xb, F), dim3(RB), 0, st, keys, vertices, colors, triangles, pose, model_scale, cam, IH, IW,
-                     rgb_out, depth_out, stats_out);
+  hipLaunchKernelGGL(light ? resolve_mesh_kernel<true> : resolve_mesh_kernel<false>, dim3(xb, F), dim3(RB), 0, st, keys, vertices, colors,
+                     triangles, pose, model_scale, cam, IH, IW, normals, normal_mode, light, rgb_out, depth_out, stats_out);
   hipLaunchKernelGGL(finish_kernel, dim3(cdiv(F, RB)), dim3(RB), 0, st, F, IH, IW, stats_out);
   hipLaunchKernelGGL(mask_kernel, dim3(xb, F), dim3(RB), 0, st, depth_out, stats_out, IH, IW, mask_mode, mask_out);
-  return check_launch("cad_render_mesh");
+  return check_launch(name);
+}
+
+extern "C" int df_cad_render_mesh(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const double *pose,
+                                  double model_scale, const int *hole_idx, const double *hole_r, int K, const double *proj, int F, int IH,
+                                  int IW, int cull, int mask_mode, unsigned char *rgb_out, unsigned short *depth_out,
+                                  unsigned short *mask_out, int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+  return render_mesh("cad_render_mesh", vertices, colors, V, triangles, T, pose, model_scale, hole_idx, hole_r, K, proj, F, IH, IW, cull,
+                     mask_mode, nullptr, 0, nullptr, rgb_out, depth_out, mask_out, stats_out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int df_cad_render_mesh_lit(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T,
+                                      const double *pose, double model_scale, const int *hole_idx, const double *hole_r, int K,
+                                      const double *proj, int F, int IH, int IW, int cull, int mask_mode, const float *normals,
+                                      int normal_mode, const double *light, unsigned char *rgb_out, unsigned short *depth_out,
+                                      unsigned short *mask_out, int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+  return render_mesh("cad_render_mesh_lit", vertices, colors, V, triangles, T, pose, model_scale, hole_idx, hole_r, K, proj, F, IH, IW, cull,
+                     mask_mode, normals, normal_mode, light, rgb_out, depth_out, mask_out, stats_out, scratch, scratch_bytes, stream);
 }

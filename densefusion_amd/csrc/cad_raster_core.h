@@ -1,8 +1,8 @@
 // What the two triangle rasterisers share (cad_raster.hip: one mesh per frame, with holes; cad_scene.hip: several objects per frame with
 // occlusion): steps V2..V5 and T1..T7 of df_cad_render_mesh (include/dfusion.h) and the winner's shading as device functions, from the
 // corner and the node up to the triangle's set-up (load_triangle, setup_triangle), the two walks of a wave (walk_triangles) and the
-// covered pixel of the resolve pass (shade_winner).  A kernel adds where pose, scale and owner come from, its hole test and how it hands
-// its counts over.  Each translation unit gets its own copy; both are built with -ffp-contract=off, so the same code gives the same bits
+// covered pixel of the resolve pass, unlit or lit (shade_winner).  A kernel adds where pose, scale and owner come from, its hole test
+// and how it hands its counts over.  Each translation unit gets its own copy; both are built with -ffp-contract=off, so the same code gives the same bits
 // in both.
 #pragma once
 #include "cad_frame.h"
@@ -155,12 +155,35 @@ __device__ __forceinline__ int walk_triangles(const Setup &s, bool live, long ba
 
 __device__ inline unsigned char to_channel(double v) { return (unsigned char)(v >= 0.0 ? (v <= 255.0 ? v : 255.0) : 0.0); }      // NaN -> 0
 
+// What the lit resolve adds to a frame's covered pixels (steps L1..L6 of df_cad_render_mesh_lit): the normals of the call and the light
+// record of the block's frame, {L, ambient, diffuse, colour}.  The record is the same in all lanes of a block (scalar loads).
+struct Shading {
+  const float *normals;
+  int mode;                             // 0: one normal per triangle, 1: one per vertex
+  double L[3], ambient, diffuse, c[3];
+};
+
+__device__ inline Shading load_shading(const float *__restrict__ normals, int mode, const double *__restrict__ rec) {
+  Shading sh;
+  sh.normals = normals; sh.mode = mode;
+  sh.L[0] = rec[0]; sh.L[1] = rec[1]; sh.L[2] = rec[2]; sh.ambient = rec[3]; sh.diffuse = rec[4];
+  sh.c[0] = rec[5]; sh.c[1] = rec[6]; sh.c[2] = rec[7];
+  return sh;
+}
+
+// L1, L2: component j of the normal at n, turned by the pose's R as step 3 of df_cad_render turns a point's
+__device__ inline double rotated_normal(const Pose &P, int j, const float *__restrict__ n) {
+  return (P.R[j][0] * (double)n[0] + P.R[j][1] * (double)n[1]) + P.R[j][2] * (double)n[2];
+}
+
 // The covered pixel (r, q) of the resolve pass: depth from the key, the perspective-correct colour from the winner's recomputed corners
-// and edge functions.  The winner passed T1..T7 in the raster pass: its indices are in range and its corners in front of the camera.
+// and edge functions, with LIT times the diffuse term of the frame's light (L1..L6; `sh` is not read otherwise).  The winner passed
+// T1..T7 in the raster pass: its indices are in range and its corners in front of the camera.
+template <bool LIT>
 __device__ __forceinline__ void shade_winner(unsigned long long key, int r, int q, const float *__restrict__ vertices,
                                              const unsigned char *__restrict__ colors, const int *__restrict__ triangles, const Pose &P,
-                                             double model_scale, const Camera &cam, int IH, int IW, unsigned short *__restrict__ depth,
-                                             unsigned char *__restrict__ px) {
+                                             double model_scale, const Camera &cam, int IH, int IW, const Shading &sh,
+                                             unsigned short *__restrict__ depth, unsigned char *__restrict__ px) {
   const size_t t = (size_t)(unsigned)(key & 0xffffffffu);
   Tri tri;
 #pragma unroll
@@ -169,14 +192,36 @@ __device__ __forceinline__ void shade_winner(unsigned long long key, int r, int 
   project_corner<1>(tri, vertices, P, model_scale, cam, IH, IW);
   project_corner<2>(tri, vertices, P, model_scale, cam, IH, IW);
   double w[3], W;
-  node_weights(tri, signed_area(tri) < 0.0, r, q, w, W);
+  const double A = signed_area(tri);
+  node_weights(tri, A < 0.0, r, q, w, W);
   const double u0 = w[0] / tri.c3[0], u1 = w[1] / tri.c3[1], u2 = w[2] / tri.c3[2];
   const double U = (u0 + u1) + u2;
   const unsigned char *c0 = colors + (size_t)tri.id[0] * 3, *c1 = colors + (size_t)tri.id[1] * 3, *c2 = colors + (size_t)tri.id[2] * 3;
   *depth = (unsigned short)(key >> 32);
+  double s = 1.0;
+  if constexpr (LIT) {
+    double N[3];
+    if (sh.mode == 0) {                                                       // L1, L2: the triangle's normal
+      const float *n = sh.normals + t * 3;
 #pragma unroll
-  for (int ch = 0; ch < 3; ++ch)
-    px[ch] = to_channel(rint(((u0 * (double)c0[ch] + u1 * (double)c1[ch]) + u2 * (double)c2[ch]) / U));
+      for (int j = 0; j < 3; ++j) N[j] = rotated_normal(P, j, n);
+    } else {                                                                  // the corners' normals, each turned first; no re-normalising
+      const float *n0 = sh.normals + (size_t)tri.id[0] * 3, *n1 = sh.normals + (size_t)tri.id[1] * 3;
+      const float *n2 = sh.normals + (size_t)tri.id[2] * 3;
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        N[j] = ((u0 * rotated_normal(P, j, n0) + u1 * rotated_normal(P, j, n1)) + u2 * rotated_normal(P, j, n2)) / U;
+    }
+    if (A > 0.0) { N[0] = -N[0]; N[1] = -N[1]; N[2] = -N[2]; }                // L3: a back face is lit as the side the camera sees
+    double c = (N[0] * sh.L[0] + N[1] * sh.L[1]) + N[2] * sh.L[2];            // L4
+    c = c > 0.0 ? c : 0.0;                                                    // NaN -> 0
+    s = sh.ambient + sh.diffuse * c;                                          // L5
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const double a = ((u0 * (double)c0[ch] + u1 * (double)c1[ch]) + u2 * (double)c2[ch]) / U;
+    px[ch] = to_channel(rint(LIT ? a * (s * sh.c[ch]) : a));                  // L6
+  }
 }
 
 }  // namespace

@@ -7,8 +7,9 @@
 // runs the set-up and the walks of cad_raster_core.h as raster_kernel does -- one triangle per lane, small node ranges walked by the
 // lane, large ones by the whole wave -- with the owner looked up in the tri_begin table and the pose and model scale per lane, since
 // the object ranges do not align to waves, and hands its key-test counts over per owner.  scene_resolve_kernel finds the winner's owner
-// in the same table, writes depth and colour (shade_winner, with the owner's pose and scale) and the label, and counts pixels and boxes
-// per owner: a lane gathers for one owner at a time, the wave reduces per distinct owner when a lane meets another one, then one set of
+// in the same table, writes depth and colour (shade_winner, with the owner's pose and scale; its LIT instantiation, for
+// df_cad_render_scene_lit with a light, applies steps L1..L6 with the owner's R and the frame's light record) and the label, and
+// counts pixels and boxes per owner: a lane gathers for one owner at a time, the wave reduces per distinct owner when a lane meets another one, then one set of
 // integer atomics (the max-encoded scheme of reduce_frame_stats).  scene_finish_kernel decodes the boxes.  The object table (tri_begin,
 // model_scale) is checked on the host and travels as a launch argument.
 #include "cad_raster_core.h"
@@ -123,14 +124,20 @@ __device__ inline void flush_gather(Gather &g, int *__restrict__ sf) {
   g.cnt = g.a_r = g.b_r = g.a_c = g.b_c = 0;
 }
 
+// LIT: the covered pixels take the diffuse term of light[f] (L1..L6); normals, normal_mode and light are not read otherwise
+template <bool LIT>
 __global__ __launch_bounds__(RB) void scene_resolve_kernel(const unsigned long long *__restrict__ keys, const float *__restrict__ vertices,
                                                            const unsigned char *__restrict__ colors, const int *__restrict__ triangles,
                                                            Objects objects, int O, const double *__restrict__ pose, Camera cam, int IH,
-                                                           int IW, unsigned char *__restrict__ rgb, unsigned short *__restrict__ depth,
-                                                           unsigned short *__restrict__ label, int *__restrict__ stats) {
+                                                           int IW, const float *__restrict__ normals, int normal_mode,
+                                                           const double *__restrict__ light, unsigned char *__restrict__ rgb,
+                                                           unsigned short *__restrict__ depth, unsigned short *__restrict__ label,
+                                                           int *__restrict__ stats) {
   __shared__ ObjectsLds tab;
   stage_objects(tab, objects);
   const int f = blockIdx.y;
+  Shading sh = {};
+  if constexpr (LIT) sh = load_shading(normals, normal_mode, light + (size_t)f * 8);
   const int npix = IH * IW;
   const unsigned long long *kf = keys + (size_t)f * npix;
   unsigned char *cf = rgb + (size_t)f * npix * 3;
@@ -156,7 +163,8 @@ __global__ __launch_bounds__(RB) void scene_resolve_kernel(const unsigned long l
       continue;
     }
     const int r = p / IW, q = p - r * IW;
-    shade_winner(key, r, q, vertices, colors, triangles, load_pose(pose + ((size_t)f * O + o) * 12), tab.scale[o], cam, IH, IW, df + p, px);
+    shade_winner<LIT>(key, r, q, vertices, colors, triangles, load_pose(pose + ((size_t)f * O + o) * 12), tab.scale[o], cam, IH, IW, sh, df + p,
+                      px);
     lf[p] = (unsigned short)(o + 1);
     ++g.cnt;
     g.a_r = max(g.a_r, IH - r); g.b_r = max(g.b_r, r + 1);
@@ -214,36 +222,58 @@ extern "C" size_t df_cad_render_scene_scratch_bytes(int F, int IH, int IW, int V
   return sizes_ok(F, IH, IW) && V > 0 && T > 0 && objects_ok(O) ? (size_t)F * IH * IW * sizeof(unsigned long long) : 0;
 }
 
-extern "C" int df_cad_render_scene(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const int *tri_begin,
-                                   const double *model_scale, int O, const double *pose, const unsigned char *present, const double *proj,
-                                   int F, int IH, int IW, int cull, unsigned char *rgb_out, unsigned short *depth_out,
-                                   unsigned short *label_out, int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+// df_cad_render_scene (light == NULL) and df_cad_render_scene_lit: `name` is the call's name in front of every message
+static int render_scene(const char *name, const float *vertices, const unsigned char *colors, int V, const int *triangles, int T,
+                        const int *tri_begin, const double *model_scale, int O, const double *pose, const unsigned char *present,
+                        const double *proj, int F, int IH, int IW, int cull, const float *normals, int normal_mode, const double *light,
+                        unsigned char *rgb_out, unsigned short *depth_out, unsigned short *label_out, int *stats_out, void *scratch,
+                        size_t scratch_bytes, df_stream_t stream) {
   if (!vertices || !colors || !triangles || !tri_begin || !model_scale || !pose || !proj || !rgb_out || !depth_out || !label_out ||
       !stats_out || !scratch)
-    return set_error(DF_ERR_ARG, "cad_render_scene: null pointer");
-  if (!objects_ok(O)) return set_error(DF_ERR_ARG, "cad_render_scene: O = %d objects outside 1..%d", O, MAX_OBJECTS);
-  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "cad_render_scene: bad sizes");
-  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "cad_render_scene: cull %d is neither 0 nor 1", cull);
-  if (int e = check_scratch_and_proj("cad_render_scene", scratch, scratch_bytes, df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O), proj))
-    return e;
-  if (tri_begin[0] != 0) return set_error(DF_ERR_ARG, "cad_render_scene: tri_begin[0] = %d, not 0", tri_begin[0]);
+    return set_error(DF_ERR_ARG, "%s: null pointer", name);
+  if (light && !normals) return set_error(DF_ERR_ARG, "%s: null pointer (a light needs normals)", name);
+  if (light && normal_mode != 0 && normal_mode != 1)
+    return set_error(DF_ERR_ARG, "%s: normal_mode %d is neither 0 (per triangle) nor 1 (per vertex)", name, normal_mode);
+  if (!objects_ok(O)) return set_error(DF_ERR_ARG, "%s: O = %d objects outside 1..%d", name, O, MAX_OBJECTS);
+  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
+  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
+  if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O), proj)) return e;
+  if (tri_begin[0] != 0) return set_error(DF_ERR_ARG, "%s: tri_begin[0] = %d, not 0", name, tri_begin[0]);
   for (int o = 0; o < O; ++o)
     if (tri_begin[o + 1] < tri_begin[o])
-      return set_error(DF_ERR_ARG, "cad_render_scene: tri_begin decreases from %d to %d at object %d", tri_begin[o], tri_begin[o + 1], o);
-  if (tri_begin[O] != T) return set_error(DF_ERR_ARG, "cad_render_scene: tri_begin[O] = %d, not T = %d", tri_begin[O], T);
+      return set_error(DF_ERR_ARG, "%s: tri_begin decreases from %d to %d at object %d", name, tri_begin[o], tri_begin[o + 1], o);
+  if (tri_begin[O] != T) return set_error(DF_ERR_ARG, "%s: tri_begin[O] = %d, not T = %d", name, tri_begin[O], T);
   hipStream_t st = to_stream(stream);
   const Camera cam = make_camera(proj);
   const Objects objects = make_objects(tri_begin, model_scale, O, T);
   const long npix = (long)IH * IW;
-  if (!clear_frames(scratch, F, npix, stats_out, (size_t)F * O, st)) return check_launch("cad_render_scene (clear)");
+  if (!clear_frames(scratch, F, npix, stats_out, (size_t)F * O, st)) return check_launch(name);
   unsigned long long *keys = static_cast<unsigned long long *>(scratch);
   const int tb = grid_blocks(T, RASTER_MAX_BLOCKS), xb = grid_blocks(npix, RESOLVE_MAX_BLOCKS);
   hipLaunchKernelGGL(scene_raster_kernel, dim3(tb, F), dim3(RB), 0, st, vertices, V, triangles, T, objects, O, pose, present, cam, IH, IW,
                      cull, keys, stats_out);
-  hipLaunchKernelGGL(scene_resolve_kernel, dim3(xb, F), dim3(RB), 0, st, keys, vertices, colors, triangles, objects, O, pose, cam, IH, IW,
-                     rgb_out, depth_out, label_out, stats_out);
+  hipLaunchKernelGGL(light ? scene_resolve_kernel<true> : scene_resolve_kernel<false>, dim3(xb, F), dim3(RB), 0, st, keys, vertices, colors,
+                     triangles, objects, O, pose, cam, IH, IW, normals, normal_mode, light, rgb_out, depth_out, label_out, stats_out);
   hipLaunchKernelGGL(scene_finish_kernel, dim3(cdiv((long)F * O, RB)), dim3(RB), 0, st, F * O, IH, IW, stats_out);
-  return check_launch("cad_render_scene");
+  return check_launch(name);
+}
+
+extern "C" int df_cad_render_scene(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const int *tri_begin,
+                                   const double *model_scale, int O, const double *pose, const unsigned char *present, const double *proj,
+                                   int F, int IH, int IW, int cull, unsigned char *rgb_out, unsigned short *depth_out,
+                                   unsigned short *label_out, int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+  return render_scene("cad_render_scene", vertices, colors, V, triangles, T, tri_begin, model_scale, O, pose, present, proj, F, IH, IW, cull,
+                      nullptr, 0, nullptr, rgb_out, depth_out, label_out, stats_out, scratch, scratch_bytes, stream);
+}
+
+extern "C" int df_cad_render_scene_lit(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T,
+                                       const int *tri_begin, const double *model_scale, int O, const double *pose,
+                                       const unsigned char *present, const double *proj, int F, int IH, int IW, int cull,
+                                       const float *normals, int normal_mode, const double *light, unsigned char *rgb_out,
+                                       unsigned short *depth_out, unsigned short *label_out, int *stats_out, void *scratch,
+                                       size_t scratch_bytes, df_stream_t stream) {
+  return render_scene("cad_render_scene_lit", vertices, colors, V, triangles, T, tri_begin, model_scale, O, pose, present, proj, F, IH, IW,
+                      cull, normals, normal_mode, light, rgb_out, depth_out, label_out, stats_out, scratch, scratch_bytes, stream);
 }
 
 extern "C" int df_cad_scene_mask(const unsigned short *label, const int *stats, int F, int O, int IH, int IW, const int *pairs, int N,

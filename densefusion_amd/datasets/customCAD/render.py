@@ -12,6 +12,13 @@ Different by design (DESIGN.md "customCAD renderer"): the camera is the loader's
 non-linear code, not the pinhole / millimetre images of :181-188,236; the facing test uses each point's own view ray; depth and colour
 share one winner; a hole is a plain radius test around the drawn point.  Nothing here is checked against open3d or OpenCV, which this
 build does not have: ``sample_view`` is pinned by restatement only.
+
+Lighting (``df_cad_render_mesh_lit`` / ``df_cad_render_scene_lit``): the two triangle renderers take ``normals``
+(``"flat"``: ``face_normals``, one per triangle; ``"smooth"``: ``vertex_normals``, one per vertex; or the arrays themselves) and
+``render(..., light=)`` one record {Lx, Ly, Lz, ambient, diffuse, cr, cg, cb} per frame, L the unit direction towards the light in
+camera space ((0, 0, 1): a head-light).  A covered pixel's colour is multiplied by ambient + diffuse * max(N.L, 0) and the light's
+colour; geometry, depth and masks do not change.  ``sample_light`` draws a record per seed from a stream of its own.  The reference
+has no counterpart: its frames were lit by Unity.  The point renderer stays unlit.
 """
 from __future__ import annotations
 
@@ -136,6 +143,82 @@ def check_triangles(triangles, n_vertices):
     return np.ascontiguousarray(tri, dtype=np.int32)
 
 
+def _face_crosses(vertices, triangles):
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    return v, t, np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+
+
+def _unit_rows(a):
+    """rows / their length as float32; a zero (or non-finite) row gives zeros"""
+    n = np.linalg.norm(a, axis=1, keepdims=True)
+    ok = np.isfinite(n) & (n > 0)
+    return np.ascontiguousarray(np.where(ok, a / np.where(ok, n, 1.0), 0.0), dtype=np.float32)
+
+
+def face_normals(vertices, triangles):
+    """float32 [T,3]: the fp64 cross product (v1 - v0) x (v2 - v0) of every triangle, normalised -- outward for triangles wound
+    counter-clockwise seen from outside.  A degenerate triangle gives zeros."""
+    return _unit_rows(_face_crosses(vertices, triangles)[2])
+
+
+def vertex_normals(vertices, triangles):
+    """float32 [V,3]: per vertex the sum of the unnormalised crosses of its faces (area weighting), normalised.  A vertex that no
+    triangle names gives zeros."""
+    v, t, cross = _face_crosses(vertices, triangles)
+    acc = np.zeros_like(v)
+    for k in range(3):
+        np.add.at(acc, t[:, k], cross)
+    return _unit_rows(acc)
+
+
+def sample_light(seed, max_angle=np.radians(60.0), ambient=(0.3, 0.6), diffuse=(0.4, 0.9), tint=0.1):
+    """One light record (8,) float64 {Lx, Ly, Lz, ambient, diffuse, cr, cg, cb} from ``np.random.default_rng((seed, 2))``, which leaves
+    the global stream and ``sample_scene``'s (seed, 1) stream alone.  The draws, in this order: ``u = random()`` and
+    ``phi = uniform(0, 2 pi)`` for a direction uniform on the cap of half angle ``max_angle`` around +z (cos theta = 1 - u (1 - cos
+    max_angle)), ``uniform(*ambient)``, ``uniform(*diffuse)``, ``uniform(1 - tint, 1, 3)`` for the colour.  The ranges are design
+    defaults, not measurements."""
+    rng = np.random.default_rng((int(seed), 2))
+    u = rng.random()
+    phi = rng.uniform(0, np.pi * 2)
+    cos_t = 1.0 - u * (1.0 - np.cos(max_angle))
+    sin_t = np.sqrt(max(0.0, 1.0 - cos_t * cos_t))
+    L = np.array([sin_t * np.cos(phi), sin_t * np.sin(phi), cos_t])
+    L /= np.linalg.norm(L)
+    return np.concatenate([L, [rng.uniform(*ambient), rng.uniform(*diffuse)], rng.uniform(1.0 - tint, 1.0, 3)])
+
+
+HEAD_LIGHT = (0.0, 0.0, 1.0, 0.4, 0.6, 1.0, 1.0, 1.0)      # lit from the camera: a facing surface keeps its colour
+
+
+def check_light(light, F):
+    """light as float64 [F,8]; ``ValueError`` on any other shape, a non-finite entry, a negative ambient, diffuse or colour, or a
+    direction whose length differs from 1 by more than 1e-6 (host only)."""
+    light = np.ascontiguousarray(light, dtype=np.float64)
+    if light.shape != (F, 8):
+        raise ValueError(f"light must be [F,8] = [{F},8], one record per frame; got {light.shape}")
+    if not np.isfinite(light).all():
+        raise ValueError("light holds a non-finite entry")
+    if (light[:, 3:] < 0).any():
+        raise ValueError("light: ambient, diffuse and colour must not be negative")
+    if (np.abs(np.linalg.norm(light[:, :3], axis=1) - 1.0) > 1e-6).any():
+        raise ValueError("light: the direction must be of unit length")
+    return light
+
+
+def _make_normals(normals, vertices, triangles):
+    """``normals`` of a renderer -> (float32 array, normal_mode): "flat" / "smooth" are computed, an array is [T,3] (mode 0) or [V,3]
+    (mode 1; when T == V an array counts as per-triangle)."""
+    if isinstance(normals, str):
+        if normals not in ("flat", "smooth"):
+            raise ValueError('normals must be None, "flat", "smooth" or an array')
+        return (face_normals(vertices, triangles), 0) if normals == "flat" else (vertex_normals(vertices, triangles), 1)
+    n = np.ascontiguousarray(normals, dtype=np.float32)
+    if n.ndim != 2 or n.shape[1] != 3 or n.shape[0] not in (len(triangles), len(vertices)):
+        raise ValueError(f"normals must be [T,3] = [{len(triangles)},3] or [V,3] = [{len(vertices)},3]")
+    return n, 0 if n.shape[0] == len(triangles) else 1
+
+
 def sample_view(seed, n_points, center, scene_scale, max_holes=3, *, hole_mean, hole_std):
     """The draws of one view on ``np.random.seed(seed)``, in the reference's order (cad_to_dataset.py:264-276, then :145-160): three
     ``uniform(-1, 1)`` for the axis (normalised), ``uniform(0, 2 pi)`` for the angle, per axis ``uniform(0, 0.5 | 0.5 | 0.3)`` for the
@@ -249,11 +332,14 @@ class CadMeshRenderer:
     """A coloured triangle mesh on the device and the camera of one object directory (``df_cad_render_mesh``).  The triangle indices
     are checked on the host before anything is uploaded (``check_triangles``).  ``render(poses, holes, cull, mask)``: as
     ``CadRenderer.render`` without ``splat``; hole indices name vertices, ``cull`` 1 drops the triangles that face away;
-    stats[:, 1] counts the triangles that reached the z-buffer."""
+    stats[:, 1] counts the triangles that reached the z-buffer.  ``normals``: None, "flat", "smooth" or an array ([T,3] or [V,3]);
+    with them ``render(..., light=[F,8])`` lights the frames (``df_cad_render_mesh_lit``); the light is checked on the host
+    (``check_light``) before anything is uploaded, and a light without normals is a ``ValueError``."""
 
-    def __init__(self, vertices, triangles, colors, proj_mat, image_dims, device="cuda", model_scale=10.0):
+    def __init__(self, vertices, triangles, colors, proj_mat, image_dims, device="cuda", model_scale=10.0, normals=None):
         vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         triangles = check_triangles(triangles, len(vertices))
+        made = None if normals is None else _make_normals(normals, vertices, triangles)
         self.device = torch.device(device)
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
         self.vertices = up(vertices, np.float32)
@@ -262,18 +348,24 @@ class CadMeshRenderer:
         self.proj_mat = np.ascontiguousarray(proj_mat, dtype=np.float64)
         self.image_dims = (int(image_dims[0]), int(image_dims[1]))
         self.model_scale = float(model_scale)
+        self.normals, self.normal_mode = (None, 0) if made is None else (up(made[0], np.float32), made[1])
         self._scratch = None
 
     pack_holes = staticmethod(CadRenderer.pack_holes)
 
-    def render(self, poses, holes=None, cull=1, mask="box"):
+    def render(self, poses, holes=None, cull=1, mask="box", light=None):
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3, 4)
         F = poses.shape[0]
+        if light is not None:
+            if self.normals is None:
+                raise ValueError("a light needs normals: build the renderer with normals=")
+            light = check_light(light, F)
         need = F * self.image_dims[0] * self.image_dims[1] * 8
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         return pp.cad_render_mesh(self.vertices, self.colors, self.triangles, poses, self.model_scale, self.proj_mat, self.image_dims,
-                                  holes=self.pack_holes(holes, F), cull=cull, mask_mode=MASK_MODES[mask], scratch=self._scratch)
+                                  holes=self.pack_holes(holes, F), cull=cull, mask_mode=MASK_MODES[mask], scratch=self._scratch,
+                                  normals=self.normals, normal_mode=self.normal_mode, light=light)
 
 
 class CadSceneRenderer:
@@ -282,15 +374,22 @@ class CadSceneRenderer:
     (``check_triangles``); the meshes are concatenated once (indices made global) and uploaded once; the scratch buffer is reused.
     ``render(poses [F,O,3,4], present, cull)`` -> device tensors (rgb [F,IH,IW,3] uint8, depth and label [F,IH,IW] uint16 with label =
     object + 1 on the pixels it won, stats [F,O,6] int32 = {pixels won, triangles tested, rmin, rmax, cmin, cmax});
-    ``masks(label, stats, pairs, mask)`` -> the loader's mask [N,IH,IW] uint16 of each (frame, object) pair."""
+    ``masks(label, stats, pairs, mask)`` -> the loader's mask [N,IH,IW] uint16 of each (frame, object) pair.
+    ``normals``: None, "flat", "smooth" or one array per mesh (all per triangle or all per vertex), concatenated like the vertices and
+    triangles; with them ``render(..., light=[F,8])`` lights the frames, one light per frame for all objects
+    (``df_cad_render_scene_lit``), checked as in ``CadMeshRenderer``."""
 
-    def __init__(self, meshes, proj_mat, image_dims, model_scales, device="cuda"):
+    def __init__(self, meshes, proj_mat, image_dims, model_scales, device="cuda", normals=None):
         if len(meshes) == 0 or len(meshes) != len(np.atleast_1d(model_scales)):
             raise ValueError("one model scale per mesh, at least one mesh")
-        verts, tris, cols, begin = [], [], [], [0]
-        for v, t, c in meshes:
+        if normals is not None and not isinstance(normals, str) and len(normals) != len(meshes):
+            raise ValueError("normals: one array per mesh")
+        verts, tris, cols, begin, nrms = [], [], [], [0], []
+        for o, (v, t, c) in enumerate(meshes):
             v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
             t = check_triangles(t, len(v))
+            if normals is not None:
+                nrms.append(_make_normals(normals if isinstance(normals, str) else normals[o], v, t))
             c = np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 3)
             if len(c) != len(v):
                 raise ValueError("one colour per vertex")
@@ -307,16 +406,26 @@ class CadSceneRenderer:
         self.n_objects = len(meshes)
         self.proj_mat = np.ascontiguousarray(proj_mat, dtype=np.float64)
         self.image_dims = (int(image_dims[0]), int(image_dims[1]))
+        self.normals, self.normal_mode = None, 0
+        if nrms:
+            if len({m for _, m in nrms}) != 1:
+                raise ValueError("normals: per triangle for all meshes or per vertex for all meshes")
+            self.normals, self.normal_mode = up(np.concatenate([n for n, _ in nrms]), np.float32), nrms[0][1]
         self._scratch = None
 
-    def render(self, poses, present=None, cull=1):
+    def render(self, poses, present=None, cull=1, light=None):
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, self.n_objects, 3, 4)
         F = poses.shape[0]
+        if light is not None:
+            if self.normals is None:
+                raise ValueError("a light needs normals: build the renderer with normals=")
+            light = check_light(light, F)
         need = F * self.image_dims[0] * self.image_dims[1] * 8
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         return pp.cad_render_scene(self.vertices, self.colors, self.triangles, self.tri_begin, self.model_scales, poses, self.proj_mat,
-                                   self.image_dims, present=present, cull=cull, scratch=self._scratch)
+                                   self.image_dims, present=present, cull=cull, scratch=self._scratch, normals=self.normals,
+                                   normal_mode=self.normal_mode, light=light)
 
     def masks(self, label, stats, pairs, mask="box"):
         return pp.cad_scene_mask(label, stats, pairs, mask_mode=MASK_MODES[mask])

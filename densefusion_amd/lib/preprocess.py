@@ -230,6 +230,21 @@ def _cad_mesh(vertices, colors, triangles, name):
     return V, triangles.shape[0]
 
 
+def _cad_light(normals, normal_mode, light, V, T, F, dev, name):
+    """The lit calls' three arguments, checked: normals [T,3] (normal_mode 0) or [V,3] (1) float32 on the device, light [F,8] float64,
+    host or device -> (normals, normal_mode, the light on the device)"""
+    if normals is None:
+        raise RuntimeError(f"{name}: a light needs normals")
+    if normal_mode not in (0, 1):
+        raise RuntimeError(f"{name}: normal_mode {normal_mode} is neither 0 (per triangle) nor 1 (per vertex)")
+    rows = V if normal_mode else T
+    if not torch.is_tensor(normals) or not normals.is_cuda or normals.dtype != torch.float32 or tuple(normals.shape) != (rows, 3):
+        raise RuntimeError(f"{name}: normals must be a [{rows},3] float32 device tensor for normal_mode {normal_mode}")
+    light = _on_device(light, np.float64, dev, lambda p: p.dtype == torch.float64 and tuple(p.shape) == (F, 8),
+                       f"{name}: light must be [F,8] float64")
+    return normals, int(normal_mode), light
+
+
 def cad_render(points, normals, colors, pose, model_scale, proj, image_dims, holes=None, splat=0, mask_mode=0, scratch=None):
     """F views of a coloured cloud as customCAD frames (``df_cad_render``; the contract is its comment in include/dfusion.h).
     points [P,3] float32, normals [P,3] float32 or None, colors [P,3] uint8 -- device tensors; pose [F,3,4] / [F,12] float64 [R|t] into
@@ -264,11 +279,14 @@ def cad_render(points, normals, colors, pose, model_scale, proj, image_dims, hol
     return rgb, depth, mask, stats
 
 
-def cad_render_mesh(vertices, colors, triangles, pose, model_scale, proj, image_dims, holes=None, cull=1, mask_mode=0, scratch=None):
+def cad_render_mesh(vertices, colors, triangles, pose, model_scale, proj, image_dims, holes=None, cull=1, mask_mode=0, scratch=None,
+                    normals=None, normal_mode=0, light=None):
     """F views of a coloured triangle mesh as customCAD frames (``df_cad_render_mesh``; the contract is its comment in include/dfusion.h).
     vertices [V,3] float32, colors [V,3] uint8, triangles [T,3] int32 -- device tensors; pose, proj, image_dims, holes (indices name
     vertices), mask_mode and scratch as for ``cad_render`` (scratch: at least ``df_cad_render_mesh_scratch_bytes``); cull 1 drops the
-    triangles that face away.
+    triangles that face away.  With ``light`` ([F,8] float64 {Lx, Ly, Lz, ambient, diffuse, cr, cg, cb}, host or device) the covered
+    pixels are lit (``df_cad_render_mesh_lit``, steps L1..L6): normals is then a float32 device tensor, [T,3] for normal_mode 0 (flat)
+    or [V,3] for normal_mode 1 (smooth).  Without a light normals and normal_mode are ignored.
     Returns rgb [F,IH,IW,3] uint8, depth and mask [F,IH,IW] uint16, stats [F,6] int32 on the device; no read-back, no synchronisation."""
     V, T = _cad_mesh(vertices, colors, triangles, "cad_render_mesh")
     dev = vertices.device
@@ -279,22 +297,30 @@ def cad_render_mesh(vertices, colors, triangles, pose, model_scale, proj, image_
     L = _lib.lib()
     scratch = _cad_scratch(scratch, L.df_cad_render_mesh_scratch_bytes(F, IH, IW, V, T), dev, "cad_render_mesh",
                            f"F={F}, IH={IH}, IW={IW}, V={V}, T={T}")
+    if light is not None:
+        normals, normal_mode, light = _cad_light(normals, normal_mode, light, V, T, F, dev, "cad_render_mesh")
     rgb, depth, mask = _cad_frames(F, IH, IW, dev)
     stats = torch.empty(F, 6, dtype=torch.int32, device=dev)
+    head = (_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, pose.data_ptr(), float(model_scale),
+            hole_idx.ctypes.data if K else None, hole_r.ctypes.data if K else None, K, proj.ctypes.data, F, IH, IW, int(cull), int(mask_mode))
+    outs = (rgb.data_ptr(), depth.data_ptr(), mask.data_ptr(), stats.data_ptr(), scratch.data_ptr(), scratch.numel())
     with _lib.device_guard(dev):
-        st = L.df_cad_render_mesh(_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, pose.data_ptr(), float(model_scale),
-                                  hole_idx.ctypes.data if K else None, hole_r.ctypes.data if K else None, K, proj.ctypes.data, F, IH, IW,
-                                  int(cull), int(mask_mode), rgb.data_ptr(), depth.data_ptr(), mask.data_ptr(), stats.data_ptr(),
-                                  scratch.data_ptr(), scratch.numel(), _lib.current_stream())
+        if light is None:
+            st = L.df_cad_render_mesh(*head, *outs, _lib.current_stream())
+        else:
+            st = L.df_cad_render_mesh_lit(*head, _lib.dptr(normals), normal_mode, light.data_ptr(), *outs, _lib.current_stream())
     _lib.check(st, "cad_render_mesh")
     return rgb, depth, mask, stats
 
 
-def cad_render_scene(vertices, colors, triangles, tri_begin, model_scales, pose, proj, image_dims, present=None, cull=1, scratch=None):
+def cad_render_scene(vertices, colors, triangles, tri_begin, model_scales, pose, proj, image_dims, present=None, cull=1, scratch=None,
+                     normals=None, normal_mode=0, light=None):
     """F frames of O objects with occlusion (``df_cad_render_scene``; the contract is its comment in include/dfusion.h).
     vertices [V,3] float32, colors [V,3] uint8, triangles [T,3] int32 -- device tensors, shared by all objects, the indices global;
     tri_begin [O+1] and model_scales [O] -- HOST; pose [F,O,3,4] / [F,O,12] float64, host or device; present: None (all) or [F,O]
-    uint8, host or device; proj, image_dims and scratch (at least ``df_cad_render_scene_scratch_bytes``) as for ``cad_render_mesh``.
+    uint8, host or device; proj, image_dims and scratch (at least ``df_cad_render_scene_scratch_bytes``) as for ``cad_render_mesh``;
+    normals, normal_mode and light ([F,8]: one light per frame for all objects) too, the per-triangle normals indexed globally
+    (``df_cad_render_scene_lit``).
     Returns rgb [F,IH,IW,3] uint8, depth and label [F,IH,IW] uint16 (label = owner + 1, 0 = horizon), stats [F,O,6] int32 on the
     device; no read-back, no synchronisation."""
     V, T = _cad_mesh(vertices, colors, triangles, "cad_render_scene")
@@ -314,13 +340,18 @@ def cad_render_scene(vertices, colors, triangles, tri_begin, model_scales, pose,
     L = _lib.lib()
     scratch = _cad_scratch(scratch, L.df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O), dev, "cad_render_scene",
                            f"F={F}, IH={IH}, IW={IW}, V={V}, T={T}, O={O}")
+    if light is not None:
+        normals, normal_mode, light = _cad_light(normals, normal_mode, light, V, T, F, dev, "cad_render_scene")
     rgb, depth, label = _cad_frames(F, IH, IW, dev)
     stats = torch.empty(F, O, 6, dtype=torch.int32, device=dev)
+    head = (_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, tri_begin.ctypes.data, model_scales.ctypes.data, O,
+            pose.data_ptr(), None if present is None else present.data_ptr(), proj.ctypes.data, F, IH, IW, int(cull))
+    outs = (rgb.data_ptr(), depth.data_ptr(), label.data_ptr(), stats.data_ptr(), scratch.data_ptr(), scratch.numel())
     with _lib.device_guard(dev):
-        st = L.df_cad_render_scene(_lib.dptr(vertices), _lib.dptr(colors), V, _lib.dptr(triangles), T, tri_begin.ctypes.data,
-                                   model_scales.ctypes.data, O, pose.data_ptr(), None if present is None else present.data_ptr(),
-                                   proj.ctypes.data, F, IH, IW, int(cull), rgb.data_ptr(), depth.data_ptr(), label.data_ptr(),
-                                   stats.data_ptr(), scratch.data_ptr(), scratch.numel(), _lib.current_stream())
+        if light is None:
+            st = L.df_cad_render_scene(*head, *outs, _lib.current_stream())
+        else:
+            st = L.df_cad_render_scene_lit(*head, _lib.dptr(normals), normal_mode, light.data_ptr(), *outs, _lib.current_stream())
     _lib.check(st, "cad_render_scene")
     return rgb, depth, label, stats
 

@@ -378,6 +378,44 @@ int df_cad_render_mesh(const float *vertices, const unsigned char *colors, int V
                        int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Diffuse lighting for the two triangle renderers: df_cad_render_mesh_lit and df_cad_render_scene_lit (declared after
+ * df_cad_render_scene) take the parameters of df_cad_render_mesh / df_cad_render_scene with three more directly before rgb_out, and
+ * write the same frames with the colour of every covered pixel multiplied by ambient + diffuse * max(N.L, 0) times a light colour.
+ * Only the colour of covered pixels changes: depth, label, stats, masks, the horizon colour and every rule of V1..V5, T1..T7 and S1..S3
+ * are those of the unlit calls, whose scratch-size functions these calls share (the scratch is still the keys only).  The rules carry
+ * over: no allocation, no synchronisation, the caller's stream, bit-reproducible, a frame's outputs independent of the other frames.
+ * The point renderer df_cad_render has no lit form.
+ *
+ *   DEVICE: normals, float, model space, expected to be of unit length (not checked): normal_mode 0 = one per triangle, [T][3], indexed
+ *   by the call's triangle index (the GLOBAL index in a scene) -- flat shading; normal_mode 1 = one per vertex, [V][3] -- smooth shading.
+ *   light [F][8] double = {Lx, Ly, Lz, ambient, diffuse, cr, cg, cb} per frame (a scene has one light per frame for all its objects):
+ *   L is the direction from the surface towards the light in camera space (x right, y up, the camera looks along -z: (0, 0, 1) is a
+ *   head-light), expected to be of unit length and used as given.
+ *   light == NULL is the unlit call exactly: normals may then be NULL and normal_mode is ignored.
+ *   DF_ERR_ARG, before anything is launched or written: light != NULL with normals == NULL or with normal_mode outside 0..1, and
+ *   everything the unlit call refuses.
+ *   Per covered pixel, after the resolve has recomputed the winner's w_k, u_k = w_k / c_3(i_k) and U = (u0 + u1) + u2; all in fp64, one
+ *   rounding per operation (no fused multiply-add), in exactly this order; t = (i0, i1, i2) is the winner, R the rotation of pose[f]
+ *   (mesh) or of pose[f][o], o the winner's owner (scene):
+ *   L1. Mode 0: n = (double)normals[t].  Mode 1: n_k = (double)normals[i_k] for the three corners.
+ *   L2. Rotated as step 3 of df_cad_render rotates: n'_j = (R[j][0]*n_x + R[j][1]*n_y) + R[j][2]*n_z.  Mode 0: N = n'.  Mode 1: each
+ *       corner's normal is rotated first, then N_j = ((u0*n'0_j + u1*n'1_j) + u2*n'2_j) / U: the perspective-correct mix.  THE MIX IS NOT
+ *       RE-NORMALISED (inside a triangle |N| falls short of 1 by at most 1 - cos(half the largest angle between two of its corner
+ *       normals)), so there is no square root anywhere in the contract.  R is taken to be a rotation; this is not checked.
+ *   L3. When the winner faces away (A > 0 in T3, possible only with cull == 0): N = -N.  A back face is lit as the side the camera sees.
+ *   L4. c = (N_x*L_x + N_y*L_y) + N_z*L_z;  c = c > 0 ? c : 0 (a NaN gives 0).
+ *   L5. s = ambient + diffuse * c.
+ *   L6. Per channel, with a = ((u0*C_i0 + u1*C_i1) + u2*C_i2) / U, the value the unlit resolve rounds:
+ *       channel = rint(a * (s * c_ch)) clamped to 0..255 (a NaN gives 0).  The only rounding to 8 bits is this last one.
+ *   Hence the record {., ., ., 1, 0, 1, 1, 1} multiplies by exactly 1.0 and gives the unlit bytes, and a light that saturates clamps
+ *   at 255. */
+int df_cad_render_mesh_lit(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const double *pose,
+                           double model_scale, const int *hole_idx, const double *hole_r, int K, const double *proj, int F, int IH, int IW,
+                           int cull, int mask_mode, const float *normals, int normal_mode, const double *light, unsigned char *rgb_out,
+                           unsigned short *depth_out, unsigned short *mask_out, int *stats_out, void *scratch, size_t scratch_bytes,
+                           df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-object customCAD scenes with occlusion: F frames of O meshes, each with its own pose per frame, drawn into one z-buffer, so that
  * a target can be covered by another object and a frame can hold distractors (the Unity scenes the reference was fed; the YCB path has
  * df_compose_frame for it).  The rules of df_cad_render_mesh carry over: no allocation, no synchronisation, the caller's stream; integer
@@ -422,6 +460,12 @@ int df_cad_render_scene(const float *vertices, const unsigned char *colors, int 
                         const double *model_scale, int O, const double *pose, const unsigned char *present, const double *proj, int F,
                         int IH, int IW, int cull, unsigned char *rgb_out, unsigned short *depth_out, unsigned short *label_out,
                         int *stats_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
+/* the contract of the lit call is the comment of df_cad_render_mesh_lit */
+int df_cad_render_scene_lit(const float *vertices, const unsigned char *colors, int V, const int *triangles, int T, const int *tri_begin,
+                            const double *model_scale, int O, const double *pose, const unsigned char *present, const double *proj, int F,
+                            int IH, int IW, int cull, const float *normals, int normal_mode, const double *light, unsigned char *rgb_out,
+                            unsigned short *depth_out, unsigned short *label_out, int *stats_out, void *scratch, size_t scratch_bytes,
+                            df_stream_t stream);
 int df_cad_scene_mask(const unsigned short *label, const int *stats, int F, int O, int IH, int IW, const int *pairs, int N, int mask_mode,
                       unsigned short *mask_out, df_stream_t stream);
 

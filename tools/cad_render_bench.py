@@ -16,6 +16,11 @@ mesh alone at the same poses (without occlusion: what the single-object path cos
 
     python tools/cad_render_bench.py --scene --subdiv 7 --chunk 32
 
+``--light`` (with ``--mesh`` or ``--scene``) times the lit calls instead (``df_cad_render_mesh_lit`` / ``df_cad_render_scene_lit``) with
+the light ``render.sample_light`` draws for each frame's seed and ``--shading flat|smooth`` normals; the point path stays unlit.
+
+    python tools/cad_render_bench.py --scene --subdiv 7 --chunk 32 --light
+
 ``--visibility N`` draws the scenes of seeds 0..N-1 as tools/render_cad_dataset.py --scene does for the meshes of its test
 (tests/cad_scene_np.py: two spheres as models, a box as distractor, 96 x 144 frames) and prints the histogram of the visible fractions
 of the models that are present, in ten bins.
@@ -54,6 +59,13 @@ def timed(render, calls):
     return times, out
 
 
+def lights_of(opt):
+    """(normals argument of the renderers, light [chunk,8] or None)"""
+    if not opt.light:
+        return None, None
+    return opt.shading, np.stack([cr.sample_light(s) for s in range(opt.chunk)])
+
+
 def mesh_bench(opt):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import cad_raster_np as mnp
@@ -69,10 +81,11 @@ def mesh_bench(opt):
         poses.append(np.concatenate([R, t[:, None]], axis=1))
     poses = np.stack(poses)
     dims = (opt.height, opt.width)
-    res = {"frame": list(dims), "chunk": opt.chunk, "holes": 0}
+    normals, light = lights_of(opt)
+    res = {"frame": list(dims), "chunk": opt.chunk, "holes": 0, "light": bool(opt.light), "shading": opt.shading if opt.light else None}
     for name, v, f in (("icosphere", sv, sf), ("box", bv, bf)):
-        r = cr.CadMeshRenderer(v, f, rng.integers(0, 256, (len(v), 3), dtype=np.uint8), PROJ, dims)
-        times, out = timed(lambda: r.render(poses, cull=1, mask="box"), opt.calls)
+        r = cr.CadMeshRenderer(v, f, rng.integers(0, 256, (len(v), 3), dtype=np.uint8), PROJ, dims, normals=normals)
+        times, out = timed(lambda: r.render(poses, cull=1, mask="box", light=light), opt.calls)
         stats = out[3].cpu().numpy()
         res[name] = {"triangles": int(len(f)), "device_ms_per_frame_median": float(np.median(times)) / opt.chunk,
                      "device_ms_per_call": [round(t, 3) for t in times], "covered_mean": float(stats[:, 0].mean()),
@@ -111,17 +124,19 @@ def scene_bench(opt):
             R, t = cr.view_pose(axis, angle, xyz, np.zeros(3), 10.0)
             poses[s, o] = np.concatenate([R, t[:, None]], axis=1)
     dims = (opt.height, opt.width)
-    scene = cr.CadSceneRenderer(meshes, PROJ, dims, [10.0] * O)
-    times, out = timed(lambda: scene.render(poses, cull=1), opt.calls)
+    normals, light = lights_of(opt)
+    scene = cr.CadSceneRenderer(meshes, PROJ, dims, [10.0] * O, normals=normals)
+    times, out = timed(lambda: scene.render(poses, cull=1, light=light), opt.calls)
     stats = out[3].cpu().numpy()
     res = {"frame": list(dims), "chunk": opt.chunk, "objects": O, "triangles": [int(len(m[1])) for m in meshes],
+           "light": bool(opt.light), "shading": opt.shading if opt.light else None,
            "scene": {"device_ms_per_frame_median": float(np.median(times)) / opt.chunk, "device_ms_per_call": [round(t, 3) for t in times],
                      "pixels_won_mean": [float(x) for x in stats[:, :, 0].mean(axis=0)],
                      "triangles_tested_mean": [float(x) for x in stats[:, :, 1].mean(axis=0)]},
            "solo": []}
     for o, (v, f, c) in enumerate(meshes):
-        r = cr.CadMeshRenderer(v, f, c, PROJ, dims)
-        times, out = timed(lambda: r.render(poses[:, o], cull=1, mask="box"), opt.calls)
+        r = cr.CadMeshRenderer(v, f, c, PROJ, dims, normals=normals)
+        times, out = timed(lambda: r.render(poses[:, o], cull=1, mask="box", light=light), opt.calls)
         res["solo"].append({"triangles": int(len(f)), "device_ms_per_frame_median": float(np.median(times)) / opt.chunk,
                             "covered_mean": float(out[3].cpu().numpy()[:, 0].mean())})
     res["solo_sum_device_ms_per_frame"] = float(sum(x["device_ms_per_frame_median"] for x in res["solo"]))
@@ -161,6 +176,8 @@ def main(argv=None):
     ap.add_argument("--scene", action="store_true", help="time df_cad_render_scene (six objects) next to the sum of the solo df_cad_render_mesh calls")
     ap.add_argument("--visibility", type=int, default=0, help="histogram of the visible fractions sample_scene gives over this many seeds")
     ap.add_argument("--mesh", action="store_true", help="time df_cad_render_mesh (icosphere, box) and the point path on points of that icosphere")
+    ap.add_argument("--light", action="store_true", help="--mesh / --scene: time the lit calls, one sample_light record per frame")
+    ap.add_argument("--shading", type=str, default="flat", choices=("flat", "smooth"), help="--light: one normal per triangle, or per vertex")
     ap.add_argument("--subdiv", type=int, default=7, help="--mesh: icosphere subdivisions (20 * 4^n triangles)")
     ap.add_argument("--points", type=int, default=1000000)
     ap.add_argument("--height", type=int, default=520)
@@ -170,6 +187,8 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--cpu", action="store_true", help="also time the numpy restatement on one frame")
     opt = ap.parse_args(argv)
+    if opt.light and not (opt.mesh or opt.scene):
+        ap.error("--light needs --mesh or --scene: the point renderer is unlit")
     if opt.visibility:
         return visibility(opt)
     if opt.scene:

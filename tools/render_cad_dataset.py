@@ -31,6 +31,13 @@ is present, won at least ``--min_pixels`` pixels and is visible to at least ``--
 scene's, its mask, record and numbering its own.  No holes are cut in scenes.  ``--mask box`` marks the occluder's pixels inside the box
 as the object -- the reference's own rule (mask_generator.py:21-28) -- so the loader's cloud then holds points of the occluder;
 ``--mask pixels`` marks only the pixels the object won and is the mode that keeps them out.
+
+``--light head|random`` (with ``--raster mesh`` or ``--scene``) lights the frames (``df_cad_render_mesh_lit`` /
+``df_cad_render_scene_lit``): ``head`` is ``render.HEAD_LIGHT`` in every frame, ``random`` draws ``render.sample_light(seed)`` within
+``--light_angle`` degrees of the viewing direction; ``--shading flat|smooth`` takes one normal per triangle or per vertex.  A scene has
+one light per shared frame for all its objects.  ``data/XX/meta/lights.txt`` then holds one line per written frame: the frame number and
+the eight values of its record with ``repr``; as with the poses the frame is rendered from the parsed text.  The loader ignores the
+file.  With ``--light none`` (the default) no such file is written and the trees are what they were without the flag.
 """
 from __future__ import annotations
 
@@ -77,6 +84,10 @@ def build_parser():
     ap.add_argument("--raster", type=str, default="points", choices=("points", "mesh"), help="splat a sampled cloud, or rasterise the triangles")
     ap.add_argument("--cull", type=int, default=1, choices=(0, 1), help="--raster mesh: 1 drops the triangles that face away from the camera")
     ap.add_argument("--mask", type=str, default="box", choices=sorted(cr.MASK_MODES))
+    ap.add_argument("--light", type=str, default="none", choices=("none", "head", "random"),
+                    help="--raster mesh / --scene: light the frames from the camera, or from a direction drawn per seed")
+    ap.add_argument("--shading", type=str, default="flat", choices=("flat", "smooth"), help="--light: one normal per triangle, or per vertex")
+    ap.add_argument("--light_angle", type=float, default=60.0, help="--light random: largest angle between light and viewing direction, degrees")
     ap.add_argument("--points", type=int, default=0, help="points to draw from a mesh (default 1 000 000) or to keep of a cloud (default all)")
     ap.add_argument("--max_holes", type=int, default=3)
     ap.add_argument("--hole_mean", type=float, default=30.0, help="model file units")
@@ -96,6 +107,27 @@ def parse_record(text):
     """(pos, quat) of one record, token by token like the loader's ``parse_transforms``."""
     lines = text.split("\n")
     return tuple(np.array([float(x.rstrip()) for x in ln.replace("(", "").replace(")", "").replace(",", "").split(" ")]) for ln in lines[1:3])
+
+
+def light_text(light):
+    """The eight values of a light record as they stand in ``lights.txt`` after the frame number."""
+    return " ".join(repr(float(v)) for v in light)
+
+
+def parse_light(text):
+    return np.array([float(x) for x in text.split()], dtype=np.float64)
+
+
+def draw_light(opt, seed):
+    """The light of seed ``seed`` as (text, record parsed back from it): rendered from the file's own values."""
+    light = cr.HEAD_LIGHT if opt.light == "head" else cr.sample_light(seed, max_angle=np.radians(opt.light_angle))
+    text = light_text(light)
+    return text, parse_light(text)
+
+
+def write_lights(sub, texts):
+    with open(os.path.join(sub, "meta", "lights.txt"), "w") as f:
+        f.write("".join("%d %s\n" % (n, t) for n, t in enumerate(texts)))
 
 
 def write_vertex_ply(path, pts):
@@ -160,7 +192,8 @@ def main_scene(opt, ap):
         with open(os.path.join(sub, "meta", "proj_mat.txt"), "w") as f:
             f.write("".join("\t".join(repr(float(v)) for v in row) + "\n" for row in proj) + "\n")
     proj = read_proj_mat(os.path.join(subs[0], "meta", "proj_mat.txt"))      # what the loader will read
-    renderer = cr.CadSceneRenderer(meshes, proj, (opt.height, opt.width), [opt.model_scale] * O)
+    lit = opt.light != "none"
+    renderer = cr.CadSceneRenderer(meshes, proj, (opt.height, opt.width), [opt.model_scale] * O, normals=opt.shading if lit else None)
     centroids = [m[0].astype(np.float64).mean(axis=0) for m in meshes]
 
     def save(sub, n, rgb, depth, mask):
@@ -171,6 +204,7 @@ def main_scene(opt, ap):
     records = [[] for _ in range(n_targets)]
     visible = [[] for _ in range(n_targets)]
     seeds = [[] for _ in range(n_targets)]
+    light_texts = [[] for _ in range(n_targets)]
     skipped, seed, device_ms = 0, opt.seed, []
     t_start = time.time()
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
@@ -191,11 +225,13 @@ def main_scene(opt, ap):
                     row_t.append(text); row_p.append(np.concatenate([R, t[:, None]], axis=1))
                     present[j, o] = here
                 texts.append(row_t); poses.append(np.stack(row_p))
+            lights = [draw_light(opt, s) for s in range(seed, seed + opt.chunk)] if lit else None
             seed += opt.chunk
             poses = np.stack(poses)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-            rgb, depth, label, stats = renderer.render(poses, present=present, cull=opt.cull)
+            rgb, depth, label, stats = renderer.render(poses, present=present, cull=opt.cull,
+                                                       light=np.stack([l for _, l in lights]) if lit else None)
             ev1.record()
             rows = stats.cpu().numpy()                                        # the chunk's read-backs before its frames
             device_ms.append(ev0.elapsed_time(ev1))
@@ -223,6 +259,8 @@ def main_scene(opt, ap):
                 pending.append(pool.submit(save, subs[k], len(records[k]), rgb[j], depth[j], mask[n]))
                 records[k].append(parse_record(texts[j][k]))
                 visible[k].append(float(frac)); seeds[k].append(seed - opt.chunk + j)
+                if lit:
+                    light_texts[k].append(lights[j][0])
             for p in pending:
                 p.result()
     for k, sub in enumerate(subs):
@@ -230,6 +268,8 @@ def main_scene(opt, ap):
             for idx, (pos, quat) in enumerate([records[k][0]] + records[k]):
                 f.write(record_text(idx, pos, quat))
         write_split(sub, len(records[k]), opt.seed)
+        if lit:
+            write_lights(sub, light_texts[k])
     wall = time.time() - t_start
     per_view = float(np.median(device_ms)) / opt.chunk
     summary = {"objects": {}, "skipped": skipped, "device_ms_per_view": per_view}
@@ -254,6 +294,9 @@ def main(argv=None):
     mesh = opt.raster == "mesh"
     if mesh and (opt.splat != ap.get_default("splat") or opt.points != ap.get_default("points")):
         ap.error("--splat and --points belong to --raster points; --raster mesh draws the triangles themselves")
+    lit = opt.light != "none"
+    if lit and not mesh:
+        ap.error("--light needs --raster mesh or --scene: the point renderer is unlit")
     if not torch.cuda.is_available():
         raise SystemExit("render_cad_dataset needs a GPU (no CPU path)")
     np.random.seed(opt.seed)
@@ -276,7 +319,8 @@ def main(argv=None):
         f.write("".join("\t".join(repr(float(v)) for v in row) + "\n" for row in proj) + "\n")
     proj = read_proj_mat(os.path.join(sub, "meta", "proj_mat.txt"))          # what the loader will read
     if mesh:
-        renderer = cr.CadMeshRenderer(pts, tris, col, proj, (opt.height, opt.width), model_scale=opt.model_scale)
+        renderer = cr.CadMeshRenderer(pts, tris, col, proj, (opt.height, opt.width), model_scale=opt.model_scale,
+                                      normals=opt.shading if lit else None)
     else:
         renderer = cr.CadRenderer(pts, nrm, col, proj, (opt.height, opt.width), model_scale=opt.model_scale)
     centroid = pts.astype(np.float64).mean(axis=0)
@@ -286,7 +330,7 @@ def main(argv=None):
         Image.fromarray(depth).save(os.path.join(sub, "depth", "Depth_%04d.png" % n))
         Image.fromarray(mask).save(os.path.join(sub, "mask", "%04d.png" % n))
 
-    records, written, skipped, seed, device_ms = [], 0, 0, opt.seed, []
+    records, light_texts, written, skipped, seed, device_ms = [], [], 0, 0, opt.seed, []
     t_start = time.time()
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
         pending = []
@@ -301,11 +345,13 @@ def main(argv=None):
                 R, t = cr.transform_to_pose(*parse_record(text))              # rendered from the record's own values
                 texts.append(text); holes.append(hs)
                 poses.append(np.concatenate([R, t[:, None]], axis=1))
+            lights = [draw_light(opt, s) for s in range(seed, seed + opt.chunk)] if lit else None
             seed += opt.chunk
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
             if mesh:
-                rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, cull=opt.cull, mask=opt.mask)
+                rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, cull=opt.cull, mask=opt.mask,
+                                                          light=np.stack([l for _, l in lights]) if lit else None)
             else:
                 rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, splat=opt.splat, mask=opt.mask)
             ev1.record()
@@ -320,6 +366,8 @@ def main(argv=None):
                     continue
                 pos, quat = parse_record(texts[k])
                 records.append((pos, quat))
+                if lit:
+                    light_texts.append(lights[k][0])
                 pending.append(pool.submit(save, written, rgb[k], depth[k], mask[k]))
                 written += 1
             for p in pending:
@@ -329,6 +377,8 @@ def main(argv=None):
         for idx, (pos, quat) in enumerate([records[0]] + records):
             f.write(record_text(idx, pos, quat))
     write_split(sub, written, opt.seed)
+    if lit:
+        write_lights(sub, light_texts)
     wall = time.time() - t_start
     per_view = float(np.median(device_ms)) / opt.chunk            # the median call: the first one also loads the kernels
     what = (f"{len(tris)} triangles", f"cull {opt.cull}") if mesh else (f"{len(pts)} points", f"splat {opt.splat}")
