@@ -93,6 +93,7 @@ SIGNATURES = {
     "df_cad_render_scene_lit": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                      ctypes.c_size_t, _vp]),
     "df_cad_scene_mask": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "df_cad_depth_sensor": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_uint, ctypes.c_uint, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "df_color_jitter": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "df_compose_frame": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "df_conv2d_nhwc": (_i, [ctypes.POINTER(ConvDesc), _vp]),

@@ -19,6 +19,11 @@ Lighting (``df_cad_render_mesh_lit`` / ``df_cad_render_scene_lit``, DESIGN.md 12
 camera space ((0, 0, 1): a head-light).  A covered pixel's colour is multiplied by ambient + diffuse * max(N.L, 0) and the light's
 colour; geometry, depth and masks do not change.  ``sample_light`` draws a record per seed from a stream of its own.  The reference
 has no counterpart: its frames were lit by Unity.  The point renderer stays unlit.
+
+Depth sensor (``df_cad_depth_sensor``): ``apply_sensor(depth, DepthSensor(...), seed, first_frame)`` turns the exact
+depth of any of the three renderers into what a range camera would report -- noise of constant sigma in code units (the code is a
+disparity, so the range noise grows with z squared), drop-out along depth discontinuities and at random, quantisation -- in integer
+arithmetic on the codes.  Colour, masks, labels and the render's statistics stay those of the clean render.
 """
 from __future__ import annotations
 
@@ -429,3 +434,52 @@ class CadSceneRenderer:
 
     def masks(self, label, stats, pairs, mask="box"):
         return pp.cad_scene_mask(label, stats, pairs, mask_mode=MASK_MODES[mask])
+
+
+NOISE_VARIANCE = 1431655765          # of the centred sum of four 16-bit uniforms (step D5): 4 (2^32 - 1) / 12
+
+
+class DepthSensor:
+    """The record of the depth-sensor model (steps D0..D6 of ``df_cad_depth_sensor``).  ``sigma_code``: standard deviation of the
+    disparity noise in code units (``sigma_code_at`` gives the one that means a range noise at a range); ``edge_radius`` R 0..4: a
+    pixel is an edge pixel when its (2R+1)^2 window holds a horizon pixel or a code further than ``edge_step`` from its own;
+    ``edge_drop``: probability that an edge pixel goes missing; ``drop``: probability that any pixel does; ``quant`` 1..4096: the codes
+    are rounded to multiples of it.  The defaults are the identity.  A bad value is a ``ValueError`` (host only).
+    ``record()`` -> (noise_mul, edge_radius, edge_step, edge_drop24, drop24, quant), the six integers of the call."""
+
+    def __init__(self, sigma_code=0.0, edge_radius=0, edge_step=0, edge_drop=0.0, drop=0.0, quant=1):
+        sigma_code, edge_drop, drop = float(sigma_code), float(edge_drop), float(drop)
+        if not np.isfinite(sigma_code) or sigma_code < 0:
+            raise ValueError(f"sigma_code {sigma_code} must be finite and not negative")
+        noise_mul = int(np.rint(sigma_code * 2.0 ** 32 / np.sqrt(float(NOISE_VARIANCE))))
+        if noise_mul > 2 ** 31 - 1:
+            raise ValueError(f"sigma_code {sigma_code} is too large: noise_mul {noise_mul} above 2^31 - 1")
+        for name, v, lo, hi in (("edge_radius", edge_radius, 0, 4), ("edge_step", edge_step, 0, 65535), ("quant", quant, 1, 4096)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} {v!r} must be an integer in {lo}..{hi}")
+        for name, v in (("edge_drop", edge_drop), ("drop", drop)):
+            if not 0.0 <= v <= 1.0:                                             # a NaN fails too
+                raise ValueError(f"{name} {v} must be a probability")
+        self.sigma_code, self.edge_radius, self.edge_step = sigma_code, int(edge_radius), int(edge_step)
+        self.edge_drop, self.drop, self.quant = edge_drop, drop, int(quant)
+        self._record = (noise_mul, self.edge_radius, self.edge_step, int(np.rint(edge_drop * 2.0 ** 24)), int(np.rint(drop * 2.0 ** 24)),
+                        self.quant)
+
+    def record(self):
+        return self._record
+
+    @staticmethod
+    def sigma_code_at(proj_mat, sigma_z, z):
+        """The code-space sigma that gives range noise ``sigma_z`` at range ``z``, both in the units of
+        ``UnityDepthProjector.project_depth``: code = 65534 ((1 + p22) + p23 / z), so |d code / d z| = 65534 |p23| / z^2."""
+        return 65534.0 * abs(float(np.asarray(proj_mat, dtype=np.float64)[2, 3])) * float(sigma_z) / (float(z) * float(z))
+
+
+def apply_sensor(depth, sensor, seed, first_frame=0):
+    """``sensor`` (a ``DepthSensor``) over rendered depth [F,IH,IW] uint16 on the device, after any of the three renderers: frame f draws
+    from (seed, first_frame + f), so a frame's result does not depend on how the frames are cut into calls.
+    Returns (depth_out, stats [F,4] int32 = {edge pixels, dropped at random, dropped at an edge, kept and changed}); ``depth`` is left
+    as it is, nothing is read back."""
+    if not isinstance(sensor, DepthSensor):
+        raise ValueError("sensor must be a DepthSensor")
+    return pp.cad_depth_sensor(depth, sensor.record(), seed, first_frame)

@@ -381,6 +381,33 @@ def cad_scene_mask(label, stats, pairs, mask_mode=0):
     return mask
 
 
+def cad_depth_sensor(depth, record, seed, first_frame=0, out=None):
+    """The depth-sensor model over rendered frames (``df_cad_depth_sensor``; steps D0..D6 of its comment in include/dfusion.h):
+    depth [F,IH,IW] uint16 device tensor, the clean render; record = (noise_mul, edge_radius, edge_step, edge_drop24, drop24, quant),
+    six integers (``render.DepthSensor.record``); seed and first_frame are taken mod 2^32, frame f of the call draws from
+    first_frame + f.  ``out``: an optional [F,IH,IW] uint16 device tensor that shares no memory with ``depth``.
+    Returns (depth_out [F,IH,IW] uint16, stats [F,4] int32 = {edge pixels, dropped at random, dropped at an edge, kept and changed})
+    on the device; no read-back, no synchronisation."""
+    if not depth.is_cuda or depth.dtype != torch.uint16 or depth.dim() != 3:
+        raise RuntimeError("cad_depth_sensor: depth must be a [F,IH,IW] uint16 device tensor (no CPU path)")
+    record = tuple(int(v) for v in record)
+    if len(record) != 6 or any(not -2 ** 31 <= v < 2 ** 31 for v in record):
+        raise RuntimeError("cad_depth_sensor: record must hold six 32-bit integers (noise_mul, edge_radius, edge_step, edge_drop24, drop24, quant)")
+    dev = depth.device
+    F, IH, IW = depth.shape
+    depth = depth.contiguous()
+    if out is None:
+        out = torch.empty(F, IH, IW, dtype=torch.int16, device=dev).view(torch.uint16)
+    elif not out.is_cuda or out.device != dev or out.dtype != torch.uint16 or out.shape != depth.shape or not out.is_contiguous():
+        raise RuntimeError("cad_depth_sensor: out must be a contiguous [F,IH,IW] uint16 tensor on the depth's device")
+    stats = torch.empty(F, 4, dtype=torch.int32, device=dev)
+    with _lib.device_guard(dev):
+        st = _lib.lib().df_cad_depth_sensor(depth.data_ptr(), out.data_ptr(), F, IH, IW, int(seed) & 0xFFFFFFFF, int(first_frame) & 0xFFFFFFFF,
+                                            *record, stats.data_ptr(), _lib.current_stream())
+    _lib.check(st, "cad_depth_sensor")
+    return out, stats
+
+
 def color_jitter(frames_u8, plans, out=None):
     """The training colour jitter on the device (``df_color_jitter``): frames_u8 [F,H,W,3] uint8 device tensor, plans [F,8] float32
     (``datasets.augment.plan_row`` rows; host or device).  Returns the jittered uint8 frames, bit-identical to

@@ -470,6 +470,38 @@ int df_cad_scene_mask(const unsigned short *label, const int *stats, int F, int 
                       unsigned short *mask_out, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * A depth-sensor model over rendered customCAD depth frames, applied after any of the render calls above.  It changes depth only.  The
+ * Unity code rint(65534 ((1 + p22) + p23 / z)) is affine in 1 / z, a disparity; a structured-light or stereo sensor's noise is constant
+ * in disparity (sigma_z ~ z^2), hence of constant sigma in code units, and the whole model is integer arithmetic on the codes.  No
+ * allocation, no copy, no synchronisation, the caller's stream; integer atomics only (the counts), so the outputs are bit-reproducible.
+ *
+ * df_cad_depth_sensor: depth_in [F][IH][IW] u16 (the clean render), depth_out the same shape, stats [F][4] int32 -- all DEVICE; the two
+ *   depth ranges must not overlap (the edge test reads the clean neighbours).  Everything else travels as launch arguments.  The call
+ *   zeroes stats itself.  stats[f] = {edge pixels, pixels dropped at random, pixels dropped at an edge, kept pixels whose code changed}.
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer; overlapping depth ranges; F, IH, IW as for df_cad_render;
+ *   noise_mul < 0; edge_radius outside 0..4; edge_step outside 0..65535; edge_drop24 or drop24 outside 0..2^24; quant outside 1..4096.
+ *   mix32 is the function of df_preprocess_objects' RNG contract (csrc/choose_core.h); C0 = 0x243F6A88, C1 = 0x85A308D3,
+ *   C2 = 0x13198A2E, C3 = 0x03707344.  For pixel p (flat index within its frame) of frame f with clean code c = depth_in[f][p]:
+ *   D0. Frame seed: s = mix32(seed, (first_frame + f) mod 2^32).  Frame f of a call with first_frame = a is frame 0 of a call with
+ *       first_frame = a + f: a frame depends on nothing else in its call.
+ *   D1. Horizon: c == 65535 -> out = 65535, nothing is counted.
+ *   D2. Edge: with R = edge_radius > 0, p is an edge pixel when at least one pixel of the (2R+1)^2 window around it is a horizon pixel or
+ *       has |c_n - c| > edge_step.  Window pixels outside the frame are ignored (the window never reaches another frame's memory).  The
+ *       test is on the CLEAN input.  stats[f][0] += 1 for an edge pixel, whatever happens to it next.
+ *   D3. Random drop-out: (mix32(s ^ C3, p) >> 8) < drop24 -> out = 65535, stats[f][1] += 1.
+ *   D4. Edge drop-out: otherwise, an edge pixel with (mix32(s ^ C2, p) >> 8) < edge_drop24 -> out = 65535, stats[f][2] += 1.
+ *   D5. Disparity noise: otherwise h0 = mix32(s ^ C0, p), h1 = mix32(s ^ C1, p),
+ *       S = (h0 & 0xFFFF) + (h0 >> 16) + (h1 & 0xFFFF) + (h1 >> 16) - 131070: a centred sum of four 16-bit uniforms, variance 1431655765;
+ *       n = floor((noise_mul * S + 2^31) / 2^32) in 64-bit signed arithmetic; c1 = clamp(c + n, 0, 65534).
+ *   D6. Quantisation: c2 = min(65534, ((c1 + quant / 2) / quant) * quant), integer divisions (quant == 1 leaves c1); out = c2,
+ *       stats[f][3] += (c2 != c).
+ *   A kept pixel is never 65535: the model invents horizon by D3 and D4 only.  noise_mul = rint(sigma * 2^32 / sqrt(1431655765)) gives
+ *   noise of standard deviation sigma codes (plus the 1/12 of the rounding). */
+int df_cad_depth_sensor(const unsigned short *depth_in, unsigned short *depth_out, int F, int IH, int IW, unsigned seed,
+                        unsigned first_frame, int noise_mul, int edge_radius, int edge_step, int edge_drop24, int drop24, int quant,
+                        int *stats, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Training-time pixel augmentation on whole uint8 frames, bit-identical to the host path (densefusion_amd/datasets/augment.py over PIL;
  * datasets/ycb/dataset.py).  Same conventions as df_preprocess_objects: no allocation, no synchronisation, the caller's stream.
  *

@@ -21,6 +21,12 @@ the light ``render.sample_light`` draws for each frame's seed and ``--shading fl
 
     python tools/cad_render_bench.py --scene --subdiv 7 --chunk 32 --light
 
+``--sensor`` times ``df_cad_depth_sensor`` (record: sigma 4 codes, R 2, edge_step 64, edge_drop 0.5, drop 0.01, quant 1) on the depth of
+``--chunk`` frames that ``df_cad_render_mesh`` renders from the icosphere of ``--subdiv`` subdivisions, next to that render call and to
+a plain device copy of the same depth buffer (4 bytes of traffic per pixel: the floor), all in one run.
+
+    python tools/cad_render_bench.py --sensor --subdiv 7 --chunk 32
+
 ``--visibility N`` draws the scenes of seeds 0..N-1 as tools/render_cad_dataset.py --scene does for the meshes of its test
 (tests/cad_scene_np.py: two spheres as models, a box as distractor, 96 x 144 frames) and prints the histogram of the visible fractions
 of the models that are present, in ten bins.
@@ -107,6 +113,37 @@ def mesh_bench(opt):
     return res
 
 
+def sensor_bench(opt):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cad_raster_np as mnp
+    rng = np.random.default_rng(0)
+    sv, sf = mnp.icosphere(opt.subdiv, 60.0)
+    poses = []
+    for s in range(opt.chunk):
+        axis, angle, xyz, _ = cr.sample_view(s, len(sv), (0.0, 0.0, 4.0), 1.0, hole_mean=30.0, hole_std=10.0)
+        R, t = cr.view_pose(axis, angle, xyz, np.zeros(3), 10.0)
+        poses.append(np.concatenate([R, t[:, None]], axis=1))
+    poses = np.stack(poses)
+    dims = (opt.height, opt.width)
+    r = cr.CadMeshRenderer(sv, sf, rng.integers(0, 256, (len(sv), 3), dtype=np.uint8), PROJ, dims)
+    render_ms, out = timed(lambda: r.render(poses, cull=1, mask="box"), opt.calls)
+    depth = out[1]
+    sensor = cr.DepthSensor(sigma_code=4.0, edge_radius=2, edge_step=64, edge_drop=0.5, drop=0.01, quant=1)
+    from densefusion_amd.lib import preprocess as pp
+    dst = torch.empty_like(depth)
+    sensor_ms, (_, stats) = timed(lambda: pp.cad_depth_sensor(depth, sensor.record(), 0, 0, out=dst), opt.calls)
+    copy_ms, _ = timed(lambda: dst.copy_(depth), opt.calls)
+    med = lambda t: float(np.median(t))
+    res = {"frame": list(dims), "chunk": opt.chunk, "triangles": int(len(sf)), "record": list(sensor.record()),
+           "covered_mean": float(out[3].cpu().numpy()[:, 0].mean()), "sensor_counts_mean": [float(x) for x in stats.cpu().numpy().mean(axis=0)],
+           "render_ms_per_call_median": med(render_ms), "sensor_ms_per_call_median": med(sensor_ms), "copy_ms_per_call_median": med(copy_ms),
+           "render_ms_per_call": [round(t, 4) for t in render_ms], "sensor_ms_per_call": [round(t, 4) for t in sensor_ms],
+           "copy_ms_per_call": [round(t, 4) for t in copy_ms], "sensor_over_render": med(sensor_ms) / med(render_ms),
+           "sensor_over_copy": med(sensor_ms) / med(copy_ms)}
+    print(json.dumps(res))
+    return res
+
+
 def scene_bench(opt):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import cad_raster_np as mnp
@@ -176,6 +213,7 @@ def main(argv=None):
     ap.add_argument("--scene", action="store_true", help="time df_cad_render_scene (six objects) next to the sum of the solo df_cad_render_mesh calls")
     ap.add_argument("--visibility", type=int, default=0, help="histogram of the visible fractions sample_scene gives over this many seeds")
     ap.add_argument("--mesh", action="store_true", help="time df_cad_render_mesh (icosphere, box) and the point path on points of that icosphere")
+    ap.add_argument("--sensor", action="store_true", help="time df_cad_depth_sensor next to the mesh render it follows and to a device copy")
     ap.add_argument("--light", action="store_true", help="--mesh / --scene: time the lit calls, one sample_light record per frame")
     ap.add_argument("--shading", type=str, default="flat", choices=("flat", "smooth"), help="--light: one normal per triangle, or per vertex")
     ap.add_argument("--subdiv", type=int, default=7, help="--mesh: icosphere subdivisions (20 * 4^n triangles)")
@@ -191,6 +229,8 @@ def main(argv=None):
         ap.error("--light needs --mesh or --scene: the point renderer is unlit")
     if opt.visibility:
         return visibility(opt)
+    if opt.sensor:
+        return sensor_bench(opt)
     if opt.scene:
         return scene_bench(opt)
     if opt.mesh:

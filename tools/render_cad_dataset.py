@@ -38,6 +38,17 @@ as the object -- the reference's own rule (mask_generator.py:21-28) -- so the lo
 one light per shared frame for all its objects.  ``data/XX/meta/lights.txt`` then holds one line per written frame: the frame number and
 the eight values of its record with ``repr``; as with the poses the frame is rendered from the parsed text.  The loader ignores the
 file.  With ``--light none`` (the default) no such file is written and the trees are what they were without the flag.
+
+``--sensor_sigma CODES`` (or ``--sensor_sigma_z S --sensor_z Z``: the code sigma that means range noise S at range Z, in the units of
+``UnityDepthProjector.project_depth``), ``--sensor_edge R --sensor_edge_step STEP --sensor_edge_drop P``, ``--sensor_drop P`` and
+``--sensor_quant Q`` put a depth-sensor model (``df_cad_depth_sensor``, ``render.DepthSensor``) over each chunk's depth after the render
+and before the read-back, with any renderer and with ``--scene`` (once on the shared depth): disparity noise, pixels missing along depth
+discontinuities and at random, quantisation.  Only the depth files change: colour, masks, records, ``--min_pixels`` and
+``--min_visible`` are those of the clean render.  Frame j of a chunk draws from (``--sensor_seed``, the view's seed), so a frame's
+noise does not depend on ``--chunk``.  ``data/XX/meta/sensor.txt`` holds the record (the sensor seed and the six integers of the call)
+and one line per written frame: the frame number, its view's seed and the four counts {edge pixels, dropped at random, dropped at an
+edge, kept with another code}.  The loader ignores the file; it paints the dropped pixels grey and leaves them out of ``choose``, as it
+does with Unity's own horizon.  Without any of these flags nothing of this runs and no such file is written.
 """
 from __future__ import annotations
 
@@ -88,6 +99,15 @@ def build_parser():
                     help="--raster mesh / --scene: light the frames from the camera, or from a direction drawn per seed")
     ap.add_argument("--shading", type=str, default="flat", choices=("flat", "smooth"), help="--light: one normal per triangle, or per vertex")
     ap.add_argument("--light_angle", type=float, default=60.0, help="--light random: largest angle between light and viewing direction, degrees")
+    ap.add_argument("--sensor_sigma", type=float, default=None, help="depth sensor: sigma of the disparity noise in 16-bit codes")
+    ap.add_argument("--sensor_sigma_z", type=float, default=None, help="depth sensor: range noise at --sensor_z instead of --sensor_sigma")
+    ap.add_argument("--sensor_z", type=float, default=None, help="depth sensor: the range at which --sensor_sigma_z holds")
+    ap.add_argument("--sensor_edge", type=int, default=None, help="depth sensor: radius 0..4 of the window that finds depth discontinuities")
+    ap.add_argument("--sensor_edge_step", type=int, default=None, help="depth sensor: a neighbour further than this many codes makes an edge")
+    ap.add_argument("--sensor_edge_drop", type=float, default=None, help="depth sensor: probability that an edge pixel goes missing")
+    ap.add_argument("--sensor_drop", type=float, default=None, help="depth sensor: probability that any pixel goes missing")
+    ap.add_argument("--sensor_quant", type=int, default=None, help="depth sensor: codes are rounded to multiples of this, 1..4096")
+    ap.add_argument("--sensor_seed", type=int, default=0, help="depth sensor: seed of its draws, next to each view's own seed")
     ap.add_argument("--points", type=int, default=0, help="points to draw from a mesh (default 1 000 000) or to keep of a cloud (default all)")
     ap.add_argument("--max_holes", type=int, default=3)
     ap.add_argument("--hole_mean", type=float, default=30.0, help="model file units")
@@ -128,6 +148,34 @@ def draw_light(opt, seed):
 def write_lights(sub, texts):
     with open(os.path.join(sub, "meta", "lights.txt"), "w") as f:
         f.write("".join("%d %s\n" % (n, t) for n, t in enumerate(texts)))
+
+
+def make_sensor(opt, ap, proj):
+    """The ``DepthSensor`` of the --sensor_* flags, or None when none of them is given."""
+    given = [opt.sensor_sigma, opt.sensor_sigma_z, opt.sensor_z, opt.sensor_edge, opt.sensor_edge_step, opt.sensor_edge_drop,
+             opt.sensor_drop, opt.sensor_quant]
+    if all(v is None for v in given):
+        return None
+    if (opt.sensor_sigma_z is None) != (opt.sensor_z is None) or (opt.sensor_sigma is not None and opt.sensor_sigma_z is not None):
+        ap.error("the depth sensor's noise is --sensor_sigma CODES, or --sensor_sigma_z S together with --sensor_z Z")
+    sigma = opt.sensor_sigma or 0.0
+    if opt.sensor_sigma_z is not None:
+        if opt.sensor_z == 0:
+            ap.error("--sensor_z must not be 0")
+        sigma = cr.DepthSensor.sigma_code_at(proj, opt.sensor_sigma_z, opt.sensor_z)
+    try:
+        return cr.DepthSensor(sigma_code=sigma, edge_radius=opt.sensor_edge or 0, edge_step=opt.sensor_edge_step or 0,
+                              edge_drop=opt.sensor_edge_drop or 0.0, drop=opt.sensor_drop or 0.0,
+                              quant=1 if opt.sensor_quant is None else opt.sensor_quant)
+    except ValueError as e:
+        ap.error(f"depth sensor: {e}")
+
+
+def write_sensor(sub, opt, sensor, rows):
+    """meta/sensor.txt: the record, then per written frame its number, its view's seed and its four counts"""
+    with open(os.path.join(sub, "meta", "sensor.txt"), "w") as f:
+        f.write("sensor %d %s\n" % (opt.sensor_seed & 0xFFFFFFFF, " ".join("%d" % v for v in sensor.record())))
+        f.write("".join("%d %d %s\n" % (n, view, " ".join("%d" % c for c in counts)) for n, (view, counts) in enumerate(rows)))
 
 
 def write_vertex_ply(path, pts):
@@ -193,6 +241,7 @@ def main_scene(opt, ap):
             f.write("".join("\t".join(repr(float(v)) for v in row) + "\n" for row in proj) + "\n")
     proj = read_proj_mat(os.path.join(subs[0], "meta", "proj_mat.txt"))      # what the loader will read
     lit = opt.light != "none"
+    sensor = make_sensor(opt, ap, proj)
     renderer = cr.CadSceneRenderer(meshes, proj, (opt.height, opt.width), [opt.model_scale] * O, normals=opt.shading if lit else None)
     centroids = [m[0].astype(np.float64).mean(axis=0) for m in meshes]
 
@@ -205,6 +254,7 @@ def main_scene(opt, ap):
     visible = [[] for _ in range(n_targets)]
     seeds = [[] for _ in range(n_targets)]
     light_texts = [[] for _ in range(n_targets)]
+    sensor_rows = [[] for _ in range(n_targets)]
     skipped, seed, device_ms = 0, opt.seed, []
     t_start = time.time()
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
@@ -233,6 +283,9 @@ def main_scene(opt, ap):
             rgb, depth, label, stats = renderer.render(poses, present=present, cull=opt.cull,
                                                        light=np.stack([l for _, l in lights]) if lit else None)
             ev1.record()
+            if sensor is not None:                                            # once on the shared depth; masks and counts stay the clean render's
+                depth, counts = cr.apply_sensor(depth, sensor, opt.sensor_seed, seed - opt.chunk)
+                counts = counts.cpu().numpy()
             rows = stats.cpu().numpy()                                        # the chunk's read-backs before its frames
             device_ms.append(ev0.elapsed_time(ev1))
             solo = np.zeros((opt.chunk, n_targets), dtype=np.int64)
@@ -261,6 +314,8 @@ def main_scene(opt, ap):
                 visible[k].append(float(frac)); seeds[k].append(seed - opt.chunk + j)
                 if lit:
                     light_texts[k].append(lights[j][0])
+                if sensor is not None:
+                    sensor_rows[k].append((seed - opt.chunk + j, counts[j]))
             for p in pending:
                 p.result()
     for k, sub in enumerate(subs):
@@ -270,6 +325,8 @@ def main_scene(opt, ap):
         write_split(sub, len(records[k]), opt.seed)
         if lit:
             write_lights(sub, light_texts[k])
+        if sensor is not None:
+            write_sensor(sub, opt, sensor, sensor_rows[k])
     wall = time.time() - t_start
     per_view = float(np.median(device_ms)) / opt.chunk
     summary = {"objects": {}, "skipped": skipped, "device_ms_per_view": per_view}
@@ -318,6 +375,7 @@ def main(argv=None):
     with open(os.path.join(sub, "meta", "proj_mat.txt"), "w") as f:
         f.write("".join("\t".join(repr(float(v)) for v in row) + "\n" for row in proj) + "\n")
     proj = read_proj_mat(os.path.join(sub, "meta", "proj_mat.txt"))          # what the loader will read
+    sensor = make_sensor(opt, ap, proj)
     if mesh:
         renderer = cr.CadMeshRenderer(pts, tris, col, proj, (opt.height, opt.width), model_scale=opt.model_scale,
                                       normals=opt.shading if lit else None)
@@ -330,7 +388,7 @@ def main(argv=None):
         Image.fromarray(depth).save(os.path.join(sub, "depth", "Depth_%04d.png" % n))
         Image.fromarray(mask).save(os.path.join(sub, "mask", "%04d.png" % n))
 
-    records, light_texts, written, skipped, seed, device_ms = [], [], 0, 0, opt.seed, []
+    records, light_texts, sensor_rows, written, skipped, seed, device_ms = [], [], [], 0, 0, opt.seed, []
     t_start = time.time()
     with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
         pending = []
@@ -355,6 +413,9 @@ def main(argv=None):
             else:
                 rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, splat=opt.splat, mask=opt.mask)
             ev1.record()
+            if sensor is not None:                                            # the mask and the counts stay the clean render's
+                depth, counts = cr.apply_sensor(depth, sensor, opt.sensor_seed, seed - opt.chunk)
+                counts = counts.cpu().numpy()
             rows = stats.cpu().numpy()                                        # the chunk's one read-back before its frames
             device_ms.append(ev0.elapsed_time(ev1))
             rgb, depth, mask = rgb.cpu().numpy(), depth.cpu().numpy(), mask.cpu().numpy()
@@ -368,6 +429,8 @@ def main(argv=None):
                 records.append((pos, quat))
                 if lit:
                     light_texts.append(lights[k][0])
+                if sensor is not None:
+                    sensor_rows.append((seed - opt.chunk + k, counts[k]))
                 pending.append(pool.submit(save, written, rgb[k], depth[k], mask[k]))
                 written += 1
             for p in pending:
@@ -379,6 +442,8 @@ def main(argv=None):
     write_split(sub, written, opt.seed)
     if lit:
         write_lights(sub, light_texts)
+    if sensor is not None:
+        write_sensor(sub, opt, sensor, sensor_rows)
     wall = time.time() - t_start
     per_view = float(np.median(device_ms)) / opt.chunk            # the median call: the first one also loads the kernels
     what = (f"{len(tris)} triangles", f"cull {opt.cull}") if mesh else (f"{len(pts)} points", f"splat {opt.splat}")
