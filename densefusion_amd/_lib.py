@@ -79,6 +79,9 @@ SIGNATURES = {
     "df_cad_frame_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "df_preprocess_objects_cad": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _i, _i, _i, _i, _f,
                                        _vp, _vp, _vp, _vp, _vp, _vp]),
+    "df_cad_item_table": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "df_cad_targets_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "df_cad_targets": (_i, [_vp, _i, ctypes.c_double, _vp, _vp, _i, _i, _f, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "df_cad_render_scratch_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "df_cad_render": (_i, [_vp, _vp, _vp, _i, _vp, ctypes.c_double, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                            ctypes.c_size_t, _vp]),

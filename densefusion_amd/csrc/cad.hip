@@ -3,71 +3,13 @@
 // colour crop is grey where the depth is that "infinite" value, the cloud comes from a per-pixel ray map and Unity's non-linear depth
 // decode instead of pinhole intrinsics, and the box is the mask's own (df_cad_frame_stats finds it).  The `choose` rule is the shared one
 // of choose_core.h.
+#include "cad_stats.h"
 #include "choose_core.h"
 
 namespace df {
 namespace {
 
 using namespace prep;
-
-constexpr int SB = 256;               // frame_stats: threads per block
-constexpr int STATS_MAX_BLOCKS = 64;   // ... and blocks per frame
-
-// Per-frame integer statistics.  While the blocks reduce, a row of `stats` holds maxima only, so that zero means "nothing seen":
-// {max depth, label pixels, max(IH - row), max(row + 1), max(IW - col), max(col + 1)}; stats_finish_kernel decodes the row in place.
-// Integer atomics: the result does not depend on the order of arrival.  grid = (blocks, F).
-__global__ __launch_bounds__(SB) void frame_stats_kernel(const unsigned short *__restrict__ depth, const unsigned short *__restrict__ label,
-                                                         int IH, int IW, int label_value, int *__restrict__ stats) {
-  const int f = blockIdx.y;
-  const int npix = IH * IW;
-  const unsigned short *d = depth + (size_t)f * npix, *l = label + (size_t)f * npix;
-  int dmax = 0, cnt = 0, a_r = 0, b_r = 0, a_c = 0, b_c = 0;
-  auto see = [&](int i, int dv, int lv) {
-    dmax = max(dmax, dv);
-    if (lv == label_value) {
-      const int r = i / IW, c = i - r * IW;
-      ++cnt;
-      a_r = max(a_r, IH - r); b_r = max(b_r, r + 1);
-      a_c = max(a_c, IW - c); b_c = max(b_c, c + 1);
-    }
-  };
-  const int first = blockIdx.x * SB + threadIdx.x, step = gridDim.x * SB;
-  int done = 0;
-  if (((reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(l)) & 7u) == 0) {       // this frame starts on an 8-byte boundary: four pixels a load
-    const int nq = npix / 4;
-    const ushort4 *d4 = reinterpret_cast<const ushort4 *>(d), *l4 = reinterpret_cast<const ushort4 *>(l);
-    for (int q = first; q < nq; q += step) {
-      const ushort4 dv = d4[q], lv = l4[q];
-      see(4 * q, dv.x, lv.x); see(4 * q + 1, dv.y, lv.y); see(4 * q + 2, dv.z, lv.z); see(4 * q + 3, dv.w, lv.w);
-    }
-    done = 4 * nq;
-  }
-  for (int i = done + first; i < npix; i += step) see(i, d[i], l[i]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    dmax = max(dmax, __shfl_down(dmax, off, 64));
-    cnt += __shfl_down(cnt, off, 64);
-    a_r = max(a_r, __shfl_down(a_r, off, 64)); b_r = max(b_r, __shfl_down(b_r, off, 64));
-    a_c = max(a_c, __shfl_down(a_c, off, 64)); b_c = max(b_c, __shfl_down(b_c, off, 64));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    int *s = stats + (size_t)f * 6;
-    if (dmax) atomicMax(&s[0], dmax);
-    if (cnt) {
-      atomicAdd(&s[1], cnt);
-      atomicMax(&s[2], a_r); atomicMax(&s[3], b_r); atomicMax(&s[4], a_c); atomicMax(&s[5], b_c);
-    }
-  }
-}
-
-// {depth_max, n_label, rmin, rmax, cmin, cmax}, the box inclusive like get_bbox (dataset.py:247-249); zero box without the label
-__global__ void stats_finish_kernel(int F, int IH, int IW, int *__restrict__ stats) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  int *s = stats + (size_t)f * 6;
-  if (s[1] == 0) { s[2] = s[3] = s[4] = s[5] = 0; return; }
-  s[2] = IH - s[2]; s[3] = s[3] - 1; s[4] = IW - s[4]; s[5] = s[5] - 1;
-}
 
 // grid = B objects, block = 1024.  rgb [F][IH][IW][3] u8, depth / label [F][IH][IW] u16, ray_map [IH][IW][3] f64.
 __global__ __launch_bounds__(PB) void preprocess_cad_kernel(const unsigned char *__restrict__ rgb, const unsigned short *__restrict__ depth,
@@ -132,14 +74,12 @@ using namespace df;
 extern "C" int df_cad_frame_stats(const unsigned short *depth, const unsigned short *label, int num_frames, int IH, int IW, int label_value,
                                   int *stats, df_stream_t stream) {
   if (!depth || !label || !stats) return set_error(DF_ERR_ARG, "cad_frame_stats: null pointer");
-  if (num_frames <= 0 || num_frames > 65535 || IH <= 0 || IW <= 0 || (long)IH * IW > (1L << 30) || label_value < 0 || label_value > 65535)
+  if (!stats_sizes_ok(num_frames, IH, IW, label_value))
     return set_error(DF_ERR_ARG, "cad_frame_stats: bad sizes");
   hipStream_t st = to_stream(stream);
   if (hipMemsetAsync(stats, 0, sizeof(int) * 6 * num_frames, st) != hipSuccess) return check_launch("cad_frame_stats (init)");
-  const long quads = ((long)IH * IW + 3) / 4;
-  const int blocks = (int)(cdiv(quads, SB) < STATS_MAX_BLOCKS ? cdiv(quads, SB) : STATS_MAX_BLOCKS);
-  hipLaunchKernelGGL(frame_stats_kernel, dim3(blocks, num_frames), dim3(SB), 0, st, depth, label, IH, IW, label_value, stats);
-  hipLaunchKernelGGL(stats_finish_kernel, dim3(cdiv(num_frames, SB)), dim3(SB), 0, st, num_frames, IH, IW, stats);
+  hipLaunchKernelGGL(frame_stats_kernel, dim3(stats_blocks(IH, IW), num_frames), dim3(SB), 0, st, depth, label, IH, IW, label_value, stats, 6);
+  hipLaunchKernelGGL(stats_finish_kernel, dim3(cdiv(num_frames, SB)), dim3(SB), 0, st, num_frames, IH, IW, stats, 6);
   return check_launch("cad_frame_stats");
 }
 

@@ -94,19 +94,19 @@ class ColorJitter:
             img = op(img)
         return img
 
-    def draw(self):
+    def draw(self, rng=random):
         """The draws of ``get_params()`` as a plan: the same ``random.uniform`` calls in the same order, then ``random.shuffle`` on a
         list of as many op codes (its consumption depends on the length only), so ``random`` is left in the state ``get_params()``
-        leaves it in."""
+        leaves it in.  ``rng``: a ``random.Random`` to draw from instead of the module's global stream."""
         alpha, shift, ops = [np.float32(1.0)] * 3, 0, []
-        for k, rng in enumerate((self.brightness, self.contrast, self.saturation)):
-            if rng is not None:
-                alpha[k] = np.float32(random.uniform(*rng))
+        for k, span in enumerate((self.brightness, self.contrast, self.saturation)):
+            if span is not None:
+                alpha[k] = np.float32(rng.uniform(*span))
                 ops.append(k)
         if self.hue is not None:
-            shift = hue_shift(random.uniform(*self.hue))
+            shift = hue_shift(rng.uniform(*self.hue))
             ops.append(OP_HUE)
-        random.shuffle(ops)
+        rng.shuffle(ops)
         return JitterPlan(alpha[0], alpha[1], alpha[2], shift, tuple(ops))
 
     @staticmethod

@@ -22,7 +22,9 @@ Different by design:
   * ``ply_vtx`` is a small reader of its own for ASCII and binary little-endian PLY.  A vertex-only file is subsampled with the reference's
     ``np.random.choice(n, 3000)`` (:261); a mesh is sampled area-weighted with ``np.random`` -- there is no open3d here, so the mesh
     sampling is UNPINNED against open3d's ``sample_points_uniformly`` (:256);
-  * the random pixel subset follows the key rule of include/dfusion.h instead of ``np.random.shuffle`` (:151-155);
+  * the random pixel subset follows the key rule of include/dfusion.h instead of ``np.random.shuffle`` (:151-155).  The mesh subset
+    keeps ``random.sample`` here; ``online.RenderedPoseDataset`` draws it by the same key rule on the device (``df_cad_targets``: the
+    model points with the smallest ``mix32(seed, index)`` keys, in index order -- the same distribution, without Python's stream);
   * the host only decodes the PNGs: ``batch()`` finds depth maximum and box of every frame with ``df_cad_frame_stats`` (one small read-back
     of [F][6] per call, the only one), then mask, ``choose``, cloud and crop of all frames of one crop size run as one launch and stay on the
     device.  ``host_item`` (the loader's worker processes) finds the box in numpy instead;
@@ -106,7 +108,11 @@ def ply_vtx(path, number_of_points=3000):
     """`number_of_points` model points, float64 [n,3] (dataset.py:251-265).  Vertex-only file: ``pts[np.random.choice(n, number_of_points)]``
     like the reference; mesh: points drawn uniformly over the surface with ``np.random`` (triangle by area, then uniform barycentric
     coordinates) -- the job of open3d's ``sample_points_uniformly``, not its stream."""
-    verts, tris = read_ply(path)
+    return sample_model_points(*read_ply(path), number_of_points)
+
+
+def sample_model_points(verts, tris, number_of_points=3000):
+    """The draw of ``ply_vtx`` for a model that is already in memory: verts float64 [n,3], tris integer [m,3] (m = 0: a cloud)."""
     if len(tris) == 0:
         return verts[np.random.choice(verts.shape[0], number_of_points)]
     a, b, c = verts[tris[:, 0]], verts[tris[:, 1]], verts[tris[:, 2]]

@@ -29,9 +29,20 @@ def read_proj_mat(proj_file):
 
 class UnityDepthProjector:
     def __init__(self, proj_file, image_dims):
+        self._setup(read_proj_mat(proj_file), image_dims)
+
+    @classmethod
+    def from_matrix(cls, proj_mat, image_dims):
+        """The projector of a matrix that is already in memory (a renderer's own): what the constructor builds from a
+        ``proj_mat.txt`` that holds these sixteen values."""
+        self = cls.__new__(cls)
+        self._setup(np.array(proj_mat, dtype=np.float64).reshape(4, 4), image_dims)
+        return self
+
+    def _setup(self, proj_mat, image_dims):
         self.image_dims = (int(image_dims[0]), int(image_dims[1]))
         H, W = self.image_dims
-        self.proj_mat = read_proj_mat(proj_file)
+        self.proj_mat = proj_mat
         self.inverse_proj_mat = np.linalg.inv(self.proj_mat)                     # :20
         x_range = np.arange(-1, 1, 2.0 / W)[:W]                                 # :22-26 reads the first W (H) values
         y_range = np.arange(-1, 1, 2.0 / H)[:H]

@@ -35,6 +35,47 @@ from ...lib import preprocess as pp
 from .dataset import _PLY_TYPES, Y_180, convert_quat
 
 MASK_MODES = {"box": 0, "pixels": 1}
+# the reference's shipped dataset_processed/data/01/meta/proj_mat.txt and its 520 x 1109 frames (dataset.py:99)
+DEFAULT_PROJ = [[1.16667, 0.0, 0.0, 0.0], [0.0, 2.48814, 0.0, 0.0], [0.0, 0.0, 0.5, 3000.0], [0.0, 0.0, -1.0, 0.0]]
+
+
+def add_view_arguments(ap):
+    """The options that describe the views and the renderer, shared by tools/render_cad_dataset.py and everything that renders the
+    same views on the fly (``online.RenderedPoseDataset.from_options``)."""
+    ap.add_argument("--min_visible", type=float, default=0.3, help="--scene: smallest visible fraction of a frame that enters a model's tree")
+    ap.add_argument("--p_present", type=float, default=0.7, help="--scene: probability that an object other than the view's own is in the frame")
+    ap.add_argument("--lateral", type=float, default=0.8, help="--scene: largest sideways offset of the others, units of transforms.txt")
+    ap.add_argument("--depth", type=float, default=0.8, help="--scene: largest offset of the others towards or away from the camera")
+    ap.add_argument("--proj_mat", type=str, default=None, help="a proj_mat.txt (four tab-separated lines); default: the reference's shipped matrix")
+    ap.add_argument("--height", type=int, default=520)
+    ap.add_argument("--width", type=int, default=1109)
+    ap.add_argument("--center", type=float, nargs=3, default=[0.0, 0.0, 4.0], help="mean position in the units of transforms.txt")
+    ap.add_argument("--scene_scale", type=float, default=1.0)
+    ap.add_argument("--model_scale", type=float, default=10.0, help="the loader's `model * 10`")
+    ap.add_argument("--min_pixels", type=int, default=500)
+    ap.add_argument("--splat", type=int, default=1)
+    ap.add_argument("--raster", type=str, default="points", choices=("points", "mesh"), help="splat a sampled cloud, or rasterise the triangles")
+    ap.add_argument("--cull", type=int, default=1, choices=(0, 1), help="--raster mesh: 1 drops the triangles that face away from the camera")
+    ap.add_argument("--mask", type=str, default="box", choices=sorted(MASK_MODES))
+    ap.add_argument("--light", type=str, default="none", choices=("none", "head", "random"),
+                    help="--raster mesh / --scene: light the frames from the camera, or from a direction drawn per seed")
+    ap.add_argument("--shading", type=str, default="flat", choices=("flat", "smooth"), help="--light: one normal per triangle, or per vertex")
+    ap.add_argument("--light_angle", type=float, default=60.0, help="--light random: largest angle between light and viewing direction, degrees")
+    ap.add_argument("--sensor_sigma", type=float, default=None, help="depth sensor: sigma of the disparity noise in 16-bit codes")
+    ap.add_argument("--sensor_sigma_z", type=float, default=None, help="depth sensor: range noise at --sensor_z instead of --sensor_sigma")
+    ap.add_argument("--sensor_z", type=float, default=None, help="depth sensor: the range at which --sensor_sigma_z holds")
+    ap.add_argument("--sensor_edge", type=int, default=None, help="depth sensor: radius 0..4 of the window that finds depth discontinuities")
+    ap.add_argument("--sensor_edge_step", type=int, default=None, help="depth sensor: a neighbour further than this many codes makes an edge")
+    ap.add_argument("--sensor_edge_drop", type=float, default=None, help="depth sensor: probability that an edge pixel goes missing")
+    ap.add_argument("--sensor_drop", type=float, default=None, help="depth sensor: probability that any pixel goes missing")
+    ap.add_argument("--sensor_quant", type=int, default=None, help="depth sensor: codes are rounded to multiples of this, 1..4096")
+    ap.add_argument("--sensor_seed", type=int, default=0, help="depth sensor: seed of its draws, next to each view's own seed")
+    ap.add_argument("--points", type=int, default=0, help="points to draw from a mesh (default 1 000 000) or to keep of a cloud (default all)")
+    ap.add_argument("--max_holes", type=int, default=3)
+    ap.add_argument("--hole_mean", type=float, default=30.0, help="model file units")
+    ap.add_argument("--hole_std", type=float, default=10.0)
+    ap.add_argument("--chunk", type=int, default=32, help="views per device call")
+    return ap
 
 
 def _read_ply_elements(path):
@@ -136,6 +177,16 @@ def read_colored_mesh(path):
             np.ascontiguousarray(np.clip(np.rint(col), 0, 255), dtype=np.uint8))
 
 
+def load_cloud(path, n_points=0):
+    """The cloud the point renderer splats, as the render tool loads it: a mesh is sampled into ``n_points`` points (default
+    1 000 000) with ``np.random``; a cloud with more than ``n_points`` > 0 vertices keeps a sorted random subset of that many."""
+    pts, nrm, col = read_colored_ply(path, n_points=n_points if n_points > 0 else 1000000)
+    if 0 < n_points < len(pts):                      # a cloud with more vertices than asked for
+        keep = np.sort(np.random.choice(len(pts), n_points, replace=False))
+        pts, col, nrm = pts[keep], col[keep], None if nrm is None else nrm[keep]
+    return pts, nrm, col
+
+
 def check_triangles(triangles, n_vertices):
     """triangles as int32 [T,3] with T >= 1; ``ValueError`` on any other shape or on an index outside 0..n_vertices-1 (host only)."""
     tri = np.asarray(triangles)
@@ -224,27 +275,33 @@ def _make_normals(normals, vertices, triangles):
     return n, 0 if n.shape[0] == len(triangles) else 1
 
 
-def sample_view(seed, n_points, center, scene_scale, max_holes=3, *, hole_mean, hole_std):
+def sample_view(seed, n_points, center, scene_scale, max_holes=3, *, hole_mean, hole_std, private=False):
     """The draws of one view on ``np.random.seed(seed)``, in the reference's order (cad_to_dataset.py:264-276, then :145-160): three
     ``uniform(-1, 1)`` for the axis (normalised), ``uniform(0, 2 pi)`` for the angle, per axis ``uniform(0, 0.5 | 0.5 | 0.3)`` for the
     offset and ``rand() < 0.5`` for its sign, ``randint(max_holes)`` holes of ``randint(n_points)`` and ``max(0, normal(mean, std))``.
+    ``private``: the same draws from ``np.random.RandomState(seed)`` -- the same generator in the same state, so the same values --
+    which leaves the global stream alone: for callers on several threads.
     Returns (axis (3,), angle, xyz (3,): the centroid's position in the units of ``transforms.txt``, holes: [(index, radius), ...])."""
-    np.random.seed(seed)
-    axis = np.random.uniform(-1, 1, size=3)
+    if private:
+        rs = np.random.RandomState(seed)
+    else:
+        rs = np.random
+        rs.seed(seed)
+    axis = rs.uniform(-1, 1, size=3)
     axis /= np.linalg.norm(axis)
-    angle = np.random.uniform(0, np.pi * 2)
+    angle = rs.uniform(0, np.pi * 2)
     xyz = np.array(center, dtype=np.float64)
     for k, span in enumerate((0.5, 0.5, 0.3)):
-        xyz[k] += np.random.uniform(0, span) * (-1 if np.random.rand() < 0.5 else 1) * scene_scale
+        xyz[k] += rs.uniform(0, span) * (-1 if rs.rand() < 0.5 else 1) * scene_scale
     holes = []
-    for _ in range(np.random.randint(max_holes)):
-        h = int(np.random.randint(n_points))
-        holes.append((h, float(max(0, np.random.normal(hole_mean, hole_std)))))
+    for _ in range(rs.randint(max_holes)):
+        h = int(rs.randint(n_points))
+        holes.append((h, float(max(0, rs.normal(hole_mean, hole_std)))))
     return axis, float(angle), xyz, holes
 
 
 def sample_scene(seed, n_points, center, scene_scale, n_objects, target=0, max_holes=3, *, hole_mean, hole_std, p_present=0.7,
-                 lateral=0.8, depth=0.8):
+                 lateral=0.8, depth=0.8, private=False):
     """One scene of ``n_objects`` objects around object ``target``.  The target's view is exactly ``sample_view(seed, n_points, center,
     scene_scale, max_holes, hole_mean=, hole_std=)``: seed s shows the target where the single-object tool shows it (its holes are
     drawn and returned, and not applied: in a scene the occluders play that part).  Everything else comes from
@@ -253,7 +310,8 @@ def sample_scene(seed, n_points, center, scene_scale, n_objects, target=0, max_h
     target's: ``uniform(-lateral, lateral)`` for x and for y and ``uniform(-depth, depth)`` for z (nearer or farther), in the units of
     ``transforms.txt``, times ``scene_scale``.  The draws are made whether or not the object is present.
     Returns (views: per object (present, axis (3,), angle, xyz (3,)), holes: the target's)."""
-    axis, angle, xyz, holes = sample_view(seed, n_points, center, scene_scale, max_holes, hole_mean=hole_mean, hole_std=hole_std)
+    axis, angle, xyz, holes = sample_view(seed, n_points, center, scene_scale, max_holes, hole_mean=hole_mean, hole_std=hole_std,
+                                          private=private)
     rng = np.random.default_rng((int(seed), 1))
     views = []
     for o in range(n_objects):
@@ -291,6 +349,88 @@ def view_pose(axis, angle, xyz, centroid, model_scale):
     R = Rotation.from_rotvec(np.asarray(axis, dtype=np.float64) * angle).as_matrix()
     centre = np.array([xyz[0] * 1000, xyz[1] * 1000, -xyz[2] * 1000], dtype=np.float64)
     return R, centre - R @ (model_scale * np.asarray(centroid, dtype=np.float64))
+
+
+# ---- the view rules the render tool and the online dataset (online.py) share: records, their text round trip, lights, skips -------
+def record_text(index, pos, quat):
+    """One ``transforms.txt`` record in the generator's format: index / (x, y, z) / (x, y, z, w)."""
+    return "%d\n(%s)\n(%s)\n" % (index, ", ".join(repr(float(v)) for v in pos), ", ".join(repr(float(v)) for v in quat))
+
+
+def parse_record(text):
+    """(pos, quat) of one record, token by token like the loader's ``parse_transforms``."""
+    lines = text.split("\n")
+    return tuple(np.array([float(x.rstrip()) for x in ln.replace("(", "").replace(")", "").replace(",", "").split(" ")]) for ln in lines[1:3])
+
+
+def light_text(light):
+    """The eight values of a light record as they stand in ``lights.txt`` after the frame number."""
+    return " ".join(repr(float(v)) for v in light)
+
+
+def parse_light(text):
+    return np.array([float(x) for x in text.split()], dtype=np.float64)
+
+
+def draw_light(kind, seed, light_angle=60.0):
+    """The light of seed ``seed`` as (text, record parsed back from it), rendered from the file's own values: ``kind`` "head" is
+    ``HEAD_LIGHT``, "random" is ``sample_light(seed)`` within ``light_angle`` degrees of the viewing direction."""
+    if kind not in ("head", "random"):
+        raise ValueError(f'light must be "head" or "random", got {kind!r}')
+    light = HEAD_LIGHT if kind == "head" else sample_light(seed, max_angle=np.radians(light_angle))
+    text = light_text(light)
+    return text, parse_light(text)
+
+
+def record_pose(axis, angle, xyz, centroid, model_scale):
+    """A drawn view as (its ``transforms.txt`` record with index 0, the pose [3,4] = [R|t] of the values parsed back from that text):
+    the frame is rendered from the record's own values, so images and records agree exactly."""
+    text = record_text(0, *pose_to_transform(*view_pose(axis, angle, xyz, centroid, model_scale)))
+    R, t = transform_to_pose(*parse_record(text))
+    return text, np.concatenate([R, t[:, None]], axis=1)
+
+
+def draw_view_records(seeds, n_points, centroid, center, scene_scale, model_scale, max_holes=3, *, hole_mean, hole_std, private=False):
+    """``sample_view`` and ``record_pose`` per seed: (texts [F], poses [F,3,4], holes: per frame a list of (index, radius))."""
+    texts, poses, holes = [], [], []
+    for s in seeds:
+        axis, angle, xyz, hs = sample_view(s, n_points, center, scene_scale, max_holes, hole_mean=hole_mean, hole_std=hole_std,
+                                           private=private)
+        text, pose = record_pose(axis, angle, xyz, centroid, model_scale)
+        texts.append(text); poses.append(pose); holes.append(hs)
+    return texts, np.stack(poses), holes
+
+
+def draw_scene_records(seeds, n_vertices, centroids, n_targets, center, scene_scale, model_scale, max_holes=3, *, hole_mean, hole_std,
+                       p_present=0.7, lateral=0.8, depth=0.8, private=False):
+    """``sample_scene`` per seed for O = len(centroids) objects, the first ``n_targets`` of them targets: the scene of seed s is drawn
+    around object s mod n_targets (``n_vertices[o]`` its vertex count), every object's view goes through ``record_pose``.
+    Returns (texts [F][O], poses [F,O,3,4], present [F,O] uint8)."""
+    O = len(centroids)
+    texts, poses, present = [], [], np.zeros((len(seeds), O), dtype=np.uint8)
+    for j, s in enumerate(seeds):
+        primary = s % n_targets
+        views, _ = sample_scene(s, n_vertices[primary], center, scene_scale, O, primary, max_holes, hole_mean=hole_mean,
+                                hole_std=hole_std, p_present=p_present, lateral=lateral, depth=depth, private=private)
+        row_t, row_p = [], []
+        for o, (here, axis, angle, xyz) in enumerate(views):
+            text, pose = record_pose(axis, angle, xyz, centroids[o], model_scale)
+            row_t.append(text); row_p.append(pose)
+            present[j, o] = here
+        texts.append(row_t); poses.append(np.stack(row_p))
+    return texts, np.stack(poses), present
+
+
+def view_kept(covered, min_pixels):
+    """The skip rule of a single-object view (cad_to_dataset.py:219-221): kept with at least ``min_pixels`` covered pixels."""
+    return covered >= min_pixels
+
+
+def scene_view_kept(won, alone, min_pixels, min_visible):
+    """The skip rule of one object in a scene frame: (kept, visible fraction = pixels won in the scene / pixels won alone at the same
+    poses); kept with at least ``min_pixels`` pixels won and a visible fraction of at least ``min_visible``."""
+    frac = won / alone if alone > 0 else 0.0
+    return not (won < min_pixels or frac < min_visible), frac
 
 
 class CadRenderer:
@@ -473,6 +613,25 @@ class DepthSensor:
         """The code-space sigma that gives range noise ``sigma_z`` at range ``z``, both in the units of
         ``UnityDepthProjector.project_depth``: code = 65534 ((1 + p22) + p23 / z), so |d code / d z| = 65534 |p23| / z^2."""
         return 65534.0 * abs(float(np.asarray(proj_mat, dtype=np.float64)[2, 3])) * float(sigma_z) / (float(z) * float(z))
+
+
+def sensor_from_flags(proj_mat, sigma=None, sigma_z=None, z=None, edge=None, edge_step=None, edge_drop=None, drop=None, quant=None):
+    """The ``DepthSensor`` of the render tool's ``--sensor_*`` flags (None = not given), or None when none of them is given.  The noise
+    is ``sigma`` in codes, or the range noise ``sigma_z`` at range ``z`` (``sigma_code_at``).  ``ValueError`` with the tool's message."""
+    if all(v is None for v in (sigma, sigma_z, z, edge, edge_step, edge_drop, drop, quant)):
+        return None
+    if (sigma_z is None) != (z is None) or (sigma is not None and sigma_z is not None):
+        raise ValueError("the depth sensor's noise is --sensor_sigma CODES, or --sensor_sigma_z S together with --sensor_z Z")
+    sigma = sigma or 0.0
+    if sigma_z is not None:
+        if z == 0:
+            raise ValueError("--sensor_z must not be 0")
+        sigma = DepthSensor.sigma_code_at(proj_mat, sigma_z, z)
+    try:
+        return DepthSensor(sigma_code=sigma, edge_radius=edge or 0, edge_step=edge_step or 0, edge_drop=edge_drop or 0.0, drop=drop or 0.0,
+                           quant=1 if quant is None else quant)
+    except ValueError as e:
+        raise ValueError(f"depth sensor: {e}") from None
 
 
 def apply_sensor(depth, sensor, seed, first_frame=0):

@@ -125,6 +125,61 @@ def cad_frame_stats(depth, label, label_value=65535):
     return stats
 
 
+def cad_item_table(depth, label, label_value=65535, min_side=8):
+    """customCAD frames that stay on the device (``df_cad_item_table``): depth, label [F,IH,IW] 16-bit device tensors -> table [F,8]
+    int32 on the device: the six entries of ``cad_frame_stats``, then ``count``, the mask pixels ``(label == label_value) & (depth !=
+    depth_max)`` of the half-open crop ``[rmin:rmax, cmin:cmax]`` (``PoseDataset._count``), and ``live``: ``n_label > 0``, both crop
+    sides at least ``min_side`` and ``count > 0`` (``PoseDataset._live_box`` plus the count test).  No read-back here."""
+    if not (depth.is_cuda and label.is_cuda):
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if depth.dim() != 3 or depth.shape != label.shape:
+        raise RuntimeError("cad_item_table: depth and label must both be [F,IH,IW]")
+    depth, label = _u16(depth, "cad_item_table: depth"), _u16(label, "cad_item_table: label")
+    F, IH, IW = depth.shape
+    table = torch.empty(F, 8, dtype=torch.int32, device=depth.device)
+    with _lib.device_guard(depth.device):
+        st = _lib.lib().df_cad_item_table(depth.data_ptr(), label.data_ptr(), F, IH, IW, int(label_value), int(min_side), table.data_ptr(),
+                                          _lib.current_stream())
+    _lib.check(st, "cad_item_table")
+    return table
+
+
+def cad_targets(model, pose, seeds, num_points, model_scale=10.0, cloud_div=10000.0):
+    """The pose half of a customCAD item on the device (``df_cad_targets``).  model [P,3] float64 device tensor (the loader's ``pt[obj]``);
+    pose [B,3,4] / [B,12] float64, host or device, ``[R|T]`` with ``R = target_r @ Y_180`` and ``T = target_t`` (``+ add_t * 10000`` with
+    noise); seeds: B integers (their low 32 bits) or a [B] int32 device tensor of those bits.  Per item the ``num_points`` model points
+    with the smallest ``mix32(seed, index)`` keys, in index order, scaled by ``model_scale``.
+    Returns (target, model_points), both [B,num_points,3] float32 on the device, already divided by ``cloud_div``."""
+    if not model.is_cuda:
+        raise RuntimeError("densefusion_amd needs device tensors (no CPU path)")
+    if model.dim() != 2 or model.shape[1] != 3 or model.dtype != torch.float64:
+        raise RuntimeError("cad_targets: model must be [P,3] float64")
+    dev, model = model.device, model.contiguous()
+    pose = _cad_pose(pose, dev, "cad_targets")
+    B, P, M = pose.shape[0], model.shape[0], int(num_points)
+    if torch.is_tensor(seeds):
+        if tuple(seeds.shape) != (B,) or seeds.dtype != torch.int32 or not seeds.is_cuda:
+            raise RuntimeError("cad_targets: seeds as a tensor must be [B] int32 on the device")
+        seeds = seeds.contiguous()
+    else:
+        bits = np.array([int(s) & 0xFFFFFFFF for s in seeds], dtype=np.uint32).view(np.int32)
+        if bits.shape != (B,):
+            raise RuntimeError("cad_targets: one seed per pose")
+        seeds = torch.from_numpy(bits).pin_memory().to(dev, non_blocking=True)
+    with _lib.device_guard(dev):
+        L = _lib.lib()
+        need = L.df_cad_targets_scratch_bytes(B, P, M)
+        if need == 0:
+            raise RuntimeError(f"cad_targets: bad sizes (B 1..65535, 1 <= num_points <= P <= 2^24); got B {B}, P {P}, num_points {M}")
+        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        model_points = torch.empty(B, M, 3, device=dev)
+        target = torch.empty(B, M, 3, device=dev)
+        st = L.df_cad_targets(model.data_ptr(), P, float(model_scale), pose.data_ptr(), seeds.data_ptr(), B, M, float(cloud_div),
+                              scratch.data_ptr(), need, model_points.data_ptr(), target.data_ptr(), _lib.current_stream())
+    _lib.check(st, "cad_targets")
+    return target, model_points
+
+
 def preprocess_objects_cad(rgb, depth, label, objects, num_points, frame_stats, ray_map, p22, p23, add_t=None, cloud_div=10000.0, choose_in=None):
     """The customCAD counterpart of ``preprocess_objects`` (``df_preprocess_objects_cad``).  rgb [F,IH,IW,3] uint8, depth and label
     [F,IH,IW] 16-bit, frame_stats [F,6] int32 (``cad_frame_stats``), ray_map [IH,IW,3] float64 -- device tensors; p22, p23: the

@@ -284,6 +284,38 @@ int df_preprocess_objects_cad(const unsigned char *rgb, const unsigned short *de
                               float *img_out, float *cloud_out, int64_t *choose_out, int *count_out, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The rest of a customCAD item for frames that never reach the host (rendered frames: datasets/customCAD/online.py): the count and
+ * live test of PoseDataset.batch and the model subset and targets of PoseDataset._targets.  Plain launches on the caller's stream: no
+ * allocation, no synchronisation; integer reductions and integer atomics only, so two identical calls give identical bytes, and a
+ * row (frame or item) does not depend on the other rows of its call.  DF_ERR_ARG, before anything is launched or written: a null
+ * pointer, bad sizes, a short or misaligned scratch.
+ *
+ * df_cad_item_table: depth, label [F][IH][IW] u16 -> table [F][8] int32 (the call initialises it on the stream); F <= 65535,
+ *   IH*IW <= 2^30, label_value 0..65535, min_side >= 0.  Two passes in stream order, the host never sees the box in between:
+ *   1. Entries 0..5 = {depth_max, n_label, rmin, rmax, cmin, cmax}: exactly the row of df_cad_frame_stats (the same kernels).
+ *   2. Entry 6 = count: the pixels of the half-open crop [rmin:rmax, cmin:cmax] with label == label_value and depth != depth_max
+ *      (the loader's mask inside its crop, :120-124,137-138; the box's last row and column are left out); 0 when n_label == 0.
+ *   3. Entry 7 = live: n_label > 0 && rmax - rmin >= min_side && cmax - cmin >= min_side && count > 0, as 0 / 1 (the loader passes
+ *      min_side 8, the network's smallest crop).
+ * df_cad_targets: B items; model [P][3] double (DEVICE: the loader's pt[obj], file units), model_scale (the loader's 10),
+ *   pose [B][12] double (DEVICE, row-major [R|T]: the caller puts R = target_r @ Y_180 and T = target_t, with noise
+ *   T = target_t + add_t * 10000, computed on the host), seed [B] u32 (DEVICE), 1 <= M <= P <= 2^24, B 1..65535, cloud_div > 0 (the
+ *   loader's 10000); scratch: df_cad_targets_scratch_bytes(B, P, M) bytes (B rows of M int64 and of P + 1 int32; 0 for sizes the call
+ *   refuses), 8-byte aligned.  Outputs model_points_out, target_out [B][M][3] float.  Per item b:
+ *   1. Subset: model point i < P gets the key mix32(seed[b], i) (the RNG contract of df_preprocess_objects, csrc/choose_core.h); the M
+ *      points with the smallest keys are kept, in increasing index order (the same device routine with an all-true mask).  mix32 is a
+ *      bijection in i for a fixed seed: there are no ties.  P == M keeps every point.  A uniformly random subset with the survivors in
+ *      index order: what random.sample plus np.delete give (:169-171), without their stream.
+ *   2. Per kept point i, all in fp64, one rounding per operation, no fused multiply-add, in exactly this order:
+ *      m = model[i] * model_scale;  model_points = (float)m / cloud_div, divided in fp32;
+ *      X_j = ((R[j][0]*m_x + R[j][1]*m_y) + R[j][2]*m_z) + T_j;  target = (float)X_j / cloud_div, divided in fp32. */
+int df_cad_item_table(const unsigned short *depth, const unsigned short *label, int num_frames, int IH, int IW, int label_value,
+                      int min_side, int *table, df_stream_t stream);
+size_t df_cad_targets_scratch_bytes(int B, int P, int M);
+int df_cad_targets(const double *model, int P, double model_scale, const double *pose, const unsigned *seed, int B, int M,
+                   float cloud_div, void *scratch, size_t scratch_bytes, float *model_points_out, float *target_out, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Point-cloud renderer for customCAD training sets: F views of a coloured CAD cloud as the frames the customCAD loader reads (8-bit
  * colour, Unity's 16-bit depth, 16-bit mask) -- the job of datasets/customCAD/cad_to_dataset.py:137-243 and mask_generator.py:20-28 of
  * the reference without open3d, OpenCV or Unity.  No allocation, no synchronisation, the caller's stream; integer atomics only, so the

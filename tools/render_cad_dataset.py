@@ -67,8 +67,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from densefusion_amd.datasets.customCAD import render as cr  # noqa: E402
 from densefusion_amd.datasets.customCAD.project_unity_depth import read_proj_mat  # noqa: E402
 
-# the reference's shipped dataset_processed/data/01/meta/proj_mat.txt and its 520 x 1109 frames (dataset.py:99)
-DEFAULT_PROJ = [[1.16667, 0.0, 0.0, 0.0], [0.0, 2.48814, 0.0, 0.0], [0.0, 0.0, 0.5, 3000.0], [0.0, 0.0, -1.0, 0.0]]
+DEFAULT_PROJ = cr.DEFAULT_PROJ
 
 
 def build_parser():
@@ -77,72 +76,21 @@ def build_parser():
                     help="PLY with red / green / blue (and optionally nx / ny / nz) vertex properties; cloud or mesh.  Several only with --scene")
     ap.add_argument("--scene", action="store_true", help="render the models together, with occlusion: one tree per model from shared frames")
     ap.add_argument("--distractor", type=str, nargs="*", default=[], help="--scene: meshes that are drawn and can occlude, never targets")
-    ap.add_argument("--min_visible", type=float, default=0.3, help="--scene: smallest visible fraction of a frame that enters a model's tree")
-    ap.add_argument("--p_present", type=float, default=0.7, help="--scene: probability that an object other than the view's own is in the frame")
-    ap.add_argument("--lateral", type=float, default=0.8, help="--scene: largest sideways offset of the others, units of transforms.txt")
-    ap.add_argument("--depth", type=float, default=0.8, help="--scene: largest offset of the others towards or away from the camera")
     ap.add_argument("--output_root", type=str, required=True)
     ap.add_argument("--object", type=int, default=1, help="object directory data/XX and models/obj_XX.ply")
     ap.add_argument("--frames", type=int, default=2000)
-    ap.add_argument("--proj_mat", type=str, default=None, help="a proj_mat.txt (four tab-separated lines); default: the reference's shipped matrix")
-    ap.add_argument("--height", type=int, default=520)
-    ap.add_argument("--width", type=int, default=1109)
-    ap.add_argument("--center", type=float, nargs=3, default=[0.0, 0.0, 4.0], help="mean position in the units of transforms.txt")
-    ap.add_argument("--scene_scale", type=float, default=1.0)
-    ap.add_argument("--model_scale", type=float, default=10.0, help="the loader's `model * 10`")
-    ap.add_argument("--min_pixels", type=int, default=500)
-    ap.add_argument("--splat", type=int, default=1)
-    ap.add_argument("--raster", type=str, default="points", choices=("points", "mesh"), help="splat a sampled cloud, or rasterise the triangles")
-    ap.add_argument("--cull", type=int, default=1, choices=(0, 1), help="--raster mesh: 1 drops the triangles that face away from the camera")
-    ap.add_argument("--mask", type=str, default="box", choices=sorted(cr.MASK_MODES))
-    ap.add_argument("--light", type=str, default="none", choices=("none", "head", "random"),
-                    help="--raster mesh / --scene: light the frames from the camera, or from a direction drawn per seed")
-    ap.add_argument("--shading", type=str, default="flat", choices=("flat", "smooth"), help="--light: one normal per triangle, or per vertex")
-    ap.add_argument("--light_angle", type=float, default=60.0, help="--light random: largest angle between light and viewing direction, degrees")
-    ap.add_argument("--sensor_sigma", type=float, default=None, help="depth sensor: sigma of the disparity noise in 16-bit codes")
-    ap.add_argument("--sensor_sigma_z", type=float, default=None, help="depth sensor: range noise at --sensor_z instead of --sensor_sigma")
-    ap.add_argument("--sensor_z", type=float, default=None, help="depth sensor: the range at which --sensor_sigma_z holds")
-    ap.add_argument("--sensor_edge", type=int, default=None, help="depth sensor: radius 0..4 of the window that finds depth discontinuities")
-    ap.add_argument("--sensor_edge_step", type=int, default=None, help="depth sensor: a neighbour further than this many codes makes an edge")
-    ap.add_argument("--sensor_edge_drop", type=float, default=None, help="depth sensor: probability that an edge pixel goes missing")
-    ap.add_argument("--sensor_drop", type=float, default=None, help="depth sensor: probability that any pixel goes missing")
-    ap.add_argument("--sensor_quant", type=int, default=None, help="depth sensor: codes are rounded to multiples of this, 1..4096")
-    ap.add_argument("--sensor_seed", type=int, default=0, help="depth sensor: seed of its draws, next to each view's own seed")
-    ap.add_argument("--points", type=int, default=0, help="points to draw from a mesh (default 1 000 000) or to keep of a cloud (default all)")
-    ap.add_argument("--max_holes", type=int, default=3)
-    ap.add_argument("--hole_mean", type=float, default=30.0, help="model file units")
-    ap.add_argument("--hole_std", type=float, default=10.0)
+    cr.add_view_arguments(ap)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--chunk", type=int, default=32, help="views per device call")
     ap.add_argument("--max_skipped", type=int, default=100000, help="give up after this many skipped views")
     return ap
 
 
-def record_text(index, pos, quat):
-    """One ``transforms.txt`` record in the generator's format: index / (x, y, z) / (x, y, z, w)."""
-    return "%d\n(%s)\n(%s)\n" % (index, ", ".join(repr(float(v)) for v in pos), ", ".join(repr(float(v)) for v in quat))
-
-
-def parse_record(text):
-    """(pos, quat) of one record, token by token like the loader's ``parse_transforms``."""
-    lines = text.split("\n")
-    return tuple(np.array([float(x.rstrip()) for x in ln.replace("(", "").replace(")", "").replace(",", "").split(" ")]) for ln in lines[1:3])
-
-
-def light_text(light):
-    """The eight values of a light record as they stand in ``lights.txt`` after the frame number."""
-    return " ".join(repr(float(v)) for v in light)
-
-
-def parse_light(text):
-    return np.array([float(x) for x in text.split()], dtype=np.float64)
+record_text, parse_record, light_text, parse_light = cr.record_text, cr.parse_record, cr.light_text, cr.parse_light
 
 
 def draw_light(opt, seed):
     """The light of seed ``seed`` as (text, record parsed back from it): rendered from the file's own values."""
-    light = cr.HEAD_LIGHT if opt.light == "head" else cr.sample_light(seed, max_angle=np.radians(opt.light_angle))
-    text = light_text(light)
-    return text, parse_light(text)
+    return cr.draw_light(opt.light, seed, opt.light_angle)
 
 
 def write_lights(sub, texts):
@@ -152,23 +100,11 @@ def write_lights(sub, texts):
 
 def make_sensor(opt, ap, proj):
     """The ``DepthSensor`` of the --sensor_* flags, or None when none of them is given."""
-    given = [opt.sensor_sigma, opt.sensor_sigma_z, opt.sensor_z, opt.sensor_edge, opt.sensor_edge_step, opt.sensor_edge_drop,
-             opt.sensor_drop, opt.sensor_quant]
-    if all(v is None for v in given):
-        return None
-    if (opt.sensor_sigma_z is None) != (opt.sensor_z is None) or (opt.sensor_sigma is not None and opt.sensor_sigma_z is not None):
-        ap.error("the depth sensor's noise is --sensor_sigma CODES, or --sensor_sigma_z S together with --sensor_z Z")
-    sigma = opt.sensor_sigma or 0.0
-    if opt.sensor_sigma_z is not None:
-        if opt.sensor_z == 0:
-            ap.error("--sensor_z must not be 0")
-        sigma = cr.DepthSensor.sigma_code_at(proj, opt.sensor_sigma_z, opt.sensor_z)
     try:
-        return cr.DepthSensor(sigma_code=sigma, edge_radius=opt.sensor_edge or 0, edge_step=opt.sensor_edge_step or 0,
-                              edge_drop=opt.sensor_edge_drop or 0.0, drop=opt.sensor_drop or 0.0,
-                              quant=1 if opt.sensor_quant is None else opt.sensor_quant)
+        return cr.sensor_from_flags(proj, opt.sensor_sigma, opt.sensor_sigma_z, opt.sensor_z, opt.sensor_edge, opt.sensor_edge_step,
+                                    opt.sensor_edge_drop, opt.sensor_drop, opt.sensor_quant)
     except ValueError as e:
-        ap.error(f"depth sensor: {e}")
+        ap.error(str(e))
 
 
 def write_sensor(sub, opt, sensor, rows):
@@ -197,12 +133,7 @@ def write_mesh_ply(path, vertices, triangles):
         f.write(vertices.tobytes() + face.tobytes())
 
 
-def load_model(path, n_points):
-    pts, nrm, col = cr.read_colored_ply(path, n_points=n_points if n_points > 0 else 1000000)
-    if 0 < n_points < len(pts):                      # a cloud with more vertices than asked for
-        keep = np.sort(np.random.choice(len(pts), n_points, replace=False))
-        pts, col, nrm = pts[keep], col[keep], None if nrm is None else nrm[keep]
-    return pts, nrm, col
+load_model = cr.load_cloud
 
 
 def write_split(sub, written, seed):
@@ -262,22 +193,12 @@ def main_scene(opt, ap):
             if skipped > opt.max_skipped:
                 raise SystemExit(f"{skipped} views skipped for fewer than {opt.min_pixels} pixels or less than {opt.min_visible} visible: "
                                  "check --center, --scene_scale, --lateral, --depth and the camera")
-            texts, poses, present = [], [], np.zeros((opt.chunk, O), dtype=np.uint8)
-            for j, s in enumerate(range(seed, seed + opt.chunk)):
-                primary = s % n_targets
-                views, _ = cr.sample_scene(s, len(meshes[primary][0]), opt.center, opt.scene_scale, O, primary, opt.max_holes,
-                                           hole_mean=opt.hole_mean, hole_std=opt.hole_std, p_present=opt.p_present, lateral=opt.lateral,
-                                           depth=opt.depth)
-                row_t, row_p = [], []
-                for o, (here, axis, angle, xyz) in enumerate(views):
-                    text = record_text(0, *cr.pose_to_transform(*cr.view_pose(axis, angle, xyz, centroids[o], opt.model_scale)))
-                    R, t = cr.transform_to_pose(*parse_record(text))          # rendered from the record's own values
-                    row_t.append(text); row_p.append(np.concatenate([R, t[:, None]], axis=1))
-                    present[j, o] = here
-                texts.append(row_t); poses.append(np.stack(row_p))
+            texts, poses, present = cr.draw_scene_records(range(seed, seed + opt.chunk), [len(m[0]) for m in meshes], centroids, n_targets,
+                                                          opt.center, opt.scene_scale, opt.model_scale, opt.max_holes,
+                                                          hole_mean=opt.hole_mean, hole_std=opt.hole_std, p_present=opt.p_present,
+                                                          lateral=opt.lateral, depth=opt.depth)      # rendered from the records' own values
             lights = [draw_light(opt, s) for s in range(seed, seed + opt.chunk)] if lit else None
             seed += opt.chunk
-            poses = np.stack(poses)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
             rgb, depth, label, stats = renderer.render(poses, present=present, cull=opt.cull,
@@ -298,8 +219,8 @@ def main_scene(opt, ap):
                 for k in range(n_targets):
                     if len(records[k]) + sum(1 for p in pairs if p[1] == k) >= opt.frames or not present[j, k]:
                         continue
-                    frac = rows[j, k, 0] / solo[j, k] if solo[j, k] > 0 else 0.0
-                    if rows[j, k, 0] < opt.min_pixels or frac < opt.min_visible:
+                    kept, frac = cr.scene_view_kept(rows[j, k, 0], solo[j, k], opt.min_pixels, opt.min_visible)
+                    if not kept:
                         skipped += 1
                         continue
                     pairs.append((j, k, frac))
@@ -395,23 +316,18 @@ def main(argv=None):
         while written < opt.frames:
             if skipped > opt.max_skipped:
                 raise SystemExit(f"{skipped} views skipped for fewer than {opt.min_pixels} pixels: check --center, --scene_scale and the camera")
-            texts, poses, holes = [], [], []
-            for s in range(seed, seed + opt.chunk):
-                axis, angle, xyz, hs = cr.sample_view(s, len(pts), opt.center, opt.scene_scale, opt.max_holes, hole_mean=opt.hole_mean,
-                                                      hole_std=opt.hole_std)
-                text = record_text(0, *cr.pose_to_transform(*cr.view_pose(axis, angle, xyz, centroid, opt.model_scale)))
-                R, t = cr.transform_to_pose(*parse_record(text))              # rendered from the record's own values
-                texts.append(text); holes.append(hs)
-                poses.append(np.concatenate([R, t[:, None]], axis=1))
+            texts, poses, holes = cr.draw_view_records(range(seed, seed + opt.chunk), len(pts), centroid, opt.center, opt.scene_scale,
+                                                       opt.model_scale, opt.max_holes, hole_mean=opt.hole_mean,
+                                                       hole_std=opt.hole_std)          # rendered from the records' own values
             lights = [draw_light(opt, s) for s in range(seed, seed + opt.chunk)] if lit else None
             seed += opt.chunk
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
             if mesh:
-                rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, cull=opt.cull, mask=opt.mask,
+                rgb, depth, mask, stats = renderer.render(poses, holes=holes, cull=opt.cull, mask=opt.mask,
                                                           light=np.stack([l for _, l in lights]) if lit else None)
             else:
-                rgb, depth, mask, stats = renderer.render(np.stack(poses), holes=holes, splat=opt.splat, mask=opt.mask)
+                rgb, depth, mask, stats = renderer.render(poses, holes=holes, splat=opt.splat, mask=opt.mask)
             ev1.record()
             if sensor is not None:                                            # the mask and the counts stay the clean render's
                 depth, counts = cr.apply_sensor(depth, sensor, opt.sensor_seed, seed - opt.chunk)
@@ -422,7 +338,7 @@ def main(argv=None):
             for k in range(opt.chunk):
                 if written == opt.frames:
                     break
-                if rows[k, 0] < opt.min_pixels:
+                if not cr.view_kept(rows[k, 0], opt.min_pixels):
                     skipped += 1
                     continue
                 pos, quat = parse_record(texts[k])

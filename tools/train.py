@@ -32,6 +32,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from densefusion_amd import synth, train_ops, train_utils  # noqa: E402
+from densefusion_amd.datasets.customCAD import render as cad_render  # noqa: E402
 from densefusion_amd.lib.loss import Loss  # noqa: E402
 from densefusion_amd.lib.loss_refiner import Loss_refine  # noqa: E402
 from densefusion_amd.lib.network import PoseNet, PoseRefineNet  # noqa: E402
@@ -66,7 +67,7 @@ class SyntheticPoseDataset(torch.utils.data.Dataset):
 
 def build_parser():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dataset", type=str, default="synthetic", help="synthetic | ycb | linemod | cad")
+    ap.add_argument("--dataset", type=str, default="synthetic", help="synthetic | ycb | linemod | cad | cad_render")
     ap.add_argument("--dataset_root", type=str, default="")
     ap.add_argument("--dataset_config_dir", type=str, default="datasets/ycb/dataset_config",
                     help="ycb: the directory of classes.txt / train_data_list.txt / test_data_list.txt (the reference keeps them in its tree)")
@@ -126,6 +127,15 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=1000, help="base seed; the epoch permutation uses seed + epoch on EVERY rank")
     ap.add_argument("--dist_backend", type=str, default="nccl", help="torch.distributed backend under torch.distributed.run "
                                                                      "(nccl = RCCL over xGMI; gloo to rehearse several ranks on one GPU)")
+    # --dataset cad_render: customCAD views rendered on the fly (datasets/customCAD/online.py), no tree on disk
+    cad = ap.add_argument_group("cad_render", "the views and the renderer, under the names of tools/render_cad_dataset.py")
+    cad.add_argument("--cad_model", type=str, nargs="+", default=[], help="PLY model(s): one is rendered alone, several share scenes (object k + 1 = model k)")
+    cad.add_argument("--cad_distractor", type=str, nargs="*", default=[], help="meshes that are drawn and can occlude, never targets")
+    cad.add_argument("--cad_frames", type=int, default=2000, help="views per training epoch")
+    cad.add_argument("--cad_test_frames", type=int, default=200, help="test views: the seed range right after the training range")
+    cad.add_argument("--cad_seed", type=int, default=0, help="seed of the first training view")
+    cad.add_argument("--cad_fresh", action="store_true", help="fresh views every epoch (the seed range moves on by --cad_frames); default: a fixed set, like a tree")
+    cad_render.add_view_arguments(cad)
     return ap
 
 
@@ -134,6 +144,24 @@ def make_datasets(opt):
         tr = SyntheticPoseDataset("train", opt.num_points, opt.num_objects, opt.synthetic_train_frames)
         te = SyntheticPoseDataset("test", opt.num_points, opt.num_objects, opt.synthetic_test_frames)
         return tr, te
+    if opt.dataset == "cad_render":
+        from densefusion_amd.datasets.customCAD.online import RenderedPoseDataset
+        if not opt.cad_model:
+            raise SystemExit("--dataset cad_render needs --cad_model")
+        opt.num_objects, opt.num_points = 5, 500                    # those of `cad`
+        if len(opt.cad_model) > opt.num_objects:
+            raise SystemExit("--cad_model: at most %d models" % opt.num_objects)
+        if opt.jitter != "device":
+            logging.getLogger("train").info("--jitter %s ignored: rendered frames never reach the host, the jitter runs on the device", opt.jitter)
+        try:
+            # the test views follow the last training view of the last epoch --cad_fresh can reach
+            test_seed = opt.cad_seed + opt.cad_frames * (max(opt.nepoch, 1) if opt.cad_fresh else 1)
+            return (RenderedPoseDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=opt.cad_seed, frames=opt.cad_frames,
+                                                     num=opt.num_points, add_noise=True, noise_trans=opt.noise_trans, refine=opt.refine_start),
+                    RenderedPoseDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=test_seed, frames=opt.cad_test_frames,
+                                                     num=opt.num_points, add_noise=False, noise_trans=0.0, refine=opt.refine_start))
+        except ValueError as e:
+            raise SystemExit(f"--dataset cad_render: {e}")
     if opt.dataset not in ("ycb", "linemod", "cad"):
         raise SystemExit("Unknown dataset")
     opt.num_objects, opt.num_points = {"ycb": (21, 1000), "linemod": (13, 500), "cad": (5, 500)}[opt.dataset]      # tools/train.py:57-73 of the reference
@@ -449,7 +477,10 @@ def main(argv=None):
             log.warning("epoch %d: %d training frames are fewer than ranks x batch_size = %d: no optimizer step this epoch", epoch, len(dataset),
                         world * opt.batch_size)
         # `repeat_epoch` passes over the set per epoch, each with its own permutation (seed, epoch, pass) shared by every rank
-        order = np.concatenate([np.random.RandomState((opt.seed + epoch) * 1009 + rep).permutation(len(dataset))[:steps * world * opt.batch_size][rank::world]
+        if opt.dataset == "cad_render" and opt.cad_fresh:
+            dataset.set_epoch(epoch - 1)                            # fresh views: the seed range moves on by --cad_frames
+        permute = getattr(dataset, "permutation", None) or (lambda rs: rs.permutation(len(dataset)))      # a rendering set walks its chunks
+        order = np.concatenate([permute(np.random.RandomState((opt.seed + epoch) * 1009 + rep))[:steps * world * opt.batch_size][rank::world]
                                 for rep in range(opt.repeat_epoch)]) if steps else np.zeros(0, dtype=np.int64)
         window, slots = [], 0
         window_dis = torch.zeros((), device=dev)
