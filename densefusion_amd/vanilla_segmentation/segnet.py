@@ -84,19 +84,23 @@ class SegNet(nn.Module):
             if not isinstance(item, str):
                 self._layer(item[0])
 
-    def _train_forward(self, x):
+    def _train_forward(self, x, taps=None):
         C = x.shape[1]
         self._folded = {}                     # the BatchNorm buffers are rewritten below, behind torch's version counters
         a = x.detach().float().permute(0, 2, 3, 1)
         a = F.pad(a, (0, _pad4(C) - C)).contiguous()
         seq = _ENC + _DEC
         indices = []
+        if taps is not None:
+            taps["x"] = a
         with _lib.device_guard(x.device):
             for k, item in enumerate(seq):
                 if item == "P":
                     continue                  # fused into the BatchNorm before it
                 if item == "U":
                     a = MaxUnpool2x2.apply(a, indices.pop())
+                    if taps is not None:
+                        taps["u" + seq[k + 1][0]] = a
                     continue
                 name = item[0]
                 conv = getattr(self, "conv" + name)
@@ -110,6 +114,8 @@ class SegNet(nn.Module):
                     w = F.pad(w, (0, _pad4(cin) - cin, 0, 0, 0, 0, 0, cpad - cout))
                     b = F.pad(b, (0, cpad - cout))
                 z = ConvAct.apply(a, w.contiguous(), b.contiguous(), None, None, 1, 1, 1, 0)
+                if taps is not None:
+                    taps["z" + name] = z
                 bn = getattr(self, "bn" + name, None)
                 if bn is None:
                     a = z
@@ -120,13 +126,22 @@ class SegNet(nn.Module):
                 if k + 1 < len(seq) and seq[k + 1] == "P":
                     a, idx = BatchNormReLUMaxPool.apply(*args)
                     indices.append(idx)
+                    if taps is not None:
+                        taps["p" + name], taps["i" + name] = a, idx
                 else:
                     a = BatchNormReLU.apply(*args)
+                    if taps is not None:
+                        taps["y" + name] = a
         out = a[..., :self.label_nbr].permute(0, 3, 1, 2)
         out._nhwc = a                         # Loss (loss.py) takes the channels-last logits from here
         return out
 
-    def forward(self, x):
+    def forward(self, x, taps=None):
+        """``taps``: an optional dict that receives the intermediate tensors in forward order, channels-last and not copied (the
+        tests' layer-by-layer view).  Keys: "x" the padded input; per layer NAME "zNAME" the convolution's output (training, and the
+        classifier "z11d" in both modes), "yNAME" the BatchNorm + ReLU output (eval: of the folded convolution), "pNAME" / "iNAME"
+        the pooled tensor and its uint8 index where a pool follows (training fuses the pool, so no "yNAME" there), "uNAME" the
+        un-pooled input of decoder layer NAME.  In training they are the tape's own tensors."""
         if self.training and not self.trainable:
             raise NotImplementedError("SegNet: train() forward needs a module built with SegNet(trainable=True) (or net.trainable = True); "
                                       "the default module is inference-only")
@@ -136,15 +151,16 @@ class SegNet(nn.Module):
         if C != self.input_nbr or H % 32 or W % 32:
             raise RuntimeError(f"SegNet.forward: expected [B,{self.input_nbr},H,W] with H, W multiples of 32, got {tuple(x.shape)}")
         if self.training:
-            return self._train_forward(x)
+            return self._train_forward(x, taps)
         with torch.no_grad():
             a = x.detach().float().permute(0, 2, 3, 1)
             a = F.pad(a, (0, _pad4(C) - C)).contiguous()                  # NHWC, channels padded to 4
-            return self.forward_nhwc(a)[..., :self.label_nbr].permute(0, 3, 1, 2).contiguous()
+            return self.forward_nhwc(a, taps)[..., :self.label_nbr].permute(0, 3, 1, 2).contiguous()
 
-    def forward_nhwc(self, x):
+    def forward_nhwc(self, x, taps=None):
         """Eval forward on the channels-last input x [B,H,W,pad4(input_nbr)] fp32 (padding channels zero; what df_segment_input
-        writes) -> the channels-last activation [B,H,W,pad4(label_nbr)] whose first label_nbr channels are the logits."""
+        writes) -> the channels-last activation [B,H,W,pad4(label_nbr)] whose first label_nbr channels are the logits.
+        ``taps``: see ``forward``."""
         if self.training:
             raise NotImplementedError("SegNet.forward_nhwc: eval mode only")
         if not x.is_cuda:
@@ -156,7 +172,10 @@ class SegNet(nn.Module):
         with torch.no_grad(), _lib.device_guard(x.device):
             a = x.contiguous()
             indices = []
-            for item in _ENC + _DEC:
+            seq = _ENC + _DEC
+            if taps is not None:
+                taps["x"] = a
+            for k, item in enumerate(seq):
                 if item == "P":
                     b_, h, w_, c = a.shape
                     y = torch.empty(b_, h // 2, w_ // 2, c, device=a.device)
@@ -164,12 +183,16 @@ class SegNet(nn.Module):
                     _lib.check(L.df_maxpool2x2_idx(a.data_ptr(), y.data_ptr(), idx.data_ptr(), b_, h, w_, c, _lib.current_stream()), "maxpool2x2_idx")
                     indices.append(idx)
                     a = y
+                    if taps is not None:
+                        taps["p" + seq[k - 1][0]], taps["i" + seq[k - 1][0]] = y, idx
                 elif item == "U":
                     idx = indices.pop()
                     b_, h, w_, c = a.shape
                     y = torch.empty(b_, 2 * h, 2 * w_, c, device=a.device)
                     _lib.check(L.df_maxunpool2x2(a.data_ptr(), idx.data_ptr(), y.data_ptr(), b_, h, w_, c, _lib.current_stream()), "maxunpool2x2")
                     a = y
+                    if taps is not None:
+                        taps["u" + seq[k + 1][0]] = y
                 else:
                     name = item[0]
                     w, b = self._layer(name)
@@ -178,4 +201,6 @@ class SegNet(nn.Module):
                         a = ops.conv3x3_winograd_nhwc(a, w, b, dil=1, act=act)
                     else:
                         a = ops.conv2d_nhwc(a, w, b, stride=1, pad=1, dil=1, act=act)
+                    if taps is not None:
+                        taps[("y" if act else "z") + name] = a
             return a

@@ -9,12 +9,11 @@ import torch
 import torch.nn.functional as F
 
 from densefusion_amd import synth
+from oracle_segnet import MEAN, STD, _frame
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
 DEV = torch.device("cuda:0")
-MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32)
-STD = np.array([0.229, 0.224, 0.225], dtype=np.float32)
 SEG = synth._SEG_LAYERS
 ENC_POOL = {"12", "22", "33", "43", "53"}            # the layers a max-pool follows
 DEC_UNPOOL = {"53d", "43d", "33d", "22d", "12d"}     # the layers an un-pool precedes
@@ -27,8 +26,10 @@ def rel(a, b):
 
 
 # ---- 1. BatchNorm + ReLU ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C,rows,shift", [(64, 19200, 0.0), (128, 4801, 0.0), (512, 3600, 0.0), (64, 4801, 1e3), (512, 3600, 1e3)])
-def test_bn_relu_against_fp64(C, rows, shift):
+def _bn_relu_case(C, rows, shift, fp32_envelope):
+    """BatchNormReLU forward and backward on z [rows, C] against fp64, every output within rel < 1e-5 -- or, with ``fp32_envelope``,
+    within max(4 x the error of fp32 CPU F.batch_norm + autograd on the same inputs, 1e-5); the kernel's own mean / variance outputs;
+    bit-identical reruns."""
     from densefusion_amd.segtrain_ops import BatchNormReLU
     g = torch.Generator().manual_seed(C + rows)
     z = (torch.randn(1, 1, rows, C, generator=g) * torch.rand(C, generator=g).add(0.5) + shift + torch.randn(C, generator=g)).float()
@@ -51,9 +52,20 @@ def test_bn_relu_against_fp64(C, rows, shift):
     mu, var = z64.mean(0), z64.var(0, unbiased=False)
     y64 = F.relu((z64 - mu) / torch.sqrt(var + 1e-5) * g64 + b64)
     y64.backward(dy.double().reshape(rows, C))
-    for got, want in ((y.reshape(rows, C), y64), (dz.reshape(rows, C), z64.grad), (dg, g64.grad), (db, b64.grad),
-                      (rm, 0.9 * rm0.double() + 0.1 * mu), (rv, 0.9 * rv0.double() + 0.1 * z64.var(0, unbiased=True))):
-        assert rel(got, want.detach()) < 1e-5
+    wants = (y64, z64.grad, g64.grad, b64.grad, 0.9 * rm0.double() + 0.1 * mu, 0.9 * rv0.double() + 0.1 * z64.var(0, unbiased=True))
+    bounds = [1e-5] * 6
+    if fp32_envelope:
+        z32 = z.reshape(rows, C).clone().requires_grad_(True)
+        g32, b32 = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+        rm32, rv32 = rm0.clone(), rv0.clone()
+        y32 = F.relu(F.batch_norm(z32.t()[None], rm32, rv32, g32, b32, training=True, momentum=0.1, eps=1e-5))[0].t()
+        y32.backward(dy.reshape(rows, C))
+        bounds = [max(4 * rel(a, b.detach()), 1e-5) for a, b in zip((y32.detach(), z32.grad, g32.grad, b32.grad, rm32, rv32), wants)]
+    names = ("y", "dz", "dgamma", "dbeta", "running_mean", "running_var")
+    errs = [rel(got.reshape(want.shape), want.detach()) for got, want in zip((y, dz, dg, db, rm, rv), wants)]
+    print(f"C {C} rows {rows} shift {shift}: " + ", ".join(f"{n} {e:.1e} (< {b:.1e})" for n, e, b in zip(names, errs, bounds)))
+    for n, e, b in zip(names, errs, bounds):
+        assert e < b, (n, e, b)
     assert int(nbt) == 8
     # mean / variance outputs of the kernel itself
     from densefusion_amd.segtrain_ops import _bn_fwd
@@ -63,6 +75,84 @@ def test_bn_relu_against_fp64(C, rows, shift):
     assert rel(v.cpu(), var.detach()) < 1e-6
     again = run()
     assert all(torch.equal(a, b) for a, b in zip(again, (y, dz, dg, db, rm, rv, nbt)))          # bit-identical reruns
+
+
+@pytest.mark.parametrize("C,rows,shift", [(64, 19200, 0.0), (128, 4801, 0.0), (512, 3600, 0.0), (64, 4801, 1e3), (512, 3600, 1e3)])
+def test_bn_relu_against_fp64(C, rows, shift):
+    _bn_relu_case(C, rows, shift, fp32_envelope=False)
+
+
+# The statistics passes give lane t channels 4 (t % c4) .. +3 (c4 = C / 4) and rows t / c4, + rpi, ... (rpi = 256 // c4); they run
+# ceil(rows / (16 rpi)) workgroups, at most 1024, and the finish passes take 16 channels per workgroup.  The shapes: C below 16 and no
+# multiple of 16 (a finish workgroup partly idle); c4 = 3 and 129, which do not divide 256 (idle lanes: lane 255 at C = 12, 127 of 256
+# at C = 516); the largest C; rows on both sides of the first grid step (16 rpi: 4096 at C = 4, 1360 at C = 12, 256 at C = 64, 64 at
+# C = 256); fewer rows than lanes of a channel group; rows past the workgroup cap at rpi = 2 (32 x 1024 = 32768); a mean of 1e3 on
+# the smallest of them.
+BN_EDGES = [(4, 2), (4, 4095), (4, 4096), (4, 4097), (12, 3), (12, 1359), (12, 1361), (24, 2000), (64, 255), (64, 256), (64, 257),
+            (256, 4), (256, 63), (256, 65), (516, 17), (1024, 2), (1024, 33), (512, 40000)]
+
+
+@pytest.mark.parametrize("C,rows,shift", [(c, r, 0.0) for c, r in BN_EDGES] + [(512, 4, 1e3), (12, 3, 1e3)])
+def test_bn_relu_edge_shapes_against_fp64(C, rows, shift):
+    _bn_relu_case(C, rows, shift, fp32_envelope=True)
+
+
+def test_bn_relu_one_row():
+    """rows = 1 (torch refuses it): the rule the kernel documents.  The batch variance is 0 and xhat is 0, so y = relu(beta),
+    running_var <- (1 - m) running_var + m * 0 (no unbiased factor), dz = 0, dgamma = 0 and dbeta = dy where beta > 0."""
+    from densefusion_amd.segtrain_ops import BatchNormReLU
+    C = 64
+    g = torch.Generator().manual_seed(65)
+    z, dy = torch.randn(1, 1, 1, C, generator=g) * 3 + 1, torch.randn(1, 1, 1, C, generator=g)
+    gamma, beta = torch.rand(C, generator=g).add(0.5), torch.randn(C, generator=g) * 0.3
+    rm0, rv0 = torch.randn(C, generator=g), torch.rand(C, generator=g).add(0.5)
+    rm, rv, nbt = rm0.to(DEV), rv0.to(DEV), torch.tensor(7, dtype=torch.int64, device=DEV)
+    zz, ga, be = z.to(DEV).requires_grad_(True), gamma.to(DEV).requires_grad_(True), beta.to(DEV).requires_grad_(True)
+    y = BatchNormReLU.apply(zz, ga, be, rm, rv, nbt, 0.1, 1e-5)
+    y.backward(dy.to(DEV))
+    assert torch.equal(y.detach().cpu().reshape(C), F.relu(beta))
+    assert torch.equal(zz.grad.cpu(), torch.zeros_like(z)) and torch.equal(ga.grad.cpu(), torch.zeros(C))
+    assert torch.equal(be.grad.cpu(), torch.where(beta > 0, dy.reshape(C), torch.zeros(C)))
+    assert rel(rm, 0.9 * rm0.double() + 0.1 * z.double().reshape(C)) < 1e-7
+    assert rel(rv, 0.9 * rv0.double()) < 1e-7
+    assert int(nbt) == 8
+
+
+@pytest.mark.parametrize("B,H,W,C", [(1, 2, 2, 512), (2, 2, 4, 12), (1, 6, 10, 64)])
+def test_bn_relu_maxpool_backward_against_fp64_with_the_index_forced(B, H, W, C):
+    """The pooled-gradient path of df_bn_relu_bwd against fp64 autograd of BatchNorm + ReLU + the gather at the kernel's own pool index
+    (oracle_segnet.pool_forced), within max(4 x the same in fp32 on the CPU, 1e-5) like the BatchNorm cases above, the index itself
+    against torch's max-pool of the unfused BatchNormReLU output, and bit-equal with the unfused pair."""
+    import oracle_segnet as osn
+    from densefusion_amd.segtrain_ops import BatchNormReLU, BatchNormReLUMaxPool, MaxPool2x2Idx
+    g = torch.Generator().manual_seed(B * H * W + C)
+    z = torch.randn(B, H, W, C, generator=g) * torch.rand(C, generator=g).add(0.5) + torch.randn(C, generator=g)
+    gamma, beta = torch.rand(C, generator=g).add(0.5), torch.randn(C, generator=g) * 0.3
+    dp = torch.randn(B, H // 2, W // 2, C, generator=g)
+    outs = []
+    for fused in (True, False):
+        zz, g_, b_ = z.to(DEV).requires_grad_(True), gamma.to(DEV).requires_grad_(True), beta.to(DEV).requires_grad_(True)
+        if fused:
+            p, idx = BatchNormReLUMaxPool.apply(zz, g_, b_, None, None, None, 0.1, 1e-5)
+        else:
+            full = BatchNormReLU.apply(zz, g_, b_, None, None, None, 0.1, 1e-5)
+            p, idx = MaxPool2x2Idx.apply(full)
+        p.backward(dp.to(DEV))
+        outs.append([t.detach().cpu() for t in (p, idx, zz.grad, g_.grad, b_.grad)])
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+    p, idx, dz, dg, db = outs[0]
+    pe, ie = osn.pool_exact(full.detach().cpu())
+    assert torch.equal(p, pe) and torch.equal(idx, ie)
+    refs = {}
+    for dt in (torch.float64, torch.float32):
+        z_, g_, b_ = (t.to(dt).requires_grad_(True) for t in (z, gamma, beta))
+        pr = osn.pool_forced(osn.bn_relu(z_, g_, b_), idx)
+        refs[dt] = (pr.detach(),) + torch.autograd.grad(pr, (z_, g_, b_), dp.to(dt))
+    for n, got, w64, w32 in zip(("pooled", "dz", "dgamma", "dbeta"), (p, dz, dg, db), refs[torch.float64], refs[torch.float32]):
+        bound = max(4 * rel(w32, w64), 1e-5)
+        print(f"{(B, H, W, C)} {n}: {rel(got, w64):.1e} (< {bound:.1e})")
+        assert rel(got, w64) < bound, n
 
 
 def test_bn_relu_maxpool_fused_matches_unfused():
@@ -88,8 +178,15 @@ def test_bn_relu_maxpool_fused_matches_unfused():
 def test_pool_adjoints_bit_exact():
     from densefusion_amd.segtrain_ops import MaxPool2x2Idx, MaxUnpool2x2
     torch.manual_seed(1)
-    x = F.relu(torch.randn(2, 8, 12, 16, device=DEV)).round()                  # ReLU zeros and rounding: many tied windows
-    dy = torch.randn(2, 4, 6, 16, device=DEV)
+    # the last two: one window per channel group (a 1 x 1 pooled map), and C = 12 with one row of windows per image
+    for B, H, W, C in ((2, 8, 12, 16), (1, 2, 2, 4), (3, 2, 6, 12)):
+        _pool_adjoints_case(B, H, W, C)
+
+
+def _pool_adjoints_case(B, H, W, C):
+    from densefusion_amd.segtrain_ops import MaxPool2x2Idx, MaxUnpool2x2
+    x = F.relu(torch.randn(B, H, W, C, device=DEV)).round()                    # ReLU zeros and rounding: many tied windows
+    dy = torch.randn(B, H // 2, W // 2, C, device=DEV)
     xx = x.clone().requires_grad_(True)
     y, idx = MaxPool2x2Idx.apply(xx)
     y.backward(dy)
@@ -137,6 +234,52 @@ def test_cross_entropy_against_fp64():
         CrossEntropyNHWC.apply(logits, bad, K)
     again = CrossEntropyNHWC.apply(logits, target, K)                           # the process and the flag are fine afterwards
     assert torch.isfinite(again)
+
+
+def _ce_case(rows, classes, ld, logits):
+    """loss within 1e-6 relative and gradient within rel < 1e-6 of fp64 F.cross_entropy, the padding channels exactly zero."""
+    from densefusion_amd.segtrain_ops import CrossEntropyNHWC
+    target = torch.randint(0, classes, (rows,), generator=torch.Generator().manual_seed(rows + ld))
+    lg = logits.to(DEV).requires_grad_(True)
+    loss = CrossEntropyNHWC.apply(lg, target.to(DEV), classes)
+    loss.backward()
+    l64 = logits[:, :classes].double().requires_grad_(True)
+    want = F.cross_entropy(l64, target)
+    want.backward()
+    grad = lg.grad.cpu()
+    assert torch.isfinite(loss) and torch.isfinite(grad).all()
+    print(f"rows {rows} classes {classes} ld {ld}: loss {float(loss):.7f} vs {float(want):.7f}, gradient {rel(grad[:, :classes], l64.grad):.1e}")
+    assert abs(float(loss.detach()) - float(want)) <= 1e-6 * abs(float(want))
+    assert rel(grad[:, :classes], l64.grad) < 1e-6
+    assert torch.equal(grad[:, classes:], torch.zeros(rows, ld - classes))
+    return target
+
+
+# rows: one row, one workgroup of 256 less / exactly / plus one row, and 2048 * 256 + 259 (the grid of at most 2048 workgroups wraps);
+# (classes, ld): the trainer's own (22 classes in the classifier's 32 padded channels), the loss module's (22 in 24), no padding at
+# all, two classes
+@pytest.mark.parametrize("rows,classes,ld", [(1, 22, 32), (255, 22, 32), (256, 22, 32), (257, 22, 32), (524547, 22, 32),
+                                             (257, 2, 4), (257, 22, 24), (257, 32, 32)])
+def test_cross_entropy_edge_shapes_against_fp64(rows, classes, ld):
+    from densefusion_amd.segtrain_ops import CrossEntropyNHWC
+    logits = torch.randn(rows, ld, generator=torch.Generator().manual_seed(rows * ld + classes)) * 3.0
+    target = _ce_case(rows, classes, ld, logits)
+    if rows == 524547:
+        bad = target.clone()
+        bad[-1] = classes                       # the last row, which only the wrapped grid stride reaches
+        with pytest.raises(ValueError):
+            CrossEntropyNHWC.apply(logits.to(DEV), bad.to(DEV), classes)
+    if (rows, classes, ld) == (257, 22, 32):
+        _ce_case(rows, classes, ld, torch.randn(rows, ld, generator=torch.Generator().manual_seed(5)).sign() * 80)      # +-80 everywhere
+
+
+def test_cross_entropy_one_class():
+    """classes = 1: every row's softmax is 1 on its label, so the loss and the gradient are exactly zero."""
+    from densefusion_amd.segtrain_ops import CrossEntropyNHWC
+    logits = (torch.randn(257, 4, generator=torch.Generator().manual_seed(6)) * 3.0).to(DEV).requires_grad_(True)
+    loss = CrossEntropyNHWC.apply(logits, torch.zeros(257, dtype=torch.int64, device=DEV), 1)
+    loss.backward()
+    assert float(loss) == 0.0 and torch.equal(logits.grad, torch.zeros_like(logits))
 
 
 # ---- the fp64 functional restatement of one training step ------------------------------------------------------------------------
@@ -191,22 +334,6 @@ def gpu_step(sd, x, target, steps=1, lr=1e-4):
 
 def _is_bn_bias(k):
     return k.startswith("conv") and k.endswith(".bias") and not k.startswith("conv11d.")
-
-
-def _frame(seed, B, H, W):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    label = np.zeros((B, H, W), dtype=np.int64)
-    img = np.zeros((B, 3, H, W), dtype=np.float32)
-    colours = rng.integers(0, 256, (22, 3)).astype(np.float32)
-    yy, xx = np.mgrid[0:H, 0:W]
-    for b in range(B):
-        for _ in range(12):
-            c = int(rng.integers(1, 22))
-            cy, cx, ry, rx = rng.uniform(0, H), rng.uniform(0, W), rng.uniform(H / 10, H / 3), rng.uniform(W / 10, W / 3)
-            label[b][((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 < 1] = c
-        img[b] = colours[label[b]].transpose(2, 0, 1) + rng.normal(0, 3, (3, H, W))
-    x = (img - MEAN[None, :, None, None]) / STD[None, :, None, None]
-    return torch.from_numpy(x.astype(np.float32)), torch.from_numpy(label)
 
 
 # ---- 4. one step against the fp64 restatement ------------------------------------------------------------------------------------
