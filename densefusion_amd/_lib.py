@@ -140,6 +140,8 @@ SIGNATURES = {
     "df_segment_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "df_segment_input": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "df_segment_detect": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "df_seg_batch_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "df_seg_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

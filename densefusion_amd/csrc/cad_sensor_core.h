@@ -42,6 +42,16 @@ __host__ __device__ inline bool is_edge(const unsigned short *__restrict__ frame
   return false;
 }
 
+// The noise term of D5 for index p under seed s: floor((noise_mul * S + 2^31) / 2^32), S the centred sum of four 16-bit uniforms.
+// df_seg_batch's step G4 draws its pixel noise from the same function.
+__host__ __device__ inline int noise_term(unsigned s, unsigned p, int noise_mul) {
+  const unsigned h0 = prep::mix32(s ^ C0, p), h1 = prep::mix32(s ^ C1, p);
+  const int S = (int)((h0 & 0xFFFFu) + (h0 >> 16) + (h1 & 0xFFFFu) + (h1 >> 16)) - 131070;
+  const long long prod = (long long)noise_mul * S + (1LL << 31);                                 // |.| < 2^49
+  const long long fl = prod >= 0 ? prod >> 32 : -((-prod + ((1LL << 32) - 1)) >> 32);            // floor(prod / 2^32)
+  return (int)fl;
+}
+
 // D1..D6 for pixel p = r * IW + q, whose clean code is c = frame[p], of a frame whose seed is s (D0); `frame` is the CLEAN frame, of
 // which only pixels inside the frame are read.  Returns the sensor's code and adds the pixel's share to `n`.
 __host__ __device__ inline unsigned short sense_pixel(const unsigned short *__restrict__ frame, int IH, int IW, int r, int q, int c, unsigned s,
@@ -52,11 +62,7 @@ __host__ __device__ inline unsigned short sense_pixel(const unsigned short *__re
   n.edge += edge;
   if ((prep::mix32(s ^ C3, p) >> 8) < (unsigned)rec.drop24) { n.drop += 1; return HORIZON; }     // D3
   if (edge && (prep::mix32(s ^ C2, p) >> 8) < (unsigned)rec.edge_drop24) { n.edge_drop += 1; return HORIZON; }   // D4
-  const unsigned h0 = prep::mix32(s ^ C0, p), h1 = prep::mix32(s ^ C1, p);                       // D5
-  const int S = (int)((h0 & 0xFFFFu) + (h0 >> 16) + (h1 & 0xFFFFu) + (h1 >> 16)) - 131070;
-  const long long prod = (long long)rec.noise_mul * S + (1LL << 31);                             // |.| < 2^49
-  const long long fl = prod >= 0 ? prod >> 32 : -((-prod + ((1LL << 32) - 1)) >> 32);            // floor(prod / 2^32)
-  int c1 = c + (int)fl;
+  int c1 = c + noise_term(s, p, rec.noise_mul);                                                  // D5
   c1 = c1 < 0 ? 0 : (c1 > MAX_CODE ? MAX_CODE : c1);
   int c2 = (c1 + rec.quant / 2) / rec.quant * rec.quant;                                         // D6
   c2 = c2 > MAX_CODE ? MAX_CODE : c2;

@@ -10,11 +10,11 @@
 #include <climits>
 
 #include "common.h"
+#include "seg_norm.h"
 
 namespace df {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int TB = 256;              // threads of the label pass = pixels per tile
 constexpr int SEG_PPB = 4096;        // pixels per workgroup of the label pass
 constexpr int SEG_MAX_C = 64;        // classes: lane c of a wave keeps class c's running statistics
@@ -24,19 +24,7 @@ constexpr int FIN_TB = 1024;         // finish: 16 lane groups per frame add the
 
 inline int seg_parts(long hw) { return cdiv(hw, SEG_PPB); }
 
-// ((float)v - mean) / std with true division, per channel, on the 0..255 values (no / 255: the reference's own normalisation,
-// vanilla_segmentation/data_controller.py:79); the constants are the fp32 roundings numpy makes of the reference's literals
-__device__ __forceinline__ f32x4 seg_norm(unsigned r, unsigned g, unsigned b) {
-  const float m0 = (float)0.485, m1 = (float)0.456, m2 = (float)0.406, s0 = (float)0.229, s1 = (float)0.224, s2 = (float)0.225;
-  f32x4 o;
-  o[0] = ((float)r - m0) / s0;
-  o[1] = ((float)g - m1) / s1;
-  o[2] = ((float)b - m2) / s2;
-  o[3] = 0.f;
-  return o;
-}
-
-// four pixels per lane: three aligned dword loads (12 bytes), four float4 stores; the npix % 4 tail pixel by pixel
+// four pixels per lane (seg_norm: seg_norm.h): three aligned dword loads (12 bytes), four float4 stores; the npix % 4 tail pixel by pixel
 __global__ __launch_bounds__(TB) void seg_input_kernel(const unsigned char *__restrict__ rgb, float *__restrict__ out, long npix) {
   f32x4 *o4 = reinterpret_cast<f32x4 *>(out);
   const long nq = npix / 4;

@@ -24,7 +24,8 @@ Per chunk of views: one render call (plus the solo call in scene mode), the sens
 (a frame's noise does not depend on the chunking), the jitter, ``df_cad_item_table``, ONE read-back of the table (with the render's
 pixel counts appended: [F][10] integers), then ``df_preprocess_objects_cad`` per crop size and ``df_cad_targets`` per model for the
 live items.  Poses, plans, seeds and descriptors go up; nothing else crosses the bus.  ``__getitem__`` is served from a small,
-lock-protected cache of prepared chunks; ``permutation`` gives an epoch order that walks the chunks one after the other.
+lock-protected cache of prepared chunks; ``permutation`` gives an epoch order that walks the chunks one after the other.  Cache,
+ready event, ``permutation`` and ``set_epoch`` are ``ChunkedViews``, which ``online_seg.RenderedSegDataset`` shares.
 """
 from __future__ import annotations
 
@@ -55,7 +56,72 @@ class _Chunk:
         self.ready = None            # recorded on the preparing stream after the last launch
 
 
-class RenderedPoseDataset:
+class ChunkedViews:
+    """Views of consecutive seeds served from a small, lock-protected cache of prepared chunks (shared by ``RenderedPoseDataset`` and
+    ``online_seg.RenderedSegDataset``).  A subclass provides ``_prepare(epoch, a, b)`` -> (items, info, ready): per view of the span
+    its item and what ``view_info`` returns, and an event recorded on the preparing stream after the last launch; it holds
+    ``_device_lock`` around its device work (the renderers keep one scratch buffer each)."""
+
+    def _init_views(self, chunk, first_seed, frames, cache_chunks, device):
+        if int(chunk) < 1 or int(frames) < 1 or int(first_seed) < 0:
+            raise ValueError("chunk and frames must be positive, first_seed not negative")
+        self.chunk, self.first_seed, self.frames, self.epoch = int(chunk), int(first_seed), int(frames), 0
+        self.device = torch.device(device)
+        self._cache, self._cache_chunks, self._lock, self._device_lock = OrderedDict(), max(1, int(cache_chunks)), threading.Lock(), threading.Lock()
+        self._offset = 0
+
+    def __len__(self):
+        return self.frames
+
+    def set_epoch(self, epoch):
+        """Moves the seed range by ``epoch * frames``: item i becomes the view of seed ``first_seed + epoch * frames + i``."""
+        if int(epoch) < 0:
+            raise ValueError("epoch must not be negative")
+        self.epoch = int(epoch)
+        return self
+
+    def view_seed(self, index):
+        return self.first_seed + self.epoch * self.frames + int(index)
+
+    def permutation(self, rs):
+        """An epoch order from ``rs`` (a ``np.random.RandomState``) that a chunk cache can serve: the set is cut into runs of ``chunk``
+        consecutive views at an offset drawn per call, the runs are shuffled and each run's views are shuffled.  (The views of
+        consecutive seeds are independent draws; a plain permutation would have every fetch render a chunk to serve one item.)  The cache
+        cuts its chunks at the offset of the latest call; items do not depend on the cut."""
+        self._offset = off = int(rs.randint(self.chunk))
+        cuts = [0] + list(range(off, self.frames, self.chunk)) if off else list(range(0, self.frames, self.chunk))
+        runs = [np.arange(a, b) for a, b in zip(cuts, cuts[1:] + [self.frames])]
+        return np.concatenate([rs.permutation(runs[k]) for k in rs.permutation(len(runs))])
+
+    def _span(self, index):
+        off = self._offset
+        if index < off:
+            return 0, min(off, self.frames)
+        a = off + (index - off) // self.chunk * self.chunk
+        return a, min(a + self.chunk, self.frames)
+
+    def _chunk_of(self, index):
+        index = int(index)
+        if not 0 <= index < self.frames:
+            raise IndexError(index)
+        a, b = self._span(index)
+        key = (self.epoch, a, b)
+        with self._lock:
+            slot = self._cache.get(key)
+            if slot is None:
+                slot = self._cache[key] = _Chunk()
+                while len(self._cache) > self._cache_chunks:
+                    self._cache.popitem(last=False)
+            else:
+                self._cache.move_to_end(key)
+        with slot.lock:
+            if slot.items is None:
+                slot.items, slot.info, slot.ready = self._prepare(*key)
+        torch.cuda.current_stream(self.device).wait_event(slot.ready)      # a chunk may have been prepared on another stream
+        return slot, index - a
+
+
+class RenderedPoseDataset(ChunkedViews):
     """``models``: a model or a list of them, each a PLY path or arrays -- (points, normals or None, colours) for ``raster="points"``,
     (vertices, triangles, colours) for ``raster="mesh"`` and for scenes.  One model is rendered by the single-object renderers;
     several models, or ``distractors``, or ``scene=True`` make scenes (meshes only; model k is object k + 1 of ``objlist``).  The
@@ -83,8 +149,7 @@ class RenderedPoseDataset:
             raise ValueError("light needs raster mesh or a scene: the point renderer is unlit")
         if sensor is not None and not isinstance(sensor, cr.DepthSensor):
             raise ValueError("sensor must be a render.DepthSensor")
-        if int(chunk) < 1 or int(frames) < 1 or int(first_seed) < 0:
-            raise ValueError("chunk and frames must be positive, first_seed not negative")
+        self._init_views(chunk, first_seed, frames, cache_chunks, device)
         self.num, self.add_noise, self.noise_trans, self.refine = int(num), bool(add_noise), noise_trans, refine
         self.raster, self.splat, self.cull, self.mask = raster, int(splat), int(cull), mask
         self.light, self.light_angle, self.sensor, self.sensor_seed = light, float(light_angle), sensor, int(sensor_seed)
@@ -92,9 +157,7 @@ class RenderedPoseDataset:
         self.min_pixels, self.min_visible = int(min_pixels), float(min_visible)
         self.p_present, self.lateral, self.depth = float(p_present), float(lateral), float(depth)
         self.max_holes, self.hole_mean, self.hole_std = int(max_holes), float(hole_mean), float(hole_std)
-        self.chunk, self.first_seed, self.frames, self.epoch = int(chunk), int(first_seed), int(frames), 0
         self.jitter = jitter
-        self.device = torch.device(device)
         self.trancolor = augment.ColorJitter(0.2, 0.2, 0.2, 0.05)
         proj = cr.DEFAULT_PROJ if proj_mat is None else (read_proj_mat(proj_mat) if _is_path(proj_mat) else proj_mat)
         self.proj_mat = np.array(proj, dtype=np.float64).reshape(4, 4)
@@ -133,8 +196,6 @@ class RenderedPoseDataset:
             self.pt[1] = sample_model_points(np.asarray(pts, dtype=np.float32).astype(np.float64), np.zeros((0, 3), dtype=np.int64))
         self._pt_dev = {o: torch.from_numpy(np.ascontiguousarray(p, dtype=np.float64)).to(self.device) for o, p in self.pt.items()}
         self.num_pt_mesh_large = self.num_pt_mesh_small = 500
-        self._cache, self._cache_chunks, self._lock, self._device_lock = OrderedDict(), max(1, int(cache_chunks)), threading.Lock(), threading.Lock()
-        self._offset = 0
 
     @classmethod
     def from_options(cls, opt, models, distractors=(), *, first_seed=0, frames=2000, num=500, add_noise=False, noise_trans=0.0, refine=False,
@@ -152,41 +213,11 @@ class RenderedPoseDataset:
                    p_present=opt.p_present, lateral=opt.lateral, depth=opt.depth, max_holes=opt.max_holes, hole_mean=opt.hole_mean,
                    hole_std=opt.hole_std, chunk=opt.chunk, points=opt.points, first_seed=first_seed, frames=frames, device=device)
 
-    def __len__(self):
-        return self.frames
-
     def get_sym_list(self):
         return []
 
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small
-
-    def set_epoch(self, epoch):
-        """Moves the seed range by ``epoch * frames``: item i becomes the view of seed ``first_seed + epoch * frames + i``."""
-        if int(epoch) < 0:
-            raise ValueError("epoch must not be negative")
-        self.epoch = int(epoch)
-        return self
-
-    def view_seed(self, index):
-        return self.first_seed + self.epoch * self.frames + int(index)
-
-    def permutation(self, rs):
-        """An epoch order from ``rs`` (a ``np.random.RandomState``) that a chunk cache can serve: the set is cut into runs of ``chunk``
-        consecutive views at an offset drawn per call, the runs are shuffled and each run's views are shuffled.  (The views of
-        consecutive seeds are independent draws; a plain permutation would have every fetch render a chunk to serve one item.)  The cache
-        cuts its chunks at the offset of the latest call; items do not depend on the cut."""
-        self._offset = off = int(rs.randint(self.chunk))
-        cuts = [0] + list(range(off, self.frames, self.chunk)) if off else list(range(0, self.frames, self.chunk))
-        runs = [np.arange(a, b) for a, b in zip(cuts, cuts[1:] + [self.frames])]
-        return np.concatenate([rs.permutation(runs[k]) for k in rs.permutation(len(runs))])
-
-    def _span(self, index):
-        off = self._offset
-        if index < off:
-            return 0, min(off, self.frames)
-        a = off + (index - off) // self.chunk * self.chunk
-        return a, min(a + self.chunk, self.frames)
 
     # -- the draws of one item that are not its view ------------------------------------------------------------------------------------
     def _draws(self, view):
@@ -276,26 +307,6 @@ class RenderedPoseDataset:
             ready = torch.cuda.Event()
             ready.record()
         return items, info, ready
-
-    def _chunk_of(self, index):
-        index = int(index)
-        if not 0 <= index < self.frames:
-            raise IndexError(index)
-        a, b = self._span(index)
-        key = (self.epoch, a, b)
-        with self._lock:
-            slot = self._cache.get(key)
-            if slot is None:
-                slot = self._cache[key] = _Chunk()
-                while len(self._cache) > self._cache_chunks:
-                    self._cache.popitem(last=False)
-            else:
-                self._cache.move_to_end(key)
-        with slot.lock:
-            if slot.items is None:
-                slot.items, slot.info, slot.ready = self._prepare(*key)
-        torch.cuda.current_stream(self.device).wait_event(slot.ready)      # a chunk may have been prepared on another stream
-        return slot, index - a
 
     def __getitem__(self, index):
         slot, j = self._chunk_of(index)

@@ -510,3 +510,57 @@ def compose_frame(rgb, back=None, mask_back=None, front=None, mask_front=None):
         st = _lib.lib().df_compose_frame(_lib.dptr(rgb), *ptrs, H, W, _lib.current_stream())
     _lib.check(st, "compose_frame")
     return rgb
+
+
+def seg_batch_check(desc, F, IH, IW, H, W, NB, BH, BW):
+    """``ValueError`` for the first bad row of desc [B,8] (the descriptor rule of ``df_seg_batch``); host integers only."""
+    for n, (f, y0, x0, flip, b, by0, bx0, _) in enumerate(np.asarray(desc).reshape(-1, 8).tolist()):
+        if not 0 <= f < F or not 0 <= y0 <= IH - H or not 0 <= x0 <= IW - W:
+            raise ValueError(f"seg_batch: item {n}: frame {f} or window corner ({y0}, {x0}) outside {F} frames of {IH} x {IW} for a {H} x {W} window")
+        if not 0 <= flip <= 3 or not -1 <= b < NB:
+            raise ValueError(f"seg_batch: item {n}: flip {flip} outside 0..3 or background {b} outside -1..{NB - 1}")
+        if b >= 0 and (not 0 <= by0 <= BH - H or not 0 <= bx0 <= BW - W):
+            raise ValueError(f"seg_batch: item {n}: background corner ({by0}, {bx0}) outside the {BH} x {BW} pool for a {H} x {W} window")
+
+
+def seg_batch(rgb, label, class_map, n_classes, desc, window, back=None, blur=1, noise_mul=0, check=True):
+    """SegNet training items from rendered scenes (``df_seg_batch``; steps G1..G5 of its comment in include/dfusion.h): rgb
+    [F,IH,IW,3] uint8 and label [F,IH,IW] uint16 as ``cad_render_scene`` returns them, class_map [O+1] HOST integers (label value ->
+    class, class_map[0] = 0), desc [B,8] int32 rows {f, y0, x0, flip, b, by0, bx0, seed} (host or device), window = (H, W), back
+    None or a [NB,BH,BW,3] uint8 device tensor.  A host ``desc`` is checked here and a bad row raises ``ValueError``
+    (``check=False`` or a device ``desc``: the call writes zeros for such an item).
+    Returns (x [B,H,W,4] float32, target [B,H,W] int64, counts [B,n_classes] int32) on the device; no read-back, no synchronisation."""
+    if not (rgb.is_cuda and label.is_cuda) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[3] != 3 or label.dtype != torch.uint16 or \
+            tuple(label.shape) != tuple(rgb.shape[:3]):
+        raise RuntimeError("seg_batch: rgb must be a [F,IH,IW,3] uint8 and label a [F,IH,IW] uint16 device tensor (no CPU path)")
+    dev = rgb.device
+    F, IH, IW, _ = rgb.shape
+    H, W = int(window[0]), int(window[1])
+    NB, BH, BW = 0, 0, 0
+    if back is not None:
+        if not back.is_cuda or back.device != dev or back.dtype != torch.uint8 or back.dim() != 4 or back.shape[3] != 3 or back.shape[0] == 0:
+            raise RuntimeError("seg_batch: back must be a non-empty [NB,BH,BW,3] uint8 tensor on the frames' device")
+        NB, BH, BW, _ = back.shape
+    class_map = np.ascontiguousarray(class_map, dtype=np.int32).reshape(-1)
+    if not torch.is_tensor(desc):
+        desc = np.ascontiguousarray(desc, dtype=np.int64).reshape(-1, 8)
+        if check:
+            seg_batch_check(desc, F, IH, IW, H, W, NB, BH, BW)
+        desc = (desc & 0xFFFFFFFF).astype(np.uint32).view(np.int32)       # a seed may be given as unsigned
+    desc = _on_device(desc, np.int32, dev, lambda d: d.dtype == torch.int32 and d.dim() == 2 and d.shape[1] == 8 and d.shape[0] != 0,
+                      "seg_batch: desc must be a non-empty [B,8] int32")
+    B = desc.shape[0]
+    L = _lib.lib()
+    need = L.df_seg_batch_scratch_bytes(B, H, W, int(n_classes))
+    if need == 0:
+        raise RuntimeError(f"seg_batch: sizes the call refuses (B={B}, H={H}, W={W}, C={n_classes})")
+    x = torch.empty(B, H, W, 4, dtype=torch.float32, device=dev)
+    target = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    counts = torch.empty(B, int(n_classes), dtype=torch.int32, device=dev)
+    scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    with _lib.device_guard(dev):
+        st = L.df_seg_batch(_lib.dptr(rgb), _lib.dptr(label), F, IH, IW, None if back is None else _lib.dptr(back), NB, BH, BW,
+                            class_map.ctypes.data, class_map.shape[0] - 1, int(n_classes), desc.data_ptr(), B, H, W, int(blur), int(noise_mul),
+                            x.data_ptr(), target.data_ptr(), counts.data_ptr(), scratch.data_ptr(), scratch.numel(), _lib.current_stream())
+    _lib.check(st, "seg_batch")
+    return x, target, counts

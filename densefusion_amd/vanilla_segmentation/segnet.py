@@ -17,7 +17,9 @@ tape of segtrain_ops / train_ops: the UNFOLDED parameters (each
 convolution with its bias on the fp32-MFMA kernel, weights arranged OHWI and padded like the eval path's), then BatchNorm2d with
 batch statistics fused with the ReLU (and, at the encoder's stage ends, with the max-pool), writing the module's own
 ``running_mean`` / ``running_var`` / ``num_batches_tracked``.  It returns a [B,label_nbr,H,W] view of the channels-last logits; the
-segmentation ``Loss`` (loss.py) reads the channels-last tensor behind it directly.
+segmentation ``Loss`` (loss.py) reads the channels-last tensor behind it directly.  ``forward_nhwc`` of a trainable module in
+``train()`` mode takes the channels-last [B,H,W,4] input ``df_seg_batch`` writes and returns the same.  ``label_nbr`` 2..64 trains: the
+classifier's outputs are padded to a power of two and to 4 at the least.
 """
 from __future__ import annotations
 
@@ -86,14 +88,17 @@ class SegNet(nn.Module):
 
     def _train_forward(self, x, taps=None):
         C = x.shape[1]
-        self._folded = {}                     # the BatchNorm buffers are rewritten below, behind torch's version counters
         a = x.detach().float().permute(0, 2, 3, 1)
-        a = F.pad(a, (0, _pad4(C) - C)).contiguous()
+        return self._train_forward_nhwc(F.pad(a, (0, _pad4(C) - C)).contiguous(), x.device, taps)
+
+    def _train_forward_nhwc(self, a, device, taps=None):
+        """The training graph on the channels-last, channel-padded input ``a`` (the tape's first tensor, not copied)."""
+        self._folded = {}                     # the BatchNorm buffers are rewritten below, behind torch's version counters
         seq = _ENC + _DEC
         indices = []
         if taps is not None:
             taps["x"] = a
-        with _lib.device_guard(x.device):
+        with _lib.device_guard(device):
             for k, item in enumerate(seq):
                 if item == "P":
                     continue                  # fused into the BatchNorm before it
@@ -108,8 +113,9 @@ class SegNet(nn.Module):
                 w = conv.weight.permute(0, 2, 3, 1)                                   # OIHW -> OHWI
                 b = conv.bias
                 # the classifier's outputs are padded to a power of two: its data gradient runs the flipped convolution, whose
-                # input channels (these) the MFMA kernel takes in powers of two only (22 classes -> 32)
-                cpad = 1 << (cout - 1).bit_length() if name == "11d" else _pad4(cout)
+                # input channels (these) the MFMA kernel takes in powers of two only (22 classes -> 32), and in fours at the least (2 or 3
+                # classes -> 4)
+                cpad = max(4, 1 << (cout - 1).bit_length()) if name == "11d" else _pad4(cout)
                 if _pad4(cin) != cin or cpad != cout:
                     w = F.pad(w, (0, _pad4(cin) - cin, 0, 0, 0, 0, 0, cpad - cout))
                     b = F.pad(b, (0, cpad - cout))
@@ -158,16 +164,21 @@ class SegNet(nn.Module):
             return self.forward_nhwc(a, taps)[..., :self.label_nbr].permute(0, 3, 1, 2).contiguous()
 
     def forward_nhwc(self, x, taps=None):
-        """Eval forward on the channels-last input x [B,H,W,pad4(input_nbr)] fp32 (padding channels zero; what df_segment_input
-        writes) -> the channels-last activation [B,H,W,pad4(label_nbr)] whose first label_nbr channels are the logits.
+        """Forward on the channels-last input x [B,H,W,pad4(input_nbr)] fp32 (padding channels zero; what df_segment_input and
+        df_seg_batch write).  eval(): -> the channels-last activation [B,H,W,pad4(label_nbr)] whose first label_nbr channels are the
+        logits.  train() (a trainable module only): x goes straight onto the tape, without the permute + pad copy of ``forward``, and
+        the result is what ``forward`` returns in training: the [B,label_nbr,H,W] view with the channels-last logits attached.
         ``taps``: see ``forward``."""
-        if self.training:
-            raise NotImplementedError("SegNet.forward_nhwc: eval mode only")
+        if self.training and not self.trainable:
+            raise NotImplementedError("SegNet.forward_nhwc: train() needs a module built with SegNet(trainable=True); the default "
+                                      "module is inference-only")
         if not x.is_cuda:
             raise RuntimeError("densefusion_amd needs device tensors (no CPU path): call .cuda() on the input")
         if x.dim() != 4 or x.shape[3] != _pad4(self.input_nbr) or x.shape[1] % 32 or x.shape[2] % 32 or x.dtype != torch.float32:
             raise RuntimeError(f"SegNet.forward_nhwc: expected fp32 [B,H,W,{_pad4(self.input_nbr)}] with H, W multiples of 32, "
                                f"got {tuple(x.shape)} {x.dtype}")
+        if self.training:
+            return self._train_forward_nhwc(x.detach().contiguous(), x.device, taps)
         L = _lib.lib()
         with torch.no_grad(), _lib.device_guard(x.device):
             a = x.contiguous()

@@ -573,6 +573,48 @@ int df_segment_detect(const float *logits, const unsigned short *depth, int F, i
                       df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SegNet training batches from rendered customCAD scenes (the work of the reference's SegDataset.__getitem__,
+ * vanilla_segmentation/data_controller.py, on frames that never leave the device): B items, each a window of one rendered frame, composited
+ * over a background, blurred, given pixel noise, flipped, normalised.  No allocation, no synchronisation, the caller's stream; integer
+ * atomics only (the counts), so the outputs are bit-reproducible; an item's outputs do not depend on the other items of the call.
+ *
+ * df_seg_batch_scratch_bytes: bytes of scratch the call asks for (small: the call keeps nothing in memory between steps); 0 for sizes the
+ *   call refuses (B, H*W, C below).
+ * df_seg_batch:
+ *   DEVICE: rgb [F][IH][IW][3] u8 and label [F][IH][IW] u16, the outputs of df_cad_render_scene[_lit] (label 0 = horizon, o + 1 = object
+ *   o); back [NB][BH][BW][3] u8, NULL exactly when NB == 0; desc [B][8] int32, row n = {f, y0, x0, flip, b, by0, bx0, seed}: the frame,
+ *   the window's corner in it, flip bit 0 = left-right and bit 1 = up-down, the background index (-1 = none) and its window's corner,
+ *   the noise seed (taken as unsigned); the outputs; scratch.
+ *   HOST, read during the call, a launch argument: class_map [O+1] int32, label value -> class 0..C-1; class_map[0] must be 0 (models
+ *   map to their class, distractors to 0: they keep their colour and are background for the loss).
+ *   Outputs: x_out [B][H][W][4] fp32 (16-byte aligned), the layout SegNet's channels-last input takes, channel 3 = 0;
+ *   target_out [B][H][W] int64; counts_out [B][C] int32, zeroed by the call.
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer (back as above); F, IH, IW as for df_cad_render; H outside 1..IH
+ *   or W outside 1..IW; H*W > 2^24; B outside 1..65535; O or C outside 1..64; a class_map entry outside 0..C-1 or class_map[0] != 0;
+ *   NB > 0 with BH < H or BW < W; blur outside 0..1; noise_mul < 0; misaligned outputs; a short scratch.
+ *   A BAD DESCRIPTOR -- f outside 0..F-1, the window not inside the frame, flip outside 0..3, b outside -1..NB-1, or (b >= 0) the
+ *   background window not inside the pool -- gives zeros in all of the item's x_out, target_out and counts_out, and nothing is read
+ *   through it (the rule of df_cad_scene_mask for a bad pair).
+ *   Per item n and window pixel (i, j), 0 <= i < H, 0 <= j < W, which is frame pixel (y0 + i, x0 + j); p = i*W + j:
+ *   G1. Class: l = label[f][y0+i][x0+j]; cls = class_map[l] if l <= O, else 0; counts_out[n][cls] += 1.
+ *   G2. Composite: c_k = back[b][by0+i][bx0+j][k] if l == 0 and b >= 0, else rgb[f][y0+i][x0+j][k] (with no background the renderer's
+ *       (130, 130, 130) horizon stays).
+ *   G3. Blur (blur == 1): v_k = (sum of w * c_k + 8) >> 4 over the 3 x 3 neighbourhood, w = [1 2 1; 2 4 2; 1 2 1], the neighbour's
+ *       indices clamped to the window 0..H-1, 0..W-1 (nothing outside the window is read); the sum is over COMPOSITED values, so an
+ *       object's edge mixes with the background.  blur == 0: v_k = c_k.  Labels are never blurred.
+ *   G4. Noise (noise_mul > 0): step D5 of df_cad_depth_sensor with s = seed and index 3p + k: h0 = mix32(seed ^ C0, 3p + k),
+ *       h1 = mix32(seed ^ C1, 3p + k), S and n = floor((noise_mul * S + 2^31) / 2^32) as there; v_k = clamp(v_k + n, 0, 255).
+ *       noise_mul = rint(sigma * 2^32 / sqrt(1431655765)); the reference's N(0, 5) is sigma = 5.
+ *   G5. Write at the flipped position i' = H-1-i if flip bit 1 else i, j' = W-1-j if flip bit 0 else j:
+ *       x_out[n][i'][j'] = {((float)v_k - mean_k) / std_k, 0}, the rule of df_segment_input; target_out[n][i'][j'] = cls.
+ *   Noise and background are indexed in the source orientation: a flipped item is the mirror image of the unflipped one, in x and target
+ *   alike, and the counts are equal.  Everything up to G5 is integer arithmetic. */
+size_t df_seg_batch_scratch_bytes(int B, int H, int W, int C);
+int df_seg_batch(const unsigned char *rgb, const unsigned short *label, int F, int IH, int IW, const unsigned char *back, int NB, int BH,
+                 int BW, const int *class_map, int O, int C, const int *desc, int B, int H, int W, int blur, int noise_mul, float *x_out,
+                 int64_t *target_out, int *counts_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]

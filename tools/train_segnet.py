@@ -8,6 +8,14 @@ FlatAdam over one flat parameter buffer (df_adam_step); --dataset_config_dir loc
 tools/train.py does.
 
     python tools/train_segnet.py --dataset_root YCB_Video_Dataset --dataset_config_dir datasets/ycb/dataset_config
+
+``--dataset cad_render`` trains a mask network for CAD models with no tree on disk: customCAD scenes rendered on the fly
+(datasets/customCAD/online_seg.py, ``RenderedSegDataset``), one class per ``--cad_model`` plus the background, the views and the
+renderer under the names of tools/train.py and tools/render_cad_dataset.py.  Batches come channels-last from ``dataset.batch`` over
+``dataset.permutation``, fed by ``--workers`` threads, into ``SegNet.forward_nhwc``; the test views follow the training seed range;
+``model_current.pth`` is also written after every training pass, and the log ends an epoch with the share of pixels per class.
+
+    python tools/train_segnet.py --dataset cad_render --cad_model a.ply b.ply --backgrounds photos/ --light random
 """
 from __future__ import annotations
 
@@ -25,6 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from densefusion_amd import train_utils  # noqa: E402
+from densefusion_amd.datasets.customCAD import render as cad_render  # noqa: E402
 from densefusion_amd.train_utils import FlatAdam, FlatParams  # noqa: E402
 from densefusion_amd.vanilla_segmentation.data_controller import SegDataset  # noqa: E402
 from densefusion_amd.vanilla_segmentation.loss import Loss  # noqa: E402
@@ -47,6 +57,20 @@ def build_parser():
     ap.add_argument("--train_length", type=int, default=5000, help="frames per training epoch")
     ap.add_argument("--test_length", type=int, default=1000, help="frames per test pass")
     ap.add_argument("--seed", type=int, default=None, help="random seed (default: drawn, as the reference does)")
+    ap.add_argument("--dataset", type=str, default="ycb", choices=("ycb", "cad_render"), help="a YCB-Video tree, or customCAD scenes rendered on the fly")
+    cad = ap.add_argument_group("cad_render", "the views and the renderer, under the names of tools/train.py and tools/render_cad_dataset.py")
+    cad.add_argument("--cad_model", type=str, nargs="+", default=[], help="PLY mesh(es): model k is class k + 1")
+    cad.add_argument("--cad_distractor", type=str, nargs="*", default=[], help="meshes that are drawn and can occlude; background for the loss")
+    cad.add_argument("--cad_frames", type=int, default=2000, help="views per training epoch")
+    cad.add_argument("--cad_test_frames", type=int, default=200, help="test views: the seed range right after the training range")
+    cad.add_argument("--cad_seed", type=int, default=0, help="seed of the first training view")
+    cad.add_argument("--cad_fresh", action="store_true", help="fresh views every epoch (the seed range moves on by --cad_frames); default: a fixed set, like a tree")
+    cad.add_argument("--seg_height", type=int, default=None, help="window height, a multiple of 32 (default: the largest inside the frame)")
+    cad.add_argument("--seg_width", type=int, default=None, help="window width, a multiple of 32 (default: the largest inside the frame)")
+    cad.add_argument("--backgrounds", type=str, default=None, help="directory of images that stand behind the objects (default: the grey horizon)")
+    cad.add_argument("--seg_blur", type=int, default=1, choices=(0, 1), help="1: the 3 x 3 binomial blur over the composited window")
+    cad.add_argument("--seg_noise", type=float, default=5.0, help="sigma of the pixel noise in grey levels (0: none)")
+    cad_render.add_view_arguments(cad)
     return ap
 
 
@@ -71,6 +95,102 @@ def _plain_state_dict(model):
     return {k: v.detach().clone() for k, v in model.state_dict().items()}
 
 
+def cad_datasets(opt):
+    """(training set, test set) of --dataset cad_render; the test views follow the last training view --cad_fresh can reach."""
+    from densefusion_amd.datasets.customCAD.online_seg import RenderedSegDataset, default_window
+    if not opt.cad_model:
+        raise SystemExit("--dataset cad_render needs --cad_model")
+    h, w = default_window((opt.height, opt.width))
+    kw = dict(window=(h if opt.seg_height is None else opt.seg_height, w if opt.seg_width is None else opt.seg_width),
+              backgrounds=opt.backgrounds, blur=opt.seg_blur, noise_sigma=opt.seg_noise)
+    test_seed = opt.cad_seed + opt.cad_frames * (max(opt.n_epochs - 1, 1) if opt.cad_fresh else 1)
+    try:
+        return (RenderedSegDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=opt.cad_seed, frames=opt.cad_frames,
+                                                use_noise=True, **kw),
+                RenderedSegDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=test_seed, frames=opt.cad_test_frames,
+                                                use_noise=False, **kw))
+    except ValueError as e:
+        raise SystemExit(f"--dataset cad_render: {e}")
+
+
+def train_cad(opt):
+    """The loop of ``main`` over rendered scenes; returns {"train": per epoch the batch losses, "test": the same, "shares": per epoch
+    the class pixel shares of the training pass}."""
+    dataset, test_dataset = cad_datasets(opt)
+    print(len(dataset), len(test_dataset))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    K = dataset.n_classes
+    model = SegNet(label_nbr=K, trainable=True).cuda()
+    if opt.resume_model != "":
+        model.load_state_dict(torch.load(os.path.join(opt.model_save_path, opt.resume_model), map_location="cuda"))
+        for log in os.listdir(opt.log_dir):
+            os.remove(os.path.join(opt.log_dir, log))
+    flat = FlatParams(model)
+    optimizer = FlatAdam(flat, lr=opt.lr)
+    criterion = Loss()
+    best_val_cost = np.inf
+    st_time = time.time()
+    history = {"train": [], "test": [], "shares": []}
+
+    def feed(ds, order, batch_size):
+        batches = ds.batches(order, batch_size)
+        return train_utils.Prefetcher(batches, range(len(batches)), dev, workers=opt.workers)
+
+    for epoch in range(1, opt.n_epochs):
+        model.train()
+        costs, train_time = [], 0
+        logger = setup_logger("epoch%d" % epoch, os.path.join(opt.log_dir, "epoch_%d_log.txt" % epoch))
+        logger.info("Train time {0}".format(_clock(st_time) + ", " + "Training started"))
+        if opt.cad_fresh:
+            dataset.set_epoch(epoch - 1)
+        pixels = torch.zeros(K, dtype=torch.int64, device=dev)
+        pf = feed(dataset, dataset.permutation(np.random.RandomState(opt.manualSeed + epoch)), opt.batch_size)
+        try:
+            for x, target, counts in pf:
+                semantic = model.forward_nhwc(x)
+                flat.zero_grad()
+                semantic_loss = criterion(semantic, target)
+                semantic_loss.backward()
+                optimizer.step()
+                pixels += counts
+                costs.append(semantic_loss.item())
+                logger.info("Train time {0} Batch {1} CEloss {2}".format(_clock(st_time), train_time, costs[-1]))
+                train_time += 1
+        finally:
+            pf.close()
+        torch.save(_plain_state_dict(model), os.path.join(opt.model_save_path, "model_current.pth"))
+        logger.info("Train Finish Avg CEloss: {0}".format(sum(costs) / max(train_time, 1)))
+        shares = (pixels.double() / pixels.sum().clamp(min=1)).tolist()        # the epoch's one read-back of the counts
+        logger.info("Class pixel shares: {0}".format(" ".join("%.4f" % s for s in shares)))
+        history["train"].append(costs)
+        history["shares"].append(shares)
+
+        model.eval()
+        costs = []
+        logger = setup_logger("epoch%d_test" % epoch, os.path.join(opt.log_dir, "epoch_%d_test_log.txt" % epoch))
+        logger.info("Test time {0}".format(_clock(st_time) + ", " + "Testing started"))
+        pf = feed(test_dataset, range(len(test_dataset)), 1)
+        try:
+            with torch.no_grad():
+                for x, target, _ in pf:
+                    a = model.forward_nhwc(x)
+                    semantic = a[..., :K].permute(0, 3, 1, 2)
+                    semantic._nhwc = a                                          # Loss reads the channels-last logits directly
+                    costs.append(criterion(semantic, target).item())
+                    logger.info("Test time {0} Batch {1} CEloss {2}".format(_clock(st_time), len(costs), costs[-1]))
+        finally:
+            pf.close()
+        test_all_cost = sum(costs) / max(len(costs), 1)
+        logger.info("Test Finish Avg CEloss: {0}".format(test_all_cost))
+        history["test"].append(costs)
+
+        if test_all_cost <= best_val_cost:
+            best_val_cost = test_all_cost
+            torch.save(_plain_state_dict(model), os.path.join(opt.model_save_path, "model_{}_{}.pth".format(epoch, test_all_cost)))
+            print("----------->BEST SAVED<-----------")
+    return history
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     opt.manualSeed = random.randint(1, 10000) if opt.seed is None else opt.seed
@@ -81,6 +201,8 @@ def main(argv=None):
         raise SystemExit("train_segnet.py needs a GPU (densefusion_amd has no CPU path)")
     os.makedirs(opt.model_save_path, exist_ok=True)
     os.makedirs(opt.log_dir, exist_ok=True)
+    if opt.dataset == "cad_render":
+        return train_cad(opt)
 
     cfg = opt.dataset_config_dir
     dataset = SegDataset(opt.dataset_root, os.path.join(cfg, "train_data_list.txt"), True, opt.train_length)
