@@ -142,6 +142,9 @@ SIGNATURES = {
     "df_segment_detect": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "df_seg_batch_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "df_seg_batch": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "df_seg_score_block_pixels": (_i, []),
+    "df_seg_score": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "df_seg_masks": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 

@@ -10,6 +10,7 @@
 #include <climits>
 
 #include "common.h"
+#include "seg_argmax.h"
 #include "seg_norm.h"
 
 namespace df {
@@ -45,7 +46,7 @@ __global__ __launch_bounds__(TB) void seg_input_kernel(const unsigned char *__re
 // Label pass.  Grid (parts, F); workgroup b of frame f covers pixels [b SEG_PPB, (b + 1) SEG_PPB) of the frame in tiles of TB
 // pixels.  A tile's logits (TB x ld floats, contiguous) come in with coalesced float4 loads, issued one tile ahead into registers,
 // and go through LDS (rows of s = (ld / 4) | 1 float4s: an odd stride, so a lane's row reads are free of bank conflicts); lane t then
-// takes the arg-max of pixel t over the first C channels: first maximum wins, NaN counts as maximal (torch.argmax).
+// takes the arg-max of pixel t over the first C channels (seg_argmax.h: first maximum wins, NaN counts as maximal, torch.argmax).
 // Statistics: per tile, each wave walks the classes present among its 64 pixels (ballots); lane c of the wave adds class c's share
 // to its running count / depth-valid count / box.  The waves meet in LDS at the end and lane c writes the workgroup's row for class c.
 // MAXN4: the float4s per pixel the registers hold (8: ld <= 32, 16: ld <= 64).
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(TB) void seg_label_stats_kernel(const float *__rest
   extern __shared__ f32x4 tile[];
   __shared__ int wave_acc[TB / 64][SEG_MAX_C][NF];
   const int f = blockIdx.y, b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int n4 = ld >> 2, s = n4 | 1, cq = (C + 3) >> 2;
+  const int n4 = ld >> 2, s = n4 | 1;
   const long fbase = (long)f * HW;
   const int p0 = b * SEG_PPB, p1 = p0 + SEG_PPB < HW ? p0 + SEG_PPB : HW;
   const f32x4 *src = reinterpret_cast<const f32x4 *>(logits) + fbase * n4;
@@ -94,20 +95,8 @@ __global__ __launch_bounds__(TB) void seg_label_stats_kernel(const float *__rest
     const int p = q0 + t;
     int lab = -1;
     if (t < np) {
-      const f32x4 *x = tile + t * s;
-      f32x4 v = x[0];
-      float best = v[0];
-      int bi = 0;
-      for (int j = 0; j < cq; ++j) {
-        if (j) v = x[j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * j + e;
-          if (c > 0 && c < C && (v[e] > best || (__builtin_isnan(v[e]) && !__builtin_isnan(best)))) { best = v[e]; bi = c; }
-        }
-      }
-      lab = bi;
-      label[fbase + p] = bi;
+      lab = seg_argmax(tile + t * s, C);
+      label[fbase + p] = lab;
     }
     const int row = p / W, col = p - row * W;
     unsigned long long rem = __ballot(lab >= 0);

@@ -26,6 +26,10 @@ pixel counts appended: [F][10] integers), then ``df_preprocess_objects_cad`` per
 live items.  Poses, plans, seeds and descriptors go up; nothing else crosses the bus.  ``__getitem__`` is served from a small,
 lock-protected cache of prepared chunks; ``permutation`` gives an epoch order that walks the chunks one after the other.  Cache,
 ready event, ``permutation`` and ``set_epoch`` are ``ChunkedViews``, which ``online_seg.RenderedSegDataset`` shares.
+
+With ``segnet=`` (scenes only) the masks are SegNet's instead of the renderer's, and SegNet is scored against the rendered labels on the
+way: between the jitter and ``df_cad_item_table`` the chunk runs ``df_seg_batch`` on the centred window, SegNet,
+``df_seg_score`` and ``df_seg_masks``; the read-back stays the one table.
 """
 from __future__ import annotations
 
@@ -38,6 +42,7 @@ import numpy as np
 import torch
 
 from ...lib import preprocess as pp
+from ...lib import segment_score as ss
 from .. import augment
 from . import render as cr
 from .dataset import LABEL_VALUE, MIN_CROP, _sentinel, sample_model_points
@@ -129,13 +134,19 @@ class RenderedPoseDataset(ChunkedViews):
     none / head / random, ``sensor`` a ``render.DepthSensor`` with ``sensor_seed``, ``points`` = --points); ``num``, ``add_noise``,
     ``noise_trans``, ``refine`` are the loader's; ``first_seed`` and ``frames`` name the views: the tool's --seed and the set's length.
     ``raster="points"`` seeds ``np.random`` with ``first_seed`` before a mesh is sampled into a cloud, as the tool does; ``pt[o]`` is
-    then drawn like ``ply_vtx`` draws it from the model file the tool would write."""
+    then drawn like ``ply_vtx`` draws it from the model file the tool would write.
+    ``segnet`` (scenes only): an eval-mode ``SegNet`` with ``label_nbr`` = models + 1 whose masks take the place of the renderer's.  Per
+    chunk, after render, sensor and jitter: ``df_seg_batch`` cuts the centred ``seg_window`` (default ``online_seg.default_window``) of
+    every frame with no background, no noise, no flip and ``seg_blur``; SegNet (``_seg_logits``); ``df_seg_score`` against the rendered
+    labels, summed in ``seg_score`` (a ``segment_score.SegScore``); ``df_seg_masks`` of the pairs (view, own model + 1).  From
+    ``df_cad_item_table`` on the path is the same.  ``kept`` stays the truth render's, so a run with either mask judges the same views;
+    ``live`` follows the mask in use.  With ``segnet=None`` nothing changes by a byte."""
 
     def __init__(self, models, num=500, add_noise=False, noise_trans=0.0, refine=False, *, distractors=(), scene=None, raster="points",
                  splat=1, cull=1, mask="box", light="none", shading="flat", light_angle=60.0, sensor=None, sensor_seed=0, proj_mat=None,
                  image_dims=(520, 1109), center=(0.0, 0.0, 4.0), scene_scale=1.0, model_scale=10.0, min_pixels=500, min_visible=0.3,
                  p_present=0.7, lateral=0.8, depth=0.8, max_holes=3, hole_mean=30.0, hole_std=10.0, chunk=32, points=0, first_seed=0,
-                 frames=2000, jitter="device", device="cuda", cache_chunks=4):
+                 frames=2000, jitter="device", device="cuda", cache_chunks=4, segnet=None, seg_window=None, seg_blur=1):
         models = [models] if _is_path(models) or (isinstance(models, tuple) and not _is_path(models[0]) and np.ndim(models[0]) == 2) else list(models)
         distractors = list(distractors)
         self.scene = bool(scene) if scene is not None else (len(models) > 1 or len(distractors) > 0)
@@ -196,13 +207,28 @@ class RenderedPoseDataset(ChunkedViews):
             self.pt[1] = sample_model_points(np.asarray(pts, dtype=np.float32).astype(np.float64), np.zeros((0, 3), dtype=np.int64))
         self._pt_dev = {o: torch.from_numpy(np.ascontiguousarray(p, dtype=np.float64)).to(self.device) for o, p in self.pt.items()}
         self.num_pt_mesh_large = self.num_pt_mesh_small = 500
+        self.segnet, self.mask_source = segnet, "truth" if segnet is None else "segnet"
+        if segnet is not None:
+            from .online_seg import check_window
+            if not self.scene:
+                raise ValueError("segnet masks need a scene: the label plane is the scene renderer's")
+            if segnet.training or segnet.label_nbr != self.n_models + 1:
+                raise ValueError(f"segnet must be in eval mode with label_nbr = {self.n_models + 1} (models + background), got "
+                                 f"{segnet.label_nbr}{' in training mode' if segnet.training else ''}")
+            if int(seg_blur) not in (0, 1):
+                raise ValueError("seg_blur is 0 / 1")
+            self.seg_window, self.seg_blur = check_window(seg_window, self.image_dims), int(seg_blur)
+            # the centred window, for every view; online_seg's class map: model k is class k + 1, distractors are background
+            self.seg_corner = ((self.image_dims[0] - self.seg_window[0]) // 2, (self.image_dims[1] - self.seg_window[1]) // 2)
+            self.seg_class_map = np.array([0] + list(range(1, self.n_models + 1)) + [0] * len(distractors), dtype=np.int32)
+            self.seg_score, self._scored = ss.SegScore(self.n_models + 1, self.device), set()
 
     @classmethod
     def from_options(cls, opt, models, distractors=(), *, first_seed=0, frames=2000, num=500, add_noise=False, noise_trans=0.0, refine=False,
-                     device="cuda"):
+                     device="cuda", scene=None, segnet=None, seg_window=None, seg_blur=1):
         """The dataset of parsed ``render.add_view_arguments`` options: the views tools/render_cad_dataset.py renders with the same
         flags, ``--model`` = ``models``, ``--distractor`` = ``distractors`` and ``--seed`` = ``first_seed`` (several models or a
-        distractor: ``--scene``).  ``ValueError`` for flags the tool refuses."""
+        distractor: ``--scene``, which ``scene=True`` also asks of one model alone).  ``ValueError`` for flags the tool refuses."""
         proj = read_proj_mat(opt.proj_mat) if opt.proj_mat else np.array(cr.DEFAULT_PROJ)
         sensor = cr.sensor_from_flags(proj, opt.sensor_sigma, opt.sensor_sigma_z, opt.sensor_z, opt.sensor_edge, opt.sensor_edge_step,
                                       opt.sensor_edge_drop, opt.sensor_drop, opt.sensor_quant)
@@ -211,7 +237,8 @@ class RenderedPoseDataset(ChunkedViews):
                    sensor_seed=opt.sensor_seed, proj_mat=proj, image_dims=(opt.height, opt.width), center=opt.center,
                    scene_scale=opt.scene_scale, model_scale=opt.model_scale, min_pixels=opt.min_pixels, min_visible=opt.min_visible,
                    p_present=opt.p_present, lateral=opt.lateral, depth=opt.depth, max_holes=opt.max_holes, hole_mean=opt.hole_mean,
-                   hole_std=opt.hole_std, chunk=opt.chunk, points=opt.points, first_seed=first_seed, frames=frames, device=device)
+                   hole_std=opt.hole_std, chunk=opt.chunk, points=opt.points, first_seed=first_seed, frames=frames, device=device,
+                   scene=scene, segnet=segnet, seg_window=seg_window, seg_blur=seg_blur)
 
     def get_sym_list(self):
         return []
@@ -225,6 +252,30 @@ class RenderedPoseDataset(ChunkedViews):
         add_t = np.array([rng.uniform(-self.noise_trans, self.noise_trans) for _ in range(3)])
         plan = augment.plan_row(self.trancolor.draw(rng=rng)) if self.add_noise else None
         return add_t, plan, rng.getrandbits(32), rng.getrandbits(32)
+
+    # -- SegNet's masks in place of the renderer's ------------------------------------------------------------------------------------
+    def _seg_logits(self, x, target):
+        """Channels-last logits [F,H,W,ld] of the window batch x [F,H,W,4]; ``target`` is the rendered truth, which SegNet does not
+        see (the seam a test overrides to put known logits in)."""
+        with torch.no_grad():
+            return self.segnet.forward_nhwc(x)
+
+    def _segnet_masks(self, rgb, label, own, seeds):
+        """The masks of the pairs (view, own model + 1) from SegNet's label map of the centred window of each frame, and the frames'
+        confusion matrices [F,C,C] against the rendered labels: ``df_seg_batch`` (no background, no noise, no flip), SegNet,
+        ``df_seg_score``, ``df_seg_masks``.  Nothing is read back.  A view enters ``seg_score`` once, however often the cache prepares its
+        chunk again (its matrix is a function of its seed)."""
+        F, (y0, x0) = rgb.shape[0], self.seg_corner
+        desc = np.array([[j, y0, x0, 0, -1, 0, 0, 0] for j in range(F)], dtype=np.int64)
+        x, target, counts = pp.seg_batch(rgb, label, self.seg_class_map, self.n_models + 1, desc, self.seg_window, blur=self.seg_blur)
+        conf, skipped, seg_label = ss.seg_score(self._seg_logits(x, target), target, self.n_models + 1)
+        fresh = [j for j in range(F) if seeds[j] not in self._scored]
+        if fresh:
+            rows = slice(None) if len(fresh) == F else torch.tensor(fresh, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+            self.seg_score.add(conf[rows], skipped[rows])
+            self._scored.update(seeds[j] for j in fresh)
+        mask = ss.seg_masks(seg_label, [[y0, x0]] * F, [[j, own[j] + 1] for j in range(F)], self.image_dims)
+        return mask, conf, counts
 
     # -- one chunk of consecutive views -------------------------------------------------------------------------------------------------
     def _prepare(self, epoch, a, b):
@@ -254,7 +305,8 @@ class RenderedPoseDataset(ChunkedViews):
                 pairs = torch.from_numpy(np.stack([np.arange(F), own], axis=1).astype(np.int32)).pin_memory().to(dev, non_blocking=True)
                 f_idx, o_idx = pairs[:, 0].long(), pairs[:, 1].long()
                 counts = torch.stack([stats[f_idx, o_idx, 0], solo[f_idx, o_idx, 0]], dim=1)
-                mask = self.renderer.masks(label, stats, pairs, mask=self.mask)
+                if self.segnet is None:
+                    mask = self.renderer.masks(label, stats, pairs, mask=self.mask)
             else:
                 if self.raster == "mesh":
                     rgb, depth, mask, stats = self.renderer.render(poses, holes=holes, cull=self.cull, mask=self.mask, light=light)
@@ -265,6 +317,9 @@ class RenderedPoseDataset(ChunkedViews):
                 depth, _ = cr.apply_sensor(depth, self.sensor, self.sensor_seed, seeds[0])
             if self.add_noise:
                 rgb = pp.color_jitter(rgb, np.stack([d[1] for d in draws]), out=rgb)
+            seg_conf = seg_counts = None
+            if self.segnet is not None:                          # SegNet sees the frame the pose path sees; kept stays the truth render's
+                mask, seg_conf, seg_counts = self._segnet_masks(rgb, label, own, seeds)
             table = pp.cad_item_table(depth, mask, LABEL_VALUE, MIN_CROP)
             rows = torch.cat([table, counts], dim=1).tolist()    # the chunk's one read-back: [F][10]
             info, live = [], []
@@ -274,7 +329,8 @@ class RenderedPoseDataset(ChunkedViews):
                     (bool(cr.view_kept(won, self.min_pixels)), 1.0)
                 info.append(dict(seed=seeds[j], object=self.objlist[own[j]], record=texts[j], pose=own_pose[j], table=row[:8], pixels=won,
                                  visible=float(frac), kept=bool(kept), live=bool(kept and row[7]), add_t=draws[j][0], plan=draws[j][1],
-                                 choose_seed=draws[j][2], subset_seed=draws[j][3]))
+                                 choose_seed=draws[j][2], subset_seed=draws[j][3], mask_source=self.mask_source,
+                                 conf=None if seg_conf is None else seg_conf[j], seg_counts=None if seg_counts is None else seg_counts[j]))
                 if info[-1]["live"]:
                     live.append(j)
             items = [_sentinel() for _ in range(F)]
@@ -319,6 +375,8 @@ class RenderedPoseDataset(ChunkedViews):
     def view_info(self, index):
         """What is known on the host about item ``index``: its view seed, object, ``transforms.txt`` record and pose [R|t], the row of
         ``df_cad_item_table``, the pixels it won and its visible fraction, ``kept`` (the tool's skip rules), ``live`` (kept and served),
-        and its own draws (``add_t``, the jitter plan row, the ``choose`` and subset seeds)."""
+        its own draws (``add_t``, the jitter plan row, the ``choose`` and subset seeds), ``mask_source`` (truth / segnet: whose mask
+        ``table`` and ``live`` follow; ``kept`` is always the truth render's) and, with a SegNet, ``conf`` and ``seg_counts``: the
+        view's confusion matrix [C,C] against the rendered labels and its window's class pixel counts [C], DEVICE tensors."""
         slot, j = self._chunk_of(index)
         return slot.info[j]

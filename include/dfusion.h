@@ -615,6 +615,41 @@ int df_seg_batch(const unsigned char *rgb, const unsigned short *label, int F, i
                  int64_t *target_out, int *counts_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scoring SegNet against rendered truth, and SegNet's label map as the masks of the customCAD pose path (densefusion_amd/lib/
+ * segment_score.py).  No allocation, no synchronisation, the caller's stream; integer atomics only, so the outputs are bit-reproducible
+ * and a frame's rows do not depend on the other frames of the call.
+ *
+ * df_seg_score_block_pixels: the pixels of a frame one workgroup of df_seg_score covers (host only; the tests put a frame on each side
+ *   of it).
+ * df_seg_score:
+ *   DEVICE: logits [F][H][W][ld] fp32 channels-last (16-byte aligned), the first C channels the classes, as df_segment_detect reads
+ *   them; target [F][H][W] int64, what df_seg_batch writes; label_out [F][H][W] int32 or NULL; conf [F][C][C] int32, indexed
+ *   conf[f][truth][predicted]; skipped [F] int32.  The call sets conf and skipped to zero on the stream.
+ *   DF_ERR_ARG, before anything is launched or written: a null logits, target, conf or skipped; F outside 1..65535; H or W below 1;
+ *   H*W > 2^30; C outside 2..64; ld below C, above 64 or no multiple of 4; a misaligned pointer.
+ *   Per frame f and pixel p:
+ *   S1. pred = the arg-max of logits[f][p][0..C-1]: the first maximum wins and NaN counts as maximal (the rule of
+ *       df_segment_detect, one text for both).  Channels C..ld-1 are never read as classes.  label_out[f][p] = pred, if given.
+ *   S2. t = target[f][p], compared as 64 bits.  0 <= t < C: conf[f][t][pred] += 1.
+ *   S3. Otherwise skipped[f] += 1 and no cell changes; label_out is written all the same.
+ *   So conf[f] sums to H*W - skipped[f], its rows sum to the truth's class counts and its columns to the prediction's.
+ * df_seg_masks:
+ *   DEVICE: label [F][H][W] int32, F label maps in window coordinates (label_out above); mask_out [N][IH][IW] u16.
+ *   HOST, read during the call, launch arguments: win [F][2] int32 = {y0, x0}, the corner of frame f's window in its IH x IW frame;
+ *   pairs [N][2] int32 = {frame, class}.  A pair may repeat.
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer; F outside 1..65535; N below 1; IH outside 1..65535; IW below 1;
+ *   IH*IW > 2^30; H outside 1..IH or W outside 1..IW; a window that leaves the frame (y0 outside 0..IH-H or x0 outside 0..IW-W); a
+ *   pair's frame outside 0..F-1 or its class outside 0..64; a misaligned pointer.
+ *   M1. mask_out[n][y][x] = 65535 where (y, x) lies inside the window of the pair's frame and label[frame][y-y0][x-x0] == class, and 0
+ *       everywhere else.  EVERY element is written: the caller clears nothing.  The result is what df_cad_item_table and
+ *       df_preprocess_objects_cad read as `label` with label_value 65535. */
+int df_seg_score_block_pixels(void);
+int df_seg_score(const float *logits, const int64_t *target, int F, int H, int W, int ld, int C, int *label_out, int *conf, int *skipped,
+                 df_stream_t stream);
+int df_seg_masks(const int *label, int F, int H, int W, const int *win, const int *pairs, int N, int IH, int IW, unsigned short *mask_out,
+                 df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]

@@ -1,0 +1,141 @@
+#!/usr/bin/env python
+"""Evaluate a SegNet and a pose network pair on customCAD scenes rendered on the fly, with no tree on disk.
+
+    python tools/eval_cad_render.py --cad_model a.ply b.ply --cad_distractor box.ply --segnet segnet.pth \\
+        --model pose_model.pth --refine_model pose_refine_model.pth --cad_frames 500 --light random
+
+The views are those of ``RenderedPoseDataset`` (datasets/customCAD/online.py) for ``--cad_seed`` and ``--cad_frames`` and the view
+options of tools/render_cad_dataset.py.  ``--masks truth`` scores the poses from the renderer's own masks, as tools/eval_cad.py does on a
+tree; ``--masks segnet`` from the masks SegNet predicts for the same frames (``df_seg_score`` and ``df_seg_masks``);
+``--masks both`` (the default) runs the two on the same view seeds.  The loop is ``evaluate()`` of tools/eval_linemod.py with the
+thresholds of tools/eval_cad.py: ``--threshold_frac`` x the diameter of each model's cloud.
+
+Per mask source the log ``eval_result_logs_<source>.txt`` holds the reference-format lines, then per object and overall the ADD success
+over the SERVED views (a view whose mask gives an item), the same over the KEPT views (the views the renderer's skip rules keep, the same
+set for both sources: a kept view whose mask yields no item counts as a miss) and the numbers of kept and served views.  For ``segnet``
+it also holds per-class IoU, precision and recall, mean IoU and pixel accuracy against the rendered labels.  ``main`` returns all of it
+as a dict.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from densefusion_amd.datasets.customCAD import render as cad_render  # noqa: E402
+from densefusion_amd.lib.network import PoseNet, PoseRefineNet  # noqa: E402
+from eval_cad import NUM_OBJECTS, NUM_POINTS, cloud_diameter  # noqa: E402
+from eval_linemod import evaluate  # noqa: E402
+
+
+def build_parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cad_model", type=str, nargs="+", required=True, help="PLY mesh(es): model k is object k + 1 and SegNet's class k + 1")
+    ap.add_argument("--cad_distractor", type=str, nargs="*", default=[], help="meshes that are drawn and can occlude; background for SegNet")
+    ap.add_argument("--segnet", type=str, default="", help="SegNet checkpoint (tools/train_segnet.py --dataset cad_render); needed unless --masks truth")
+    ap.add_argument("--model", type=str, default="trained_models/cad/pose_model_current.pth", help="PoseNet checkpoint")
+    ap.add_argument("--refine_model", type=str, default="trained_models/cad/pose_refine_model_current.pth", help="PoseRefineNet checkpoint")
+    ap.add_argument("--masks", type=str, default="both", choices=("truth", "segnet", "both"), help="whose masks the pose path reads")
+    ap.add_argument("--cad_seed", type=int, default=0, help="seed of the first view")
+    ap.add_argument("--cad_frames", type=int, default=200, help="views")
+    ap.add_argument("--seg_height", type=int, default=None, help="SegNet's window height, a multiple of 32 (default: the largest inside the frame)")
+    ap.add_argument("--seg_width", type=int, default=None, help="SegNet's window width, a multiple of 32 (default: the largest inside the frame)")
+    ap.add_argument("--seg_blur", type=int, default=1, choices=(0, 1), help="1: the 3 x 3 binomial blur SegNet was trained behind")
+    ap.add_argument("--output_result_dir", type=str, default="experiments/eval_result/cad_render")
+    ap.add_argument("--iteration", type=int, default=4)
+    ap.add_argument("--threshold_frac", type=float, default=0.1, help="a view passes when its ADD is below this fraction of the model cloud's diameter")
+    ap.add_argument("--max_frames", type=int, default=0)
+    ap.add_argument("--window", type=int, default=64, help="views per device call of the pose networks")
+    ap.add_argument("--workers", type=int, default=2, help="threads that prepare chunks ahead of the device calls (0 = in the loop)")
+    ap.add_argument("--feed", type=str, default="threads", choices=["threads"])
+    cad_render.add_view_arguments(ap.add_argument_group("views", "the views and the renderer, under the names of tools/render_cad_dataset.py"))
+    return ap
+
+
+def load_segnet(path, n_classes):
+    from densefusion_amd.vanilla_segmentation.segnet import SegNet
+    net = SegNet(label_nbr=n_classes).cuda()
+    if path:
+        net.load_state_dict(torch.load(path, map_location="cuda", weights_only=True))
+    return net.eval()
+
+
+def _rate(a, b):
+    return float(a) / b if b else 0.0
+
+
+def run_source(source, dataset, estimator, refiner, diameter, opt):
+    """``evaluate()`` over ``dataset`` and the tallies of one mask source."""
+    objlist = list(dataset.objlist)
+    n = len(dataset) if opt.max_frames <= 0 else min(opt.max_frames, len(dataset))
+    with open(os.path.join(opt.output_result_dir, "eval_result_logs_%s.txt" % source), "w") as fw:
+        def say(m):
+            print(m)
+            fw.write(m + "\n")
+        success, served = evaluate(dataset, estimator, refiner, diameter, opt, fw)
+        success, served = success[:len(objlist)], served[:len(objlist)]
+        kept = [0] * len(objlist)
+        for i in range(n):                                          # host records of chunks the loop has prepared (or prepares again)
+            info = dataset.view_info(i)
+            kept[objlist.index(info["object"])] += bool(info["kept"])
+        out = dict(source=source, views=n, success=success, served=served, kept=kept,
+                   success_served=[_rate(s, m) for s, m in zip(success, served)], success_kept=[_rate(s, k) for s, k in zip(success, kept)],
+                   all_served=_rate(sum(success), sum(served)), all_kept=_rate(sum(success), sum(kept)))
+        say("[{0} masks] views {1}, kept {2}, served {3}".format(source, n, sum(kept), sum(served)))
+        for k, obj in enumerate(objlist):
+            say("[{0} masks] Object {1} success rate: {2} of {3} served views, {4} of {5} kept views".format(
+                source, obj, out["success_served"][k], served[k], out["success_kept"][k], kept[k]))
+        say("[{0} masks] ALL success rate: {1} of served views, {2} of kept views".format(source, out["all_served"], out["all_kept"]))
+        if source == "segnet":
+            m = dataset.seg_score.summary()
+            out["seg"] = m
+            names = ["background"] + ["object %d" % o for o in objlist]
+            for c, name in enumerate(names):
+                say("[segnet masks] {0}: IoU {1:.4f} precision {2:.4f} recall {3:.4f}".format(name, m["iou"][c], m["precision"][c], m["recall"][c]))
+            say("[segnet masks] mIoU {0:.4f} pixel accuracy {1:.4f} over {2} pixels".format(m["miou"], m["pixel_accuracy"], m["pixels"]))
+    return out
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
+    if len(opt.cad_model) > NUM_OBJECTS:
+        raise SystemExit("at most %d models: the pose networks of tools/eval_cad.py have that many objects" % NUM_OBJECTS)
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_cad_render.py needs a GPU (densefusion_amd has no CPU path)")
+    from densefusion_amd.datasets.customCAD.online import RenderedPoseDataset
+    estimator = PoseNet(num_points=NUM_POINTS, num_obj=NUM_OBJECTS).cuda()
+    refiner = PoseRefineNet(num_points=NUM_POINTS, num_obj=NUM_OBJECTS).cuda()
+    estimator.load_state_dict(torch.load(opt.model, map_location="cuda", weights_only=True))
+    refiner.load_state_dict(torch.load(opt.refine_model, map_location="cuda", weights_only=True))
+    estimator.eval(); refiner.eval()
+    sources = ("truth", "segnet") if opt.masks == "both" else (opt.masks,)
+    segnet = load_segnet(opt.segnet, len(opt.cad_model) + 1) if "segnet" in sources else None
+    if segnet is not None and not opt.segnet:
+        print("no --segnet checkpoint: SegNet runs on its initial weights")
+    window = None if opt.seg_height is None and opt.seg_width is None else \
+        (opt.seg_height or opt.height // 32 * 32, opt.seg_width or opt.width // 32 * 32)
+    os.makedirs(opt.output_result_dir, exist_ok=True)
+    result = {}
+    for source in sources:
+        np.random.seed(opt.cad_seed)                                # the model points of ``pt`` are drawn with np.random: the same for both
+        kw = dict(segnet=segnet, seg_window=window, seg_blur=opt.seg_blur) if source == "segnet" else {}
+        try:
+            # SegNet's masks need the scene renderer's label plane; the truth run of the same call renders the same scenes
+            dataset = RenderedPoseDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=opt.cad_seed, frames=opt.cad_frames,
+                                                       num=NUM_POINTS, scene=True if segnet is not None else None, **kw)
+        except ValueError as e:
+            raise SystemExit(f"eval_cad_render.py: {e}")
+        # the loader's clouds are in units of 10000 (model * 10 / 10000): so is the threshold (tools/eval_cad.py)
+        diameter = [opt.threshold_frac * cloud_diameter(dataset.pt[obj] * 10 / 10000.) for obj in dataset.objlist]
+        diameter += [0.0] * (NUM_OBJECTS - len(diameter))
+        result[source] = run_source(source, dataset, estimator, refiner, diameter, opt)
+    return result
+
+
+if __name__ == "__main__":
+    main()

@@ -14,6 +14,7 @@ tools/train.py does.
 renderer under the names of tools/train.py and tools/render_cad_dataset.py.  Batches come channels-last from ``dataset.batch`` over
 ``dataset.permutation``, fed by ``--workers`` threads, into ``SegNet.forward_nhwc``; the test views follow the training seed range;
 ``model_current.pth`` is also written after every training pass, and the log ends an epoch with the share of pixels per class.
+``--seg_score`` scores the test pass on the device (``df_seg_score`` on the logits the loss reads) and logs ``Test Finish mIoU``.
 
     python tools/train_segnet.py --dataset cad_render --cad_model a.ply b.ply --backgrounds photos/ --light random
 """
@@ -70,6 +71,7 @@ def build_parser():
     cad.add_argument("--backgrounds", type=str, default=None, help="directory of images that stand behind the objects (default: the grey horizon)")
     cad.add_argument("--seg_blur", type=int, default=1, choices=(0, 1), help="1: the 3 x 3 binomial blur over the composited window")
     cad.add_argument("--seg_noise", type=float, default=5.0, help="sigma of the pixel noise in grey levels (0: none)")
+    cad.add_argument("--seg_score", action="store_true", help="score the test pass on the device: log mIoU and per-class IoU (df_seg_score)")
     cad_render.add_view_arguments(cad)
     return ap
 
@@ -115,7 +117,7 @@ def cad_datasets(opt):
 
 def train_cad(opt):
     """The loop of ``main`` over rendered scenes; returns {"train": per epoch the batch losses, "test": the same, "shares": per epoch
-    the class pixel shares of the training pass}."""
+    the class pixel shares of the training pass}; with --seg_score also "miou": per epoch the test pass's mean IoU."""
     dataset, test_dataset = cad_datasets(opt)
     print(len(dataset), len(test_dataset))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -131,6 +133,10 @@ def train_cad(opt):
     best_val_cost = np.inf
     st_time = time.time()
     history = {"train": [], "test": [], "shares": []}
+    score = None
+    if opt.seg_score:
+        from densefusion_amd.lib.segment_score import SegScore
+        score, history["miou"] = SegScore(K, dev), []
 
     def feed(ds, order, batch_size):
         batches = ds.batches(order, batch_size)
@@ -170,6 +176,8 @@ def train_cad(opt):
         logger = setup_logger("epoch%d_test" % epoch, os.path.join(opt.log_dir, "epoch_%d_test_log.txt" % epoch))
         logger.info("Test time {0}".format(_clock(st_time) + ", " + "Testing started"))
         pf = feed(test_dataset, range(len(test_dataset)), 1)
+        if score is not None:
+            score.reset()
         try:
             with torch.no_grad():
                 for x, target, _ in pf:
@@ -177,12 +185,18 @@ def train_cad(opt):
                     semantic = a[..., :K].permute(0, 3, 1, 2)
                     semantic._nhwc = a                                          # Loss reads the channels-last logits directly
                     costs.append(criterion(semantic, target).item())
+                    if score is not None:
+                        score.update(a, target)                                 # on the logits the loss just read; nothing comes back
                     logger.info("Test time {0} Batch {1} CEloss {2}".format(_clock(st_time), len(costs), costs[-1]))
         finally:
             pf.close()
         test_all_cost = sum(costs) / max(len(costs), 1)
         logger.info("Test Finish Avg CEloss: {0}".format(test_all_cost))
         history["test"].append(costs)
+        if score is not None:
+            m = score.summary()                                                 # the test pass's one read-back of the matrix
+            logger.info("Test Finish mIoU: {0:.4f} IoU: {1}".format(m["miou"], " ".join("%.4f" % v for v in m["iou"])))
+            history["miou"].append(m["miou"])
 
         if test_all_cost <= best_val_cost:
             best_val_cost = test_all_cost
