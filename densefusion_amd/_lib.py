@@ -145,6 +145,10 @@ SIGNATURES = {
     "df_seg_score_block_pixels": (_i, []),
     "df_seg_score": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "df_seg_masks": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "df_mesh_closest_tile_triangles": (_i, []),
+    "df_mesh_closest_scratch_bytes": (_sz, [_i]),
+    "df_mesh_closest": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "df_fp64_rate_probe": (_i, [_i, _i, _vp, _vp]),
 }
 
 

@@ -47,6 +47,7 @@ from .. import augment
 from . import render as cr
 from .dataset import LABEL_VALUE, MIN_CROP, _sentinel, sample_model_points
 from .project_unity_depth import UnityDepthProjector, read_proj_mat
+from .symmetry import parse_sym_option
 
 
 def _is_path(m):
@@ -140,13 +141,18 @@ class RenderedPoseDataset(ChunkedViews):
     every frame with no background, no noise, no flip and ``seg_blur``; SegNet (``_seg_logits``); ``df_seg_score`` against the rendered
     labels, summed in ``seg_score`` (a ``segment_score.SegScore``); ``df_seg_masks`` of the pairs (view, own model + 1).  From
     ``df_cad_item_table`` on the path is the same.  ``kept`` stays the truth render's, so a run with either mask judges the same views;
-    ``live`` follows the mask in use.  With ``segnet=None`` nothing changes by a byte."""
+    ``live`` follows the mask in use.  With ``segnet=None`` nothing changes by a byte.
+    ``symmetry``: "none" (``get_sym_list() == []``), "auto" (meshes only: ``symmetry.detect_symmetry`` per model at construction with
+    ``tol`` = ``symmetry_tol``, the reports kept in ``self.symmetry`` by model index) or a list of model indices.  The list holds the
+    values an item's index takes (model k = index k = object k + 1), which is what the losses, the native trainer and ``evaluate()``
+    compare.  No item changes by a byte: the detection draws from a generator of its own."""
 
     def __init__(self, models, num=500, add_noise=False, noise_trans=0.0, refine=False, *, distractors=(), scene=None, raster="points",
                  splat=1, cull=1, mask="box", light="none", shading="flat", light_angle=60.0, sensor=None, sensor_seed=0, proj_mat=None,
                  image_dims=(520, 1109), center=(0.0, 0.0, 4.0), scene_scale=1.0, model_scale=10.0, min_pixels=500, min_visible=0.3,
                  p_present=0.7, lateral=0.8, depth=0.8, max_holes=3, hole_mean=30.0, hole_std=10.0, chunk=32, points=0, first_seed=0,
-                 frames=2000, jitter="device", device="cuda", cache_chunks=4, segnet=None, seg_window=None, seg_blur=1):
+                 frames=2000, jitter="device", device="cuda", cache_chunks=4, segnet=None, seg_window=None, seg_blur=1, symmetry="none",
+                 symmetry_tol=0.01):
         models = [models] if _is_path(models) or (isinstance(models, tuple) and not _is_path(models[0]) and np.ndim(models[0]) == 2) else list(models)
         distractors = list(distractors)
         self.scene = bool(scene) if scene is not None else (len(models) > 1 or len(distractors) > 0)
@@ -207,6 +213,24 @@ class RenderedPoseDataset(ChunkedViews):
             self.pt[1] = sample_model_points(np.asarray(pts, dtype=np.float32).astype(np.float64), np.zeros((0, 3), dtype=np.int64))
         self._pt_dev = {o: torch.from_numpy(np.ascontiguousarray(p, dtype=np.float64)).to(self.device) for o, p in self.pt.items()}
         self.num_pt_mesh_large = self.num_pt_mesh_small = 500
+        # which models take ADD-S: the values an item's index takes (model k = index k), as Loss, the trainer and evaluate() compare them
+        self.symmetry, self._sym_list = {}, []
+        if isinstance(symmetry, str):
+            if symmetry not in ("none", "auto"):
+                raise ValueError('symmetry is "none", "auto" or a list of model indices')
+            if symmetry == "auto":
+                if not self.scene and raster != "mesh":
+                    raise ValueError('symmetry "auto" needs triangles: a scene or raster mesh (a point cloud has none)')
+                from .symmetry import detect_symmetry
+                found = meshes[:self.n_models] if self.scene else [(pts, tris, col)]
+                with torch.cuda.device(self.device):
+                    for k, (mv, mt, mc) in enumerate(found):
+                        self.symmetry[k] = detect_symmetry(mv, mt, mc, tol=float(symmetry_tol))
+                self._sym_list = [k for k in sorted(self.symmetry) if self.symmetry[k].symmetric]
+        else:
+            self._sym_list = sorted({int(k) for k in symmetry})
+            if any(not 0 <= k < self.n_models for k in self._sym_list):
+                raise ValueError(f"symmetry: model indices lie in 0..{self.n_models - 1}, got {self._sym_list}")
         self.segnet, self.mask_source = segnet, "truth" if segnet is None else "segnet"
         if segnet is not None:
             from .online_seg import check_window
@@ -225,7 +249,7 @@ class RenderedPoseDataset(ChunkedViews):
 
     @classmethod
     def from_options(cls, opt, models, distractors=(), *, first_seed=0, frames=2000, num=500, add_noise=False, noise_trans=0.0, refine=False,
-                     device="cuda", scene=None, segnet=None, seg_window=None, seg_blur=1):
+                     device="cuda", scene=None, segnet=None, seg_window=None, seg_blur=1, symmetry=None):
         """The dataset of parsed ``render.add_view_arguments`` options: the views tools/render_cad_dataset.py renders with the same
         flags, ``--model`` = ``models``, ``--distractor`` = ``distractors`` and ``--seed`` = ``first_seed`` (several models or a
         distractor: ``--scene``, which ``scene=True`` also asks of one model alone).  ``ValueError`` for flags the tool refuses."""
@@ -238,10 +262,13 @@ class RenderedPoseDataset(ChunkedViews):
                    scene_scale=opt.scene_scale, model_scale=opt.model_scale, min_pixels=opt.min_pixels, min_visible=opt.min_visible,
                    p_present=opt.p_present, lateral=opt.lateral, depth=opt.depth, max_holes=opt.max_holes, hole_mean=opt.hole_mean,
                    hole_std=opt.hole_std, chunk=opt.chunk, points=opt.points, first_seed=first_seed, frames=frames, device=device,
-                   scene=scene, segnet=segnet, seg_window=seg_window, seg_blur=seg_blur)
+                   scene=scene, segnet=segnet, seg_window=seg_window, seg_blur=seg_blur,
+                   symmetry=symmetry if symmetry is not None else parse_sym_option(getattr(opt, "cad_sym", "none")),
+                   symmetry_tol=getattr(opt, "cad_sym_tol", 0.01))
 
     def get_sym_list(self):
-        return []
+        """The item indices (model k = index k) that are trained and scored with ADD-S: [] unless ``symmetry`` asked for some."""
+        return list(self._sym_list)
 
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small

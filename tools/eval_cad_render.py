@@ -9,6 +9,8 @@ options of tools/render_cad_dataset.py.  ``--masks truth`` scores the poses from
 tree; ``--masks segnet`` from the masks SegNet predicts for the same frames (``df_seg_score`` and ``df_seg_masks``, DESIGN.md 12h);
 ``--masks both`` (the default) runs the two on the same view seeds.  The loop is ``evaluate()`` of tools/eval_linemod.py with the
 thresholds of tools/eval_cad.py: ``--threshold_frac`` x the diameter of each model's cloud.
+``--cad_sym auto`` (default ``none``; or model indices) scores the models ``datasets/customCAD/symmetry.py`` finds symmetric with ADD-S
+through the dataset's ``get_sym_list()``; the line ``symmetry object list: ...`` shows which.
 
 Per mask source the log ``eval_result_logs_<source>.txt`` holds the reference-format lines, then per object and overall the ADD success
 over the SERVED views (a view whose mask gives an item), the same over the KEPT views (the views the renderer's skip rules keep, the same
@@ -28,6 +30,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from densefusion_amd.datasets.customCAD import render as cad_render  # noqa: E402
+from densefusion_amd.datasets.customCAD import symmetry as cad_symmetry  # noqa: E402
 from densefusion_amd.lib.network import PoseNet, PoseRefineNet  # noqa: E402
 from eval_cad import NUM_OBJECTS, NUM_POINTS, cloud_diameter  # noqa: E402
 from eval_linemod import evaluate  # noqa: E402
@@ -53,7 +56,9 @@ def build_parser():
     ap.add_argument("--window", type=int, default=64, help="views per device call of the pose networks")
     ap.add_argument("--workers", type=int, default=2, help="threads that prepare chunks ahead of the device calls (0 = in the loop)")
     ap.add_argument("--feed", type=str, default="threads", choices=["threads"])
-    cad_render.add_view_arguments(ap.add_argument_group("views", "the views and the renderer, under the names of tools/render_cad_dataset.py"))
+    views = ap.add_argument_group("views", "the views and the renderer, under the names of tools/render_cad_dataset.py")
+    cad_render.add_view_arguments(views)
+    cad_symmetry.add_sym_arguments(views)
     return ap
 
 
@@ -133,7 +138,9 @@ def main(argv=None):
         # the loader's clouds are in units of 10000 (model * 10 / 10000): so is the threshold (tools/eval_cad.py)
         diameter = [opt.threshold_frac * cloud_diameter(dataset.pt[obj] * 10 / 10000.) for obj in dataset.objlist]
         diameter += [0.0] * (NUM_OBJECTS - len(diameter))
+        print("symmetry object list: %s" % dataset.get_sym_list())
         result[source] = run_source(source, dataset, estimator, refiner, diameter, opt)
+        result[source]["sym_list"] = dataset.get_sym_list()
     return result
 
 

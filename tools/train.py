@@ -33,6 +33,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from densefusion_amd import synth, train_ops, train_utils  # noqa: E402
 from densefusion_amd.datasets.customCAD import render as cad_render  # noqa: E402
+from densefusion_amd.datasets.customCAD import symmetry as cad_symmetry  # noqa: E402
 from densefusion_amd.lib.loss import Loss  # noqa: E402
 from densefusion_amd.lib.loss_refiner import Loss_refine  # noqa: E402
 from densefusion_amd.lib.network import PoseNet, PoseRefineNet  # noqa: E402
@@ -136,6 +137,7 @@ def build_parser():
     cad.add_argument("--cad_seed", type=int, default=0, help="seed of the first training view")
     cad.add_argument("--cad_fresh", action="store_true", help="fresh views every epoch (the seed range moves on by --cad_frames); default: a fixed set, like a tree")
     cad_render.add_view_arguments(cad)
+    cad_symmetry.add_sym_arguments(cad)
     return ap
 
 
