@@ -137,6 +137,8 @@ SIGNATURES = {
     "df_net_profile_read": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(_i)]),
     "df_net_profile_read_split": (_i, [_vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(_i)]),
     "df_gemm_route": (_i, [_i, _i, _i]),
+    "df_split_walk": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i), _i]),
+    "df_gemm_rows": (_i, [_vp] * 6 + [_i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "df_segment_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "df_segment_input": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "df_segment_detect": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

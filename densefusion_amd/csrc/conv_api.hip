@@ -11,6 +11,34 @@ using namespace df;
 // routing of a plain-GEMM layer of the inference engine (csrc/split_gemm.hip split_route)
 extern "C" int df_gemm_route(int n, int k, int epilogue) { return split_route(n, k, epilogue); }
 
+// the launch plan of the 256 x 256 form's tile walk (csrc/split_gemm.hip split_walk): host only
+extern "C" int df_split_walk(int tiles_m, int tiles_n, int zcount, int workgroups, int *grid, int *tiles_total, int *trips, int cap) {
+  if (tiles_m <= 0 || tiles_n <= 0 || zcount <= 0 || (long)((tiles_m + 7) / 8) * 8 * tiles_n * zcount >= (1L << 30))
+    return set_error(DF_ERR_ARG, "split_walk: need positive tile counts with fewer than 2^30 positions");
+  const SplitWalk w = split_walk(tiles_m, tiles_n, zcount, workgroups);
+  if (grid) *grid = w.grid;
+  if (tiles_total) *tiles_total = w.tiles_total;
+  for (int b = 0; trips && b < w.grid && b < cap; ++b) trips[b] = split_walk_trips(w, b);
+  return DF_OK;
+}
+
+// one plain-GEMM launch with the engine's epilogue options (kernel tests): dense operands, zcount batches one behind the other
+extern "C" int df_gemm_rows(const float *in, const float *wgt, const float *bias, const float *res, float *out, float *colsum, int64_t M, int N,
+                            int K, int zcount, int act, int rows_per_group, int rows_valid, int bias_group_ld, df_stream_t stream) {
+  if (!in || !wgt || (!out && !colsum)) return set_error(DF_ERR_ARG, "gemm_rows: null pointer");
+  if (M <= 0 || M >= (1L << 31) || N <= 0 || K <= 0 || zcount <= 0) return set_error(DF_ERR_ARG, "gemm_rows: bad shape");
+  if (act != ACT_NONE && act != ACT_RELU) return set_error(DF_ERR_ARG, "gemm_rows: activation must be none or ReLU");
+  if (rows_per_group < 0 || (rows_per_group == 0 ? rows_valid != 0 || bias_group_ld != 0 : M % rows_per_group != 0 || rows_valid <= 0 || rows_valid > rows_per_group))
+    return set_error(DF_ERR_ARG, "gemm_rows: row groups must divide M, with 1 .. rows_per_group real rows each");
+  if (zcount > 1 && (res || bias_group_ld > 0)) return set_error(DF_ERR_ARG, "gemm_rows: a z batch takes neither a residual nor per-group bias");
+  ConvParams p;
+  p.in = in; p.wgt = wgt; p.bias = bias; p.res = res; p.out = out; p.colsum = colsum;
+  p.B = (int)M; p.Cin = K; p.in_ld = K; p.Cout = N; p.out_ld = N; p.res_ld = N; p.act = act;
+  p.rows_per_group = rows_per_group; p.rows_valid = rows_valid; p.bias_group_ld = bias_group_ld;
+  p.zcount = zcount; p.z_in_coff = M * K; p.z_wgt = (long)N * K; p.z_bias = bias ? N : 0; p.z_out_coff = M * N;
+  return launch_conv(p, to_stream(stream));
+}
+
 static void desc_fields(const df_conv_desc *d, ConvParams &p) {
   p.in = d->in; p.wgt = d->wgt; p.bias = d->bias; p.res = d->res; p.prelu = d->prelu; p.out = d->out;
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.in_ld = d->in_ld; p.in_coff = d->in_coff;

@@ -115,6 +115,13 @@ int gemm_epi_kind(const ConvParams &p);
 // 1: a layer with N output channels, reduction K and this epilogue kind runs on the bf16 x 6 kernel when its weights have planes.  A pure
 // function of the layer (no M, batch, crop size, z count, stream or device state): B objects in one call and B solo calls take the same path
 int split_route(int N, int K, int epi);
+// The 256 x 256 form's launch: `grid` workgroups walk `tiles_total` tile positions.  A z batch has ceil(tiles_m / 8) * 8 * tiles_n positions
+// (whole groups of 8 row tiles: positions whose row tile is past tiles_m are padding), the batches lie one behind the other.  workgroups: the
+// most the launch may have (one per compute unit); <= 0: one per position.  grid is a multiple of 8, at least 8 and at most tiles_total;
+// workgroup b makes split_walk_trips(w, b) loop trips, padding positions included.  Host only (tests: df_split_walk)
+struct SplitWalk { int grid, tiles_total; };
+SplitWalk split_walk(int tiles_m, int tiles_n, int zcount, int workgroups);
+int split_walk_trips(const SplitWalk &w, int b);
 // cut `elems` weights into their three bf16 planes (term p of w[i] at planes[p * stride + i], bf16 elements) on stream st
 void cut_weight_planes(const float *w, void *planes, long elems, long stride, hipStream_t st);
 // launch_conv's first step: 1 when the launch was taken by the bf16 x 6 kernel (p.wpl set and split_route true; development build: also

@@ -22,10 +22,11 @@
 // Operand domain of the cut: finite values whose magnitude does not round to bf16 infinity.  An infinity, or a magnitude from 2^127 (2 - 2^-8)
 // up, cuts into hi = inf, mid = -inf or NaN, and the product is NaN where the fp32 kernel's is an infinity or a finite number.
 // Development build only: DF_GEMM_SPLIT_OFF=1 keeps every launch on fp32; DF_GEMM_SPLIT_BF16=1 also takes eligible launches without planes
-// (their weights are cut per launch into a per-stream scratch).  Measurements: DESIGN.md section 6, profiles/r04_experiments/README.md.
+// (their weights are cut per launch into a per-stream scratch); DF_GEMM_SPLIT_WGS=N caps the workgroups of a 256 x 256 launch (0: one per
+// tile position, no walk).  Measurements: DESIGN.md section 6, profiles/r04_experiments/README.md.
 //
 // Layout of this file.  What the three tile forms must agree on is stated once, ahead of the kernels: the order of the six pairs (pair_a /
-// pair_b), the cut of eight floats (cut4 / cut8), the tile walk and z offsets (split_tile), the fragment addresses of the two 128-column
+// pair_b), the cut of eight floats (cut4 / cut8), the tile order and z offsets (split_tile_at; split_walk_next: the 256 x 256 form's walk), the fragment addresses of the two 128-column
 // forms (SPLIT_FRAG_OFFSETS), and the epilogue's rules (epi_rules, epi_finish, epi_colsum) under its two store paths.  The kernels keep what was
 // tuned per form: the fetch / stage / multiply pipelines and their issue-order pins.  On the host plan_split decides everything about a
 // launch (taken or not, form, grid, LDS bytes, kernel arguments) without a HIP call or an environment read; try_split_gemm reads the
@@ -101,6 +102,7 @@ struct SplitArgs {
   int N, K, in_ld, in_coff, out_ld, out_coff, res_ld, res_coff, act, rows_per_group, rows_valid, bias_group_ld;
   long z_in_coff, z_wgt, z_bias, z_out_coff;
   int tiles_m, tiles_n;         // of the launched kernel's tile
+  int tiles_total;              // 256 x 256 form: the tile positions of the whole launch, every z, padding included (igemm.h SplitWalk)
   long cs_rows;                 // rows of the column-sum partial buffer per z (igemm.h colsum_partial_rows)
 };
 
@@ -109,16 +111,27 @@ struct SplitArgs {
 __device__ __forceinline__ int piece(int row, int slot) { return row * 64 + ((slot ^ ((row >> 2) & 3)) << 4); }
 
 // A workgroup's tile and its z batch.  XCD-aware order: the 8 XCDs take whole row tiles, the column tiles of a row tile run back to back on
-// one XCD (its A rows stay in that L2).  false: a padding workgroup of the grid (no tile)
+// one XCD (its A rows stay in that L2).  false: a padding position of the grid (no tile)
 struct SplitTile { int tm, tn, z; const float *in; const __bf16 *wpl; };
-__device__ __forceinline__ bool split_tile(const SplitArgs &a, SplitTile &t) {
-  const int xcd = blockIdx.x & 7, seq = blockIdx.x >> 3;
+__device__ __forceinline__ bool split_tile_at(const SplitArgs &a, int xcd, int seq, int z, SplitTile &t) {
   t.tm = (seq / a.tiles_n) * 8 + xcd;
   t.tn = seq % a.tiles_n;
-  t.z = blockIdx.z;
+  t.z = z;
   t.in = a.in + t.z * a.z_in_coff + a.in_coff;
   t.wpl = a.wpl + t.z * a.z_wgt;
   return t.tm < a.tiles_m;
+}
+// The two 128-column forms: one workgroup per position, blockIdx.z the z batch
+__device__ __forceinline__ bool split_tile(const SplitArgs &a, SplitTile &t) { return split_tile_at(a, blockIdx.x & 7, blockIdx.x >> 3, blockIdx.z, t); }
+// The 256 x 256 form: one workgroup walks many tiles.  The launch has a.tiles_total positions (igemm.h SplitWalk): per z batch the order above,
+// the z batches one behind the other in each XCD's sequence.  A workgroup keeps its XCD (blockIdx.x & 7) and takes the sequence numbers
+// (blockIdx.x >> 3) + i (gridDim.x >> 3), i = 0, 1, ...: a static stride, the loop count known on the host, no counter in memory and no wait
+// between workgroups.  Moves seq on to the workgroup's next tile (padding positions are passed over); false: the walk is over
+__device__ __forceinline__ bool split_walk_next(const SplitArgs &a, int &seq, SplitTile &t) {
+  const int seq_z = ((a.tiles_m + 7) >> 3) * a.tiles_n;
+  for (; seq < (a.tiles_total >> 3); seq += (int)(gridDim.x >> 3))
+    if (split_tile_at(a, blockIdx.x & 7, seq % seq_z, seq / seq_z, t)) return true;
+  return false;
 }
 
 // Steps the kernels' pipelines share, as macros over the kernels' own names like the pipeline steps they are part of (a, tid, row0, n0, wg,
@@ -264,9 +277,10 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs &a, const f32x16 
 // of 2 rows x 128; a residual is read the same way, and added (with the activation behind it) on the way out.  Column sums are taken in the
 // fragment layout, in split_epilogue's order (launches with column sums have no residual: GEMM_EPI_OTHER is not routed).  Needs 16-byte aligned
 // output / residual rows (plan_split checks)
-__device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f32x16 (&acc)[2][2], int z, long row0, int wrow, int nb, int lane, float *blk) {
-  const int fr = lane & 31, fh = lane >> 5;
-  const EpiRules ru = epi_rules(a, z, row0, wrow);
+// (ACT: the activation applied on the way into LDS, a constant per copy.  Inside the tile walk's loop the compiler no longer lifts the
+// launch-wide choices out of the 64 elements; left to it, every element branches on them)
+template <int ACT>
+__device__ __forceinline__ void split_block_to_lds(const SplitArgs &a, const f32x16 (&acc)[2][2], const EpiRules &ru, int z, int wrow, int nb, int fr, int fh, float *blk) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int n = nb + j * 32 + fr;
@@ -277,12 +291,20 @@ __device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f3
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int br = i * 32 + 4 * fh + (e & 3) + 8 * (e >> 2);          // row inside the block
-        const float v = a.res ? epi_finish(acc[i][j][e], &b1, nullptr, ACT_NONE, 0.f) : epi_finish(acc[i][j][e], &b1, nullptr, a.act, ru.slope);
+        const float v = epi_finish(acc[i][j][e], &b1, nullptr, ACT, ru.slope);
         blk[br * 64 + j * 32 + fr] = v;
         csum += wrow + br < ru.limit ? v : 0.f;
       }
     epi_colsum(a, ru, z, n, fh, csum);
   }
+}
+__device__ __forceinline__ void split_epilogue_rows(const SplitArgs &a, const f32x16 (&acc)[2][2], int z, long row0, int wrow, int nb, int lane, float *blk) {
+  const int fr = lane & 31, fh = lane >> 5;
+  const EpiRules ru = epi_rules(a, z, row0, wrow);
+  const int act = a.res ? ACT_NONE : a.act;          // (with a residual the activation comes behind it, on the way out)
+  if (act == ACT_RELU) split_block_to_lds<ACT_RELU>(a, acc, ru, z, wrow, nb, fr, fh, blk);
+  else if (act == ACT_PRELU) split_block_to_lds<ACT_PRELU>(a, acc, ru, z, wrow, nb, fr, fh, blk);
+  else split_block_to_lds<ACT_NONE>(a, acc, ru, z, wrow, nb, fr, fh, blk);
   if (!a.out) return;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -466,21 +488,40 @@ constexpr int V3_LDS = 8 * 64 * 64 * 4;                          // the epilogue
 // 256-byte bank row once each, and the 8 x 8-lane groups of the staging ds_write_b128 (row = tid / 2) write 128 contiguous bytes
 __device__ __forceinline__ int piece16(int row, int half) { return row * 32 + ((half ^ ((row >> 3) & 1)) << 4); }
 
+// DF_STRACE(i, s): time stamp i of every wave, filed under the tile with sequence number s, for tools/dev/split_gemm_trace.hip (which compiles
+// this file with the hooks defined); nothing otherwise
+#ifndef DF_STRACE
+#define DF_STRACE_ENTRY()
+#define DF_STRACE(i, s) ((void)(s))
+#endif
+
+// A workgroup walks its tiles (split_walk_next) with one hand-over between two of them: the next tile's first fetches (weight planes of group 0,
+// activations of groups 0 and 1) are issued into the fetch registers, dead by then, BEFORE the finished tile's epilogue, whose output stores are
+// issued and not waited for; one workgroup barrier separates the epilogue's last LDS read from the next tile's stage-0 write (a wave's 16 KB
+// epilogue block lies across both stages).
 __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v3_kernel(const SplitArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds3[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  DF_STRACE_ENTRY();
   SplitTile wg;
-  if (!split_tile(a, wg)) return;
-  const long row0 = (long)wg.tm * 256;
-  const int n0 = wg.tn * 256;
+  int seq = blockIdx.x >> 3;
+  if (!split_walk_next(a, seq, wg)) return;
 
   // staging roles: piece tid of the 512 (row, 8-k) pieces of the activation tile and of each weight plane's tile
   const int srow = tid >> 1, shalf = tid & 1;
   const int soff = piece16(srow, shalf);
-  long r = row0 + srow;
-  r = r < a.M ? r : a.M - 1;                                      // the last row tile re-reads row M - 1 (its results are not stored)
-  const float *ag = wg.in + r * a.in_ld + shalf * 8;
-  const __bf16 *bg = wg.wpl + (long)(n0 + srow) * a.K + shalf * 8;
+  const float *ag;
+  const __bf16 *bg;
+  // (the last row tile re-reads row M - 1: its results are not stored.  The empty asm keeps the address arithmetic per tile: see the epilogue's)
+#define V3_TILE_ROLES()                                                          \
+  do {                                                                           \
+    int t = tid;                                                                 \
+    asm volatile("" : "+v"(t));                                                  \
+    long r = (long)wg.tm * 256 + (t >> 1);                                       \
+    r = r < a.M ? r : a.M - 1;                                                   \
+    ag = wg.in + r * a.in_ld + (t & 1) * 8;                                      \
+    bg = wg.wpl + (long)(wg.tn * 256 + (t >> 1)) * a.K + (t & 1) * 8;            \
+  } while (0)
   // activations (HBM) two groups ahead in two register sets, weight planes (L2) one group ahead
   float4 xa0, xa1, ya0, ya1;
   uint4 b0, b1, b2;
@@ -499,7 +540,6 @@ __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v3_kernel(const SplitA
 #define V3_WRITE_B(base) SPLIT_STORE3((base) + 3 * V3_PL, V3_PL, soff, b0, b1, b2)
 
   const int wr = wave >> 2, wc = wave & 3, fr = lane & 31, fh = lane >> 5;
-  f32x16 acc[2][2][2] = {};          // [64-row block of the wave][32-row tile][32-column tile]
   // (a tile's 32-row offset leaves bit 3 of the row alone: the four A and two B fragments of a plane are one address plus constants)
   const int offa = piece16(wr * 128 + fr, fh), offb = 3 * V3_PL + piece16(wc * 64 + fr, fh);
   // pair-major as in the second form.  V3_READ(q), q = 0..2: the six fragments pair q is the first to use (pair_brings_new_planes)
@@ -560,27 +600,63 @@ __global__ __launch_bounds__(512, 1) void gemm_split_bf16_v3_kernel(const SplitA
   unsigned char *const st0 = lds3, *const st1 = lds3 + V3_STAGE;
   const int nk = a.K / 16;          // even: K % 32 == 0
   const int klast = a.K - 16;
-  V3_FETCH_B(0);
-  V3_FETCH_A(x, 0);
-  V3_FETCH_A(y, 16);
-  {
-    uint4 ch, cm, cl;
-    V3_CUT0(x);
-    V3_CUT1(x);
-    V3_WRITE_A(st0);
-    V3_WRITE_B(st0);
+  // a tile's first fetches: weight planes of group 0, activations of groups 0 and 1
+#define V3_FIRST_FETCHES()                                                       \
+  do {                                                                           \
+    V3_TILE_ROLES();                                                             \
+    V3_FETCH_B(0);                                                               \
+    V3_FETCH_A(x, 0);                                                            \
+    V3_FETCH_A(y, 16);                                                           \
+  } while (0)
+  V3_FIRST_FETCHES();
+  DF_STRACE(0, seq);
+  DF_STRACE(1, seq);
+  for (;;) {
+    const long row0 = (long)wg.tm * 256;
+    const int n0 = wg.tn * 256, z = wg.z, seq0 = seq;
+    f32x16 acc[2][2][2] = {};          // [64-row block of the wave][32-row tile][32-column tile]
+    {
+      uint4 ch, cm, cl;
+      V3_CUT0(x);
+      V3_CUT1(x);
+      V3_WRITE_A(st0);
+      V3_WRITE_B(st0);
+    }
+    __syncthreads();
+    DF_STRACE(2, seq0);
+    for (int s = 0; s < nk; s += 2) {
+      // stage 0: group s; set y: group s + 1
+      const int k1 = (s + 1) * 16, k2 = (s + 2) * 16, k3 = (s + 3) * 16;
+      V3_BODY(x, y, k2 < klast ? k2 : klast, k1, st0, st1);
+      // stage 1: group s + 1; set x: group s + 2
+      V3_BODY(y, x, k3 < klast ? k3 : klast, k2 < klast ? k2 : klast, st1, st0);
+    }
+    // (every wave is past the loop's last barrier: the stages are free, the fetch registers dead.)  The next tile's first fetches go out ahead
+    // of this tile's epilogue and stay in flight under it
+    DF_STRACE(3, seq0);
+    seq += (int)(gridDim.x >> 3);
+    const bool more = split_walk_next(a, seq, wg);
+    if (more) {
+      V3_FIRST_FETCHES();
+      DF_STRACE(1, seq);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // (the empty asm keeps the epilogue's lane arithmetic -- 64 row numbers, as many LDS addresses -- inside the walk's loop: lifted out of it as
+    // loop invariants they live across the main loop, which has no register to spare, and go to scratch)
+    int et = tid;
+    asm volatile("" : "+v"(et));
+    const int elane = et & 63, ewr = et >> 8, ewc = (et >> 6) & 3;
+    float *const blk = reinterpret_cast<float *>(lds3) + (et >> 6) * (64 * 64);          // the wave's epilogue block
+    split_epilogue_rows(a, acc[0], z, row0, ewr * 128, n0 + ewc * 64, elane, blk);
+    DF_STRACE(4, seq0);
+    split_epilogue_rows(a, acc[1], z, row0, ewr * 128 + 64, n0 + ewc * 64, elane, blk);
+    DF_STRACE(5, seq0);
+    if (!more) {
+      DF_STRACE(6, seq0);
+      break;
+    }
+    __syncthreads();          // the epilogue's last LDS read of every wave, before the next tile's stage-0 write
   }
-  __syncthreads();
-  for (int s = 0; s < nk; s += 2) {
-    // stage 0: group s; set y: group s + 1
-    const int k1 = (s + 1) * 16, k2 = (s + 2) * 16, k3 = (s + 3) * 16;
-    V3_BODY(x, y, k2 < klast ? k2 : klast, k1, st0, st1);
-    // stage 1: group s + 1; set x: group s + 2
-    V3_BODY(y, x, k3 < klast ? k3 : klast, k2 < klast ? k2 : klast, st1, st0);
-  }
-  float *const blk = reinterpret_cast<float *>(lds3) + wave * (64 * 64);          // (every wave is past the loop's last barrier: the stages are free)
-  split_epilogue_rows(a, acc[0], wg.z, row0, wr * 128, n0 + wc * 64, lane, blk);
-  split_epilogue_rows(a, acc[1], wg.z, row0, wr * 128 + 64, n0 + wc * 64, lane, blk);
 }
 
 #ifdef DF_DEV
@@ -621,8 +697,9 @@ struct SplitPlan {
 };
 
 // 0: not taken (the fp32 kernels' launch), 1: taken, pl filled, DF_ERR_ARG: a routed launch outside the kernels' cover.  variant: the highest
-// form allowed (DF_GEMM_SPLIT_V; 3 = all), all: DF_GEMM_SPLIT_BF16 (DF_GEMM_SPLIT_OFF never gets here)
-int plan_split(const ConvParams &p, int compute_units, int variant, bool all, SplitPlan &pl) {
+// form allowed (DF_GEMM_SPLIT_V; 3 = all), all: DF_GEMM_SPLIT_BF16 (DF_GEMM_SPLIT_OFF never gets here), workgroups: the most a 256 x 256 launch
+// may have (DF_GEMM_SPLIT_WGS; 0: one per tile position; < 0: one per compute unit)
+int plan_split(const ConvParams &p, int compute_units, int variant, bool all, int workgroups, SplitPlan &pl) {
   pl = SplitPlan{};
   if (p.splitk_ws || (!p.wpl && !all)) return 0;
   pl.examined = true;
@@ -651,12 +728,18 @@ int plan_split(const ConvParams &p, int compute_units, int variant, bool all, Sp
   // (its epilogue moves whole 16-byte pieces of output and residual rows)
   const bool rows16 = (!p.out || (reinterpret_cast<uintptr_t>(p.out) % 16 == 0 && p.out_ld % 4 == 0 && p.out_coff % 4 == 0 && p.z_out_coff % 4 == 0)) &&
                       (!p.res || (reinterpret_cast<uintptr_t>(p.res) % 16 == 0 && p.res_ld % 4 == 0 && p.res_coff % 4 == 0));
-  const bool v3 = v2 && variant >= 3 && p.Cout % 256 == 0 && rows16 && tiles3 >= compute_units;
+  // (the walk counts the positions of all z batches, padding included, in an int)
+  const bool v3 = v2 && variant >= 3 && p.Cout % 256 == 0 && rows16 && tiles3 >= compute_units && tiles3 < (1L << 27);
   pl.form = v3 ? FORM_256x256 : v2 ? FORM_256x128 : FORM_128x128;
   const FormDesc &f = FORMS[pl.form];
   a.tiles_m = (int)((M + f.bm - 1) / f.bm);
   a.tiles_n = p.Cout / f.bn;
   pl.grid = dim3((unsigned)(((a.tiles_m + 7) / 8) * 8 * a.tiles_n), 1, p.zcount);      // (whole groups of 8 row tiles: split_tile)
+  if (v3) {          // one workgroup per compute unit walks the positions of all z batches (split_walk_next)
+    const SplitWalk w = split_walk(a.tiles_m, a.tiles_n, p.zcount, workgroups < 0 ? compute_units : workgroups);
+    a.tiles_total = w.tiles_total;
+    pl.grid = dim3((unsigned)w.grid, 1, 1);
+  }
   pl.threads = f.threads;
   pl.lds = f.lds;
   return 1;
@@ -671,6 +754,18 @@ int split_route(int N, int K, int epi) {
   // 118 - 128), and K <= 64 (the point layers csrc/pointfeat.hip chains) stays fp32 so that the chained and the per-layer launches agree
   if (N <= 0 || N % SBN != 0 || K % SBK != 0 || K < 384) return 0;
   return epi == GEMM_EPI_PLAIN || epi == GEMM_EPI_RESIDUAL || epi == GEMM_EPI_GROUPS;
+}
+
+SplitWalk split_walk(int tiles_m, int tiles_n, int zcount, int workgroups) {
+  SplitWalk w;
+  w.tiles_total = ((tiles_m + 7) / 8) * 8 * tiles_n * zcount;
+  w.grid = workgroups <= 0 || workgroups >= w.tiles_total ? w.tiles_total : workgroups < 8 ? 8 : workgroups / 8 * 8;
+  return w;
+}
+
+int split_walk_trips(const SplitWalk &w, int b) {
+  const int seqs = w.tiles_total / 8, step = w.grid / 8, first = b / 8;
+  return first < seqs ? (seqs - first + step - 1) / step : 0;
 }
 
 int gemm_epi_kind(const ConvParams &p) {
@@ -702,9 +797,10 @@ int try_split_gemm(const ConvParams &p, hipStream_t st, ConvRoute &r) {
   static const bool all = dev_getenv("DF_GEMM_SPLIT_BF16") != nullptr;
   static const bool verbose = dev_getenv("DF_GEMM_SPLIT_VERBOSE") != nullptr;
   static const int variant = dev_getenv("DF_GEMM_SPLIT_V") ? atoi(dev_getenv("DF_GEMM_SPLIT_V")) : 3;
+  static const int workgroups = dev_getenv("DF_GEMM_SPLIT_WGS") ? atoi(dev_getenv("DF_GEMM_SPLIT_WGS")) : -1;
   if (off) return 0;
   SplitPlan pl;
-  const int rc = plan_split(p, compute_units(), variant, all, pl);
+  const int rc = plan_split(p, compute_units(), variant, all, workgroups, pl);
   if (verbose && pl.examined) fprintf(stderr, "[df-split] M=%ld N=%d K=%d z%d -> %s\n", pl.a.M, p.Cout, p.Cin, p.zcount, rc == 1 ? "bf16 x 6" : "fp32");
   if (rc != 1) return rc;
 #ifdef DF_DEV
@@ -715,7 +811,7 @@ int try_split_gemm(const ConvParams &p, hipStream_t st, ConvRoute &r) {
   }
 #endif
   const FormDesc &f = FORMS[pl.form];
-  if (verbose) fprintf(stderr, "[df-split]   form %s\n", f.name);
+  if (verbose) fprintf(stderr, "[df-split]   form %s\n[df-split]   workgroups %u\n", f.name, pl.grid.x * pl.grid.z);
   if (f.raise) {
     const int e = raise_lds_limit(reinterpret_cast<const void *>(f.kernel), pl.lds);
     if (e != DF_OK) return e;

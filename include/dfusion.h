@@ -855,6 +855,24 @@ int df_net_profile_read_split(df_net *net, double *gemm_ms, double *gemm_flops, 
  * stream of a call.  Only the handles' own weights are routed; df_conv2d_nhwc and the trainers always run fp32. */
 int df_gemm_route(int n, int k, int epilogue);
 
+/* How the routed kernel's 256 x 256 tile form launches tiles_m x tiles_n output tiles in zcount batches (host only, no device call; for
+ * tests).  The launch has *tiles_total tile positions, ceil(tiles_m / 8) * 8 * tiles_n per batch, the batches one behind the other: position
+ * p belongs to XCD lane p % 8 and has sequence number s = p / 8; with S = ceil(tiles_m / 8) * tiles_n sequence numbers per batch it is batch
+ * s / S, row tile (s % S / tiles_n) * 8 + p % 8 (a padding position when that is not below tiles_m) and column tile s % S % tiles_n.
+ * *grid workgroups run (a multiple of 8 and at most *tiles_total; `workgroups` is the most allowed, e.g. the compute units; <= 0: one
+ * per position); workgroup b keeps lane b % 8 and takes the sequence numbers b / 8 + i (*grid / 8), i = 0 .. trips[b] - 1.  trips (may be
+ * NULL) receives min(*grid, cap) entries. */
+int df_split_walk(int tiles_m, int tiles_n, int zcount, int workgroups, int *grid, int *tiles_total, int *trips, int cap);
+
+/* One plain-GEMM launch as the engines make them, with every epilogue option (for kernel tests; like df_conv2d_nhwc it runs the fp32 kernels):
+ *   out[z][m][n] = act(sum_k in[z][m][k] wgt[z][n][k] + bias + res[m][n]),  z < zcount, m < M, n < N, dense fp32 device operands.
+ * bias: NULL, [zcount][N], or with bias_group_ld > 0 one row of bias_group_ld floats per row group (row m is in group m / rows_per_group).
+ * res: NULL or [M][N] (zcount 1).  act: 0 none, 1 ReLU.  colsum: NULL, or [zcount][2 ceil(M / 128)][N]: row r receives the column sums of the
+ * activated rows 64 r .. 64 r + 63 that are real (below M and, with row groups, m % rows_per_group < rows_valid); out may then be NULL.
+ * rows_per_group: 0 or a multiple of 128 that divides M. */
+int df_gemm_rows(const float *in, const float *wgt, const float *bias, const float *res, float *out, float *colsum, int64_t M, int N,
+                 int K, int zcount, int act, int rows_per_group, int rows_valid, int bias_group_ld, df_stream_t stream);
+
 /* Debug taps: with df_net_debug_taps(net, 1) armed, a single-bucket PoseNet forward keeps device copies of its named
  * intermediates (channels-last): "stem" [B][H/2][W/2][64] (conv1 + ReLU, lib/extractors.py:115-117), "layer1".."layer4",
  * "psp" [B][H/8][W/8][1024] (lib/pspnet.py:20-24), "up_1" [B][H/4][W/4][256], "up_2" [B][H/2][W/2][64], "up_3" [B][Npad][64]
