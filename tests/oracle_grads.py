@@ -65,7 +65,22 @@ WINDOWS = {
     # workgroup, so its last workgroup holds 6 (every other fixture has N % 8 == 0 or one pose per workgroup); frames 1, 4, 7, 10 are symmetric
     "tiny11": dict(K=3, N=70, M=60, wseed=47, oseed=3000,
                    sizes=[(8, 8), (16, 16), (8, 24), (24, 8), (12, 20), (32, 32), (36, 28), (8, 8), (16, 40), (8, 3200), (3200, 8)]),
+    # upd4: the window of the parameter-update tests (tests/test_trainer_updates_gpu.py): the smallest crops that put both routes of the
+    # stride-1 3x3 trunk convolutions into one pass.  44 x 44 (6 x 6 trunk maps, the smallest square ones at which the dilated layer3.1
+    # takes F(4x4,3x3); twice: a bucket of two frames), 24 x 24 (3 x 3 maps, the smallest at which any layer does: layer3.0.conv2 and
+    # layer4.0.conv2) and 40 x 40 (5 x 5 maps: the direct kernel on every layer); frame 1 is symmetric.  upd5: the same frames and an
+    # 80 x 120 one, for the change of shape between two steps of one handle
+    "upd4": dict(K=3, N=70, M=60, wseed=61, oseed=3200, sizes=[(44, 44), (40, 40), (44, 44), (24, 24)]),
+    "upd5": dict(K=3, N=70, M=60, wseed=61, oseed=3200, sizes=[(44, 44), (40, 40), (44, 44), (24, 24), (80, 120)]),
 }
+# the further parameter sets of the update tests: the state dict of the full reload and the one that lends its layer3.1.conv2 weight.
+# With four frames of 70 points about one seed in three keeps ``point_relu_margin`` above RELU_MARGIN: the seeds, the two scales below and
+# the lanes' jobs were picked one stage after the other on the CPU so that it holds at every parameter set of the sequence
+# (tests/test_oracle_updates.py asserts and prints them: 1.5e-5 .. 3.3e-5)
+UPDATE_WSEEDS = (101, 151)
+UPDATE_KEY = "cnn.model.module.feats.layer3.1.conv2.weight"
+UPDATE_GRAPH_FRAMES = (0, 2)             # the graph_safe batch step: the two 44 x 44 frames as one bucket
+UPDATE_LANE_JOBS = (0, 1, 2, 0, 1)       # the five bs = 1 jobs of the lanes' window (frames of upd4: two crop sizes, one symmetric)
 # one-bucket windows (no bucket to lose: tests/test_oracle_grads.py leaves them out).  ones3: three 8 x 8 frames, 1 x 1 trunk maps only, so
 # that a defect of the one-pixel map cannot hide behind larger frames in the summed gradients; frame 1 is symmetric.  The seed keeps
 # ``point_relu_margin`` at 2.0e-5 (oseed 3100 has a conv6 pre-activation at 1.1e-6: a ReLU the GPU's fp32 sum may flip)
@@ -85,6 +100,55 @@ def window(name):
         o["obj"][0] = i % K
         o["symmetric"] = i % K == 1
     return K, N, M, sd, objs
+
+
+# ---- the parameter-update fixtures (tests/test_trainer_updates_gpu.py, tests/test_oracle_updates.py) ----
+# FlatAdam's learning rate there: Adam moves every weight by about lr whatever its size, and the stem weights are 400x smaller than the
+# rest (synth.make_state_dict: std 2.9e-4), so 1e-6 moves the stem's output by about a percent and keeps the fixture's conditioning,
+# while it is 500 ulp of a trunk weight of 0.03: every tensor's bits change
+ADAM_LR = 1e-6
+INPLACE_SCALE, REBIND_SCALE = 0.997, 1.0035          # the in-place writer and the rebound buffer scale the whole packed buffer (fp32)
+REFINER_UPDATE = dict(K=3, N=70, M=60, wseeds=(1031, 1033), oseed=3300, eseed=7, size=(40, 40))
+
+
+def refiner_update_frames():
+    """-> (K, N, M, the two state dicts, frames): two refiner frames as tests/test_train_window_fp64_gpu.py builds them (a synthetic object's
+    cloud, target and mesh, normal embeddings), frame 1 symmetric."""
+    u = REFINER_UPDATE
+    K, N, M = u["K"], u["N"], u["M"]
+    objs = [synth.make_object(u["oseed"] + i, *u["size"], N, K, num_points_mesh=M) for i in range(2)]
+    emb = np.random.default_rng(u["eseed"]).standard_normal((2, 32, N)).astype(np.float32)
+    frames = [dict(points=o["cloud"], emb=emb[b], obj=b, target=o["target"], model_points=o["model_points"], symmetric=b == 1)
+              for b, o in enumerate(objs)]
+    return K, N, M, [synth.make_state_dict(synth.refiner_spec(K), s) for s in u["wseeds"]], frames
+
+
+def second_iteration(frames, first):
+    """The frames of the next refine iteration: the first one's new_points / new_target (``first``: per-frame tensors) in place of points / target."""
+    return [dict(f, points=torch.as_tensor(first["new_points"][b]).detach().cpu().float().reshape(-1, 3),
+                 target=torch.as_tensor(first["new_target"][b]).detach().cpu().float().reshape(-1, 3)) for b, f in enumerate(frames)]
+
+
+class AdamEmu:
+    """FlatAdam's rule (df_adam_step: torch.optim.Adam's defaults) on a state dict, in fp64 with the result rounded to fp32 -- the CPU
+    tests' stand-in for the parameter sets a GPU run reaches.  It differs from the GPU's by the rounding of the gradients only, which
+    moves a weight by a fraction of ``lr`` where the gradient is within rounding of zero."""
+
+    def __init__(self, lr=ADAM_LR, betas=(0.9, 0.999), eps=1e-8):
+        self.lr, self.betas, self.eps, self.t, self.m, self.v = lr, betas, eps, 0, {}, {}
+
+    def step(self, sd, grads):
+        self.t += 1
+        b1, b2 = self.betas
+        out = {}
+        for k, p in sd.items():
+            p = torch.as_tensor(p).double()
+            g = grads[k].double().reshape(p.shape) if k in grads else torch.zeros_like(p)
+            self.m[k] = self.m.get(k, 0.0) * b1 + (1 - b1) * g
+            self.v[k] = self.v.get(k, 0.0) * b2 + (1 - b2) * g * g
+            denom = self.v[k].sqrt() / (1 - b2 ** self.t) ** 0.5 + self.eps
+            out[k] = (p - self.lr / (1 - b1 ** self.t) * self.m[k] / denom).float().numpy()
+        return out
 
 
 # ---- per-frame oracle passes ----
@@ -119,9 +183,12 @@ def _grads(loss, psd):
     return {k: g.detach() for k, g in zip(keys, gs) if g is not None}
 
 
-def posenet_frames(sd, objs, dtype, w=0.015):
-    """One PoseNet + Loss pass per object (bs = 1) in ``dtype``: outputs and that frame's own parameter gradients."""
+def posenet_frames(sd, objs, dtype, w=0.015, on_params=None):
+    """One PoseNet + Loss pass per object (bs = 1) in ``dtype``: outputs and that frame's own parameter gradients.  ``on_params`` is
+    called with the {key: leaf tensor} dict before the passes (an emulated defect finds a layer by the leaf its functional call gets)."""
     psd = {k: torch.as_tensor(v).to(dtype).requires_grad_() for k, v in sd.items()}
+    if on_params is not None:
+        on_params(psd)
     res = []
     for o in objs:
         T = lambda k: torch.from_numpy(o[k])[None].to(dtype)
