@@ -151,6 +151,8 @@ SIGNATURES = {
     "df_mesh_closest_scratch_bytes": (_sz, [_i]),
     "df_mesh_closest": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "df_fp64_rate_probe": (_i, [_i, _i, _vp, _vp]),
+    "df_mesh_icp_scratch_bytes": (_sz, [_i, _i, _i]),
+    "df_mesh_icp": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -2,7 +2,7 @@
 // the call in include/dfusion.h (steps M1, M2, Q1, D1..D5); the per-triangle and per-pair rules are mesh_closest_core.h;
 // tests/mesh_closest_np.py restates them in numpy and the outputs are compared bit for bit.
 //
-// Two kernels on the caller's stream.  mesh_prepare_kernel: one thread per triangle writes its 32-double record (M1, M2) to scratch.
+// Two kernels on the caller's stream.  mesh_prepare_kernel (mesh_prepare.h, shared with df_mesh_icp): one thread per triangle writes its 32-double record (M1, M2) to scratch.
 // mesh_scan_kernel<SPLIT>: the scan of the 1-NN kernels of knn.hip with triangle records in place of points.  A lane owns MC_QPL
 // queries in registers (q, the best d, the best t); the records are wave-uniform: a workgroup stages MC_TILE of them at a time in LDS
 // (coalesced 16-byte copies) and every lane reads the same record, so the LDS reads are broadcasts.  D1 / D2 are branch-free selects:
@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "mesh_closest_core.h"
+#include "mesh_prepare.h"
 
 namespace df {
 namespace {
@@ -28,15 +29,6 @@ constexpr int MC_QPL = 2;            // queries per lane
 constexpr int MC_TILE = 128;         // records per LDS tile: 32 KiB
 constexpr int MC_FILL = 256;         // workgroups below which the triangle range is split over the waves: the compute units of the part
 constexpr int MC_WAVES = MC_BLOCK / 64;
-
-__global__ __launch_bounds__(MC_BLOCK) void mesh_prepare_kernel(const float *__restrict__ vertices, int V, const int *__restrict__ triangles,
-                                                                int T, TriRec *__restrict__ rec) {
-  const int t = blockIdx.x * MC_BLOCK + threadIdx.x;
-  if (t >= T) return;
-  TriRec r;
-  meshclosest::prepare_tri(vertices, V, triangles[3 * (size_t)t], triangles[3 * (size_t)t + 1], triangles[3 * (size_t)t + 2], &r);
-  rec[t] = r;
-}
 
 // grid = query blocks * K (block b: transform b / qblocks, query block b % qblocks)
 template <int SPLIT>
@@ -148,7 +140,7 @@ extern "C" int df_mesh_closest(const float *vertices, int V, const int *triangle
     return set_error(DF_ERR_ARG, "%s: vertices, triangles and tri_out must be 4-byte, points, xf, dist2_out and closest_out 8-byte aligned", name);
   hipStream_t st = to_stream(stream);
   TriRec *rec = static_cast<TriRec *>(scratch);
-  hipLaunchKernelGGL(mesh_prepare_kernel, dim3(cdiv(T, MC_BLOCK)), dim3(MC_BLOCK), 0, st, vertices, V, triangles, T, rec);
+  hipLaunchKernelGGL(mesh_prepare_kernel, dim3(cdiv(T, MESH_PREPARE_BLOCK)), dim3(MESH_PREPARE_BLOCK), 0, st, vertices, V, triangles, T, rec);
   const int whole = cdiv(P, MC_BLOCK * MC_QPL);
   if ((long)whole * K >= MC_FILL) {
     hipLaunchKernelGGL(mesh_scan_kernel<1>, dim3(whole * K), dim3(MC_BLOCK), 0, st, rec, T, points, P, xf, whole, dist2_out, tri_out, closest_out);

@@ -191,6 +191,7 @@ class RenderedPoseDataset(ChunkedViews):
             self.renderer = cr.CadSceneRenderer(meshes, self.proj_mat, self.image_dims, [self.model_scale] * len(meshes), device=self.device,
                                                 normals=normals)
             self._n_points = [len(m[0]) for m in meshes]
+            self._icp_meshes = [(m[0], m[1]) for m in meshes[:len(models)]]
             self._centroids = [np.asarray(m[0]).astype(np.float64).mean(axis=0) for m in meshes]
             for k in range(self.n_models):
                 self.pt[k + 1] = sample_model_points(np.asarray(meshes[k][0], dtype=np.float32).astype(np.float64), np.asarray(meshes[k][1]))
@@ -201,6 +202,7 @@ class RenderedPoseDataset(ChunkedViews):
             self.renderer = cr.CadMeshRenderer(pts, tris, col, self.proj_mat, self.image_dims, device=self.device, model_scale=self.model_scale,
                                                normals=normals)
             self._n_points, self._centroids = [len(pts)], [np.asarray(pts).astype(np.float64).mean(axis=0)]
+            self._icp_meshes = [(pts, tris)]
             self.pt[1] = sample_model_points(np.asarray(pts, dtype=np.float32).astype(np.float64), np.asarray(tris))
         else:
             if _is_path(models[0]):
@@ -210,6 +212,7 @@ class RenderedPoseDataset(ChunkedViews):
                 pts, nrm, col = models[0]
             self.renderer = cr.CadRenderer(pts, nrm, col, self.proj_mat, self.image_dims, device=self.device, model_scale=self.model_scale)
             self._n_points, self._centroids = [len(pts)], [np.asarray(pts).astype(np.float64).mean(axis=0)]
+            self._icp_meshes = None                              # a point cloud has no surface to fit
             self.pt[1] = sample_model_points(np.asarray(pts, dtype=np.float32).astype(np.float64), np.zeros((0, 3), dtype=np.int64))
         self._pt_dev = {o: torch.from_numpy(np.ascontiguousarray(p, dtype=np.float64)).to(self.device) for o, p in self.pt.items()}
         self.num_pt_mesh_large = self.num_pt_mesh_small = 500
@@ -269,6 +272,14 @@ class RenderedPoseDataset(ChunkedViews):
     def get_sym_list(self):
         """The item indices (model k = index k) that are trained and scored with ADD-S: [] unless ``symmetry`` asked for some."""
         return list(self._sym_list)
+
+    def mesh_icp(self):
+        """A ``lib.mesh_icp.MeshIcp`` of the models' triangles in the units of the items' clouds (vertices x ``model_scale`` / 10000):
+        an item's index k names mesh k.  ``ValueError`` in point-cloud mode: there are no triangles to fit."""
+        if self._icp_meshes is None:
+            raise ValueError('mesh_icp needs triangles: a scene or raster mesh (a point cloud has none)')
+        from ...lib.mesh_icp import MeshIcp
+        return MeshIcp(self._icp_meshes, self.model_scale / 10000.0, device=self.device)
 
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small

@@ -691,6 +691,62 @@ int df_mesh_closest(const float *vertices, int V, const int *triangles, int T, c
 int df_fp64_rate_probe(int blocks, int iters, double *sink, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point-to-plane ICP of B estimated poses against the exact surface of their CAD meshes (densefusion_amd/lib/mesh_icp.py): the last,
+ * geometric step of the customCAD pose path.  Each item brings its own observed points (camera frame), its object and a pose; the pose
+ * moves on the device between iterations with no host round trip.  No allocation, no synchronisation, the caller's stream; no atomics:
+ * the outputs are bit-reproducible and an item's outputs depend on its own points, pose, object and the mesh only, not on B or on the
+ * items next to it.  Everything is fp64, one rounding per operation in exactly the order written below (no contraction), with the dot
+ * and cross products of df_mesh_closest; only + - * / sqrt appear, so a restatement matches bit for bit (tests/mesh_icp_np.py).
+ *
+ * df_mesh_icp_scratch_bytes: the bytes of `scratch` for T triangles and B items of N points (host only; 0 when one is below 1).
+ * df_mesh_icp:
+ *   DEVICE: vertices [V][3] fp32, in the units of the points; triangles [T][3] int32; obj [B] int32; points [B][N][3] fp32; pose_in
+ *   [B][7] fp64 (q wxyz, t; camera = R model + t: what df_estimate_poses_multi writes and df_add_metric reads); pose_out [B][7] fp64;
+ *   stats [B][6] fp64 = {status, inliers and rms of the first pass, inliers and rms of the last pass, steps taken}; status 0 ok,
+ *   1 few inliers, 2 degenerate, 3 bad object; scratch (16-byte aligned).
+ *   HOST, read during the call, launch arguments: tri_begin [O+1] int32, object o owns the triangles tri_begin[o] .. tri_begin[o+1]-1;
+ *   max_dist [O] fp64, the largest point-to-surface distance of an inlier (+inf: none).
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer; V, T, B or N below 1; 3 V, 3 T or 8 B N above INT_MAX; O outside
+ *   1..64; tri_begin decreasing or outside 0..T; a max_dist that is not > 0; iters outside 0..64; cull not 0 or 1; scratch short or
+ *   misaligned; a pointer not aligned to its element; pose_out or stats overlapping an input, the scratch or each other.
+ *   Per item:
+ *   S0. q = pose_in[0..3] / sqrt(((w w + x x) + y y) + z z), every component negated when w < 0 (the sign rule of the pose loop); t =
+ *       pose_in[4..6]; stats = 0.  obj outside 0..O-1 or an empty range: status = bad object, nothing is read through it, pose_out =
+ *       (q, t) and stats stay as they are now.  (A zero or NaN quaternion gives NaNs, no inlier and so `few inliers`.)
+ *   Then pass k = 0 .. iters, steps I1..I6 for every item whose status is 0, and I7..I9 as well when k < iters:
+ *   I1. R from q by the formula of the pose loop and of df_add_metric: n = ((w w + x x) + y y) + z z; n < 4 eps: R = I; otherwise
+ *       s = sqrt(2.0 / n), (w, x, y, z) *= s, R = [(1 - y y) - z z, x y - z w, x z + y w; x y + z w, (1 - x x) - z z, y z - x w;
+ *       x z - y w, y z + x w, (1 - x x) - y y].
+ *   I2. The point in the model frame, x = R^T (p - t), in the form Q1 of df_mesh_closest: X = [R^T | o] with o_j = -((R[0][j] t_x +
+ *       R[1][j] t_y) + R[2][j] t_z), the camera centre in the model frame; x_j = ((X[j][0] p_x + X[j][1] p_y) + X[j][2] p_z) + X[j][3],
+ *       p widened exactly from fp32.
+ *   I3. The closest point of the item's triangle range by M1, M2, D1..D5 of df_mesh_closest: the winner tri (-1: none), d2, c.
+ *   I4. The point is an inlier when tri >= 0, d2 is finite and d2 <= max_dist[obj] * max_dist[obj], the winner has a face (nn > 0),
+ *       and, with cull, n . (o - c) > 0 (n the winner's e1 x e2: the face looks at the camera).
+ *   I5. sn = sqrt(nn); nh = n / sn; r = nh . (x - c); J = (x x nh, nh), six numbers.
+ *   I6. Sums over the inliers: A[a][b] = sum J_a J_b (a <= b: 21), G[a] = sum r J_a (6), D = sum d2, and the count.  Order: lane l of
+ *       256 adds its points l, l + 256, ... in ascending order onto 0; in each group of 64 lanes a binary tree (s = 32, 16, .., 1: lane
+ *       l < s adds lane l + s); the four group totals as (T0 + T1) + (T2 + T3).  rms = sqrt(D / count), 0 with no inlier; stats' last
+ *       inliers and rms = count, rms; on pass 0 the first as well.
+ *   I7. count < 6: status = few inliers.  The item keeps its pose and is frozen: no later pass touches it, so its last inliers and rms
+ *       are those of this pass, which a later pass would find again.
+ *   I8. Cholesky A = L L^T by columns j = 0..5: s = A[j][j] - L[j][0]^2 - .. - L[j][j-1]^2 (left to right); s <= 2^-40 max_a A[a][a]
+ *       (or a NaN): status = degenerate, pose kept, frozen (geometry that does not constrain six degrees of freedom: one flat face).
+ *       L[j][j] = sqrt(s); L[i][j] = (A[i][j] - L[i][0] L[j][0] - .. - L[i][j-1] L[j][j-1]) / L[j][j].  Then L y = -G forwards,
+ *       y_i = (-G_i - L[i][0] y_0 - ..) / L[i][i], and L^T z = y backwards, z_i = (y_i - L[i+1][i] z_{i+1} - .. - L[5][i] z_5) / L[i][i];
+ *       z = (omega, dt): the model-frame motion x <- x + omega x x + dt that minimises the linearised sum of r^2.
+ *   I9. h = omega * 0.5; m = sqrt(((1 + h_x h_x) + h_y h_y) + h_z h_z); c = (1 / m, -(h_x / m), -(h_y / m), -(h_z / m)), the conjugate
+ *       of dq = (1, omega / 2) / |.|; q <- q (x) c (Hamilton product, each component summed left to right in the order w, x, y, z of q's
+ *       components), normalised with the sign rule as in S0 (so R <- R dR^T); R from the new q by I1; t_j <- t_j - ((R[j][0] dt_x +
+ *       R[j][1] dt_y) + R[j][2] dt_z); steps taken += 1.  No transcendental function.
+ *   I10. pose_out = (q, t): a unit quaternion with w >= 0.  The last pass (k = iters) only scores: with iters = 0 the call is a pure fit
+ *       score of the given poses. */
+size_t df_mesh_icp_scratch_bytes(int T, int B, int N);
+int df_mesh_icp(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *max_dist, int O,
+                const int *obj, const float *points, const double *pose_in, int B, int N, int iters, int cull, double *pose_out,
+                double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]

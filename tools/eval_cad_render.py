@@ -17,6 +17,13 @@ over the SERVED views (a view whose mask gives an item), the same over the KEPT 
 set for both sources: a kept view whose mask yields no item counts as a miss) and the numbers of kept and served views.  For ``segnet``
 it also holds per-class IoU, precision and recall, mean IoU and pixel accuracy against the rendered labels.  ``main`` returns all of it
 as a dict.
+
+``--icp ITERS`` (default 0: off) adds a geometric last step: every mask source is scored a second time on the same view seeds with the
+refined pose fitted to the item's own cloud by ``ITERS`` steps of point-to-plane ICP against the model's triangles (``df_mesh_icp``,
+DESIGN.md 12j).  ``--icp_max_dist FRAC`` drops points further from the surface than that fraction of the model cloud's diameter,
+``--icp_cull`` keeps only faces that look at the camera.  The second result is the entry ``<source>_icp`` with its own log
+``eval_result_logs_<source>_icp.txt``, which also counts the items ICP left alone (too few inliers, degenerate geometry) and gives the
+mean point-to-surface rms before and after.  Without ``--icp`` nothing changes by a byte.
 """
 from __future__ import annotations
 
@@ -56,6 +63,9 @@ def build_parser():
     ap.add_argument("--window", type=int, default=64, help="views per device call of the pose networks")
     ap.add_argument("--workers", type=int, default=2, help="threads that prepare chunks ahead of the device calls (0 = in the loop)")
     ap.add_argument("--feed", type=str, default="threads", choices=["threads"])
+    ap.add_argument("--icp", type=int, default=0, help="steps of point-to-mesh ICP after the refiner (0 = off); scored as <source>_icp")
+    ap.add_argument("--icp_max_dist", type=float, default=0.1, help="ICP drops points further from the surface than this fraction of the model cloud's diameter")
+    ap.add_argument("--icp_cull", action="store_true", help="ICP fits only faces that look at the camera")
     views = ap.add_argument_group("views", "the views and the renderer, under the names of tools/render_cad_dataset.py")
     cad_render.add_view_arguments(views)
     cad_symmetry.add_sym_arguments(views)
@@ -74,15 +84,35 @@ def _rate(a, b):
     return float(a) / b if b else 0.0
 
 
-def run_source(source, dataset, estimator, refiner, diameter, opt):
-    """``evaluate()`` over ``dataset`` and the tallies of one mask source."""
+class IcpStep:
+    """``evaluate()``'s ``refine_pose`` from a dataset's ``mesh_icp()``; keeps every call's stats on the device until ``summary``."""
+
+    def __init__(self, dataset, opt):
+        self.icp, self.iters, self.cull, self.stats = dataset.mesh_icp(), opt.icp, bool(opt.icp_cull), []
+        self.max_dist = [opt.icp_max_dist * cloud_diameter(dataset.pt[obj] * 10 / 10000.) for obj in dataset.objlist]
+
+    def __call__(self, pose, points, objs):
+        obj = torch.tensor(objs, dtype=torch.int32).pin_memory().to(pose.device, non_blocking=True)
+        pose, stats = self.icp.refine(points.reshape(len(objs), -1, 3), pose, obj, iters=self.iters, max_dist=self.max_dist, cull=self.cull)
+        self.stats.append(stats)
+        return pose
+
+    def summary(self):
+        st = torch.cat(self.stats).cpu().numpy() if self.stats else np.zeros((0, 6))
+        mean = lambda a: float(a.mean()) if len(a) else 0.0
+        return dict(items=len(st), few=int((st[:, 0] == 1).sum()), degenerate=int((st[:, 0] == 2).sum()), bad_object=int((st[:, 0] == 3).sum()),
+                    mean_first_rms=mean(st[:, 2]), mean_last_rms=mean(st[:, 4]), mean_steps=mean(st[:, 5]))
+
+
+def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None):
+    """``evaluate()`` over ``dataset`` and the tallies of one mask source; with ``icp`` (an ``IcpStep``) the poses take that last step."""
     objlist = list(dataset.objlist)
     n = len(dataset) if opt.max_frames <= 0 else min(opt.max_frames, len(dataset))
     with open(os.path.join(opt.output_result_dir, "eval_result_logs_%s.txt" % source), "w") as fw:
         def say(m):
             print(m)
             fw.write(m + "\n")
-        success, served = evaluate(dataset, estimator, refiner, diameter, opt, fw)
+        success, served = evaluate(dataset, estimator, refiner, diameter, opt, fw, **({} if icp is None else {"refine_pose": icp}))
         success, served = success[:len(objlist)], served[:len(objlist)]
         kept = [0] * len(objlist)
         for i in range(n):                                          # host records of chunks the loop has prepared (or prepares again)
@@ -96,6 +126,10 @@ def run_source(source, dataset, estimator, refiner, diameter, opt):
             say("[{0} masks] Object {1} success rate: {2} of {3} served views, {4} of {5} kept views".format(
                 source, obj, out["success_served"][k], served[k], out["success_kept"][k], kept[k]))
         say("[{0} masks] ALL success rate: {1} of served views, {2} of kept views".format(source, out["all_served"], out["all_kept"]))
+        if icp is not None:
+            out["icp"] = m = icp.summary()
+            say("[{0} masks] ICP {1} steps: {2} items, {3} few inliers, {4} degenerate, mean rms {5:.6g} -> {6:.6g}".format(
+                source, icp.iters, m["items"], m["few"], m["degenerate"], m["mean_first_rms"], m["mean_last_rms"]))
         if source == "segnet":
             m = dataset.seg_score.summary()
             out["seg"] = m
@@ -110,6 +144,8 @@ def main(argv=None):
     opt = build_parser().parse_args(argv)
     if len(opt.cad_model) > NUM_OBJECTS:
         raise SystemExit("at most %d models: the pose networks of tools/eval_cad.py have that many objects" % NUM_OBJECTS)
+    if not 0 <= opt.icp <= 64 or not opt.icp_max_dist > 0:
+        raise SystemExit("--icp takes 0..64 steps and --icp_max_dist a positive fraction")
     if not torch.cuda.is_available():
         raise SystemExit("eval_cad_render.py needs a GPU (densefusion_amd has no CPU path)")
     from densefusion_amd.datasets.customCAD.online import RenderedPoseDataset
@@ -141,6 +177,13 @@ def main(argv=None):
         print("symmetry object list: %s" % dataset.get_sym_list())
         result[source] = run_source(source, dataset, estimator, refiner, diameter, opt)
         result[source]["sym_list"] = dataset.get_sym_list()
+        if opt.icp > 0:                                             # the same views (the dataset serves them again), one more step per pose
+            try:
+                step = IcpStep(dataset, opt)
+            except ValueError as e:
+                raise SystemExit(f"eval_cad_render.py: --icp: {e}")
+            result[source + "_icp"] = run_source(source + "_icp", dataset, estimator, refiner, diameter, opt, icp=step)
+            result[source + "_icp"]["sym_list"] = dataset.get_sym_list()
     return result
 
 
