@@ -1,0 +1,211 @@
+// Render-and-compare verification of B estimated poses: each item's CAD mesh is drawn at its pose into a window of its own depth frame and
+// compared node by node with the observed depth codes and, optionally, a mask.  The contract is the comment of df_pose_verify in
+// include/dfusion.h: P2 is steps V2..V5 and T1..T7 of df_cad_render_mesh through the very device functions of cad_raster_core.h (hence the
+// same bits), P0, P1 and P3 are the functions of pose_verify_core.h; tests/pose_verify_np.py restates it in numpy and the twelve tallies
+// are compared bit for bit.  Built with -ffp-contract=off: no fused multiply-add anywhere.
+//
+// Steps on the caller's stream: the keys are set to all-ones and the stats to zero; verify_raster_kernel (grid = triangle blocks of the
+// largest object range x items) derives the item's [R | t] once per workgroup (one thread, handed over through LDS), sets up one triangle
+// per lane, cuts its node range to the window and walks it into the item's own key plane (walk_triangles: small ranges by the lane, large
+// ones by the whole wave); verify_score_kernel (grid = slot blocks x items) reads the key plane once, 8 bytes a lane along the window's
+// rows, with the observed code and the mask value of the node, counts the classes per wave with ballots, adds the workgroup's waves in LDS and
+// then takes one integer atomic per class and workgroup.  Integer atomics only: two identical calls give identical bytes.
+#include "cad_raster_core.h"
+#include "pose_verify_core.h"
+
+namespace df {
+namespace {
+
+namespace pv = poseverify;
+static_assert(pv::MAX_OBJECTS == DF_CAD_SCENE_MAX_OBJECTS, "the object table of df_cad_render_scene");
+
+// Workgroups a launch aims at over all items: 8 per compute unit of a 256-CU part.  The blocks per item are capped at this over B (and
+// at RASTER_MAX_BLOCKS / RESOLVE_MAX_BLOCKS); the waves stride over the rest.
+constexpr int VERIFY_TARGET_BLOCKS = 2048;
+
+// begin[o] .. begin[o + 1] - 1 are the triangles of object o; a launch argument, read with the block's own (uniform) object
+struct ObjectTable {
+  double scale[pv::MAX_OBJECTS];
+  int begin[pv::MAX_OBJECTS + 1];
+};
+
+inline ObjectTable make_table(const int *tri_begin, const double *model_scale, int O, int T) {
+  ObjectTable tab;
+  for (int k = 0; k <= pv::MAX_OBJECTS; ++k) tab.begin[k] = k <= O ? tri_begin[k] : T;
+  for (int k = 0; k < pv::MAX_OBJECTS; ++k) tab.scale[k] = k < O ? model_scale[k] : 0.0;
+  return tab;
+}
+
+struct Frames {
+  const unsigned short *depth, *mask;     // mask may be null
+  int F, NM, IH, IW;
+};
+
+__device__ inline void load_item(const int *__restrict__ items, int b, int *item) {
+#pragma unroll
+  for (int k = 0; k < pv::ITEM_INTS; ++k) item[k] = items[(size_t)b * pv::ITEM_INTS + k];
+}
+
+// a wave's total of a per-lane count, added to *dst by lane 0 (nothing when it is zero)
+__device__ inline void wave_add(unsigned long long v, long long *dst) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  if ((threadIdx.x & 63) == 0 && v) atomicAdd(reinterpret_cast<unsigned long long *>(dst), v);
+}
+
+__global__ __launch_bounds__(RB) void verify_raster_kernel(const float *__restrict__ vertices, int V, const int *__restrict__ triangles,
+                                                           ObjectTable tab, int O, Camera cam, Frames fr,
+                                                           const int *__restrict__ items, const double *__restrict__ pose,
+                                                           double cloud_div, int WH, int WW, int cull,
+                                                           unsigned long long *__restrict__ keys, long long *__restrict__ stats) {
+  __shared__ double M[12];
+  const int b = blockIdx.y;
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  if (pv::item_bad(item, fr.F, O, fr.mask != nullptr, fr.NM)) return;         // P0; the same in every lane of the block
+  const int o = item[pv::IT_OBJECT];
+  const long t0 = tab.begin[o], t1 = tab.begin[o + 1];
+  if ((long)blockIdx.x * RB >= t1 - t0) return;                               // the grid is sized for the largest range
+  if (threadIdx.x == 0) pv::pose_matrix(pose + (size_t)b * 7, cloud_div, M);  // P1, once per workgroup
+  __syncthreads();
+  const Pose P = load_pose(M);
+  const double scale = tab.scale[o];
+  int lo[2], hi[2];
+  pv::window_nodes(item[pv::IT_R0], item[pv::IT_C0], WH, WW, fr.IH, fr.IW, lo, hi);
+  // node (r, q) of the window is kf[r * WW + q]: raster_node's addressing with IW := WW
+  unsigned long long *kf = keys + ((long)b * WH * WW - ((long)item[pv::IT_R0] * WW + item[pv::IT_C0]));
+  const int lane = threadIdx.x & 63;
+  unsigned long long reached = 0, cut = 0;
+  // `base` is the same in all lanes of a wave, so the wave stays whole for the ballots and the shuffles of the walks
+  for (long base = t0 + (long)blockIdx.x * RB + (threadIdx.x - lane); base < t1; base += (long)gridDim.x * RB) {
+    const long i = base + lane;
+    Setup s;
+    bool live = i < t1 && load_triangle(s.tri, triangles, i, V);
+    if (live) live = setup_triangle(s, vertices, P, scale, cam, fr.IH, fr.IW, cull);
+    if (live) {                                                               // P2: the T4 range within the window
+      const int r0 = max(s.r0, lo[0]), r1 = min(s.r1, hi[0]), q0 = max(s.q0, lo[1]), q1 = min(s.q1, hi[1]);
+      live = r0 <= r1 && q0 <= q1;                                            // emptied: dropped, and not counted as cut
+      cut += live && (r0 != s.r0 || r1 != s.r1 || q0 != s.q0 || q1 != s.q1);
+      s.r0 = r0; s.r1 = r1; s.q0 = q0; s.q1 = q1;
+    }
+    reached += walk_triangles(s, live, base, kf, WW);                         // T7: the key carries the global triangle index
+  }
+  long long *sb = stats + (size_t)b * pv::NSTAT;
+  wave_add(reached, sb + pv::ST_TRIANGLES);
+  wave_add(cut, sb + pv::ST_CUT);
+}
+
+__global__ __launch_bounds__(RB) void verify_score_kernel(const unsigned long long *__restrict__ keys, Frames fr, int O,
+                                                          const int *__restrict__ items, int WH, int WW, int tol,
+                                                          long long *__restrict__ stats) {
+  constexpr int NTALLY = pv::ST_SUM_ABS - pv::ST_RENDERED + 1;                // the nine entries of a row this pass counts
+  __shared__ unsigned long long acc[NTALLY];
+  const int b = blockIdx.y;
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  long long *sb = stats + (size_t)b * pv::NSTAT;
+  if (pv::item_bad(item, fr.F, O, fr.mask != nullptr, fr.NM)) {               // P0
+    if (blockIdx.x == 0 && threadIdx.x == 0) sb[pv::ST_STATUS] = 1;
+    return;
+  }
+  const int slots = WH * WW;                                                  // <= 2^30
+  const size_t npix = (size_t)fr.IH * fr.IW;
+  const unsigned long long *kb = keys + (size_t)b * slots;
+  const unsigned short *df = fr.depth + (size_t)item[pv::IT_FRAME] * npix;
+  const unsigned short *mf = fr.mask ? fr.mask + (size_t)item[pv::IT_MASK_FRAME] * npix : nullptr;
+  const int r0 = item[pv::IT_R0], c0 = item[pv::IT_C0], mv = item[pv::IT_MASK_VALUE];
+  const int lane = threadIdx.x & 63;
+  // per-wave counts, the same in every lane (ballots); sum_abs per lane
+  unsigned long long n_rend = 0, n_agree = 0, n_front = 0, n_behind = 0, n_missing = 0, n_mask = 0, n_mobs = 0, n_unex = 0, sum_abs = 0;
+  for (int base = blockIdx.x * RB + (threadIdx.x - lane); base < slots; base += gridDim.x * RB) {
+    const int s = base + lane;
+    int r = 0, q = 0;
+    const bool exists = s < slots && pv::slot_node(s, r0, c0, WW, fr.IH, fr.IW, &r, &q);
+    int cls = pv::NOT_RENDERED, co = pv::NO_OBSERVATION;
+    bool m = false;
+    if (exists) {
+      const int cr = pv::key_code(kb[s]);
+      const size_t p = (size_t)r * fr.IW + q;
+      co = df[p];
+      m = mf && mf[p] == mv;
+      cls = pv::classify(cr, co, tol);
+      if (cls == pv::AGREE) sum_abs += (unsigned)(co > cr ? co - cr : cr - co);
+    }
+    n_rend += __popcll(__ballot(cls != pv::NOT_RENDERED));
+    n_agree += __popcll(__ballot(cls == pv::AGREE));
+    n_front += __popcll(__ballot(cls == pv::FRONT));
+    n_behind += __popcll(__ballot(cls == pv::BEHIND));
+    n_missing += __popcll(__ballot(cls == pv::MISSING));
+    n_mask += __popcll(__ballot(m));
+    n_mobs += __popcll(__ballot(m && co != pv::NO_OBSERVATION));
+    n_unex += __popcll(__ballot(pv::unexplained(m, co, cls)));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sum_abs += __shfl_down(sum_abs, off, 64);
+  // the workgroup's four waves meet in LDS (integer adds: any order gives the same sum), then one atomic per non-zero class
+  if (threadIdx.x < NTALLY) acc[threadIdx.x] = 0;
+  __syncthreads();
+  if (lane == 0) {
+    const unsigned long long v[NTALLY] = {n_rend, n_agree, n_front, n_behind, n_missing, n_mask, n_mobs, n_unex, sum_abs};
+#pragma unroll
+    for (int k = 0; k < NTALLY; ++k)
+      if (v[k]) atomicAdd(&acc[k], v[k]);
+  }
+  __syncthreads();
+  if (threadIdx.x < NTALLY && acc[threadIdx.x])
+    atomicAdd(reinterpret_cast<unsigned long long *>(sb + pv::ST_RENDERED + threadIdx.x), acc[threadIdx.x]);
+}
+
+inline bool window_ok(int B, int WH, int WW) { return B >= 1 && B <= 65535 && WH >= 1 && WW >= 1 && (long)WH * WW <= (1L << 30); }
+
+// blocks per item of a launch over `items` lanes' worth of work per item
+inline int item_blocks(long items, int B, int max_blocks) {
+  const int cap = cdiv(VERIFY_TARGET_BLOCKS, B) < max_blocks ? cdiv(VERIFY_TARGET_BLOCKS, B) : max_blocks;
+  return grid_blocks(items, cap < 1 ? 1 : cap);
+}
+
+}  // namespace
+}  // namespace df
+
+using namespace df;
+
+extern "C" size_t df_pose_verify_scratch_bytes(int B, int WH, int WW) {
+  return window_ok(B, WH, WW) ? (size_t)B * WH * WW * sizeof(unsigned long long) : 0;
+}
+
+extern "C" int df_pose_verify(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale,
+                              int O, const double *proj, const unsigned short *depth, int F, int IH, int IW, const unsigned short *mask,
+                              int NM, const int *items, const double *pose, double cloud_div, int B, int WH, int WW, int tol, int cull,
+                              long long *stats, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+  const char *name = "pose_verify";
+  if (!vertices || !triangles || !tri_begin || !model_scale || !proj || !depth || !items || !pose || !stats || !scratch)
+    return set_error(DF_ERR_ARG, "%s: null pointer", name);
+  if (mask && NM < 1) return set_error(DF_ERR_ARG, "%s: a mask needs NM >= 1 frames, got %d", name, NM);
+  if (O < 1 || O > pv::MAX_OBJECTS) return set_error(DF_ERR_ARG, "%s: O = %d objects outside 1..%d", name, O, pv::MAX_OBJECTS);
+  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
+  if (!window_ok(B, WH, WW)) return set_error(DF_ERR_ARG, "%s: B = %d outside 1..65535 or WH x WW = %d x %d outside 1..2^30", name, B, WH, WW);
+  if (tol < 0 || tol > 65535) return set_error(DF_ERR_ARG, "%s: tol %d outside 0..65535", name, tol);
+  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
+  if (!(cloud_div > 0.0 && cloud_div - cloud_div == 0.0)) return set_error(DF_ERR_ARG, "%s: cloud_div must be finite and > 0", name);
+  if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, df_pose_verify_scratch_bytes(B, WH, WW), proj)) return e;
+  if (tri_begin[0] != 0) return set_error(DF_ERR_ARG, "%s: tri_begin[0] = %d, not 0", name, tri_begin[0]);
+  int longest = 0;
+  for (int o = 0; o < O; ++o) {
+    if (tri_begin[o + 1] < tri_begin[o])
+      return set_error(DF_ERR_ARG, "%s: tri_begin decreases from %d to %d at object %d", name, tri_begin[o], tri_begin[o + 1], o);
+    longest = tri_begin[o + 1] - tri_begin[o] > longest ? tri_begin[o + 1] - tri_begin[o] : longest;
+  }
+  if (tri_begin[O] != T) return set_error(DF_ERR_ARG, "%s: tri_begin[O] = %d, not T = %d", name, tri_begin[O], T);
+  hipStream_t st = to_stream(stream);
+  const long slots = (long)WH * WW;
+  if (hipMemsetAsync(scratch, 0xff, (size_t)B * slots * sizeof(unsigned long long), st) != hipSuccess ||
+      hipMemsetAsync(stats, 0, sizeof(long long) * pv::NSTAT * B, st) != hipSuccess)
+    return check_launch(name);
+  unsigned long long *keys = static_cast<unsigned long long *>(scratch);
+  const Frames fr = {depth, mask, F, NM, IH, IW};
+  const int tb = item_blocks(longest, B, RASTER_MAX_BLOCKS), xb = item_blocks(slots, B, RESOLVE_MAX_BLOCKS);
+  hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles, make_table(tri_begin, model_scale, O, T), O,
+                     make_camera(proj), fr, items, pose, cloud_div, WH, WW, cull, keys, stats);
+  hipLaunchKernelGGL(verify_score_kernel, dim3(xb, B), dim3(RB), 0, st, keys, fr, O, items, WH, WW, tol, stats);
+  return check_launch(name);
+}

@@ -145,14 +145,17 @@ class RenderedPoseDataset(ChunkedViews):
     ``symmetry``: "none" (``get_sym_list() == []``), "auto" (meshes only: ``symmetry.detect_symmetry`` per model at construction with
     ``tol`` = ``symmetry_tol``, the reports kept in ``self.symmetry`` by model index) or a list of model indices.  The list holds the
     values an item's index takes (model k = index k = object k + 1), which is what the losses, the native trainer and ``evaluate()``
-    compare.  No item changes by a byte: the detection draws from a generator of its own."""
+    compare.  No item changes by a byte: the detection draws from a generator of its own.
+    ``keep_frames``: ``view_info`` also carries ``depth`` and ``mask``, device views [IH,IW] uint16 of the frames the item was cut from
+    (after the sensor; the mask in use), and ``box`` = (rmin, rmax, cmin, cmax) of its crop: what ``pose_verifier()`` scores a pose
+    against.  The frames of a cached chunk then stay on the device as long as the chunk does.  No item changes by a byte."""
 
     def __init__(self, models, num=500, add_noise=False, noise_trans=0.0, refine=False, *, distractors=(), scene=None, raster="points",
                  splat=1, cull=1, mask="box", light="none", shading="flat", light_angle=60.0, sensor=None, sensor_seed=0, proj_mat=None,
                  image_dims=(520, 1109), center=(0.0, 0.0, 4.0), scene_scale=1.0, model_scale=10.0, min_pixels=500, min_visible=0.3,
                  p_present=0.7, lateral=0.8, depth=0.8, max_holes=3, hole_mean=30.0, hole_std=10.0, chunk=32, points=0, first_seed=0,
                  frames=2000, jitter="device", device="cuda", cache_chunks=4, segnet=None, seg_window=None, seg_blur=1, symmetry="none",
-                 symmetry_tol=0.01):
+                 symmetry_tol=0.01, keep_frames=False):
         models = [models] if _is_path(models) or (isinstance(models, tuple) and not _is_path(models[0]) and np.ndim(models[0]) == 2) else list(models)
         distractors = list(distractors)
         self.scene = bool(scene) if scene is not None else (len(models) > 1 or len(distractors) > 0)
@@ -174,7 +177,7 @@ class RenderedPoseDataset(ChunkedViews):
         self.min_pixels, self.min_visible = int(min_pixels), float(min_visible)
         self.p_present, self.lateral, self.depth = float(p_present), float(lateral), float(depth)
         self.max_holes, self.hole_mean, self.hole_std = int(max_holes), float(hole_mean), float(hole_std)
-        self.jitter = jitter
+        self.jitter, self.keep_frames = jitter, bool(keep_frames)
         self.trancolor = augment.ColorJitter(0.2, 0.2, 0.2, 0.05)
         proj = cr.DEFAULT_PROJ if proj_mat is None else (read_proj_mat(proj_mat) if _is_path(proj_mat) else proj_mat)
         self.proj_mat = np.array(proj, dtype=np.float64).reshape(4, 4)
@@ -252,7 +255,7 @@ class RenderedPoseDataset(ChunkedViews):
 
     @classmethod
     def from_options(cls, opt, models, distractors=(), *, first_seed=0, frames=2000, num=500, add_noise=False, noise_trans=0.0, refine=False,
-                     device="cuda", scene=None, segnet=None, seg_window=None, seg_blur=1, symmetry=None):
+                     device="cuda", scene=None, segnet=None, seg_window=None, seg_blur=1, symmetry=None, keep_frames=False):
         """The dataset of parsed ``render.add_view_arguments`` options: the views tools/render_cad_dataset.py renders with the same
         flags, ``--model`` = ``models``, ``--distractor`` = ``distractors`` and ``--seed`` = ``first_seed`` (several models or a
         distractor: ``--scene``, which ``scene=True`` also asks of one model alone).  ``ValueError`` for flags the tool refuses."""
@@ -267,7 +270,7 @@ class RenderedPoseDataset(ChunkedViews):
                    hole_std=opt.hole_std, chunk=opt.chunk, points=opt.points, first_seed=first_seed, frames=frames, device=device,
                    scene=scene, segnet=segnet, seg_window=seg_window, seg_blur=seg_blur,
                    symmetry=symmetry if symmetry is not None else parse_sym_option(getattr(opt, "cad_sym", "none")),
-                   symmetry_tol=getattr(opt, "cad_sym_tol", 0.01))
+                   symmetry_tol=getattr(opt, "cad_sym_tol", 0.01), keep_frames=keep_frames)
 
     def get_sym_list(self):
         """The item indices (model k = index k) that are trained and scored with ADD-S: [] unless ``symmetry`` asked for some."""
@@ -280,6 +283,15 @@ class RenderedPoseDataset(ChunkedViews):
             raise ValueError('mesh_icp needs triangles: a scene or raster mesh (a point cloud has none)')
         from ...lib.mesh_icp import MeshIcp
         return MeshIcp(self._icp_meshes, self.model_scale / 10000.0, device=self.device)
+
+    def pose_verifier(self):
+        """A ``lib.pose_verify.PoseVerifier`` of the models' triangles, in file units with the renderer's model scale, camera and frame
+        size: an item's index k names mesh k, and a pose in the units of the items' clouds is drawn as the renderer would draw it.
+        ``ValueError`` in point-cloud mode: there are no triangles to draw."""
+        if self._icp_meshes is None:
+            raise ValueError('pose_verifier needs triangles: a scene or raster mesh (a point cloud has none)')
+        from ...lib.pose_verify import PoseVerifier
+        return PoseVerifier(self._icp_meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
 
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small
@@ -369,6 +381,8 @@ class RenderedPoseDataset(ChunkedViews):
                                  visible=float(frac), kept=bool(kept), live=bool(kept and row[7]), add_t=draws[j][0], plan=draws[j][1],
                                  choose_seed=draws[j][2], subset_seed=draws[j][3], mask_source=self.mask_source,
                                  conf=None if seg_conf is None else seg_conf[j], seg_counts=None if seg_counts is None else seg_counts[j]))
+                if self.keep_frames:
+                    info[-1].update(depth=depth[j], mask=mask[j], box=tuple(int(x) for x in row[2:6]))
                 if info[-1]["live"]:
                     live.append(j)
             items = [_sentinel() for _ in range(F)]

@@ -747,6 +747,53 @@ int df_mesh_icp(const float *vertices, int V, const int *triangles, int T, const
                 double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Render-and-compare verification of B estimated poses (densefusion_amd/lib/pose_verify.py): the CAD mesh of each item is drawn at its
+ * pose into a window of the item's own depth frame and compared, node by node, with the observed depth codes and optionally with a mask;
+ * the result is twelve integer tallies per item.  No allocation, no synchronisation, the caller's stream; integer atomics only, so two
+ * identical calls give identical bytes, and an item's row depends on its own record, pose, object, frame and mask only, not on B or on
+ * the items next to it.  The fp64 part uses + - * / sqrt only, one rounding per operation in the order written (no contraction);
+ * tests/pose_verify_np.py restates the call and all twelve columns are compared bit for bit.
+ *
+ * df_pose_verify_scratch_bytes: B*WH*WW 64-bit keys; 0 for sizes the call refuses (host only).
+ * df_pose_verify:
+ *   DEVICE: vertices [V][3] fp32 (file units) and triangles [T][3] int32 of O meshes laid one after another, as for df_cad_render_scene;
+ *   depth [F][IH][IW] uint16, the observed depth codes (65535: no observation); mask [NM][IH][IW] uint16 or NULL; items [B][6] int32;
+ *   pose [B][7] fp64 (q wxyz, t; camera = R model + t in cloud units: what df_estimate_poses_multi and df_mesh_icp write); stats
+ *   [B][12] int64; scratch (8-byte aligned).
+ *   HOST, read during the call, launch arguments: tri_begin [O+1], model_scale [O] as for df_cad_render_scene; proj, 16 doubles in
+ *   df_cad_render's form.
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer (mask excepted); mask != NULL with NM < 1; B outside 1..65535;
+ *   WH or WW below 1 or WH*WW above 2^30; F, IH, IW, V, T, O, tri_begin and proj as df_cad_render_scene refuses them; tol outside
+ *   0..65535; cull not 0 or 1; cloud_div not finite or <= 0; scratch short or not 8-byte aligned.
+ *   Item record: items[b] = {frame, object, r0, c0, mask_frame, mask_value}.  The window of item b is rows r0 .. r0+WH-1 and columns
+ *   c0 .. c0+WW-1 of its frame; r0 and c0 may be negative and the window may hang over any edge of the frame: only the nodes inside both
+ *   window and frame exist (corner + size is taken in 64 bits).  Window slot (r - r0) * WW + (q - c0) of item b is key b*WH*WW + slot.
+ *   P0. Bad item: frame outside 0..F-1, object outside 0..O-1 or, with mask != NULL, mask_frame outside 0..NM-1: stats[b] = {1, 0, ...}
+ *       and nothing is read through the record.  An empty triangle range is not bad: it renders nothing.
+ *   P1. Pose: R from q by the formula of df_mesh_icp's step I1 (quat_to_mat of mesh_icp_core.h, unchanged: q need not be a unit
+ *       quaternion; n < 4 eps gives R = I); t_j = pose[4 + j] * cloud_div.  [R | t] is a renderer's pose in its camera space (x right,
+ *       y up, looking along -z).  A NaN in the pose draws nothing: T3 drops every triangle.
+ *   P2. Raster, for the triangles tri_begin[object] .. tri_begin[object+1]-1: V2..V5 with model_scale[object] and T1..T6 of
+ *       df_cad_render_mesh, verbatim, with no holes.  The node range of T4 is then intersected with the window; a triangle whose range
+ *       becomes empty is dropped.  T7 into the item's own key plane: key = code << 32 | index of the triangle in the call's array, the
+ *       smallest key per node wins (integer atomicMin).
+ *   P3. Score, per existing node (r, q), all integer: cr = key >> 32, or "not rendered" when the node took no key; co =
+ *       depth[frame][r][q], 65535 meaning "no observation"; m = mask != NULL and mask[mask_frame][r][q] == mask_value (a mask_value
+ *       outside 0..65535 matches nothing).  A rendered node is `missing` when there is no observation, otherwise `agree` when
+ *       |co - cr| <= tol, `front` when co < cr - tol (something nearer is in the way: neutral) and `behind` when co > cr + tol (the
+ *       sensor sees through the model).  A node is `unexplained` when m holds, it is observed, and it is not rendered or `front`.
+ *   stats[b] = {status (0, or 1: bad item), rendered, agree, front, behind, missing, mask (nodes with m), mask_observed (m and observed),
+ *       unexplained, sum_abs (the sum of |co - cr| over `agree`), triangles that took at least one key test, live triangles (T1..T4)
+ *       whose node range the window cut short (those it emptied are dropped and not counted)}.  A window wholly outside the frame
+ *       gives a row of zeros.  Every entry is int64: sum_abs passes 2^31 on an ordinary
+ *       window. */
+size_t df_pose_verify_scratch_bytes(int B, int WH, int WW);
+int df_pose_verify(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale, int O,
+                   const double *proj, const unsigned short *depth, int F, int IH, int IW, const unsigned short *mask, int NM,
+                   const int *items, const double *pose, double cloud_div, int B, int WH, int WW, int tol, int cull, long long *stats,
+                   void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]

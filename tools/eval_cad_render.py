@@ -24,6 +24,11 @@ DESIGN.md 12j).  ``--icp_max_dist FRAC`` drops points further from the surface t
 ``--icp_cull`` keeps only faces that look at the camera.  The second result is the entry ``<source>_icp`` with its own log
 ``eval_result_logs_<source>_icp.txt``, which also counts the items ICP left alone (too few inliers, degenerate geometry) and gives the
 mean point-to-surface rms before and after.  Without ``--icp`` nothing changes by a byte.
+``--verify`` scores every pose against the depth frame it came from by drawing the model at the pose (``df_pose_verify``):
+each entry's log gains the mean visible-surface IoU of its passes and of its misses, and with ``--icp`` a third entry
+``<source>_icp_best`` takes, per item, the ICP pose where its IoU is strictly higher and the refiner's otherwise, and says how many items
+took each.  ``--verify_tol`` is the agreement tolerance in depth codes, ``--verify_margin`` how far the window reaches beyond the item's
+crop box.  Without ``--verify`` nothing changes by a byte.
 """
 from __future__ import annotations
 
@@ -66,6 +71,10 @@ def build_parser():
     ap.add_argument("--icp", type=int, default=0, help="steps of point-to-mesh ICP after the refiner (0 = off); scored as <source>_icp")
     ap.add_argument("--icp_max_dist", type=float, default=0.1, help="ICP drops points further from the surface than this fraction of the model cloud's diameter")
     ap.add_argument("--icp_cull", action="store_true", help="ICP fits only faces that look at the camera")
+    ap.add_argument("--verify", action="store_true", help="score every pose by render-and-compare against its depth frame; with --icp also <source>_icp_best")
+    ap.add_argument("--verify_tol", type=int, default=4, help="depth codes within which rendered and observed depth agree: about three sigmas of "
+                    "the sensor's noise in codes (--sensor_sigma) plus its quantum (--sensor_quant); 4 suits a clean render")
+    ap.add_argument("--verify_margin", type=int, default=8, help="pixels the verification window reaches beyond the item's crop box")
     views = ap.add_argument_group("views", "the views and the renderer, under the names of tools/render_cad_dataset.py")
     cad_render.add_view_arguments(views)
     cad_symmetry.add_sym_arguments(views)
@@ -104,15 +113,71 @@ class IcpStep:
                     mean_first_rms=mean(st[:, 2]), mean_last_rms=mean(st[:, 4]), mean_steps=mean(st[:, 5]))
 
 
-def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None):
-    """``evaluate()`` over ``dataset`` and the tallies of one mask source; with ``icp`` (an ``IcpStep``) the poses take that last step."""
+class VerifyStep:
+    """``evaluate()``'s ``select_pose`` from a dataset's ``pose_verifier()`` (the dataset keeps its frames): every candidate is scored
+    against the item's own depth frame and mask in the window of its crop box grown by ``--verify_margin`` (one size per call: the
+    largest).  ``choose``: of two candidates the second is taken where ``better`` says so; otherwise the last candidate goes on as it is.
+    The scores stay on the device until ``summary``."""
+
+    def __init__(self, dataset, opt, choose=False):
+        self.dataset, self.ver, self.choose = dataset, dataset.pose_verifier(), bool(choose)
+        self.tol, self.margin, self.cull = opt.verify_tol, opt.verify_margin, bool(dataset.cull)
+        self.indices, self.scores, self.taken = [], [], []
+
+    def __call__(self, indices, candidates, objs):
+        from densefusion_amd.lib.pose_verify import better, vsiou
+        infos = [self.dataset.view_info(i) for i in indices]
+        dev, B = candidates[0].device, len(indices)
+        depth, mask = torch.stack([f["depth"] for f in infos]), torch.stack([f["mask"] for f in infos])
+        window = (max(f["box"][1] - f["box"][0] for f in infos) + 2 * self.margin, max(f["box"][3] - f["box"][2] for f in infos) + 2 * self.margin)
+        rec = torch.tensor([[k, objs[k], f["box"][0] - self.margin, f["box"][2] - self.margin] for k, f in enumerate(infos)],
+                           dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        stats = [self.ver.score(depth, c.contiguous(), rec[:, 0], rec[:, 1], rec[:, 2:4], window, self.tol, mask=mask, cull=self.cull)
+                 for c in (candidates if self.choose else candidates[-1:])]
+        pose, score = candidates[-1], vsiou(stats[-1])
+        take = torch.ones(B, dtype=torch.bool, device=dev)
+        if self.choose and len(candidates) == 2:
+            take = better(stats[0], stats[1])
+            pose, score = torch.where(take[:, None], candidates[1], candidates[0]), torch.where(take, score, vsiou(stats[0]))
+        self.indices += list(indices)
+        self.scores.append(score); self.taken.append(take)
+        return pose
+
+    def summary(self, passed):
+        """``passed``: {dataset index: bool} of the scored items."""
+        score = torch.cat(self.scores).cpu().numpy() if self.scores else np.zeros(0)
+        taken = torch.cat(self.taken).cpu().numpy() if self.taken else np.zeros(0, dtype=bool)
+        ok = np.array([bool(passed[i]) for i in self.indices], dtype=bool)
+        mean = lambda a: float(a.mean()) if len(a) else 0.0
+        return dict(items=len(score), passes=int(ok.sum()), mean_vsiou_pass=mean(score[ok]), mean_vsiou_miss=mean(score[~ok]),
+                    took_last=int(taken.sum()), took_first=int((~taken).sum()), tol=self.tol, margin=self.margin)
+
+
+class _PassLog:
+    """The log file of ``evaluate()`` with an ear: ``passed[i]`` of every "No.i Pass!" / "No.i NOT Pass! Distance" line that goes by."""
+
+    def __init__(self, fw):
+        self.fw, self.passed = fw, {}
+
+    def write(self, text):
+        head = text.split(" ", 1)
+        if head[0].startswith("No.") and "Lost detection" not in text:
+            self.passed[int(head[0][3:])] = head[1].startswith("Pass!")
+        return self.fw.write(text)
+
+
+def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, verify=None):
+    """``evaluate()`` over ``dataset`` and the tallies of one mask source; with ``icp`` (an ``IcpStep``) the poses take that last step,
+    with ``verify`` (a ``VerifyStep``) they are scored, or chosen, by render-and-compare."""
     objlist = list(dataset.objlist)
     n = len(dataset) if opt.max_frames <= 0 else min(opt.max_frames, len(dataset))
     with open(os.path.join(opt.output_result_dir, "eval_result_logs_%s.txt" % source), "w") as fw:
         def say(m):
             print(m)
             fw.write(m + "\n")
-        success, served = evaluate(dataset, estimator, refiner, diameter, opt, fw, **({} if icp is None else {"refine_pose": icp}))
+        steps = dict(**({} if icp is None else {"refine_pose": icp}), **({} if verify is None else {"select_pose": verify}))
+        log = fw if verify is None else _PassLog(fw)
+        success, served = evaluate(dataset, estimator, refiner, diameter, opt, log, **steps)
         success, served = success[:len(objlist)], served[:len(objlist)]
         kept = [0] * len(objlist)
         for i in range(n):                                          # host records of chunks the loop has prepared (or prepares again)
@@ -130,6 +195,12 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None):
             out["icp"] = m = icp.summary()
             say("[{0} masks] ICP {1} steps: {2} items, {3} few inliers, {4} degenerate, mean rms {5:.6g} -> {6:.6g}".format(
                 source, icp.iters, m["items"], m["few"], m["degenerate"], m["mean_first_rms"], m["mean_last_rms"]))
+        if verify is not None:
+            out["verify"] = m = verify.summary(log.passed)
+            say("[{0} masks] verify tol {1} margin {2}: mean vsiou {3:.6f} over {4} passes, {5:.6f} over {6} misses".format(
+                source, m["tol"], m["margin"], m["mean_vsiou_pass"], m["passes"], m["mean_vsiou_miss"], m["items"] - m["passes"]))
+            if verify.choose:
+                say("[{0} masks] verify: {1} items took the ICP pose, {2} kept the refiner's".format(source, m["took_last"], m["took_first"]))
         if source == "segnet":
             m = dataset.seg_score.summary()
             out["seg"] = m
@@ -146,6 +217,8 @@ def main(argv=None):
         raise SystemExit("at most %d models: the pose networks of tools/eval_cad.py have that many objects" % NUM_OBJECTS)
     if not 0 <= opt.icp <= 64 or not opt.icp_max_dist > 0:
         raise SystemExit("--icp takes 0..64 steps and --icp_max_dist a positive fraction")
+    if not 0 <= opt.verify_tol <= 65535 or not 0 <= opt.verify_margin <= 4096:
+        raise SystemExit("--verify_tol takes 0..65535 codes and --verify_margin 0..4096 pixels")
     if not torch.cuda.is_available():
         raise SystemExit("eval_cad_render.py needs a GPU (densefusion_amd has no CPU path)")
     from densefusion_amd.datasets.customCAD.online import RenderedPoseDataset
@@ -168,22 +241,35 @@ def main(argv=None):
         try:
             # SegNet's masks need the scene renderer's label plane; the truth run of the same call renders the same scenes
             dataset = RenderedPoseDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=opt.cad_seed, frames=opt.cad_frames,
-                                                       num=NUM_POINTS, scene=True if segnet is not None else None, **kw)
+                                                       num=NUM_POINTS, scene=True if segnet is not None else None, **kw,
+                                                       **({"keep_frames": True} if opt.verify else {}))
         except ValueError as e:
             raise SystemExit(f"eval_cad_render.py: {e}")
+
+        def verifier(choose=False):
+            """a fresh ``VerifyStep`` for one scored entry; None without --verify"""
+            return VerifyStep(dataset, opt, choose) if opt.verify else None
+        try:
+            first = verifier()
+        except ValueError as e:
+            raise SystemExit(f"eval_cad_render.py: --verify: {e}")
         # the loader's clouds are in units of 10000 (model * 10 / 10000): so is the threshold (tools/eval_cad.py)
         diameter = [opt.threshold_frac * cloud_diameter(dataset.pt[obj] * 10 / 10000.) for obj in dataset.objlist]
         diameter += [0.0] * (NUM_OBJECTS - len(diameter))
         print("symmetry object list: %s" % dataset.get_sym_list())
-        result[source] = run_source(source, dataset, estimator, refiner, diameter, opt)
+        result[source] = run_source(source, dataset, estimator, refiner, diameter, opt, verify=first)
         result[source]["sym_list"] = dataset.get_sym_list()
         if opt.icp > 0:                                             # the same views (the dataset serves them again), one more step per pose
             try:
                 step = IcpStep(dataset, opt)
             except ValueError as e:
                 raise SystemExit(f"eval_cad_render.py: --icp: {e}")
-            result[source + "_icp"] = run_source(source + "_icp", dataset, estimator, refiner, diameter, opt, icp=step)
+            result[source + "_icp"] = run_source(source + "_icp", dataset, estimator, refiner, diameter, opt, icp=step, verify=verifier())
             result[source + "_icp"]["sym_list"] = dataset.get_sym_list()
+            if opt.verify:                                          # per item the pose with the higher visible-surface IoU
+                name = source + "_icp_best"
+                result[name] = run_source(name, dataset, estimator, refiner, diameter, opt, icp=IcpStep(dataset, opt), verify=verifier(True))
+                result[name]["sym_list"] = dataset.get_sym_list()
     return result
 
 

@@ -47,14 +47,17 @@ def build_parser():
     return ap
 
 
-def evaluate(testdataset, estimator, refiner, diameter, opt, fw=None, on_pose=None, refine_pose=None):
+def evaluate(testdataset, estimator, refiner, diameter, opt, fw=None, on_pose=None, refine_pose=None, select_pose=None):
     """The loop of tools/eval_linemod.py:68-139; returns (success_count, num_count) per object.  Frames are taken ``--window`` at
     a time: the crops of a window are bucketed by size and run through PoseNet -> arg-max pose -> refine loop as ONE device
     call (``estimate_multi``), the ADD / ADD-S distances of the window as one ``add_metric`` launch; the log lines come out in
     frame order and do not depend on the window (per-object results are bit-identical to frame-by-frame calls).
     ``on_pose(i, pose [7], model_points [M,3], target [M,3])``, if given, sees every live frame's refined pose and the clouds it is scored on.
     ``refine_pose(pose [B,7], points [B,N,3], objs: list of B indices) -> pose [B,7]``, if given, is a last step between the refiner and
-    the metric (``lib.mesh_icp.MeshIcp.refine`` against the CAD surface); None changes nothing."""
+    the metric (``lib.mesh_icp.MeshIcp.refine`` against the CAD surface); None changes nothing.
+    ``select_pose(indices: list of B dataset indices, candidates: list of pose [B,7], objs) -> pose [B,7]``, if given, has the last word:
+    ``candidates`` is [the refiner's pose], plus the ``refine_pose`` result when that is given, and what it returns is scored (a
+    per-item choice by ``lib.pose_verify``, say); None changes nothing."""
     num_objects = len(diameter)
     pe = PoseEstimator(estimator, refiner)
     sym_list = testdataset.get_sym_list()
@@ -83,8 +86,12 @@ def evaluate(testdataset, estimator, refiner, diameter, opt, fw=None, on_pose=No
             idx = torch.stack([live[k][1][5].reshape(-1)[0] for k in order]).to(dev)
             _, pose = pe.estimate_multi(imgs, points, choose, idx, opt.iteration)
             objs = [int(live[k][1][5].reshape(-1)[0]) for k in order]
+            candidates = [pose]
             if refine_pose is not None:
                 pose = refine_pose(pose, points, objs)
+                candidates.append(pose)
+            if select_pose is not None:
+                pose = select_pose([live[k][0] for k in order], candidates, objs)
             dis = add_metric(pose, model_points, target, [1 if o in sym_list else 0 for o in objs]).cpu().tolist()
             dist = {live[k][0]: (objs[j], dis[j]) for j, k in enumerate(order)}
             if on_pose is not None:
