@@ -218,3 +218,21 @@ def dptr(t) -> int:
     if not t.is_contiguous():
         raise RuntimeError("densefusion_amd ops need contiguous tensors")
     return t.data_ptr()
+
+
+def need_tensor(t, what, name, dtypes, shape, device):
+    """`t` made contiguous, or the ``RuntimeError`` of op `what` about its argument `name`: a tensor of one of `dtypes` and of `shape` (None
+    = any size; a tuple of shapes: any one of them) on `device` (None: any GPU)."""
+    import torch
+    shapes = shape if isinstance(shape[0], tuple) else (shape,)
+    if (not torch.is_tensor(t) or not (t.is_cuda if device is None else t.device == device) or t.dtype not in dtypes
+            or not any(t.dim() == len(s) and all(n is None or t.shape[k] == n for k, n in enumerate(s)) for s in shapes)):
+        want = " or ".join(str([n if n is not None else "n" for n in s]) for s in shapes)
+        raise RuntimeError(f"{what}: {name} must be a {' or '.join(str(d) for d in dtypes)} tensor of shape {want} on {device or 'a GPU'} (no CPU path)")
+    return t.contiguous()
+
+
+def grow_scratch(old_scratch, nbytes, device):
+    """A uint8 scratch tensor of at least `nbytes` on `device`: the old one, or a new one of exactly that size when it is too small."""
+    import torch
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if old_scratch is None or old_scratch.numel() < nbytes else old_scratch

@@ -13,25 +13,12 @@
 // integer atomics (the max-encoded scheme of reduce_frame_stats).  scene_finish_kernel decodes the boxes.  The object table (tri_begin,
 // model_scale) is checked on the host and travels as a launch argument.
 #include "cad_raster_core.h"
+#include "mesh_objects.h"
 
 namespace df {
 namespace {
 
-constexpr int MAX_OBJECTS = DF_CAD_SCENE_MAX_OBJECTS;
 static_assert(MAX_OBJECTS == 64, "owner_of searches a table of 64 entries in six steps");
-
-// begin[o] .. begin[o + 1] - 1 are the triangles of object o; entries past O hold T, so that a search over all 64 stays below O
-struct Objects {
-  double scale[MAX_OBJECTS];
-  int begin[MAX_OBJECTS + 1];
-};
-
-inline Objects make_objects(const int *tri_begin, const double *model_scale, int O, int T) {
-  Objects ob;
-  for (int k = 0; k <= MAX_OBJECTS; ++k) ob.begin[k] = k <= O ? tri_begin[k] : T;
-  for (int k = 0; k < MAX_OBJECTS; ++k) ob.scale[k] = k < O ? model_scale[k] : 0.0;
-  return ob;
-}
 
 // the object table in LDS: every lane searches it with its own index
 struct ObjectsLds {
@@ -39,7 +26,7 @@ struct ObjectsLds {
   int begin[MAX_OBJECTS];
 };
 
-__device__ inline void stage_objects(ObjectsLds &s, const Objects &ob) {
+__device__ inline void stage_objects(ObjectsLds &s, const ObjectTable &ob) {
   if (threadIdx.x < MAX_OBJECTS) {
     s.scale[threadIdx.x] = ob.scale[threadIdx.x];
     s.begin[threadIdx.x] = ob.begin[threadIdx.x];
@@ -74,7 +61,7 @@ __device__ inline void flush_reached(int o, int reached, int *__restrict__ sf) {
 
 // While the blocks reduce, stats[f][o][1] counts the triangles of object o that took at least one key test.
 __global__ __launch_bounds__(RB) void scene_raster_kernel(const float *__restrict__ vertices, int V, const int *__restrict__ triangles, int T,
-                                                          Objects objects, int O, const double *__restrict__ pose,
+                                                          ObjectTable objects, int O, const double *__restrict__ pose,
                                                           const unsigned char *__restrict__ present, Camera cam, int IH, int IW, int cull,
                                                           unsigned long long *__restrict__ keys, int *__restrict__ stats) {
   __shared__ ObjectsLds tab;
@@ -128,7 +115,7 @@ __device__ inline void flush_gather(Gather &g, int *__restrict__ sf) {
 template <bool LIT>
 __global__ __launch_bounds__(RB) void scene_resolve_kernel(const unsigned long long *__restrict__ keys, const float *__restrict__ vertices,
                                                            const unsigned char *__restrict__ colors, const int *__restrict__ triangles,
-                                                           Objects objects, int O, const double *__restrict__ pose, Camera cam, int IH,
+                                                           ObjectTable objects, int O, const double *__restrict__ pose, Camera cam, int IH,
                                                            int IW, const float *__restrict__ normals, int normal_mode,
                                                            const double *__restrict__ light, unsigned char *__restrict__ rgb,
                                                            unsigned short *__restrict__ depth, unsigned short *__restrict__ label,
@@ -210,8 +197,6 @@ __global__ __launch_bounds__(RB) void scene_mask_kernel(const unsigned short *__
   }
 }
 
-inline bool objects_ok(int O) { return O >= 1 && O <= MAX_OBJECTS; }
-
 }  // namespace
 }  // namespace df
 
@@ -238,14 +223,10 @@ static int render_scene(const char *name, const float *vertices, const unsigned 
   if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
   if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
   if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, df_cad_render_scene_scratch_bytes(F, IH, IW, V, T, O), proj)) return e;
-  if (tri_begin[0] != 0) return set_error(DF_ERR_ARG, "%s: tri_begin[0] = %d, not 0", name, tri_begin[0]);
-  for (int o = 0; o < O; ++o)
-    if (tri_begin[o + 1] < tri_begin[o])
-      return set_error(DF_ERR_ARG, "%s: tri_begin decreases from %d to %d at object %d", name, tri_begin[o], tri_begin[o + 1], o);
-  if (tri_begin[O] != T) return set_error(DF_ERR_ARG, "%s: tri_begin[O] = %d, not T = %d", name, tri_begin[O], T);
+  if (int e = check_tri_begin(name, tri_begin, O, T, nullptr)) return e;
   hipStream_t st = to_stream(stream);
   const Camera cam = make_camera(proj);
-  const Objects objects = make_objects(tri_begin, model_scale, O, T);
+  const ObjectTable objects = make_object_table(tri_begin, model_scale, O, T);
   const long npix = (long)IH * IW;
   if (!clear_frames(scratch, F, npix, stats_out, (size_t)F * O, st)) return check_launch(name);
   unsigned long long *keys = static_cast<unsigned long long *>(scratch);

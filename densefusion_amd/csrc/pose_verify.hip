@@ -11,30 +11,18 @@
 // rows, with the observed code and the mask value of the node, counts the classes per wave with ballots, adds the workgroup's waves in LDS and
 // then takes one integer atomic per class and workgroup.  Integer atomics only: two identical calls give identical bytes.
 #include "cad_raster_core.h"
+#include "mesh_objects.h"
 #include "pose_verify_core.h"
 
 namespace df {
 namespace {
 
 namespace pv = poseverify;
-static_assert(pv::MAX_OBJECTS == DF_CAD_SCENE_MAX_OBJECTS, "the object table of df_cad_render_scene");
+static_assert(pv::MAX_OBJECTS == MAX_OBJECTS, "item_bad's objects are those of the object table (mesh_objects.h)");
 
 // Workgroups a launch aims at over all items: 8 per compute unit of a 256-CU part.  The blocks per item are capped at this over B (and
 // at RASTER_MAX_BLOCKS / RESOLVE_MAX_BLOCKS); the waves stride over the rest.
 constexpr int VERIFY_TARGET_BLOCKS = 2048;
-
-// begin[o] .. begin[o + 1] - 1 are the triangles of object o; a launch argument, read with the block's own (uniform) object
-struct ObjectTable {
-  double scale[pv::MAX_OBJECTS];
-  int begin[pv::MAX_OBJECTS + 1];
-};
-
-inline ObjectTable make_table(const int *tri_begin, const double *model_scale, int O, int T) {
-  ObjectTable tab;
-  for (int k = 0; k <= pv::MAX_OBJECTS; ++k) tab.begin[k] = k <= O ? tri_begin[k] : T;
-  for (int k = 0; k < pv::MAX_OBJECTS; ++k) tab.scale[k] = k < O ? model_scale[k] : 0.0;
-  return tab;
-}
 
 struct Frames {
   const unsigned short *depth, *mask;     // mask may be null
@@ -181,21 +169,15 @@ extern "C" int df_pose_verify(const float *vertices, int V, const int *triangles
   if (!vertices || !triangles || !tri_begin || !model_scale || !proj || !depth || !items || !pose || !stats || !scratch)
     return set_error(DF_ERR_ARG, "%s: null pointer", name);
   if (mask && NM < 1) return set_error(DF_ERR_ARG, "%s: a mask needs NM >= 1 frames, got %d", name, NM);
-  if (O < 1 || O > pv::MAX_OBJECTS) return set_error(DF_ERR_ARG, "%s: O = %d objects outside 1..%d", name, O, pv::MAX_OBJECTS);
+  if (!objects_ok(O)) return set_error(DF_ERR_ARG, "%s: O = %d objects outside 1..%d", name, O, MAX_OBJECTS);
   if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
   if (!window_ok(B, WH, WW)) return set_error(DF_ERR_ARG, "%s: B = %d outside 1..65535 or WH x WW = %d x %d outside 1..2^30", name, B, WH, WW);
   if (tol < 0 || tol > 65535) return set_error(DF_ERR_ARG, "%s: tol %d outside 0..65535", name, tol);
   if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
   if (!(cloud_div > 0.0 && cloud_div - cloud_div == 0.0)) return set_error(DF_ERR_ARG, "%s: cloud_div must be finite and > 0", name);
   if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, df_pose_verify_scratch_bytes(B, WH, WW), proj)) return e;
-  if (tri_begin[0] != 0) return set_error(DF_ERR_ARG, "%s: tri_begin[0] = %d, not 0", name, tri_begin[0]);
   int longest = 0;
-  for (int o = 0; o < O; ++o) {
-    if (tri_begin[o + 1] < tri_begin[o])
-      return set_error(DF_ERR_ARG, "%s: tri_begin decreases from %d to %d at object %d", name, tri_begin[o], tri_begin[o + 1], o);
-    longest = tri_begin[o + 1] - tri_begin[o] > longest ? tri_begin[o + 1] - tri_begin[o] : longest;
-  }
-  if (tri_begin[O] != T) return set_error(DF_ERR_ARG, "%s: tri_begin[O] = %d, not T = %d", name, tri_begin[O], T);
+  if (int e = check_tri_begin(name, tri_begin, O, T, &longest)) return e;
   hipStream_t st = to_stream(stream);
   const long slots = (long)WH * WW;
   if (hipMemsetAsync(scratch, 0xff, (size_t)B * slots * sizeof(unsigned long long), st) != hipSuccess ||
@@ -204,8 +186,8 @@ extern "C" int df_pose_verify(const float *vertices, int V, const int *triangles
   unsigned long long *keys = static_cast<unsigned long long *>(scratch);
   const Frames fr = {depth, mask, F, NM, IH, IW};
   const int tb = item_blocks(longest, B, RASTER_MAX_BLOCKS), xb = item_blocks(slots, B, RESOLVE_MAX_BLOCKS);
-  hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles, make_table(tri_begin, model_scale, O, T), O,
-                     make_camera(proj), fr, items, pose, cloud_div, WH, WW, cull, keys, stats);
+  hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles,
+                     make_object_table(tri_begin, model_scale, O, T), O, make_camera(proj), fr, items, pose, cloud_div, WH, WW, cull, keys, stats);
   hipLaunchKernelGGL(verify_score_kernel, dim3(xb, B), dim3(RB), 0, st, keys, fr, O, items, WH, WW, tol, stats);
   return check_launch(name);
 }

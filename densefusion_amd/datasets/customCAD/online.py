@@ -43,6 +43,7 @@ import torch
 
 from ...lib import preprocess as pp
 from ...lib import segment_score as ss
+from ...lib.mesh_set import MeshSet
 from .. import augment
 from . import render as cr
 from .dataset import LABEL_VALUE, MIN_CROP, _sentinel, sample_model_points
@@ -191,10 +192,11 @@ class RenderedPoseDataset(ChunkedViews):
             meshes = [cr.read_colored_mesh(m) if _is_path(m) else m for m in models + distractors]
             if any(len(m[1]) == 0 for m in meshes):
                 raise ValueError("a scene needs models with faces")
-            self.renderer = cr.CadSceneRenderer(meshes, self.proj_mat, self.image_dims, [self.model_scale] * len(meshes), device=self.device,
+            packed = MeshSet(meshes, colors=True)                # uploaded once; mesh_icp() and pose_verifier() read its prefix of models
+            self.renderer = cr.CadSceneRenderer(packed, self.proj_mat, self.image_dims, [self.model_scale] * len(meshes), device=self.device,
                                                 normals=normals)
+            self.meshes = packed.first(self.n_models)
             self._n_points = [len(m[0]) for m in meshes]
-            self._icp_meshes = [(m[0], m[1]) for m in meshes[:len(models)]]
             self._centroids = [np.asarray(m[0]).astype(np.float64).mean(axis=0) for m in meshes]
             for k in range(self.n_models):
                 self.pt[k + 1] = sample_model_points(np.asarray(meshes[k][0], dtype=np.float32).astype(np.float64), np.asarray(meshes[k][1]))
@@ -202,10 +204,9 @@ class RenderedPoseDataset(ChunkedViews):
             pts, tris, col = cr.read_colored_mesh(models[0]) if _is_path(models[0]) else models[0]
             if len(tris) == 0:
                 raise ValueError("raster mesh needs a model with faces")
-            self.renderer = cr.CadMeshRenderer(pts, tris, col, self.proj_mat, self.image_dims, device=self.device, model_scale=self.model_scale,
-                                               normals=normals)
+            self.meshes = MeshSet([(pts, tris, col)], colors=True)
+            self.renderer = cr.CadMeshRenderer(self.meshes, None, None, self.proj_mat, self.image_dims, self.device, self.model_scale, normals)
             self._n_points, self._centroids = [len(pts)], [np.asarray(pts).astype(np.float64).mean(axis=0)]
-            self._icp_meshes = [(pts, tris)]
             self.pt[1] = sample_model_points(np.asarray(pts, dtype=np.float32).astype(np.float64), np.asarray(tris))
         else:
             if _is_path(models[0]):
@@ -215,7 +216,7 @@ class RenderedPoseDataset(ChunkedViews):
                 pts, nrm, col = models[0]
             self.renderer = cr.CadRenderer(pts, nrm, col, self.proj_mat, self.image_dims, device=self.device, model_scale=self.model_scale)
             self._n_points, self._centroids = [len(pts)], [np.asarray(pts).astype(np.float64).mean(axis=0)]
-            self._icp_meshes = None                              # a point cloud has no surface to fit
+            self.meshes = None                                   # a point cloud has no surface to fit
             self.pt[1] = sample_model_points(np.asarray(pts, dtype=np.float32).astype(np.float64), np.zeros((0, 3), dtype=np.int64))
         self._pt_dev = {o: torch.from_numpy(np.ascontiguousarray(p, dtype=np.float64)).to(self.device) for o, p in self.pt.items()}
         self.num_pt_mesh_large = self.num_pt_mesh_small = 500
@@ -279,19 +280,19 @@ class RenderedPoseDataset(ChunkedViews):
     def mesh_icp(self):
         """A ``lib.mesh_icp.MeshIcp`` of the models' triangles in the units of the items' clouds (vertices x ``model_scale`` / 10000):
         an item's index k names mesh k.  ``ValueError`` in point-cloud mode: there are no triangles to fit."""
-        if self._icp_meshes is None:
+        if self.meshes is None:
             raise ValueError('mesh_icp needs triangles: a scene or raster mesh (a point cloud has none)')
         from ...lib.mesh_icp import MeshIcp
-        return MeshIcp(self._icp_meshes, self.model_scale / 10000.0, device=self.device)
+        return MeshIcp(self.meshes, self.model_scale / 10000.0, device=self.device)
 
     def pose_verifier(self):
         """A ``lib.pose_verify.PoseVerifier`` of the models' triangles, in file units with the renderer's model scale, camera and frame
         size: an item's index k names mesh k, and a pose in the units of the items' clouds is drawn as the renderer would draw it.
         ``ValueError`` in point-cloud mode: there are no triangles to draw."""
-        if self._icp_meshes is None:
+        if self.meshes is None:
             raise ValueError('pose_verifier needs triangles: a scene or raster mesh (a point cloud has none)')
         from ...lib.pose_verify import PoseVerifier
-        return PoseVerifier(self._icp_meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
+        return PoseVerifier(self.meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
 
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small

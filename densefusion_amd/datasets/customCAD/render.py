@@ -31,7 +31,9 @@ import numpy as np
 import torch
 from scipy.spatial.transform import Rotation
 
+from ... import _lib
 from ...lib import preprocess as pp
+from ...lib.mesh_set import MeshSet, check_triangles      # noqa: F401 (check_triangles: this module's name for the renderers' host check)
 from .dataset import _PLY_TYPES, Y_180, convert_quat
 
 MASK_MODES = {"box": 0, "pixels": 1}
@@ -185,18 +187,6 @@ def load_cloud(path, n_points=0):
         keep = np.sort(np.random.choice(len(pts), n_points, replace=False))
         pts, col, nrm = pts[keep], col[keep], None if nrm is None else nrm[keep]
     return pts, nrm, col
-
-
-def check_triangles(triangles, n_vertices):
-    """triangles as int32 [T,3] with T >= 1; ``ValueError`` on any other shape or on an index outside 0..n_vertices-1 (host only)."""
-    tri = np.asarray(triangles)
-    if tri.ndim != 2 or tri.shape[1] != 3 or tri.shape[0] == 0 or not np.issubdtype(tri.dtype, np.integer):
-        raise ValueError("triangles must be a non-empty integer array [T,3]")
-    lo, hi = int(tri.min()), int(tri.max())
-    if lo < 0 or hi >= n_vertices:
-        bad = np.argwhere((tri < 0) | (tri >= n_vertices))[0]
-        raise ValueError(f"triangle {bad[0]} names vertex {int(tri[bad[0], bad[1]])}, outside 0..{n_vertices - 1}")
-    return np.ascontiguousarray(tri, dtype=np.int32)
 
 
 def _face_crosses(vertices, triangles):
@@ -466,34 +456,28 @@ class CadRenderer:
     def render(self, poses, holes=None, splat=0, mask="box"):
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3, 4)
         F = poses.shape[0]
-        need = F * self.image_dims[0] * self.image_dims[1] * 8
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._scratch = _lib.grow_scratch(self._scratch, F * self.image_dims[0] * self.image_dims[1] * 8, self.device)
         return pp.cad_render(self.points, self.normals, self.colors, poses, self.model_scale, self.proj_mat, self.image_dims,
                              holes=self.pack_holes(holes, F), splat=splat, mask_mode=MASK_MODES[mask], scratch=self._scratch)
 
 
 class CadMeshRenderer:
-    """A coloured triangle mesh on the device and the camera of one object directory (``df_cad_render_mesh``).  The triangle indices
-    are checked on the host before anything is uploaded (``check_triangles``).  ``render(poses, holes, cull, mask)``: as
+    """A coloured triangle mesh on the device and the camera of one object directory (``df_cad_render_mesh``), checked on the host before
+    anything is uploaded (``MeshSet``; ``vertices`` may be one, with colours: the other two are unused).  ``render(poses, holes, cull, mask)``: as
     ``CadRenderer.render`` without ``splat``; hole indices name vertices, ``cull`` 1 drops the triangles that face away;
     stats[:, 1] counts the triangles that reached the z-buffer.  ``normals``: None, "flat", "smooth" or an array ([T,3] or [V,3]);
     with them ``render(..., light=[F,8])`` lights the frames (``df_cad_render_mesh_lit``); the light is checked on the host
     (``check_light``) before anything is uploaded, and a light without normals is a ``ValueError``."""
 
     def __init__(self, vertices, triangles, colors, proj_mat, image_dims, device="cuda", model_scale=10.0, normals=None):
-        vertices = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
-        triangles = check_triangles(triangles, len(vertices))
-        made = None if normals is None else _make_normals(normals, vertices, triangles)
+        ms = vertices if isinstance(vertices, MeshSet) else MeshSet([(vertices, triangles, colors)], colors=True)
+        made = None if normals is None else _make_normals(normals, ms.vertices, ms.triangles)
         self.device = torch.device(device)
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
-        self.vertices = up(vertices, np.float32)
-        self.triangles = up(triangles, np.int32)
-        self.colors = up(colors, np.uint8)
+        self.vertices, self.triangles, self.colors = ms.on(self.device)
         self.proj_mat = np.ascontiguousarray(proj_mat, dtype=np.float64)
         self.image_dims = (int(image_dims[0]), int(image_dims[1]))
         self.model_scale = float(model_scale)
-        self.normals, self.normal_mode = (None, 0) if made is None else (up(made[0], np.float32), made[1])
+        self.normals, self.normal_mode = (None, 0) if made is None else (torch.from_numpy(made[0]).to(self.device), made[1])
         self._scratch = None
 
     pack_holes = staticmethod(CadRenderer.pack_holes)
@@ -505,18 +489,16 @@ class CadMeshRenderer:
             if self.normals is None:
                 raise ValueError("a light needs normals: build the renderer with normals=")
             light = check_light(light, F)
-        need = F * self.image_dims[0] * self.image_dims[1] * 8
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._scratch = _lib.grow_scratch(self._scratch, F * self.image_dims[0] * self.image_dims[1] * 8, self.device)
         return pp.cad_render_mesh(self.vertices, self.colors, self.triangles, poses, self.model_scale, self.proj_mat, self.image_dims,
                                   holes=self.pack_holes(holes, F), cull=cull, mask_mode=MASK_MODES[mask], scratch=self._scratch,
                                   normals=self.normals, normal_mode=self.normal_mode, light=light)
 
 
 class CadSceneRenderer:
-    """Several coloured triangle meshes on the device and one camera (``df_cad_render_scene``): ``meshes`` is a list of (vertices,
-    triangles, colours), object o being meshes[o] with ``model_scales[o]``.  Each mesh's indices are checked on the host
-    (``check_triangles``); the meshes are concatenated once (indices made global) and uploaded once; the scratch buffer is reused.
+    """Several coloured triangle meshes on the device and one camera (``df_cad_render_scene``): ``meshes`` is a ``MeshSet`` with colours
+    or the list of (vertices, triangles, colours) it packs, object o being mesh o with ``model_scales[o]``.  Everything is checked on the
+    host before the set is uploaded; the scratch buffer is reused.
     ``render(poses [F,O,3,4], present, cull)`` -> device tensors (rgb [F,IH,IW,3] uint8, depth and label [F,IH,IW] uint16 with label =
     object + 1 on the pixels it won, stats [F,O,6] int32 = {pixels won, triangles tested, rmin, rmax, cmin, cmax});
     ``masks(label, stats, pairs, mask)`` -> the loader's mask [N,IH,IW] uint16 of each (frame, object) pair.
@@ -525,38 +507,25 @@ class CadSceneRenderer:
     (``df_cad_render_scene_lit``), checked as in ``CadMeshRenderer``."""
 
     def __init__(self, meshes, proj_mat, image_dims, model_scales, device="cuda", normals=None):
-        if len(meshes) == 0 or len(meshes) != len(np.atleast_1d(model_scales)):
-            raise ValueError("one model scale per mesh, at least one mesh")
-        if normals is not None and not isinstance(normals, str) and len(normals) != len(meshes):
+        ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes, colors=True)
+        if ms.colors is None or ms.n_objects != len(np.atleast_1d(model_scales)):
+            raise ValueError("one model scale per mesh, and meshes with colours")
+        if normals is not None and not isinstance(normals, str) and len(normals) != ms.n_objects:
             raise ValueError("normals: one array per mesh")
-        verts, tris, cols, begin, nrms = [], [], [], [0], []
-        for o, (v, t, c) in enumerate(meshes):
-            v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3)
-            t = check_triangles(t, len(v))
-            if normals is not None:
-                nrms.append(_make_normals(normals if isinstance(normals, str) else normals[o], v, t))
-            c = np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 3)
-            if len(c) != len(v):
-                raise ValueError("one colour per vertex")
-            tris.append(t + np.int32(sum(len(x) for x in verts)))
-            verts.append(v); cols.append(c)
-            begin.append(begin[-1] + len(t))
+        vb, tb = ms.vertex_begin, ms.tri_begin
+        nrms = [] if normals is None else [_make_normals(normals if isinstance(normals, str) else normals[o], ms.vertices[vb[o]:vb[o + 1]],
+                                                         ms.triangles[tb[o]:tb[o + 1]] - vb[o]) for o in range(ms.n_objects)]
+        if len({m for _, m in nrms}) > 1:
+            raise ValueError("normals: per triangle for all meshes or per vertex for all meshes")
         self.device = torch.device(device)
-        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
-        self.vertices = up(np.concatenate(verts), np.float32)
-        self.triangles = up(np.concatenate(tris), np.int32)
-        self.colors = up(np.concatenate(cols), np.uint8)
-        self.tri_begin = np.array(begin, dtype=np.int32)
+        self.vertices, self.triangles, self.colors = ms.on(self.device)
+        self.tri_begin, self.n_objects = ms.tri_begin, ms.n_objects
         self.model_scales = np.ascontiguousarray(model_scales, dtype=np.float64).reshape(-1)
-        self.n_objects = len(meshes)
         self.proj_mat = np.ascontiguousarray(proj_mat, dtype=np.float64)
         self.image_dims = (int(image_dims[0]), int(image_dims[1]))
-        self.normals, self.normal_mode = None, 0
+        self.normals, self.normal_mode, self._scratch = None, 0, None
         if nrms:
-            if len({m for _, m in nrms}) != 1:
-                raise ValueError("normals: per triangle for all meshes or per vertex for all meshes")
-            self.normals, self.normal_mode = up(np.concatenate([n for n, _ in nrms]), np.float32), nrms[0][1]
-        self._scratch = None
+            self.normals, self.normal_mode = torch.from_numpy(np.concatenate([n for n, _ in nrms])).to(self.device), nrms[0][1]
 
     def render(self, poses, present=None, cull=1, light=None):
         poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, self.n_objects, 3, 4)
@@ -565,9 +534,7 @@ class CadSceneRenderer:
             if self.normals is None:
                 raise ValueError("a light needs normals: build the renderer with normals=")
             light = check_light(light, F)
-        need = F * self.image_dims[0] * self.image_dims[1] * 8
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._scratch = _lib.grow_scratch(self._scratch, F * self.image_dims[0] * self.image_dims[1] * 8, self.device)
         return pp.cad_render_scene(self.vertices, self.colors, self.triangles, self.tri_begin, self.model_scales, poses, self.proj_mat,
                                    self.image_dims, present=present, cull=cull, scratch=self._scratch, normals=self.normals,
                                    normal_mode=self.normal_mode, light=light)

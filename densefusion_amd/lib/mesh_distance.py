@@ -33,18 +33,11 @@ def mesh_closest(vertices, triangles, points, xf, want_closest=True, scratch=Non
     Returns (dist2 [K,P] fp64, tri [K,P] int32, closest [K,P,3] fp64 or None) on the device.  ``scratch``: an optional contiguous uint8
     device tensor of at least ``scratch_bytes(T)`` bytes (one is allocated otherwise).  A triangle with a bad or repeated index is
     skipped; a query with no triangle left gets tri -1, dist2 +inf and closest = the transformed point."""
-    def need(t, name, dtype, tail):
-        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or t.dim() < 2 or tuple(t.shape[1:]) not in tail:
-            raise RuntimeError(f"mesh_closest: {name} must be a device {dtype} tensor of shape [n, {' or '.join(str(s) for s in tail)}] (no CPU path)")
-        return t.contiguous()
-
-    vertices = need(vertices, "vertices", torch.float32, ((3,),))
-    triangles = need(triangles, "triangles", torch.int32, ((3,),))
-    points = need(points, "points", torch.float64, ((3,),))
-    xf = need(xf, "xf", torch.float64, ((3, 4), (12,)))
-    dev = vertices.device
-    if triangles.device != dev or points.device != dev or xf.device != dev:
-        raise RuntimeError("mesh_closest: vertices, triangles, points and xf must be on one device")
+    vertices = _lib.need_tensor(vertices, "mesh_closest", "vertices", (torch.float32,), (None, 3), None)
+    dev = vertices.device                                           # the others must be on the same one
+    triangles = _lib.need_tensor(triangles, "mesh_closest", "triangles", (torch.int32,), (None, 3), dev)
+    points = _lib.need_tensor(points, "mesh_closest", "points", (torch.float64,), (None, 3), dev)
+    xf = _lib.need_tensor(xf, "mesh_closest", "xf", (torch.float64,), ((None, 3, 4), (None, 12)), dev)
     V, T, P, K = check_counts(vertices.shape[0], triangles.shape[0], points.shape[0], xf.shape[0])
     nbytes = scratch_bytes(T)
     if scratch is None:

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .mesh_set import MeshSet
 
 INT_MAX = 2 ** 31 - 1
 MAX_OBJECTS, MAX_ITERS = 64, 64
@@ -20,39 +21,22 @@ STATS = ("status", "first_inliers", "first_rms", "last_inliers", "last_rms", "st
 
 
 class MeshIcp:
-    """``meshes``: a list of (vertices [V,3], triangles [T,3]) (further entries of a tuple, such as colours, are ignored), object o being
-    meshes[o]; ``scales``: one factor per mesh (or one for all) that takes its vertices into the units of the point clouds -- for the
-    customCAD loader ``model_scale / 10000``.  The indices are checked on the host; the meshes are concatenated once (indices made
-    global), scaled in fp64, rounded to fp32 and uploaded once.  ``vertices``, ``triangles`` (device) and ``tri_begin`` (host) are what
-    ``df_mesh_icp`` reads."""
+    """``meshes``: a ``lib.mesh_set.MeshSet`` or the list of (vertices [V,3], triangles [T,3]) it packs, object o being mesh o; ``scales``:
+    one factor per mesh (or one for all) that takes its vertices into the units of the point clouds -- for the customCAD loader
+    ``model_scale / 10000`` (``MeshSet.scaled``: fp64, rounded to fp32).  ``vertices`` (device, scaled: this object's own),
+    ``triangles`` (device, the set's) and ``tri_begin`` (host) are what ``df_mesh_icp`` reads."""
 
     def __init__(self, meshes, scales=1.0, device="cuda"):
-        from ..datasets.customCAD.render import check_triangles      # the host check of the renderers
-        meshes = list(meshes)
-        if not 1 <= len(meshes) <= MAX_OBJECTS:
-            raise ValueError(f"mesh_icp: 1..{MAX_OBJECTS} meshes, got {len(meshes)}")
-        scales = np.broadcast_to(np.asarray(scales, dtype=np.float64).reshape(-1), (len(meshes),)) if np.size(scales) in (1, len(meshes)) else None
-        if scales is None or not (np.isfinite(scales).all() and (scales > 0).all()):
-            raise ValueError("mesh_icp: one positive scale per mesh, or one for all")
-        verts, tris, begin = [], [], [0]
-        for mesh, s in zip(meshes, scales):
-            v = np.ascontiguousarray(mesh[0], dtype=np.float32).reshape(-1, 3)
-            t = check_triangles(mesh[1], len(v))
-            tris.append(t + np.int32(sum(len(x) for x in verts)))
-            verts.append((v.astype(np.float64) * s).astype(np.float32))
-            begin.append(begin[-1] + len(t))
+        ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
+        if ms.n_objects > MAX_OBJECTS:
+            raise ValueError(f"mesh_icp: 1..{MAX_OBJECTS} meshes, got {ms.n_objects}")
+        scaled = ms.scaled(scales)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("mesh_icp: needs a GPU device (no CPU path)")
-        verts, tris = np.concatenate(verts), np.concatenate(tris)
-        if 3 * len(verts) > INT_MAX or 3 * len(tris) > INT_MAX:
-            raise ValueError("mesh_icp: 3 V and 3 T must fit an int")
-        self.vertices = torch.from_numpy(verts).to(self.device)
-        self.triangles = torch.from_numpy(tris).to(self.device)
+        self.vertices, self.triangles = torch.from_numpy(scaled).to(self.device), ms.on(self.device)[1]
         self.device = self.vertices.device                          # with its index
-        self.tri_begin = np.array(begin, dtype=np.int32)
-        self.n_objects = len(meshes)
-        self._scratch = None
+        self.tri_begin, self.n_objects, self._scratch = ms.tri_begin, ms.n_objects, None
 
     def scratch_bytes(self, B, N):
         return int(_lib.lib().df_mesh_icp_scratch_bytes(int(self.triangles.shape[0]), int(B), int(N)))
@@ -63,17 +47,10 @@ class MeshIcp:
         per object, in cloud units: a point further from the surface is no inlier.  ``cull``: only faces that look at the camera take
         points.  Returns (pose [B,7] fp64, stats [B,6] fp64 = ``STATS``; status as in ``STATUS``) on the device.  An item with fewer
         than six inliers or with geometry that does not hold six degrees of freedom keeps its pose."""
-        def need(t, name, dtypes, shape):
-            if (not torch.is_tensor(t) or t.device != self.device or t.dtype not in dtypes or t.dim() != len(shape)
-                    or any(s is not None and t.shape[k] != s for k, s in enumerate(shape))):
-                raise RuntimeError(f"mesh_icp: {name} must be a {' or '.join(str(d) for d in dtypes)} tensor of shape "
-                                   f"{[s if s is not None else 'n' for s in shape]} on {self.device} (no CPU path)")
-            return t.contiguous()
-
-        points = need(points, "points", (torch.float32,), (None, None, 3))
+        points = _lib.need_tensor(points, "mesh_icp", "points", (torch.float32,), (None, None, 3), self.device)
         B, N = int(points.shape[0]), int(points.shape[1])
-        pose = need(pose, "pose", (torch.float64,), (B, 7))
-        obj = need(obj, "obj", (torch.int32, torch.int64), (B,)).to(torch.int32)
+        pose = _lib.need_tensor(pose, "mesh_icp", "pose", (torch.float64,), (B, 7), self.device)
+        obj = _lib.need_tensor(obj, "mesh_icp", "obj", (torch.int32, torch.int64), (B,), self.device).to(torch.int32)
         iters = int(iters)
         if B < 1 or N < 1 or 8 * B * N > INT_MAX:
             raise ValueError(f"mesh_icp: need B, N >= 1 and 8 B N within an int (B {B}, N {N})")
@@ -85,9 +62,7 @@ class MeshIcp:
         if md.size != self.n_objects or not (md > 0).all():
             raise ValueError(f"mesh_icp: max_dist is None, one distance > 0 or one per object ({self.n_objects})")
         md = np.ascontiguousarray(md, dtype=np.float64)
-        nbytes = self.scratch_bytes(B, N)
-        if self._scratch is None or self._scratch.numel() < nbytes:
-            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._scratch = _lib.grow_scratch(self._scratch, self.scratch_bytes(B, N), self.device)
         pose_out = torch.empty(B, 7, dtype=torch.float64, device=self.device)
         stats = torch.empty(B, 6, dtype=torch.float64, device=self.device)
         with _lib.device_guard(self.device):

@@ -13,64 +13,40 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .mesh_set import MeshSet
 
-INT_MAX = 2 ** 31 - 1
 MAX_OBJECTS = 64
 STATUS = ("ok", "bad item")                                         # stats[:, 0]
 STATS = ("status", "rendered", "agree", "front", "behind", "missing", "mask", "mask_observed", "unexplained", "sum_abs", "triangles",
          "cut_triangles")
 
 
-def _need(t, name, dtypes, shape, device):
-    if (not torch.is_tensor(t) or t.device != device or t.dtype not in dtypes or t.dim() != len(shape)
-            or any(s is not None and t.shape[k] != s for k, s in enumerate(shape))):
-        raise RuntimeError(f"pose_verify: {name} must be a {' or '.join(str(d) for d in dtypes)} tensor of shape "
-                           f"{[s if s is not None else 'n' for s in shape]} on {device} (no CPU path)")
-    return t.contiguous()
-
-
 class PoseVerifier:
-    """``meshes``: a list of (vertices [V,3], triangles [T,3]) (further entries of a tuple, such as colours, are ignored), object o being
-    meshes[o] with ``model_scales[o]`` (one for all is accepted): the renderers' factor from file units to camera units.  ``proj`` is the
-    renderers' projection matrix, ``image_dims`` = (IH, IW) of the depth frames, ``cloud_div`` what takes a pose's translation (cloud
-    units) to camera units: 10000 for the customCAD loader.  The indices are checked on the host; the meshes are concatenated once
-    (indices made global) and uploaded once, in file units."""
+    """``meshes``: a ``lib.mesh_set.MeshSet`` or the list of (vertices [V,3], triangles [T,3]) it packs, object o being mesh o with
+    ``model_scales[o]`` (one for all is accepted): the renderers' factor from file units to camera units.  ``proj`` is the renderers'
+    projection matrix, ``image_dims`` = (IH, IW) of the depth frames, ``cloud_div`` what takes a pose's translation (cloud units) to
+    camera units: 10000 for the customCAD loader.  ``vertices`` (file units) and ``triangles`` are the set's device tensors."""
 
     def __init__(self, meshes, model_scales, proj, image_dims, cloud_div=10000.0, device="cuda"):
-        from ..datasets.customCAD.render import check_triangles      # the host check of the renderers
-        meshes = list(meshes)
-        if not 1 <= len(meshes) <= MAX_OBJECTS:
-            raise ValueError(f"pose_verify: 1..{MAX_OBJECTS} meshes, got {len(meshes)}")
+        ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
+        if ms.n_objects > MAX_OBJECTS:
+            raise ValueError(f"pose_verify: 1..{MAX_OBJECTS} meshes, got {ms.n_objects}")
         scales = np.asarray(model_scales, dtype=np.float64).reshape(-1)
-        if scales.size not in (1, len(meshes)) or not np.isfinite(scales).all():
+        if scales.size not in (1, ms.n_objects) or not np.isfinite(scales).all():
             raise ValueError("pose_verify: one finite model scale per mesh, or one for all")
-        self.model_scales = np.ascontiguousarray(np.broadcast_to(scales, (len(meshes),)), dtype=np.float64)
+        self.model_scales = np.ascontiguousarray(np.broadcast_to(scales, (ms.n_objects,)), dtype=np.float64)
         self.proj = np.ascontiguousarray(proj, dtype=np.float64).reshape(-1)
         if self.proj.size != 16:
             raise ValueError("pose_verify: proj is a 4 x 4 matrix")
-        self.image_dims = (int(image_dims[0]), int(image_dims[1]))
-        self.cloud_div = float(cloud_div)
+        self.image_dims, self.cloud_div = (int(image_dims[0]), int(image_dims[1])), float(cloud_div)
         if self.image_dims[0] < 1 or self.image_dims[1] < 1 or not (np.isfinite(self.cloud_div) and self.cloud_div > 0):
             raise ValueError("pose_verify: image_dims must be positive and cloud_div finite and > 0")
-        verts, tris, begin = [], [], [0]
-        for mesh in meshes:
-            v = np.ascontiguousarray(mesh[0], dtype=np.float32).reshape(-1, 3)
-            t = check_triangles(mesh[1], len(v))
-            tris.append(t + np.int32(sum(len(x) for x in verts)))
-            verts.append(v)
-            begin.append(begin[-1] + len(t))
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("pose_verify: needs a GPU device (no CPU path)")
-        verts, tris = np.concatenate(verts), np.concatenate(tris)
-        if 3 * len(verts) > INT_MAX or 3 * len(tris) > INT_MAX:
-            raise ValueError("pose_verify: 3 V and 3 T must fit an int")
-        self.vertices = torch.from_numpy(verts).to(self.device)
-        self.triangles = torch.from_numpy(tris).to(self.device)
+        self.vertices, self.triangles, _ = ms.on(self.device)
         self.device = self.vertices.device                          # with its index
-        self.tri_begin = np.array(begin, dtype=np.int32)
-        self.n_objects = len(meshes)
-        self._scratch = None
+        self.tri_begin, self.n_objects, self._scratch = ms.tri_begin, ms.n_objects, None
 
     def scratch_bytes(self, B, window):
         return int(_lib.lib().df_pose_verify_scratch_bytes(int(B), int(window[0]), int(window[1])))
@@ -83,12 +59,12 @@ class PoseVerifier:
         Returns stats [B,12] int64 = ``STATS`` on the device; nothing is read back."""
         dev, ints = self.device, (torch.int32, torch.int64)
         IH, IW = self.image_dims
-        depth = _need(depth, "depth", (torch.uint16,), (None, IH, IW), dev)
-        pose = _need(pose, "pose", (torch.float64,), (None, 7), dev)
+        depth = _lib.need_tensor(depth, "pose_verify", "depth", (torch.uint16,), (None, IH, IW), dev)
+        pose = _lib.need_tensor(pose, "pose_verify", "pose", (torch.float64,), (None, 7), dev)
         B = int(pose.shape[0])
-        frame = _need(frame, "frame", ints, (B,), dev)
-        obj = _need(obj, "obj", ints, (B,), dev)
-        corner = _need(corner, "corner", ints, (B, 2), dev)
+        frame = _lib.need_tensor(frame, "pose_verify", "frame", ints, (B,), dev)
+        obj = _lib.need_tensor(obj, "pose_verify", "obj", ints, (B,), dev)
+        corner = _lib.need_tensor(corner, "pose_verify", "corner", ints, (B, 2), dev)
         WH, WW, tol = int(window[0]), int(window[1]), int(tol)
         if not 1 <= B <= 65535 or int(depth.shape[0]) < 1 or int(depth.shape[0]) > 65535:
             raise ValueError(f"pose_verify: need 1..65535 items and frames (B {B}, F {int(depth.shape[0])})")
@@ -98,13 +74,13 @@ class PoseVerifier:
             raise ValueError(f"pose_verify: tol must be 0..65535 codes, got {tol}")
         NM = 0
         if mask is not None:
-            mask = _need(mask, "mask", (torch.uint16,), (None, IH, IW), dev)
+            mask = _lib.need_tensor(mask, "pose_verify", "mask", (torch.uint16,), (None, IH, IW), dev)
             NM = int(mask.shape[0])
             if NM < 1:
                 raise ValueError("pose_verify: an empty mask")
-            mask_frame = frame if mask_frame is None else _need(mask_frame, "mask_frame", ints, (B,), dev)
+            mask_frame = frame if mask_frame is None else _lib.need_tensor(mask_frame, "pose_verify", "mask_frame", ints, (B,), dev)
             if torch.is_tensor(mask_value):
-                mask_value = _need(mask_value, "mask_value", ints, (B,), dev)
+                mask_value = _lib.need_tensor(mask_value, "pose_verify", "mask_value", ints, (B,), dev)
         elif mask_frame is not None:
             raise ValueError("pose_verify: mask_frame without a mask")
         items = torch.zeros(B, 6, dtype=torch.int32, device=dev)
@@ -118,22 +94,20 @@ class PoseVerifier:
         call itself and nothing else is enqueued."""
         dev = self.device
         IH, IW = self.image_dims
-        depth = _need(depth, "depth", (torch.uint16,), (None, IH, IW), dev)
-        pose = _need(pose, "pose", (torch.float64,), (None, 7), dev)
+        depth = _lib.need_tensor(depth, "pose_verify", "depth", (torch.uint16,), (None, IH, IW), dev)
+        pose = _lib.need_tensor(pose, "pose_verify", "pose", (torch.float64,), (None, 7), dev)
         B = int(pose.shape[0])
-        items = _need(items, "items", (torch.int32,), (B, 6), dev)
+        items = _lib.need_tensor(items, "pose_verify", "items", (torch.int32,), (B, 6), dev)
         WH, WW, tol = int(window[0]), int(window[1]), int(tol)
         if not 1 <= B <= 65535 or not 1 <= int(depth.shape[0]) <= 65535 or WH < 1 or WW < 1 or WH * WW > 2 ** 30 or not 0 <= tol <= 65535:
             raise ValueError(f"pose_verify: B {B}, F {int(depth.shape[0])}, window {WH} x {WW} or tol {tol} out of range")
         NM = 0
         if mask is not None:
-            mask = _need(mask, "mask", (torch.uint16,), (None, IH, IW), dev)
+            mask = _lib.need_tensor(mask, "pose_verify", "mask", (torch.uint16,), (None, IH, IW), dev)
             NM = int(mask.shape[0])
             if NM < 1:
                 raise ValueError("pose_verify: an empty mask")
-        nbytes = self.scratch_bytes(B, (WH, WW))
-        if self._scratch is None or self._scratch.numel() < nbytes:
-            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self._scratch = _lib.grow_scratch(self._scratch, self.scratch_bytes(B, (WH, WW)), dev)
         stats = torch.empty(B, len(STATS), dtype=torch.int64, device=dev)
         with _lib.device_guard(dev):
             _lib.check(_lib.lib().df_pose_verify(

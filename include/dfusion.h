@@ -763,7 +763,7 @@ int df_mesh_icp(const float *vertices, int V, const int *triangles, int T, const
  *   HOST, read during the call, launch arguments: tri_begin [O+1], model_scale [O] as for df_cad_render_scene; proj, 16 doubles in
  *   df_cad_render's form.
  *   DF_ERR_ARG, before anything is launched or written: a null pointer (mask excepted); mask != NULL with NM < 1; B outside 1..65535;
- *   WH or WW below 1 or WH*WW above 2^30; F, IH, IW, V, T, O, tri_begin and proj as df_cad_render_scene refuses them; tol outside
+ *   WH or WW below 1 or WH*WW above 2^30; F, IH, IW, V, T, O and proj as df_cad_render_scene refuses them, tri_begin by its three rules (one check for both calls); tol outside
  *   0..65535; cull not 0 or 1; cloud_div not finite or <= 0; scratch short or not 8-byte aligned.
  *   Item record: items[b] = {frame, object, r0, c0, mask_frame, mask_value}.  The window of item b is rows r0 .. r0+WH-1 and columns
  *   c0 .. c0+WW-1 of its frame; r0 and c0 may be negative and the window may hang over any edge of the frame: only the nodes inside both
