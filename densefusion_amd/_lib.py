@@ -153,6 +153,13 @@ SIGNATURES = {
     "df_fp64_rate_probe": (_i, [_i, _i, _vp, _vp]),
     "df_mesh_icp_scratch_bytes": (_sz, [_i, _i, _i]),
     "df_mesh_icp": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "df_mesh_tree_leaf_triangles": (_i, []),
+    "df_mesh_tree_sizes": (_i, [_i, _i, _vp, _vp, _vp]),
+    "df_mesh_tree_build": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "df_mesh_closest_tree": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "df_mesh_closest_tree_host": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "df_mesh_icp_tree": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp,
+                              _vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
     "df_pose_verify_scratch_bytes": (_sz, [_i, _i, _i]),
     "df_pose_verify": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.c_double, _i, _i, _i, _i, _i,
                             _vp, _vp, _sz, _vp]),

@@ -13,12 +13,15 @@
 //   and writes the point's terms (I4, I5): J, r, d2 and the inlier flag.
 //   icp_reduce_kernel: one workgroup per item.  Lane l sums the terms of points l, l + 256, ... in ascending order, a binary tree runs
 //   over the 64 lanes of each wave (shuffles) and over the four waves (LDS), and lane 0 does the Cholesky solve and the update (I7..I9).
+//   df_mesh_icp_tree is the same call with icp_walk_kernel in the scan's place: the same winner found through the object's box tree
+//   (mesh_tree_core.h), one point per lane; everything before and after it is shared, so the outputs are the same bytes.
 // No atomics; an item's outputs depend on its own points, pose, object and the mesh only.
 #include <climits>
 
 #include "common.h"
 #include "mesh_icp_core.h"
 #include "mesh_prepare.h"
+#include "mesh_tree.h"
 
 namespace df {
 namespace {
@@ -132,6 +135,38 @@ __global__ __launch_bounds__(IC_BLOCK) void icp_scan_kernel(const TriRec *__rest
   }
 }
 
+// df_mesh_icp_tree's scan: icp_scan_kernel's inputs and outputs with the closest triangle found through the object's box tree
+// (mesh_tree_core.h's walk, its stack in LDS), one point per lane.  Triangles further than max_dist need not be found: such a point is
+// no inlier whichever triangle it is given (I4).  rec and the walk's indices are call-global here; the winner's record is the same.
+// grid = B * qblocks (block i: item i / qblocks, query block i % qblocks)
+__global__ __launch_bounds__(MT_BLOCK) void icp_walk_kernel(const TriRec *__restrict__ rec, IcpObjects objs, TreeArgs tree, const int *__restrict__ obj,
+                                                            const float *__restrict__ points, int N, int qblocks, int cull,
+                                                            const double *__restrict__ pose, const double *__restrict__ stats,
+                                                            double *__restrict__ terms, int *__restrict__ inlier) {
+  __shared__ int stack_words[meshtree::MAX_DEPTH * MT_BLOCK];
+  LdsStack stack{stack_words + threadIdx.x};
+  const int b = blockIdx.x / qblocks, qi = (blockIdx.x - b * qblocks) * MT_BLOCK + threadIdx.x;
+  if (stats[meshicp::NSTAT * (size_t)b + meshicp::ST_STATUS] != 0.0) return;   // frozen or bad object: the whole workgroup leaves
+  if (qi >= N) return;                                                         // no barrier follows
+  const int o = obj[b];                                                        // in range: icp_init_kernel checked it
+  const double md2 = objs.md2[o];
+  double X[12], q[3], bd;
+  int bt;
+  meshicp::model_frame(pose + 7 * (size_t)b, X);
+  const float *pf = points + 3 * ((size_t)b * N + qi);
+  const double p[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
+  meshclosest::transform_query(X, p, q);
+  meshtree::walk(tree_view(tree, o, objs.tri_begin[o], objs.tri_begin[o + 1]), rec, q, md2, stack, &bd, &bt, nullptr);
+  const double cam[3] = {X[3], X[7], X[11]};
+  const size_t at = (size_t)b * N + qi;
+  double term[meshicp::TERM_DOUBLES];
+  const bool in = meshicp::point_terms(rec, bt, bd, q, md2, cull, cam, term);
+  double2 *dst = reinterpret_cast<double2 *>(terms + meshicp::TERM_DOUBLES * at);
+#pragma unroll
+  for (int e = 0; e < meshicp::TERM_DOUBLES / 2; ++e) dst[e] = make_double2(term[2 * e], term[2 * e + 1]);
+  inlier[at] = in ? 1 : 0;
+}
+
 // grid = B.  pass: 0 for the first scan; solve: take the step (I7..I9) after the sums
 __global__ __launch_bounds__(IC_BLOCK) void icp_reduce_kernel(const double *__restrict__ terms, const int *__restrict__ inlier, int N, int pass,
                                                               int solve, double *__restrict__ pose, double *__restrict__ stats) {
@@ -191,10 +226,26 @@ extern "C" size_t df_mesh_icp_scratch_bytes(int T, int B, int N) {
   return (size_t)T * sizeof(TriRec) + terms_bytes(B, N) + ((size_t)B * N * sizeof(int) + 15) / 16 * 16;
 }
 
-extern "C" int df_mesh_icp(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *max_dist, int O,
-                           const int *obj, const float *points, const double *pose_in, int B, int N, int iters, int cull, double *pose_out,
-                           double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream) {
-  const char *name = "mesh_icp";
+namespace df {
+namespace {
+
+// the tree arrays of df_mesh_icp_tree as the caller gave them
+struct TreeGiven {
+  const void *nodes;
+  size_t n_nodes;
+  const int *node_begin, *order;
+  size_t n_order;
+  const int *loose;
+  size_t n_loose;
+  const int *loose_begin;
+};
+
+// df_mesh_icp (given == nullptr) and df_mesh_icp_tree: one set of refusals, one sequence of launches; only the scan kernel differs
+int icp_run(const char *name, const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *max_dist, int O,
+            const int *obj, const float *points, const double *pose_in, int B, int N, int iters, int cull, double *pose_out, double *stats,
+            void *scratch, size_t scratch_bytes, df_stream_t stream, const TreeGiven *given) {
+  if (given && (!given->nodes || !given->node_begin || !given->order || !given->loose || !given->loose_begin))
+    return set_error(DF_ERR_ARG, "%s: null pointer", name);
   if (!vertices || !triangles || !tri_begin || !max_dist || !obj || !points || !pose_in || !pose_out || !stats || !scratch)
     return set_error(DF_ERR_ARG, "%s: null pointer", name);
   if (V < 1 || T < 1 || B < 1 || N < 1) return set_error(DF_ERR_ARG, "%s: need V, T, B, N >= 1 (V %d, T %d, B %d, N %d)", name, V, T, B, N);
@@ -230,6 +281,11 @@ extern "C" int df_mesh_icp(const float *vertices, int V, const int *triangles, i
     if (overlap(pose_out, pose_b, in.p, in.n) || overlap(stats, stats_b, in.p, in.n))
       return set_error(DF_ERR_ARG, "%s: pose_out and stats may not overlap the inputs or the scratch", name);
   if (overlap(pose_out, pose_b, stats, stats_b)) return set_error(DF_ERR_ARG, "%s: pose_out and stats overlap", name);
+  TreeArgs tree;
+  if (given)
+    if (int rc = check_tree(name, given->nodes, given->n_nodes, given->node_begin, given->order, given->n_order, given->loose, given->n_loose,
+                            given->loose_begin, tri_begin, O, &tree))
+      return rc;
 
   hipStream_t st = to_stream(stream);
   TriRec *rec = static_cast<TriRec *>(scratch);
@@ -237,11 +293,34 @@ extern "C" int df_mesh_icp(const float *vertices, int V, const int *triangles, i
   int *inlier = reinterpret_cast<int *>(reinterpret_cast<char *>(terms) + terms_bytes(B, N));
   hipLaunchKernelGGL(mesh_prepare_kernel, dim3(cdiv(T, MESH_PREPARE_BLOCK)), dim3(MESH_PREPARE_BLOCK), 0, st, vertices, V, triangles, T, rec);
   hipLaunchKernelGGL(icp_init_kernel, dim3(cdiv(B, IC_BLOCK)), dim3(IC_BLOCK), 0, st, objs, obj, pose_in, B, pose_out, stats);
-  const int qblocks = cdiv(N, IC_QUERIES);
+  const int qblocks = cdiv(N, IC_QUERIES), wblocks = cdiv(N, MT_BLOCK);
   for (int pass = 0; pass <= iters; ++pass) {
-    hipLaunchKernelGGL(icp_scan_kernel, dim3(B * qblocks), dim3(IC_BLOCK), 0, st, rec, objs, obj, points, N, qblocks, cull, pose_out, stats, terms,
-                       inlier);
+    if (given)
+      hipLaunchKernelGGL(icp_walk_kernel, dim3(B * wblocks), dim3(MT_BLOCK), 0, st, rec, objs, tree, obj, points, N, wblocks, cull, pose_out, stats,
+                         terms, inlier);
+    else
+      hipLaunchKernelGGL(icp_scan_kernel, dim3(B * qblocks), dim3(IC_BLOCK), 0, st, rec, objs, obj, points, N, qblocks, cull, pose_out, stats, terms,
+                         inlier);
     hipLaunchKernelGGL(icp_reduce_kernel, dim3(B), dim3(IC_BLOCK), 0, st, terms, inlier, N, pass, pass < iters ? 1 : 0, pose_out, stats);
   }
   return check_launch(name);
+}
+
+}  // namespace
+}  // namespace df
+
+extern "C" int df_mesh_icp(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *max_dist, int O,
+                           const int *obj, const float *points, const double *pose_in, int B, int N, int iters, int cull, double *pose_out,
+                           double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+  return icp_run("mesh_icp", vertices, V, triangles, T, tri_begin, max_dist, O, obj, points, pose_in, B, N, iters, cull, pose_out, stats, scratch,
+                 scratch_bytes, stream, nullptr);
+}
+
+extern "C" int df_mesh_icp_tree(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *max_dist, int O,
+                                const int *obj, const float *points, const double *pose_in, int B, int N, int iters, int cull, double *pose_out,
+                                double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream, const void *nodes, size_t n_nodes,
+                                const int *node_begin, const int *order, size_t n_order, const int *loose, size_t n_loose, const int *loose_begin) {
+  const TreeGiven given = {nodes, n_nodes, node_begin, order, n_order, loose, n_loose, loose_begin};
+  return icp_run("mesh_icp_tree", vertices, V, triangles, T, tri_begin, max_dist, O, obj, points, pose_in, B, N, iters, cull, pose_out, stats,
+                 scratch, scratch_bytes, stream, &given);
 }

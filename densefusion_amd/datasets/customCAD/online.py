@@ -144,7 +144,8 @@ class RenderedPoseDataset(ChunkedViews):
     ``df_cad_item_table`` on the path is the same.  ``kept`` stays the truth render's, so a run with either mask judges the same views;
     ``live`` follows the mask in use.  With ``segnet=None`` nothing changes by a byte.
     ``symmetry``: "none" (``get_sym_list() == []``), "auto" (meshes only: ``symmetry.detect_symmetry`` per model at construction with
-    ``tol`` = ``symmetry_tol``, the reports kept in ``self.symmetry`` by model index) or a list of model indices.  The list holds the
+    ``tol`` = ``symmetry_tol`` and ``accel`` = ``symmetry_accel``: the same reports through each model's bounding-box tree; the reports
+    are kept in ``self.symmetry`` by model index) or a list of model indices.  The list holds the
     values an item's index takes (model k = index k = object k + 1), which is what the losses, the native trainer and ``evaluate()``
     compare.  No item changes by a byte: the detection draws from a generator of its own.
     ``keep_frames``: ``view_info`` also carries ``depth`` and ``mask``, device views [IH,IW] uint16 of the frames the item was cut from
@@ -156,7 +157,7 @@ class RenderedPoseDataset(ChunkedViews):
                  image_dims=(520, 1109), center=(0.0, 0.0, 4.0), scene_scale=1.0, model_scale=10.0, min_pixels=500, min_visible=0.3,
                  p_present=0.7, lateral=0.8, depth=0.8, max_holes=3, hole_mean=30.0, hole_std=10.0, chunk=32, points=0, first_seed=0,
                  frames=2000, jitter="device", device="cuda", cache_chunks=4, segnet=None, seg_window=None, seg_blur=1, symmetry="none",
-                 symmetry_tol=0.01, keep_frames=False):
+                 symmetry_tol=0.01, keep_frames=False, symmetry_accel=False):
         models = [models] if _is_path(models) or (isinstance(models, tuple) and not _is_path(models[0]) and np.ndim(models[0]) == 2) else list(models)
         distractors = list(distractors)
         self.scene = bool(scene) if scene is not None else (len(models) > 1 or len(distractors) > 0)
@@ -232,7 +233,7 @@ class RenderedPoseDataset(ChunkedViews):
                 found = meshes[:self.n_models] if self.scene else [(pts, tris, col)]
                 with torch.cuda.device(self.device):
                     for k, (mv, mt, mc) in enumerate(found):
-                        self.symmetry[k] = detect_symmetry(mv, mt, mc, tol=float(symmetry_tol))
+                        self.symmetry[k] = detect_symmetry(mv, mt, mc, tol=float(symmetry_tol), accel=bool(symmetry_accel))
                 self._sym_list = [k for k in sorted(self.symmetry) if self.symmetry[k].symmetric]
         else:
             self._sym_list = sorted({int(k) for k in symmetry})
@@ -271,19 +272,19 @@ class RenderedPoseDataset(ChunkedViews):
                    hole_std=opt.hole_std, chunk=opt.chunk, points=opt.points, first_seed=first_seed, frames=frames, device=device,
                    scene=scene, segnet=segnet, seg_window=seg_window, seg_blur=seg_blur,
                    symmetry=symmetry if symmetry is not None else parse_sym_option(getattr(opt, "cad_sym", "none")),
-                   symmetry_tol=getattr(opt, "cad_sym_tol", 0.01), keep_frames=keep_frames)
+                   symmetry_tol=getattr(opt, "cad_sym_tol", 0.01), symmetry_accel=getattr(opt, "cad_sym_accel", False), keep_frames=keep_frames)
 
     def get_sym_list(self):
         """The item indices (model k = index k) that are trained and scored with ADD-S: [] unless ``symmetry`` asked for some."""
         return list(self._sym_list)
 
-    def mesh_icp(self):
+    def mesh_icp(self, accel=False):
         """A ``lib.mesh_icp.MeshIcp`` of the models' triangles in the units of the items' clouds (vertices x ``model_scale`` / 10000):
-        an item's index k names mesh k.  ``ValueError`` in point-cloud mode: there are no triangles to fit."""
+        an item's index k names mesh k; ``accel`` is ``MeshIcp``'s.  ``ValueError`` in point-cloud mode: there are no triangles to fit."""
         if self.meshes is None:
             raise ValueError('mesh_icp needs triangles: a scene or raster mesh (a point cloud has none)')
         from ...lib.mesh_icp import MeshIcp
-        return MeshIcp(self.meshes, self.model_scale / 10000.0, device=self.device)
+        return MeshIcp(self.meshes, self.model_scale / 10000.0, device=self.device, accel=accel)
 
     def pose_verifier(self):
         """A ``lib.pose_verify.PoseVerifier`` of the models' triangles, in file units with the renderer's model scale, camera and frame

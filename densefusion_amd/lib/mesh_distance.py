@@ -28,11 +28,14 @@ def tile_triangles():
     return int(_lib.lib().df_mesh_closest_tile_triangles())
 
 
-def mesh_closest(vertices, triangles, points, xf, want_closest=True, scratch=None):
+def mesh_closest(vertices, triangles, points, xf, want_closest=True, scratch=None, accel=False, tree=None):
     """vertices [V,3] fp32, triangles [T,3] int32, points [P,3] fp64, xf [K,3,4] (or [K,12]) fp64: device tensors on one device.
     Returns (dist2 [K,P] fp64, tri [K,P] int32, closest [K,P,3] fp64 or None) on the device.  ``scratch``: an optional contiguous uint8
     device tensor of at least ``scratch_bytes(T)`` bytes (one is allocated otherwise).  A triangle with a bad or repeated index is
-    skipped; a query with no triangle left gets tri -1, dist2 +inf and closest = the transformed point."""
+    skipped; a query with no triangle left gets tri -1, dist2 +inf and closest = the transformed point.
+    ``accel``: the same outputs byte for byte through a bounding-box tree (``df_mesh_closest_tree``).  ``tree``: the
+    ``lib.mesh_set.MeshTree`` of these vertices and triangles as one object; without one it is built here from a download of the mesh,
+    a host round trip per call, so a caller with many calls on one mesh builds it once."""
     vertices = _lib.need_tensor(vertices, "mesh_closest", "vertices", (torch.float32,), (None, 3), None)
     dev = vertices.device                                           # the others must be on the same one
     triangles = _lib.need_tensor(triangles, "mesh_closest", "triangles", (torch.int32,), (None, 3), dev)
@@ -48,8 +51,15 @@ def mesh_closest(vertices, triangles, points, xf, want_closest=True, scratch=Non
     dist2 = torch.empty(K, P, dtype=torch.float64, device=dev)
     tri = torch.empty(K, P, dtype=torch.int32, device=dev)
     closest = torch.empty(K, P, 3, dtype=torch.float64, device=dev) if want_closest else None
+    call, name, extra = _lib.lib().df_mesh_closest, "mesh_closest", ()
+    if accel:
+        if tree is None:
+            from .mesh_set import MeshTree
+            tree = MeshTree(vertices.cpu().numpy(), triangles.cpu().numpy())
+        if tree.n_objects != 1 or int(tree.tri_begin[1]) != T:
+            raise ValueError(f"mesh_closest: the tree is of {tree.n_objects} objects and {int(tree.tri_begin[-1])} triangles, the mesh one of {T}")
+        call, name, extra = _lib.lib().df_mesh_closest_tree, "mesh_closest_tree", tree.args(dev)
     with _lib.device_guard(dev):
-        _lib.check(_lib.lib().df_mesh_closest(_lib.dptr(vertices), V, _lib.dptr(triangles), T, _lib.dptr(points), P, _lib.dptr(xf), K,
-                                              _lib.dptr(dist2), _lib.dptr(tri), _lib.dptr(closest) if want_closest else None,
-                                              _lib.dptr(scratch), scratch.numel(), _lib.current_stream()), "mesh_closest")
+        _lib.check(call(_lib.dptr(vertices), V, _lib.dptr(triangles), T, _lib.dptr(points), P, _lib.dptr(xf), K, _lib.dptr(dist2), _lib.dptr(tri),
+                        _lib.dptr(closest) if want_closest else None, _lib.dptr(scratch), scratch.numel(), _lib.current_stream(), *extra), name)
     return dist2, tri, closest

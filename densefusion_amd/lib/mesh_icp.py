@@ -24,9 +24,11 @@ class MeshIcp:
     """``meshes``: a ``lib.mesh_set.MeshSet`` or the list of (vertices [V,3], triangles [T,3]) it packs, object o being mesh o; ``scales``:
     one factor per mesh (or one for all) that takes its vertices into the units of the point clouds -- for the customCAD loader
     ``model_scale / 10000`` (``MeshSet.scaled``: fp64, rounded to fp32).  ``vertices`` (device, scaled: this object's own),
-    ``triangles`` (device, the set's) and ``tri_begin`` (host) are what ``df_mesh_icp`` reads."""
+    ``triangles`` (device, the set's) and ``tri_begin`` (host) are what ``df_mesh_icp`` reads.  ``accel``: find the closest triangles
+    through the set's bounding-box tree (``df_mesh_icp_tree``, ``MeshSet.tree``: built here, once per set and scale) -- the same poses
+    and stats byte for byte, in a fraction of the time on meshes of 1e4 triangles and more."""
 
-    def __init__(self, meshes, scales=1.0, device="cuda"):
+    def __init__(self, meshes, scales=1.0, device="cuda", accel=False):
         ms = meshes if isinstance(meshes, MeshSet) else MeshSet(meshes)
         if ms.n_objects > MAX_OBJECTS:
             raise ValueError(f"mesh_icp: 1..{MAX_OBJECTS} meshes, got {ms.n_objects}")
@@ -37,6 +39,7 @@ class MeshIcp:
         self.vertices, self.triangles = torch.from_numpy(scaled).to(self.device), ms.on(self.device)[1]
         self.device = self.vertices.device                          # with its index
         self.tri_begin, self.n_objects, self._scratch = ms.tri_begin, ms.n_objects, None
+        self.tree = ms.tree(scaled) if accel else None
 
     def scratch_bytes(self, B, N):
         return int(_lib.lib().df_mesh_icp_scratch_bytes(int(self.triangles.shape[0]), int(B), int(N)))
@@ -65,10 +68,12 @@ class MeshIcp:
         self._scratch = _lib.grow_scratch(self._scratch, self.scratch_bytes(B, N), self.device)
         pose_out = torch.empty(B, 7, dtype=torch.float64, device=self.device)
         stats = torch.empty(B, 6, dtype=torch.float64, device=self.device)
+        call, name, tree = (_lib.lib().df_mesh_icp, "mesh_icp", ()) if self.tree is None else (_lib.lib().df_mesh_icp_tree, "mesh_icp_tree",
+                                                                                                 self.tree.args(self.device))
         with _lib.device_guard(self.device):
-            _lib.check(_lib.lib().df_mesh_icp(_lib.dptr(self.vertices), int(self.vertices.shape[0]), _lib.dptr(self.triangles),
-                                              int(self.triangles.shape[0]), self.tri_begin.ctypes.data_as(ctypes.c_void_p),
-                                              md.ctypes.data_as(ctypes.c_void_p), self.n_objects, _lib.dptr(obj), _lib.dptr(points), _lib.dptr(pose),
-                                              B, N, iters, 1 if cull else 0, _lib.dptr(pose_out), _lib.dptr(stats), _lib.dptr(self._scratch),
-                                              self._scratch.numel(), _lib.current_stream()), "mesh_icp")
+            _lib.check(call(_lib.dptr(self.vertices), int(self.vertices.shape[0]), _lib.dptr(self.triangles),
+                            int(self.triangles.shape[0]), self.tri_begin.ctypes.data_as(ctypes.c_void_p),
+                            md.ctypes.data_as(ctypes.c_void_p), self.n_objects, _lib.dptr(obj), _lib.dptr(points), _lib.dptr(pose),
+                            B, N, iters, 1 if cull else 0, _lib.dptr(pose_out), _lib.dptr(stats), _lib.dptr(self._scratch),
+                            self._scratch.numel(), _lib.current_stream(), *tree), name)
         return pose_out, stats

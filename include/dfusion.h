@@ -747,6 +747,66 @@ int df_mesh_icp(const float *vertices, int V, const int *triangles, int T, const
                 double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * df_mesh_closest and df_mesh_icp through a bounding-box tree (densefusion_amd/lib/mesh_set.py `MeshSet.tree`): a second route to the
+ * SAME outputs, byte for byte.  Both calls above test every query against every triangle of the object; these meet only the triangles
+ * whose boxes are not provably farther than the best distance found so far.  No new numerics: a triangle's distance is D1..D3, the
+ * winner is D4's (smallest d_t, then lowest t), so which triangles are met does not show in the result as long as no skipped triangle
+ * could win or tie; DESIGN 12l proves that for rule B3.  The rules are densefusion_amd/csrc/mesh_tree_core.h.
+ *
+ * The tree (built once per mesh set on the host; its shape is not part of the contract, only the results of the walk are):
+ *   B1. One binary tree per object range of tri_begin.  It holds the kept triangles (M1) that are not `loose`; a dropped triangle is in
+ *       neither list.  A kept triangle is loose when a vertex is not finite, or it has a face (nn > 0) and nn < 2^-16 ee_i ee_j for two
+ *       of its edges (an angle with sin^2 below 2^-16): the loose triangles of an object are tested for every query.
+ *   B2. A node is 32 bytes: fp32 lo[3], hi[3] (the min / max of its triangles' fp32 vertices, exact in fp64) and int32 a, b.  Leaf: b > 0
+ *       triangles, order[a] .. order[a+b-1] (call-global indices, ascending).  Inner node i: b == 0, children i + 1 and a.  A set of more
+ *       than `leaf` triangles is split at the median of the centroids ((A + B) + C in fp64) along the longest axis of their bounds,
+ *       ordered by (coordinate, index): the lower n / 2 go left.  At most 32 inner nodes lie on a path.
+ *   B3. The walk of a query q: the loose list, then the tree from the root, the nearer child first.  A node is skipped only when
+ *       lb - slack > cut, strictly, with lb = sum_j max(lo_j - q_j, 0, q_j - hi_j)^2, slack = (2^-36 R) R, R = W + E, W = max_j max(|q_j -
+ *       lo_j|, |hi_j - q_j|) and E = max_j (hi_j - lo_j) of the root's box, and cut = the smaller of the best d_t so far and `limit` (+inf
+ *       for df_mesh_closest_tree).
+ *       A NaN query walks nothing and gets D5's result; an infinite one skips nothing.
+ * df_mesh_tree_leaf_triangles: the `leaf` the wrappers build with (host only).
+ * df_mesh_tree_sizes: the elements to allocate for T triangles in O objects: nodes (32 bytes each), order and loose (int32) (host only).
+ *   DF_ERR_ARG: a null pointer, T below 1 or 3 T above INT_MAX, O outside 1..64.
+ * df_mesh_tree_build (host only; every array is a HOST array): vertices [V][3] fp32, the scaled ones the distance calls read; triangles
+ *   [T][3]; tri_begin [O+1] as for df_mesh_icp ({0, T} for df_mesh_closest_tree); leaf in 1..64.  Writes nodes (16-byte aligned) and
+ *   order for all objects one after another, node_begin [O+1] and loose_begin [O+1] (object o owns nodes node_begin[o] ..
+ *   node_begin[o+1]-1, its root first, and loose[loose_begin[o] .. loose_begin[o+1]-1]), and used[3] = the nodes, order entries and loose
+ *   entries written.  A pure function of its inputs: two builds give equal bytes.
+ *   DF_ERR_ARG, before anything is written: a null pointer; V or T below 1; 3 V or 3 T above INT_MAX; O outside 1..64; tri_begin
+ *   decreasing or outside 0..T; leaf outside 1..64; nodes misaligned.  A tree deeper than 32 is refused with DF_ERR_ARG as well.
+ * df_mesh_closest_tree: df_mesh_closest's arguments and outputs, then the tree of tri_begin = {0, T}: DEVICE nodes [n_nodes], order
+ *   [n_order], loose [n_loose]; HOST (launch arguments) node_begin [2], loose_begin [2].  Launches df_mesh_closest's record kernel and
+ *   one walking kernel: a query per lane, the walk's stack in LDS.
+ *   DF_ERR_ARG, before anything is launched or written: every refusal of df_mesh_closest; a null tree pointer; nodes not 16-byte or
+ *   order / loose not 4-byte aligned; node_begin or loose_begin not starting at 0, decreasing, or not fitting tri_begin (an object of n
+ *   triangles, l of them loose, has at most l <= n loose entries and 2 (n - l) - 1 nodes); n_nodes below node_begin[O] or n_loose below
+ *   loose_begin[O]; n_order of 0 with nodes, or above the triangles left for the trees.  Indices read from the device arrays that point
+ *   outside the object's own ranges are not followed, so arrays that no build wrote give wrong answers but no read out of bounds.
+ * df_mesh_closest_tree_host (host only; every array is a HOST array): the same walk on the CPU over the same arrays, for tests and
+ *   stand-alone programs.  tested_out [K][P][2] int64 or NULL: the triangles and the boxes tested for the query.
+ * df_mesh_icp_tree: df_mesh_icp's arguments, outputs, scratch and refusals, then the tree of the same tri_begin as above (node_begin and
+ *   loose_begin [O+1]).  S0 and I1..I10 as they are, by the same kernels; only I3 is found by the walk, with limit = max_dist^2: a
+ *   triangle beyond max_dist may go unfound, and such a point is no inlier either way (I4), so pose_out and stats are df_mesh_icp's. */
+int df_mesh_tree_leaf_triangles(void);
+int df_mesh_tree_sizes(int T, int O, size_t *nodes, size_t *order, size_t *loose);
+int df_mesh_tree_build(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, int O, int leaf, void *nodes,
+                       int *node_begin, int *order, int *loose, int *loose_begin, size_t *used);
+int df_mesh_closest_tree(const float *vertices, int V, const int *triangles, int T, const double *points, int P, const double *xf, int K,
+                         double *dist2_out, int *tri_out, double *closest_out, void *scratch, size_t scratch_bytes, df_stream_t stream,
+                         const void *nodes, size_t n_nodes, const int *node_begin, const int *order, size_t n_order, const int *loose,
+                         size_t n_loose, const int *loose_begin);
+int df_mesh_closest_tree_host(const float *vertices, int V, const int *triangles, int T, const double *points, int P, const double *xf, int K,
+                              const void *nodes, size_t n_nodes, const int *node_begin, const int *order, size_t n_order, const int *loose,
+                              size_t n_loose, const int *loose_begin, double *dist2_out, int *tri_out, double *closest_out,
+                              long long *tested_out);
+int df_mesh_icp_tree(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *max_dist, int O,
+                     const int *obj, const float *points, const double *pose_in, int B, int N, int iters, int cull, double *pose_out,
+                     double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream, const void *nodes, size_t n_nodes,
+                     const int *node_begin, const int *order, size_t n_order, const int *loose, size_t n_loose, const int *loose_begin);
+
+/* ------------------------------------------------------------------------------------------------
  * Render-and-compare verification of B estimated poses (densefusion_amd/lib/pose_verify.py): the CAD mesh of each item is drawn at its
  * pose into a window of the item's own depth frame and compared, node by node, with the observed depth codes and optionally with a mask;
  * the result is twelve integer tallies per item.  No allocation, no synchronisation, the caller's stream; integer atomics only, so two

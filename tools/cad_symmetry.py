@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Report which proper rotations map each CAD model onto itself (datasets/customCAD/symmetry.py).
 
-    python tools/cad_symmetry.py --model washer.ply bracket.ply [--tol 0.01] [--no_color] [--write TREE]
+    python tools/cad_symmetry.py --model washer.ply bracket.ply [--tol 0.01] [--no_color] [--accel] [--write TREE]
 
 Per model: whether it is symmetric (its views are then trained and scored with ADD-S: ``--cad_sym auto`` of tools/train.py and
 tools/eval_cad_render.py runs the same detection), the axes and orders that passed and their residuals as fractions of the bounding-box
@@ -31,6 +31,7 @@ def build_parser():
     ap.add_argument("--axes", type=int, default=10, help="face-normal directions tried besides the three principal axes")
     ap.add_argument("--samples", type=int, default=2048, help="surface samples")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--accel", action="store_true", help="find the distances through the model's bounding-box tree (the same report, faster on large meshes)")
     ap.add_argument("--write", type=str, default="", metavar="TREE", help="also write data/XX/meta/symmetry.txt of this tree")
     return ap
 
@@ -46,7 +47,7 @@ def main(argv=None):
             raise SystemExit(f"{path}: no faces; symmetry is decided from the triangles")
         try:
             report = detect_symmetry(vertices, triangles, None if opt.no_color else colors, tol=opt.tol, color_tol=opt.color_tol,
-                                     max_order=opt.max_order, axes=opt.axes, samples=opt.samples, seed=opt.seed)
+                                     max_order=opt.max_order, axes=opt.axes, samples=opt.samples, seed=opt.seed, accel=opt.accel)
         except ValueError as e:
             raise SystemExit(f"{path}: {e}")
         text = "model %d (object %d): %s\n%s" % (k, k + 1, path, report)

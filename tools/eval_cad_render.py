@@ -21,7 +21,8 @@ as a dict.
 ``--icp ITERS`` (default 0: off) adds a geometric last step: every mask source is scored a second time on the same view seeds with the
 refined pose fitted to the item's own cloud by ``ITERS`` steps of point-to-plane ICP against the model's triangles (``df_mesh_icp``,
 DESIGN.md 12j).  ``--icp_max_dist FRAC`` drops points further from the surface than that fraction of the model cloud's diameter,
-``--icp_cull`` keeps only faces that look at the camera.  The second result is the entry ``<source>_icp`` with its own log
+``--icp_cull`` keeps only faces that look at the camera, ``--icp_accel`` finds the closest triangles through the models' bounding-box
+tree (``df_mesh_icp_tree``: the same poses byte for byte).  The second result is the entry ``<source>_icp`` with its own log
 ``eval_result_logs_<source>_icp.txt``, which also counts the items ICP left alone (too few inliers, degenerate geometry) and gives the
 mean point-to-surface rms before and after.  Without ``--icp`` nothing changes by a byte.
 ``--verify`` scores every pose against the depth frame it came from by drawing the model at the pose (``df_pose_verify``):
@@ -71,6 +72,7 @@ def build_parser():
     ap.add_argument("--icp", type=int, default=0, help="steps of point-to-mesh ICP after the refiner (0 = off); scored as <source>_icp")
     ap.add_argument("--icp_max_dist", type=float, default=0.1, help="ICP drops points further from the surface than this fraction of the model cloud's diameter")
     ap.add_argument("--icp_cull", action="store_true", help="ICP fits only faces that look at the camera")
+    ap.add_argument("--icp_accel", action="store_true", help="ICP finds the closest triangles through the models' bounding-box tree: the same poses, faster on large meshes")
     ap.add_argument("--verify", action="store_true", help="score every pose by render-and-compare against its depth frame; with --icp also <source>_icp_best")
     ap.add_argument("--verify_tol", type=int, default=4, help="depth codes within which rendered and observed depth agree: about three sigmas of "
                     "the sensor's noise in codes (--sensor_sigma) plus its quantum (--sensor_quant); 4 suits a clean render")
@@ -97,7 +99,7 @@ class IcpStep:
     """``evaluate()``'s ``refine_pose`` from a dataset's ``mesh_icp()``; keeps every call's stats on the device until ``summary``."""
 
     def __init__(self, dataset, opt):
-        self.icp, self.iters, self.cull, self.stats = dataset.mesh_icp(), opt.icp, bool(opt.icp_cull), []
+        self.icp, self.iters, self.cull, self.stats = dataset.mesh_icp(accel=bool(opt.icp_accel)), opt.icp, bool(opt.icp_cull), []
         self.max_dist = [opt.icp_max_dist * cloud_diameter(dataset.pt[obj] * 10 / 10000.) for obj in dataset.objlist]
 
     def __call__(self, pose, points, objs):

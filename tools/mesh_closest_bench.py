@@ -4,7 +4,10 @@
 vector rate of the part measured in the same run with a register-only multiply / add loop (``df_fp64_rate_probe``), and the time of a
 whole ``detect_symmetry`` call.  One JSON line.
 
-    python tools/mesh_closest_bench.py [--subdiv 4 7] [--passes 5] [--reps 1] [--no_closest]
+    python tools/mesh_closest_bench.py [--subdiv 4 7] [--passes 5] [--reps 1] [--no_closest] [--accel]
+
+``--accel`` times ``df_mesh_closest_tree`` on the same inputs right after the scan, the same way (``tree``: its times, the host time of
+the tree build apart, the speed-up over this run's scan, whether the outputs are the scan's bytes) and a whole ``detect_symmetry(accel=True)``.
 
 A pass is ``--reps`` calls between two device events; every figure is the median per call over ``--passes`` passes after one warm-up
 pass, with the smallest and largest pass next to it.  ``fp64_ops`` counts the contract's arithmetic per pair (include/dfusion.h): D1 is
@@ -41,6 +44,7 @@ def build_parser():
     ap.add_argument("--probe_blocks", type=int, default=2048, help="workgroups of the fp64 rate loop (256 lanes each)")
     ap.add_argument("--probe_iters", type=int, default=1000000, help="rounds of 16 fp64 operations a lane runs")
     ap.add_argument("--no_detect", action="store_true", help="skip the whole detect_symmetry call")
+    ap.add_argument("--accel", action="store_true", help="also time df_mesh_closest_tree (the bounding-box tree route) on the same inputs, right after the scan")
     return ap
 
 
@@ -106,6 +110,17 @@ def main(argv=None):
         case = {"subdiv": n, "triangles": T, "vertices": len(v), "K": K, "P": P, "pairs": pairs, "mesh_closest_ms": ms,
                 "Gpairs_per_s": pairs / ms["median"] / 1e6, "fp64_Tops": pairs * OPS_PER_PAIR / ms["median"] / 1e9}
         case["share_of_probe_rate"] = case["fp64_Tops"] / peak
+        if opt.accel:
+            from densefusion_amd.lib.mesh_set import MeshTree
+            tree = MeshTree(v, f)                                    # host, once per mesh: reported apart from the calls
+            tms = spread(device_ms(lambda: md.mesh_closest(*up, want_closest=not opt.no_closest, scratch=scratch, accel=True, tree=tree), opt.passes,
+                                   opt.reps))
+            a = md.mesh_closest(*up, want_closest=not opt.no_closest, scratch=scratch)
+            b = md.mesh_closest(*up, want_closest=not opt.no_closest, scratch=scratch, accel=True, tree=tree)
+            case["tree"] = {"leaf": tree.leaf, "nodes": tree.n_nodes, "loose": tree.n_loose, "build_host_s": tree.build_seconds,
+                            "mesh_closest_tree_ms": tms, "speedup": ms["median"] / tms["median"],
+                            "same_bytes": all(x is None or bool(torch.equal(x.view(torch.uint8), y.view(torch.uint8))) for x, y in zip(a, b))}
+            del a, b
         if not opt.no_detect:
             times = []
             for _ in range(3):                                       # host clock around a call that ends in device-to-host copies
@@ -114,6 +129,15 @@ def main(argv=None):
                 report = sym.detect_symmetry(v, f)
                 times.append((time.perf_counter() - t0) * 1e3)
             case["detect_symmetry_ms"] = spread(times[1:])
+            if opt.accel:
+                times = []
+                for _ in range(3):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fast = sym.detect_symmetry(v, f, accel=True)
+                    times.append((time.perf_counter() - t0) * 1e3)
+                case["tree"]["detect_symmetry_ms"] = spread(times[1:])                # with the tree build of every call
+                case["tree"]["same_report"] = bool(np.array_equal(fast.residuals, report.residuals))
             case["symmetric"] = bool(report.symmetric)
         out["cases"].append(case)
         del up, scratch
