@@ -163,6 +163,12 @@ SIGNATURES = {
     "df_pose_verify_scratch_bytes": (_sz, [_i, _i, _i]),
     "df_pose_verify": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.c_double, _i, _i, _i, _i, _i,
                             _vp, _vp, _sz, _vp]),
+    "df_pose_sym_error_scratch_bytes": (_sz, [_i, _i]),
+    "df_pose_sym_error_sweep_vertices": (_i, [_i]),
+    "df_pose_vsd_scratch_bytes": (_sz, [_i, _i, _i]),
+    "df_pose_vsd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _i, _i, _i, _i, _i,
+                         _vp, _vp, _sz, _vp]),
+    "df_pose_sym_error": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -13,11 +13,13 @@
 #include "cad_raster_core.h"
 #include "mesh_objects.h"
 #include "pose_verify_core.h"
+#include "pose_vsd_core.h"
 
 namespace df {
 namespace {
 
 namespace pv = poseverify;
+namespace vsd = posevsd;
 static_assert(pv::MAX_OBJECTS == MAX_OBJECTS, "item_bad's objects are those of the object table (mesh_objects.h)");
 
 // Workgroups a launch aims at over all items: 8 per compute unit of a 256-CU part.  The blocks per item are capped at this over B (and
@@ -144,6 +146,76 @@ __global__ __launch_bounds__(RB) void verify_score_kernel(const unsigned long lo
     atomicAdd(reinterpret_cast<unsigned long long *>(sb + pv::ST_RENDERED + threadIdx.x), acc[threadIdx.x]);
 }
 
+// df_pose_vsd: delta and tau of up to VSD_TABLE_OBJECTS objects, passed by value, written to the table in the scratch
+constexpr int VSD_TABLE_OBJECTS = 8;
+struct VsdRows {
+  double v[VSD_TABLE_OBJECTS][vsd::TABLE_DOUBLES];
+};
+
+__global__ void vsd_table_kernel(VsdRows rows, int o0, int n, double *__restrict__ table) {
+  const int i = threadIdx.x;
+  if (i < n * vsd::TABLE_DOUBLES) table[(size_t)o0 * vsd::TABLE_DOUBLES + i] = rows.v[i / vsd::TABLE_DOUBLES][i % vsd::TABLE_DOUBLES];
+}
+
+// S1..S4 of df_pose_vsd: verify_score_kernel's walk over the window slots with two key planes (estimate, truth), the observed code and the
+// node's ray; every tally is a ballot count, added per workgroup in LDS and then by one integer atomic per non-zero entry.
+__global__ __launch_bounds__(RB) void vsd_score_kernel(const unsigned long long *__restrict__ keys_e, const unsigned long long *__restrict__ keys_g,
+                                                       Frames fr, const double *__restrict__ rays, int O, const int *__restrict__ items,
+                                                       int WH, int WW, double p22, double p23, const double *__restrict__ table, int NT,
+                                                       long long *__restrict__ stats) {
+  constexpr int NTALLY = 3 + vsd::MAX_TAU;
+  __shared__ unsigned long long acc[NTALLY];
+  const int b = blockIdx.y;
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  long long *sb = stats + (size_t)b * (vsd::ST_BAD + NT);
+  if (pv::item_bad(item, fr.F, O, false, 0)) {                                // P0
+    if (blockIdx.x == 0 && threadIdx.x == 0) sb[vsd::ST_STATUS] = 1;
+    return;
+  }
+  const int slots = WH * WW;
+  const size_t npix = (size_t)fr.IH * fr.IW;
+  const unsigned long long *ke = keys_e + (size_t)b * slots, *kg = keys_g + (size_t)b * slots;
+  const unsigned short *df = fr.depth + (size_t)item[pv::IT_FRAME] * npix;
+  const double *tb = table + (size_t)item[pv::IT_OBJECT] * vsd::TABLE_DOUBLES;
+  const double delta = tb[0];
+  const int r0 = item[pv::IT_R0], c0 = item[pv::IT_C0];
+  const int lane = threadIdx.x & 63;
+  unsigned long long n[NTALLY];                                               // per-wave counts, the same in every lane (ballots)
+#pragma unroll
+  for (int k = 0; k < NTALLY; ++k) n[k] = 0;
+  for (int base = blockIdx.x * RB + (threadIdx.x - lane); base < slots; base += gridDim.x * RB) {
+    const int s = base + lane;
+    int r = 0, q = 0;
+    const bool exists = s < slots && pv::slot_node(s, r0, c0, WW, fr.IH, fr.IW, &r, &q);
+    bool ve = false, vg = false, re = false;
+    double gap = 0.0;
+    if (exists) {
+      const size_t p = (size_t)r * fr.IW + q;
+      const int ce = pv::key_code(ke[s]), cg = pv::key_code(kg[s]);
+      const double ray[3] = {rays[3 * p], rays[3 * p + 1], rays[3 * p + 2]};
+      vsd::node_visibility(ce, cg, df[p], p22, p23, vsd::ray_length(ray), delta, &ve, &vg, &gap);
+      re = ce != pv::NO_CODE;
+    }
+    n[0] += __popcll(__ballot(ve || vg));
+    n[1] += __popcll(__ballot(ve && vg));
+    n[2] += __popcll(__ballot(re));
+#pragma unroll
+    for (int k = 0; k < vsd::MAX_TAU; ++k)
+      if (k < NT) n[3 + k] += __popcll(__ballot(ve && vg && gap >= tb[1 + k]));
+  }
+  if (threadIdx.x < NTALLY) acc[threadIdx.x] = 0;
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < NTALLY; ++k)
+      if (n[k]) atomicAdd(&acc[k], n[k]);
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 + NT && acc[threadIdx.x])
+    atomicAdd(reinterpret_cast<unsigned long long *>(sb + vsd::ST_UNION + threadIdx.x), acc[threadIdx.x]);
+}
+
 inline bool window_ok(int B, int WH, int WW) { return B >= 1 && B <= 65535 && WH >= 1 && WW >= 1 && (long)WH * WW <= (1L << 30); }
 
 // blocks per item of a launch over `items` lanes' worth of work per item
@@ -189,5 +261,69 @@ extern "C" int df_pose_verify(const float *vertices, int V, const int *triangles
   hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles,
                      make_object_table(tri_begin, model_scale, O, T), O, make_camera(proj), fr, items, pose, cloud_div, WH, WW, cull, keys, stats);
   hipLaunchKernelGGL(verify_score_kernel, dim3(xb, B), dim3(RB), 0, st, keys, fr, O, items, WH, WW, tol, stats);
+  return check_launch(name);
+}
+
+// the parts of df_pose_vsd's scratch: two key planes of B windows, the raster passes' own tallies (not reported), the object table
+static size_t vsd_keys_bytes(int B, int WH, int WW) { return 2 * (size_t)B * WH * WW * sizeof(unsigned long long); }
+static size_t vsd_side_bytes(int B) { return (size_t)B * pv::NSTAT * sizeof(long long); }
+
+extern "C" size_t df_pose_vsd_scratch_bytes(int B, int WH, int WW) {
+  if (!window_ok(B, WH, WW)) return 0;
+  return vsd_keys_bytes(B, WH, WW) + vsd_side_bytes(B) + (size_t)MAX_OBJECTS * vsd::TABLE_DOUBLES * sizeof(double);
+}
+
+extern "C" int df_pose_vsd(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale, int O,
+                           const double *proj, const unsigned short *depth, int F, int IH, int IW, const double *rays, const int *items,
+                           const double *pose_est, const double *pose_gt, double cloud_div, const double *delta, const double *tau, int NT,
+                           int B, int WH, int WW, int cull, long long *stats, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+  const char *name = "pose_vsd";
+  if (!vertices || !triangles || !tri_begin || !model_scale || !proj || !depth || !rays || !items || !pose_est || !pose_gt || !delta || !tau ||
+      !stats || !scratch)
+    return set_error(DF_ERR_ARG, "%s: null pointer", name);
+  if (!objects_ok(O)) return set_error(DF_ERR_ARG, "%s: O = %d objects outside 1..%d", name, O, MAX_OBJECTS);
+  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
+  if (!window_ok(B, WH, WW)) return set_error(DF_ERR_ARG, "%s: B = %d outside 1..65535 or WH x WW = %d x %d outside 1..2^30", name, B, WH, WW);
+  if (NT < 1 || NT > vsd::MAX_TAU) return set_error(DF_ERR_ARG, "%s: NT = %d outside 1..%d", name, NT, vsd::MAX_TAU);
+  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
+  if (!(cloud_div > 0.0 && cloud_div - cloud_div == 0.0)) return set_error(DF_ERR_ARG, "%s: cloud_div must be finite and > 0", name);
+  for (int o = 0; o < O; ++o) {
+    if (!(delta[o] >= 0.0 && delta[o] - delta[o] == 0.0)) return set_error(DF_ERR_ARG, "%s: delta[%d] must be finite and >= 0", name, o);
+    for (int k = 0; k < NT; ++k)
+      if (!(tau[(size_t)o * NT + k] >= 0.0) || (k > 0 && !(tau[(size_t)o * NT + k] >= tau[(size_t)o * NT + k - 1])))
+        return set_error(DF_ERR_ARG, "%s: tau of object %d must be >= 0 and ascending", name, o);
+  }
+  if (reinterpret_cast<uintptr_t>(rays) % 8 || reinterpret_cast<uintptr_t>(stats) % 8)
+    return set_error(DF_ERR_ARG, "%s: rays and stats must be 8-byte aligned", name);
+  if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, df_pose_vsd_scratch_bytes(B, WH, WW), proj)) return e;
+  int longest = 0;
+  if (int e = check_tri_begin(name, tri_begin, O, T, &longest)) return e;
+  hipStream_t st = to_stream(stream);
+  const long slots = (long)WH * WW;
+  unsigned long long *keys_e = static_cast<unsigned long long *>(scratch), *keys_g = keys_e + (size_t)B * slots;
+  long long *side = reinterpret_cast<long long *>(static_cast<char *>(scratch) + vsd_keys_bytes(B, WH, WW));
+  double *table = reinterpret_cast<double *>(reinterpret_cast<char *>(side) + vsd_side_bytes(B));
+  if (hipMemsetAsync(scratch, 0xff, vsd_keys_bytes(B, WH, WW), st) != hipSuccess ||
+      hipMemsetAsync(side, 0, vsd_side_bytes(B), st) != hipSuccess ||
+      hipMemsetAsync(stats, 0, sizeof(long long) * (vsd::ST_BAD + NT) * B, st) != hipSuccess)
+    return check_launch(name);
+  for (int o0 = 0; o0 < O; o0 += VSD_TABLE_OBJECTS) {
+    VsdRows rows;
+    const int n = O - o0 < VSD_TABLE_OBJECTS ? O - o0 : VSD_TABLE_OBJECTS;
+    for (int j = 0; j < VSD_TABLE_OBJECTS; ++j)
+      for (int k = 0; k < vsd::TABLE_DOUBLES; ++k)
+        rows.v[j][k] = j >= n ? 0.0 : (k == 0 ? delta[o0 + j] : (k - 1 < NT ? tau[(size_t)(o0 + j) * NT + k - 1] : 0.0));
+    hipLaunchKernelGGL(vsd_table_kernel, dim3(1), dim3(RB), 0, st, rows, o0, n, table);
+  }
+  const Frames fr = {depth, nullptr, F, 0, IH, IW};
+  const int tb = item_blocks(longest, B, RASTER_MAX_BLOCKS), xb = item_blocks(slots, B, RESOLVE_MAX_BLOCKS);
+  const ObjectTable tab = make_object_table(tri_begin, model_scale, O, T);
+  const Camera cam = make_camera(proj);
+  // P0..P2 of df_pose_verify, verbatim, once per pose array: the same kernel, its own key plane
+  hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles, tab, O, cam, fr, items, pose_est, cloud_div, WH, WW,
+                     cull, keys_e, side);
+  hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles, tab, O, cam, fr, items, pose_gt, cloud_div, WH, WW,
+                     cull, keys_g, side);
+  hipLaunchKernelGGL(vsd_score_kernel, dim3(xb, B), dim3(RB), 0, st, keys_e, keys_g, fr, rays, O, items, WH, WW, cam.p22, cam.p23, table, NT, stats);
   return check_launch(name);
 }

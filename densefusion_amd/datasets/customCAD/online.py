@@ -295,6 +295,38 @@ class RenderedPoseDataset(ChunkedViews):
         from ...lib.pose_verify import PoseVerifier
         return PoseVerifier(self.meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
 
+    def symmetry_sets(self, step=0.01, cap=4096):
+        """One symmetry set per model (``symmetry.symmetry_set``: float64 [S,3,4], the identity first) in the units of the items' clouds:
+        the rotations of the report ``get_sym_list()`` was made from (no second detection), the translation column scaled like the
+        vertices (x ``model_scale`` / 10000).  A model outside the list gets the identity alone.  ``ValueError`` for a model listed by
+        index with no report behind it (``symmetry`` given as a list: which rotations it has is not known), and where a set does not
+        close within ``cap``."""
+        from .symmetry import symmetry_set
+        sets = []
+        for k in range(self.n_models):
+            if k not in self._sym_list:
+                sets.append(np.concatenate([np.eye(3), np.zeros((3, 1))], axis=1)[None])
+                continue
+            if k not in self.symmetry:
+                raise ValueError(f'symmetry_sets: model {k} was listed by hand; its rotations come from symmetry "auto" only')
+            s = symmetry_set(self.symmetry[k], step=step, cap=cap, name=f"model {k}")
+            s[:, :, 3] = s[:, :, 3] * (self.model_scale / 10000.0)
+            sets.append(s)
+        return sets
+
+    def pose_errors(self, step=0.01, cap=4096):
+        """A ``lib.pose_error.PoseErrors`` of the models' vertices in the units of the items' clouds with ``symmetry_sets(step, cap)``,
+        the renderer's camera and frame size: an item's index k names mesh k.  ``ValueError`` in point-cloud mode: the errors are taken
+        over the vertices of a mesh.  With ``keep_frames`` it also carries the loader's ray map, which ``.vsd`` needs; without, ``.vsd``
+        raises."""
+        if self.meshes is None:
+            raise ValueError('pose_errors needs a mesh: a scene or raster mesh (a point cloud has none)')
+        from ...lib.pose_error import PoseErrors
+        errors = PoseErrors(self.meshes, self.model_scale, self.symmetry_sets(step, cap), self.proj_mat, self.image_dims, cloud_div=10000.0,
+                            device=self.device)
+        # VSD scores against the frames an item was cut from: only a dataset that keeps them hands over the loader's rays
+        return errors.set_rays(self.udp.ray_map_on(self.device)) if self.keep_frames else errors
+
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small
 

@@ -202,6 +202,96 @@ def detect_symmetry(vertices, triangles, colors=None, *, tol=0.01, color_tol=8.0
                           color_residuals=cmax if want else None)
 
 
+# ---- the rotations themselves: the symmetry set the BOP pose errors take their minimum over (lib/pose_error.py) ---------------------------
+SET_EQUAL = 1e-6             # two rotations are the same element when every entry of R agrees within this
+SET_SNAP = 1e-9
+PERPENDICULAR = 0.05        # |a . b| of a half-turn axis b that counts as perpendicular to a revolution axis a
+
+
+def _matmul(A, B):
+    """A B for 3 x 3, every entry (A[i][0] B[0][j] + A[i][1] B[1][j]) + A[i][2] B[2][j]: the same bytes wherever it runs."""
+    return (A[:, 0:1] * B[0:1, :] + A[:, 1:2] * B[1:2, :]) + A[:, 2:3] * B[2:3, :]
+
+
+def is_revolution(report):
+    """A 1-radian probe passed: ``symmetry_set`` takes the model as a surface of revolution (a polygon of many sides, or a hexagon at a
+    loose tolerance, passes it too: the tools say which models were taken so)."""
+    return any(int(n) == 0 for _, n, _, _ in report.passed)
+
+
+def symmetry_generators(report, step=0.01):
+    """The rotations [3,3] that generate a report's symmetry set, in report order.  Without a surface of revolution: the rotation by
+    2 pi / n of every passed (axis, n > 0).  With one (a passed 1-radian probe; the first such axis, a): the rotation by 2 pi / N about
+    a, N = ceil(pi / ``step``) (the BOP discretisation of a continuous symmetry: 315 at 0.01); the finite orders that passed on a itself
+    are rotations of that continuous group and are dropped; of the half turns (n = 2) that passed on axes perpendicular to a
+    (|a . b| <= 0.05) only the first is kept, about the part of b perpendicular to a: every other is that one followed by a rotation about
+    a, which the discretisation already stands for.  Whatever else passed stays a generator (a second revolution axis, a sphere: such a
+    set does not close below the cap)."""
+    if not step > 0:
+        raise ValueError("symmetry_set: step must be > 0")
+    axes = np.asarray(report.axes, dtype=np.float64)
+    rev = next((int(i) for i, n, _, _ in report.passed if n == 0), None)
+    gens, flipped = [], False
+    for i, n, _, _ in report.passed:
+        i, n, b = int(i), int(n), axes[int(i)]
+        if rev is None:
+            if n > 0:
+                gens.append(rotation_about(b, 2 * math.pi / n, np.zeros(3))[:, :3])
+            continue
+        a = axes[rev]
+        if i == rev:
+            if n == 0:
+                gens.append(rotation_about(a, 2 * math.pi / math.ceil(math.pi / step), np.zeros(3))[:, :3])
+        elif n == 2 and abs(float(a @ b)) <= PERPENDICULAR:
+            if not flipped:
+                p = b - float(a @ b) * a
+                gens.append(rotation_about(p / math.sqrt(float(p @ p)), math.pi, np.zeros(3))[:, :3])
+                flipped = True
+        elif n == 0:
+            gens.append(rotation_about(b, 2 * math.pi / math.ceil(math.pi / step), np.zeros(3))[:, :3])
+        else:
+            gens.append(rotation_about(b, 2 * math.pi / n, np.zeros(3))[:, :3])
+    return gens
+
+
+def symmetry_set(report, step=0.01, cap=4096, name="the model"):
+    """float64 [S,3,4]: the proper rotations [R | c - R c] about ``report.centroid`` that map the model onto itself, the identity first.
+
+    The set is the closure of ``symmetry_generators(report, step)`` under composition, searched breadth first from the identity: every
+    element found, in order of discovery, is multiplied from the left by every generator in report order, and a product is new when no
+    element found so far agrees with it within 1e-6 in every entry of R.  The set is listed in order of discovery, so it is a pure
+    function of the report: two calls give equal bytes.  A set that reaches ``cap`` elements before it closes raises ``ValueError`` with
+    ``name`` in it: a set that is not closed is not a group, and a minimum over it would depend on the order.  A model that is not
+    symmetric gives the identity alone."""
+    cap = int(cap)
+    if cap < 1:
+        raise ValueError("symmetry_set: cap must be >= 1")
+    gens = symmetry_generators(report, step)
+    found = np.zeros((cap, 3, 3))
+    found[0] = np.eye(3)
+    n, at = 1, 0
+    while at < n:
+        for g in gens:
+            R = _matmul(g, found[at])
+            if (np.abs(found[:n] - R).reshape(n, 9).max(axis=1) <= SET_EQUAL).any():
+                continue
+            if n == cap:
+                raise ValueError("symmetry_set: the symmetries of %s do not close within %d rotations (a sphere, two revolution axes or "
+                                 "a tolerance that passes rotations the model does not have): not a group, no minimum to take" % (name, cap))
+            found[n] = R
+            n += 1
+        at += 1
+    c = np.asarray(report.centroid, dtype=np.float64).reshape(3)
+    out = np.zeros((n, 3, 4))
+    # an entry within 1e-9 of -1, 0 or 1 is that value (far inside the set's own equality): the half and quarter turns about the
+    # coordinate axes come out as the exact signed permutations they are, free of sin(pi)'s 1e-16
+    snap = np.rint(found[:n])
+    found[:n] = np.where(np.abs(found[:n] - snap) <= SET_SNAP, snap, found[:n])
+    out[:, :, :3] = found[:n]
+    out[:, :, 3] = c[None, :] - ((found[:n, :, 0] * c[0] + found[:n, :, 1] * c[1]) + found[:n, :, 2] * c[2])
+    return out
+
+
 # ---- the option the tools share -------------------------------------------------------------------------------------------------------------
 def add_sym_arguments(ap):
     ap.add_argument("--cad_sym", type=str, nargs="+", default=["none"], metavar="none|auto|ID",

@@ -854,6 +854,96 @@ int df_pose_verify(const float *vertices, int V, const int *triangles, int T, co
                    void *scratch, size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The two symmetry-aware BOP pose errors of B estimated poses against their true poses (densefusion_amd/lib/pose_error.py): MSSD, the
+ * maximum symmetry-aware surface distance over ALL vertices of the item's CAD mesh, and MSPD, the same distance in the image plane; the
+ * minimum runs over the whole symmetry set of the object (datasets/customCAD/symmetry.py `symmetry_set`).  No allocation, no
+ * synchronisation, the caller's stream.  Every maximum and minimum is exact and order-free (a non-negative double orders like its bit
+ * pattern: the maxima are integer atomics on the patterns; there is no floating-point atomic), so two identical calls give identical
+ * bytes, and an item's row depends on its own poses, object, vertices and symmetries only: not on the launch shape, on B or on the items
+ * next to it.  Everything is fp64, one rounding per operation in exactly the order written below (no contraction), with the dot product
+ * of df_mesh_closest; only + - * / sqrt appear, so a restatement matches bit for bit (tests/pose_error_np.py).  The rules are
+ * densefusion_amd/csrc/pose_error_core.h.
+ *
+ * df_pose_sym_error_scratch_bytes: the bytes of `scratch` for B items and S_max, the largest symmetry count of an object: per (item, s)
+ *   two 64-bit maxima and the composed G_s, per item E; 0 for B outside 1..65535 or S_max < 1 (host only).
+ * df_pose_sym_error_sweep_vertices: the vertices of one item that its workgroups take in one sweep at most, for a call of B items; an
+ *   object with more is walked in several sweeps (host only; the tests put V on each side of it).
+ * df_pose_sym_error:
+ *   DEVICE: vertices [V][3] fp32, the scaled vertices df_mesh_icp reads (the units of the poses' translations); sym [NS][12] fp64, row-major
+ *   3 x 4 matrices [R | c - R c], the sets of the objects one after another; obj [B] int32; pose_est, pose_gt [B][7] fp64 (q wxyz, t;
+ *   camera = R model + t); out [B][6] fp64 = {status, mssd, s of mssd, mspd, s of mspd, vertices used}; status 0 ok, 1 bad item; s counts
+ *   from the object's first symmetry; scratch (8-byte aligned).
+ *   HOST, read during the call, launch arguments: vertex_begin [O+1] and sym_begin [O+1] int32, object o owns the vertices vertex_begin[o]
+ *   .. vertex_begin[o+1]-1 and the symmetries sym_begin[o] .. sym_begin[o+1]-1; proj, 16 doubles in df_cad_render's form; IH, IW.
+ *   DF_ERR_ARG, before anything is launched or written: a null pointer; V or NS below 1; 3 V or 12 NS above INT_MAX; B outside 1..65535; O
+ *   outside 1..64; IH or IW below 1 or IH*IW above 2^30; proj not of df_cad_render's form (rows 2 = (0, 0, p22, p23), 3 = (0, 0, -1, 0));
+ *   vertex_begin or sym_begin decreasing or outside 0..V, 0..NS; scratch short or not 8-byte aligned; a pointer not aligned to its
+ *   element; out overlapping an input or the scratch.
+ *   Per item, o = obj[b]:
+ *   E0. Bad item: o outside 0..O-1, an empty vertex range or an empty symmetry range: out[b] = {1, 0, 0, 0, 0, 0} and nothing is read
+ *       through the record.
+ *   E1. R_e from pose_est's q and R_g from pose_gt's by the formula of df_mesh_icp's step I1 (quat_to_mat of mesh_icp_core.h, unchanged: q
+ *       need not be a unit quaternion; n < 4 eps gives R = I); E = [R_e | t_e], M = [R_g | t_g], t = pose[4..6].
+ *   E2. Per symmetry s of the object, once: G = M o S (the point goes through S first), G[j][k] = (M[j][0] S[0][k] + M[j][1] S[1][k]) +
+ *       M[j][2] S[2][k] for k = 0..3, and then G[j][3] = G[j][3] + M[j][3].
+ *   E3. Per vertex x, widened exactly from fp32: p_e = E x and p_g = G x in the form Q1 of df_mesh_closest:
+ *       p_j = ((X[j][0] x_0 + X[j][1] x_1) + X[j][2] x_2) + X[j][3].
+ *   E4. d = p_e - p_g, d2 = (d_0 d_0 + d_1 d_1) + d_2 d_2; a d2 that is not finite (a NaN included) counts as +inf.
+ *   E5. The pixel of a point p, by V3 and V4 of df_cad_render_mesh on p as it stands (a projection of this form is homogeneous in p, so the
+ *       units do not matter), with one reciprocal for the two divisions and no rounding to a node: c_k = ((P[k][0] p_0 + P[k][1] p_1) +
+ *       P[k][2] p_2) + P[k][3] for the rows k = 0, 1, 3 of proj; i = 1.0 / c_3; u = (((c_0 i) + 1.0) IW) 0.5; v = ((1.0 - (c_1 i)) IH) 0.5.
+ *       A point at or behind the camera plane (c_3 > 0 fails) has no pixel.
+ *   E6. e2 = (u_e - u_g)(u_e - u_g) + (v_e - v_g)(v_e - v_g); +inf when either point has no pixel or e2 is not finite.
+ *   E7. D_s = the largest d2 and P_s = the largest e2 over the object's vertices.  mssd = sqrt(min_s D_s), mspd = sqrt(min_s P_s), each
+ *       with the lowest s that attains it; out[b] = {0, mssd, its s, mspd, its s, the object's vertex count}.  (A NaN pose or symmetry
+ *       gives +inf with s = 0.)
+ *   fp64 operations per (vertex, symmetry) pair by this count: E3 18 (p_g), E4 8, E5 27, E6 5 = 58, one of them a division. */
+size_t df_pose_sym_error_scratch_bytes(int B, int S_max);
+int df_pose_sym_error_sweep_vertices(int B);
+int df_pose_sym_error(const float *vertices, int V, const int *vertex_begin, const double *sym, int NS, const int *sym_begin, int O,
+                      const int *obj, const double *pose_est, const double *pose_gt, int B, const double *proj, int IH, int IW, double *out,
+                      void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The third BOP pose error, the visible surface discrepancy of B estimated poses against their true poses and the observed depth
+ * (densefusion_amd/lib/pose_error.py `PoseErrors.vsd`): both poses are drawn by df_pose_verify's own raster pass into windows of the
+ * item's depth frame and compared node by node as distances from the camera.  It follows the BOP toolkit's `vsd` with visibility mode
+ * `bop19` and the step cost; the toolkit was not at hand to compare with, so this comment is the definition.  No allocation, no
+ * synchronisation, the caller's stream; integer atomics only: two identical calls give identical bytes, and an item's row depends on
+ * its own record, poses, object and frame only.  The fp64 part uses + - * / sqrt only, one rounding per operation in the order written
+ * (no contraction); tests/pose_error_np.py restates it and every column is compared bit for bit.  The rules are
+ * densefusion_amd/csrc/pose_vsd_core.h.  df_pose_verify, its kernels and its outputs are unchanged.
+ *
+ * df_pose_vsd_scratch_bytes: two planes of B*WH*WW 64-bit keys, B*12 64-bit tallies of the raster passes and the object table; 0 for
+ *   sizes the call refuses (host only).
+ * df_pose_vsd: df_pose_verify's arguments without mask, NM and tol, and with
+ *   DEVICE: rays [IH][IW][3] fp64, the loader's ray map (UnityDepthProjector.ray_map: the back-projection of node (r, q) at unit depth,
+ *   z = 1); pose_est, pose_gt [B][7] fp64 in pose's place; stats [B][4 + NT] int64 = {status, union, inter, rendered_e, bad_0 ..
+ *   bad_{NT-1}}; items [B][6] as for df_pose_verify, its two mask fields not read.
+ *   HOST, read during the call: delta [O] fp64 and tau [O][NT] fp64, NT in 1..16, in the units of the distances below (the camera units
+ *   of the renderer: cloud units x cloud_div).
+ *   DF_ERR_ARG, before anything is launched or written: every refusal of df_pose_verify that is not about mask or tol; a null rays, pose,
+ *   delta or tau; NT outside 1..16; a delta that is not finite or < 0; a tau that is < 0 (or a NaN) or below the one before it; rays or
+ *   stats not 8-byte aligned.
+ *   P0..P2 of df_pose_verify, verbatim, twice: with pose_est into the key plane E and with pose_gt into the key plane G (the same
+ *   kernel, launched once per pose array).  A bad item (P0, no mask) has stats = {1, 0, ..}.
+ *   Per existing node (r, q) of the window: c_e and c_g = key >> 32 of the planes, or "not rendered"; c_o = depth[frame][r][q], 65535
+ *   meaning "no observation".
+ *   S1. rho = sqrt((x x + y y) + z z) of rays[r][q].
+ *   S2. D(c) = |z(c)| rho with z(c) = -p23 / (p22 + (1.0 - (double)c / 65534.0)), the loader's inverse of T6 in its order (the quotient
+ *       c / 65534, the difference from 1, the sum with p22, the quotient, the negation being exact); z is negative in front of the
+ *       camera and |z| = z < 0 ? -z : z.
+ *   S3. vis_g = rendered_g and (no observation or D_g - D_o <= delta[object]); vis_e = rendered_e and (no observation or D_e - D_o <=
+ *       delta[object] or vis_g); inter = vis_g and vis_e; union = vis_g or vis_e.
+ *   S4. On inter nodes bad_k counts |D_g - D_e| >= tau[object][k] (the difference D_g - D_e, then its magnitude).
+ *   The error itself is the wrapper's: vsd_k = (bad_k + union - inter) / union in fp64, 1 when union = 0. */
+size_t df_pose_vsd_scratch_bytes(int B, int WH, int WW);
+int df_pose_vsd(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale, int O,
+                const double *proj, const unsigned short *depth, int F, int IH, int IW, const double *rays, const int *items,
+                const double *pose_est, const double *pose_gt, double cloud_div, const double *delta, const double *tau, int NT, int B,
+                int WH, int WW, int cull, long long *stats, void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]

@@ -5,8 +5,10 @@
 
 Per model: whether it is symmetric (its views are then trained and scored with ADD-S: ``--cad_sym auto`` of tools/train.py and
 tools/eval_cad_render.py runs the same detection), the axes and orders that passed and their residuals as fractions of the bounding-box
-diagonal.  ``--write TREE`` also puts model k's report into ``TREE/data/<k + 1>/meta/symmetry.txt`` of a tree tools/render_cad_dataset.py
-wrote; the disk loader does not read it.  ``main`` returns the reports.
+diagonal, and the size of its symmetry set (``symmetry_set``: the closure of what passed, a surface of revolution discretised to
+ceil(pi / ``--step``) rotations, which the line then says; the BOP pose errors of lib/pose_error.py take their minimum over it).
+``--write TREE`` also puts model k's report into ``TREE/data/<k + 1>/meta/symmetry.txt`` of a tree tools/render_cad_dataset.py wrote;
+the disk loader does not read it.  ``main`` returns the reports.
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from densefusion_amd.datasets.customCAD import render as cad_render  # noqa: E402
-from densefusion_amd.datasets.customCAD.symmetry import detect_symmetry  # noqa: E402
+from densefusion_amd.datasets.customCAD.symmetry import detect_symmetry, is_revolution, symmetry_set  # noqa: E402
 
 
 def build_parser():
@@ -32,6 +34,7 @@ def build_parser():
     ap.add_argument("--samples", type=int, default=2048, help="surface samples")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--accel", action="store_true", help="find the distances through the model's bounding-box tree (the same report, faster on large meshes)")
+    ap.add_argument("--step", type=float, default=0.01, help="a surface of revolution is discretised to ceil(pi / step) rotations in the symmetry set (BOP: 0.01)")
     ap.add_argument("--write", type=str, default="", metavar="TREE", help="also write data/XX/meta/symmetry.txt of this tree")
     return ap
 
@@ -51,6 +54,11 @@ def main(argv=None):
         except ValueError as e:
             raise SystemExit(f"{path}: {e}")
         text = "model %d (object %d): %s\n%s" % (k, k + 1, path, report)
+        try:                                                         # the rotations the BOP pose errors take their minimum over
+            text += "\nsymmetry set: %d rotations%s" % (len(symmetry_set(report, step=opt.step, name=path)),
+                                                       " (taken as a surface of revolution)" if is_revolution(report) else "")
+        except ValueError as e:
+            text += "\nsymmetry set: none (%s)" % e
         print(text)
         if opt.write:
             meta = os.path.join(opt.write, "data", "%02d" % (k + 1), "meta")

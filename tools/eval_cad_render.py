@@ -30,6 +30,17 @@ each entry's log gains the mean visible-surface IoU of its passes and of its mis
 ``<source>_icp_best`` takes, per item, the ICP pose where its IoU is strictly higher and the refiner's otherwise, and says how many items
 took each.  ``--verify_tol`` is the agreement tolerance in depth codes, ``--verify_margin`` how far the window reaches beyond the item's
 crop box.  Without ``--verify`` nothing changes by a byte.
+``--bop`` also scores every entry by the three BOP pose errors: the symmetry-aware MSSD and MSPD (``df_pose_sym_error``)
+over ALL vertices of the model's mesh and the whole symmetry set of the models ``--cad_sym auto`` finds symmetric (``--bop_step``: the
+discretisation of a surface of revolution), against the true pose of the view.  Each entry's log gains, per object and over all served
+views, the recall of MSSD below 0.05 .. 0.5 x the mesh's diameter (the largest vertex-to-vertex distance, exact, over the vertices
+of the convex hull, once per run)
+and of MSPD below 5 r .. 50 r pixels, r = width / 640, their mean AR, each model's symmetry set size and which models
+were taken as surfaces of revolution; ``main``'s dict gains ``bop``
+per entry.  VSD, the visible surface discrepancy (``df_pose_vsd``), draws both poses into the window of the item's crop box grown by
+``--verify_margin`` and compares them with the depth frame the item came from: ``--bop_delta`` x the diameter is its visibility tolerance,
+tau runs over 0.05 .. 0.5 x the diameter, and the log gives the recall of VSD below 0.05 .. 0.5 averaged over the tau.  The mean AR is over
+the three errors.  Without ``--bop`` nothing changes by a byte.
 """
 from __future__ import annotations
 
@@ -77,6 +88,11 @@ def build_parser():
     ap.add_argument("--verify_tol", type=int, default=4, help="depth codes within which rendered and observed depth agree: about three sigmas of "
                     "the sensor's noise in codes (--sensor_sigma) plus its quantum (--sensor_quant); 4 suits a clean render")
     ap.add_argument("--verify_margin", type=int, default=8, help="pixels the verification window reaches beyond the item's crop box")
+    ap.add_argument("--bop", action="store_true", help="also score every entry by the BOP pose errors MSSD and MSPD over the whole mesh and symmetry set")
+    ap.add_argument("--bop_delta", type=float, default=0.075, help="--bop: the visibility tolerance of VSD as a fraction of the mesh's diameter (the "
+                    "user's parameter, not a measurement)")
+    ap.add_argument("--bop_step", type=float, default=0.01, help="--bop: a surface of revolution counts as ceil(pi / step) rotations (the BOP toolkit's "
+                    "0.01: 315); the user's parameter, not a measurement")
     views = ap.add_argument_group("views", "the views and the renderer, under the names of tools/render_cad_dataset.py")
     cad_render.add_view_arguments(views)
     cad_symmetry.add_sym_arguments(views)
@@ -155,6 +171,104 @@ class VerifyStep:
                     took_last=int(taken.sum()), took_first=int((~taken).sum()), tol=self.tol, margin=self.margin)
 
 
+BOP_STEPS = [0.05 * k for k in range(1, 11)]                       # the ten BOP thresholds: x the diameter (MSSD), x 100 r pixels (MSPD)
+
+
+def mesh_diameter(vertices, device):
+    """The largest vertex-to-vertex distance of ``vertices`` [V,3] (host array), exact: the two vertices that attain it are vertices of
+    the convex hull (``scipy.spatial.ConvexHull`` on the host; a flat or otherwise degenerate mesh keeps all its vertices), and every
+    pair of those is taken in fp64 by a plain device reduction."""
+    from scipy.spatial import ConvexHull, QhullError
+    v = np.unique(np.asarray(vertices, dtype=np.float64).reshape(-1, 3), axis=0)
+    try:
+        v = v[ConvexHull(v).vertices]
+    except (QhullError, ValueError):
+        pass
+    v = torch.from_numpy(np.ascontiguousarray(v)).to(device)
+    best = torch.zeros((), dtype=torch.float64, device=v.device)
+    rows = max(1, (1 << 22) // len(v))
+    for a in range(0, len(v), rows):
+        d = v[a:a + rows, None, :] - v[None, :, :]
+        best = torch.maximum(best, ((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]).max())
+    return float(best.sqrt())
+
+
+def true_pose(dataset, index):
+    """[7] (q wxyz, t in the units of the clouds): the pose ``df_cad_targets`` builds item ``index``'s target from"""
+    from densefusion_amd.lib.transformations import quaternion_from_matrix
+    info = dataset.view_info(index)
+    M = np.eye(4)
+    M[:3, :3] = np.asarray(info["pose"], dtype=np.float64)[:, :3]
+    t = np.asarray(info["pose"], dtype=np.float64)[:, 3] / 10000.0
+    if dataset.add_noise:
+        t = t + np.asarray(info["add_t"], dtype=np.float64)
+    return np.concatenate([quaternion_from_matrix(M), t])
+
+
+class BopScorer:
+    """What ``--bop`` needs of a dataset, built once in ``main`` and shared by the entries: its ``pose_errors()`` (one upload of the scaled
+    vertices and the symmetry sets), each mesh's diameter, the set sizes and which models were taken as surfaces of revolution."""
+
+    def __init__(self, dataset, opt):
+        self.errors = dataset.pose_errors(step=opt.bop_step)
+        vb, scaled = self.errors.vertex_begin, self.errors.vertices.cpu().numpy()
+        self.diameter = [mesh_diameter(scaled[vb[k]:vb[k + 1]], self.errors.device) for k in range(self.errors.n_objects)]
+        self.set_sizes = [int(n) for n in np.diff(self.errors.sym_begin)]
+        self.revolution = [k for k in dataset.get_sym_list() if k in dataset.symmetry and cad_symmetry.is_revolution(dataset.symmetry[k])]
+        self.pixel = dataset.image_dims[1] / 640.0
+        # VSD works in the renderer's camera units (cloud units x 10000): delta and the ten tau per object, the crop margin of --verify
+        cam = [d * 10000.0 for d in self.diameter]
+        self.delta, self.tau = np.array([opt.bop_delta * d for d in cam]), np.array([[f * d for f in BOP_STEPS] for d in cam])
+        self.margin, self.cull = opt.verify_margin, bool(dataset.cull)
+
+
+class BopStep:
+    """``evaluate()``'s ``select_pose`` of one scored entry, from the dataset's ``BopScorer``: the pose that goes on (``inner``'s choice when
+    a ``VerifyStep`` is composed in, otherwise the last candidate) is scored against the view's true pose; the rows stay on the device
+    until ``summary``."""
+
+    def __init__(self, dataset, scorer, inner=None):
+        self.dataset, self.inner, self.errors = dataset, inner, scorer.errors
+        self.diameter, self.set_sizes, self.revolution, self.pixel = scorer.diameter, scorer.set_sizes, scorer.revolution, scorer.pixel
+        self.scorer, self.rows, self.objs, self.vsd = scorer, [], [], []
+
+    def __call__(self, indices, candidates, objs):
+        pose = self.inner(indices, candidates, objs) if self.inner is not None else candidates[-1]
+        gt = torch.from_numpy(np.stack([true_pose(self.dataset, i) for i in indices])).pin_memory().to(pose.device, non_blocking=True)
+        obj = torch.tensor(objs, dtype=torch.int32).pin_memory().to(pose.device, non_blocking=True)
+        self.rows.append(self.errors.sym_error(pose.contiguous(), gt, obj))
+        # VSD against the frame the item was cut from, in the window of its crop box grown by the margin (one size per call: the largest)
+        infos, m = [self.dataset.view_info(i) for i in indices], self.scorer.margin
+        depth = torch.stack([f["depth"] for f in infos])
+        window = (max(f["box"][1] - f["box"][0] for f in infos) + 2 * m, max(f["box"][3] - f["box"][2] for f in infos) + 2 * m)
+        rec = torch.tensor([[k, objs[k], f["box"][0] - m, f["box"][2] - m] for k, f in enumerate(infos)], dtype=torch.int32).pin_memory().to(
+            pose.device, non_blocking=True)
+        self.vsd.append(self.errors.vsd(depth, pose.contiguous(), gt, rec[:, 0], rec[:, 1], rec[:, 2:4], window, self.scorer.delta, self.scorer.tau,
+                                        cull=self.scorer.cull))
+        self.objs += list(objs)
+        return pose
+
+    def summary(self):
+        rows = torch.cat(self.rows).cpu().numpy() if self.rows else np.zeros((0, 6))       # the one read-back of the entry
+        from densefusion_amd.lib.pose_error import vsd_values
+        vsd = vsd_values(torch.cat(self.vsd).cpu().numpy()) if self.vsd else np.zeros((0, len(BOP_STEPS)))      # [items, tau], with the rows' read-back
+        objs = np.array(self.objs, dtype=np.int64)
+        ok = rows[:, 0] == 0
+
+        def recalls(pick):
+            n = int(pick.sum())
+            thr = np.array([self.diameter[k] for k in objs[pick]])
+            mssd = [float(((rows[pick, 1] < f * thr) & ok[pick]).mean()) if n else 0.0 for f in BOP_STEPS]
+            mspd = [float(((rows[pick, 3] < f * 100.0 * self.pixel) & ok[pick]).mean()) if n else 0.0 for f in BOP_STEPS]
+            # VSD: per threshold theta the recall of vsd < theta, averaged over the ten tau
+            vsd_r = [float((vsd[pick] < f).mean()) if n else 0.0 for f in BOP_STEPS]
+            ar_s, ar_p, ar_v = float(np.mean(mssd)), float(np.mean(mspd)), float(np.mean(vsd_r))
+            return dict(items=n, mssd_recall=mssd, mspd_recall=mspd, vsd_recall=vsd_r, ar_mssd=ar_s, ar_mspd=ar_p, ar_vsd=ar_v,
+                        ar=(ar_v + ar_s + ar_p) / 3.0)
+        return dict(items=len(rows), bad_items=int((~ok).sum()), set_sizes=self.set_sizes, revolution=self.revolution, diameter=self.diameter, pixel=self.pixel,
+                    objects=[recalls(objs == k) for k in range(self.errors.n_objects)], all=recalls(np.ones(len(rows), dtype=bool)))
+
+
 class _PassLog:
     """The log file of ``evaluate()`` with an ear: ``passed[i]`` of every "No.i Pass!" / "No.i NOT Pass! Distance" line that goes by."""
 
@@ -168,9 +282,10 @@ class _PassLog:
         return self.fw.write(text)
 
 
-def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, verify=None):
+def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, verify=None, bop=None):
     """``evaluate()`` over ``dataset`` and the tallies of one mask source; with ``icp`` (an ``IcpStep``) the poses take that last step,
-    with ``verify`` (a ``VerifyStep``) they are scored, or chosen, by render-and-compare."""
+    with ``verify`` (a ``VerifyStep``) they are scored, or chosen, by render-and-compare; with ``bop`` the pose that is scored is also
+    scored by the BOP pose errors (``bop``: the dataset's ``BopScorer``; a ``BopStep`` of it goes around ``verify``)."""
     objlist = list(dataset.objlist)
     n = len(dataset) if opt.max_frames <= 0 else min(opt.max_frames, len(dataset))
     with open(os.path.join(opt.output_result_dir, "eval_result_logs_%s.txt" % source), "w") as fw:
@@ -178,6 +293,8 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, ver
             print(m)
             fw.write(m + "\n")
         steps = dict(**({} if icp is None else {"refine_pose": icp}), **({} if verify is None else {"select_pose": verify}))
+        if bop is not None:
+            steps["select_pose"] = bop = BopStep(dataset, bop, inner=verify)
         log = fw if verify is None else _PassLog(fw)
         success, served = evaluate(dataset, estimator, refiner, diameter, opt, log, **steps)
         success, served = success[:len(objlist)], served[:len(objlist)]
@@ -203,6 +320,21 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, ver
                 source, m["tol"], m["margin"], m["mean_vsiou_pass"], m["passes"], m["mean_vsiou_miss"], m["items"] - m["passes"]))
             if verify.choose:
                 say("[{0} masks] verify: {1} items took the ICP pose, {2} kept the refiner's".format(source, m["took_last"], m["took_first"]))
+        if bop is not None:
+            out["bop"] = m = bop.summary()
+            say("[{0} masks] bop: symmetry set sizes {1}, mesh diameters {2}, {3} items".format(
+                source, m["set_sizes"], ["%.6g" % d for d in m["diameter"]], m["items"]))
+            say("[{0} masks] bop: models taken as surfaces of revolution (discretised to ceil(pi / {1:g}) rotations): {2}".format(
+                source, opt.bop_step, m["revolution"]))
+            for name, r in [("Object %d" % obj, m["objects"][k]) for k, obj in enumerate(objlist)] + [("ALL", m["all"])]:
+                say("[{0} masks] bop: {1} over {2} served views: MSSD recall at 0.05 .. 0.5 x diameter {3}".format(
+                    source, name, r["items"], " ".join("%.4f" % x for x in r["mssd_recall"])))
+                say("[{0} masks] bop: {1} over {2} served views: MSPD recall at {3:g} .. {4:g} px {5}".format(
+                    source, name, r["items"], 5 * m["pixel"], 50 * m["pixel"], " ".join("%.4f" % x for x in r["mspd_recall"])))
+                say("[{0} masks] bop: {1} over {2} served views: VSD recall below 0.05 .. 0.5 (over tau 0.05 .. 0.5 x diameter, delta {3:g} x) {4}".format(
+                    source, name, r["items"], opt.bop_delta, " ".join("%.4f" % x for x in r["vsd_recall"])))
+                say("[{0} masks] bop: {1} AR_VSD {2:.6f} AR_MSSD {3:.6f} AR_MSPD {4:.6f} mean AR {5:.6f}".format(
+                    source, name, r["ar_vsd"], r["ar_mssd"], r["ar_mspd"], r["ar"]))
         if source == "segnet":
             m = dataset.seg_score.summary()
             out["seg"] = m
@@ -219,6 +351,8 @@ def main(argv=None):
         raise SystemExit("at most %d models: the pose networks of tools/eval_cad.py have that many objects" % NUM_OBJECTS)
     if not 0 <= opt.icp <= 64 or not opt.icp_max_dist > 0:
         raise SystemExit("--icp takes 0..64 steps and --icp_max_dist a positive fraction")
+    if not opt.bop_step > 0 or not (opt.bop_delta >= 0 and opt.bop_delta < float("inf")):
+        raise SystemExit("--bop_step takes a positive angle step and --bop_delta a finite fraction >= 0")
     if not 0 <= opt.verify_tol <= 65535 or not 0 <= opt.verify_margin <= 4096:
         raise SystemExit("--verify_tol takes 0..65535 codes and --verify_margin 0..4096 pixels")
     if not torch.cuda.is_available():
@@ -244,7 +378,7 @@ def main(argv=None):
             # SegNet's masks need the scene renderer's label plane; the truth run of the same call renders the same scenes
             dataset = RenderedPoseDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=opt.cad_seed, frames=opt.cad_frames,
                                                        num=NUM_POINTS, scene=True if segnet is not None else None, **kw,
-                                                       **({"keep_frames": True} if opt.verify else {}))
+                                                       **({"keep_frames": True} if opt.verify or opt.bop else {}))
         except ValueError as e:
             raise SystemExit(f"eval_cad_render.py: {e}")
 
@@ -259,18 +393,24 @@ def main(argv=None):
         diameter = [opt.threshold_frac * cloud_diameter(dataset.pt[obj] * 10 / 10000.) for obj in dataset.objlist]
         diameter += [0.0] * (NUM_OBJECTS - len(diameter))
         print("symmetry object list: %s" % dataset.get_sym_list())
-        result[source] = run_source(source, dataset, estimator, refiner, diameter, opt, verify=first)
+        scorer = None
+        if opt.bop:                                                 # once per dataset: every entry of this source shares it
+            try:
+                scorer = BopScorer(dataset, opt)
+            except ValueError as e:
+                raise SystemExit(f"eval_cad_render.py: --bop: {e}")
+        result[source] = run_source(source, dataset, estimator, refiner, diameter, opt, verify=first, bop=scorer)
         result[source]["sym_list"] = dataset.get_sym_list()
         if opt.icp > 0:                                             # the same views (the dataset serves them again), one more step per pose
             try:
                 step = IcpStep(dataset, opt)
             except ValueError as e:
                 raise SystemExit(f"eval_cad_render.py: --icp: {e}")
-            result[source + "_icp"] = run_source(source + "_icp", dataset, estimator, refiner, diameter, opt, icp=step, verify=verifier())
+            result[source + "_icp"] = run_source(source + "_icp", dataset, estimator, refiner, diameter, opt, icp=step, verify=verifier(), bop=scorer)
             result[source + "_icp"]["sym_list"] = dataset.get_sym_list()
             if opt.verify:                                          # per item the pose with the higher visible-surface IoU
                 name = source + "_icp_best"
-                result[name] = run_source(name, dataset, estimator, refiner, diameter, opt, icp=IcpStep(dataset, opt), verify=verifier(True))
+                result[name] = run_source(name, dataset, estimator, refiner, diameter, opt, icp=IcpStep(dataset, opt), verify=verifier(True), bop=scorer)
                 result[name]["sym_list"] = dataset.get_sym_list()
     return result
 
