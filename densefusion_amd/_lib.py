@@ -168,6 +168,9 @@ SIGNATURES = {
     "df_pose_vsd_scratch_bytes": (_sz, [_i, _i, _i]),
     "df_pose_vsd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _i, _i, _i, _i, _i,
                          _vp, _vp, _sz, _vp]),
+    "df_pose_refine_dense_scratch_bytes": (_sz, [_i, _i, _i]),
+    "df_pose_refine_dense": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_double, _i, _i, _i,
+                                  _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "df_pose_sym_error": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 

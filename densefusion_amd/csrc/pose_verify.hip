@@ -13,6 +13,7 @@
 #include "cad_raster_core.h"
 #include "mesh_objects.h"
 #include "pose_verify_core.h"
+#include "pose_dense_core.h"
 #include "pose_vsd_core.h"
 
 namespace df {
@@ -20,6 +21,7 @@ namespace {
 
 namespace pv = poseverify;
 namespace vsd = posevsd;
+namespace dense = posedense;
 static_assert(pv::MAX_OBJECTS == MAX_OBJECTS, "item_bad's objects are those of the object table (mesh_objects.h)");
 
 // Workgroups a launch aims at over all items: 8 per compute unit of a 256-CU part.  The blocks per item are capped at this over B (and
@@ -216,6 +218,139 @@ __global__ __launch_bounds__(RB) void vsd_score_kernel(const unsigned long long 
     atomicAdd(reinterpret_cast<unsigned long long *>(sb + vsd::ST_UNION + threadIdx.x), acc[threadIdx.x]);
 }
 
+// ---- df_pose_refine_dense (D1..D6 of its comment in include/dfusion.h; the rules are pose_dense_core.h) ---------------------------------
+// The state between the launches lives in the scratch: per item the working pose (7 doubles) and its model frame X with the
+// vertex factor (posedense::FRAME_DOUBLES), which the init and the finish kernel write and the accumulation reads through uniform
+// addresses (scalar loads); the status is stats[b][0] itself, as in df_mesh_icp.
+
+constexpr int DENSE_POSE_DOUBLES = 7;                  // the raster kernel reads the working poses as a [B][7] array
+static_assert(RB == meshicp::LANES, "the accumulation order of D5 is this workgroup's shape");
+
+// S0 and P0: one thread per item
+__global__ __launch_bounds__(RB) void dense_init_kernel(const int *__restrict__ items, const double *__restrict__ pose_in, ObjectTable tab,
+                                                        int O, int F, int has_mask, int NM, double cloud_div, int B,
+                                                        double *__restrict__ work, double *__restrict__ frames,
+                                                        double *__restrict__ pose_out, double *__restrict__ stats) {
+  const int b = blockIdx.x * RB + threadIdx.x;
+  if (b >= B) return;
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  double p[7], X[12];
+  for (int e = 0; e < 7; ++e) p[e] = pose_in[7 * (size_t)b + e];
+  meshicp::normalise_quat(p);
+  meshicp::model_frame(p, X);
+  const bool bad = pv::item_bad(item, F, O, has_mask != 0, NM);
+  for (int e = 0; e < 7; ++e) {
+    pose_out[7 * (size_t)b + e] = p[e];
+    work[DENSE_POSE_DOUBLES * (size_t)b + e] = p[e];
+  }
+  double *fb = frames + dense::FRAME_DOUBLES * (size_t)b;
+  for (int e = 0; e < 12; ++e) fb[e] = X[e];
+  fb[12] = bad ? 0.0 : dense::vertex_factor(tab.scale[item[pv::IT_OBJECT]], cloud_div);   // nothing is read through a bad record
+  double *s = stats + meshicp::NSTAT * (size_t)b;
+  for (int e = 0; e < meshicp::NSTAT; ++e) s[e] = 0.0;
+  if (bad) s[meshicp::ST_STATUS] = (double)meshicp::BAD_OBJECT;
+}
+
+// D2..D5: grid = (tile blocks, items).  A workgroup takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its item; lane l adds the
+// tile's slots l, l + 256, ... in ascending order onto zero (29 accumulators in registers), the lanes of a wave meet by shuffles, the four
+// waves in LDS, and the tile's total goes to its own row of `part` by plain stores: which workgroup took a tile does not show.
+__global__ __launch_bounds__(RB) void dense_accum_kernel(const unsigned long long *__restrict__ keys, Frames fr,
+                                                         const double *__restrict__ rays, const int *__restrict__ items,
+                                                         const float *__restrict__ vertices, int V, const int *__restrict__ triangles, int T,
+                                                         const double *__restrict__ frames, const double *__restrict__ stats, int WH,
+                                                         int WW, int gate, double p22, double p23, double cloud_div, int ntiles,
+                                                         double *__restrict__ part) {
+  __shared__ double part_s[RB / 64][dense::NPART];
+  const int b = blockIdx.y;
+  if (stats[meshicp::NSTAT * (size_t)b + meshicp::ST_STATUS] != 0.0) return;  // frozen or bad item: the whole workgroup leaves
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  double X[12];
+  const double *fb = frames + dense::FRAME_DOUBLES * (size_t)b;
+#pragma unroll
+  for (int e = 0; e < 12; ++e) X[e] = fb[e];
+  const double factor = fb[12];
+  const int slots = WH * WW;                                                  // <= 2^30
+  const size_t npix = (size_t)fr.IH * fr.IW;
+  const unsigned long long *kb = keys + (size_t)b * slots;
+  const unsigned short *df = fr.depth + (size_t)item[pv::IT_FRAME] * npix;
+  const unsigned short *mf = fr.mask ? fr.mask + (size_t)item[pv::IT_MASK_FRAME] * npix : nullptr;
+  const int r0 = item[pv::IT_R0], c0 = item[pv::IT_C0], mv = item[pv::IT_MASK_VALUE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    double acc[meshicp::NSUM];
+#pragma unroll
+    for (int k = 0; k < meshicp::NSUM; ++k) acc[k] = 0.0;
+    int cnt = 0;
+    for (int j = 0; j < dense::SWEEPS; ++j) {
+      const long long sl = (long long)tile * dense::TILE + j * RB + threadIdx.x;
+      int r = 0, q = 0;
+      if (sl >= slots || !pv::slot_node((int)sl, r0, c0, WW, fr.IH, fr.IW, &r, &q)) continue;
+      const unsigned long long key = kb[sl];
+      const size_t p = (size_t)r * fr.IW + q;
+      const int co = df[p];
+      if (!dense::candidate(pv::key_code(key), co, gate, mf != nullptr, mf && mf[p] == mv)) continue;
+      const unsigned t = (unsigned)(key & 0xffffffffull);
+      if (t >= (unsigned)T) continue;                                         // not a key of the raster pass: never followed
+      const unsigned i0 = triangles[3 * (size_t)t], i1 = triangles[3 * (size_t)t + 1], i2 = triangles[3 * (size_t)t + 2];
+      if (i0 >= (unsigned)V || i1 >= (unsigned)V || i2 >= (unsigned)V) continue;
+      const double ray[3] = {rays[3 * p], rays[3 * p + 1], rays[3 * p + 2]};
+      double x[3], term[meshicp::TERM_DOUBLES];
+      dense::observed_point(co, ray, p22, p23, cloud_div, X, x);
+      if (!dense::plane_terms(vertices + 3 * (size_t)i0, vertices + 3 * (size_t)i1, vertices + 3 * (size_t)i2, factor, x, term)) continue;
+      meshicp::accumulate(term, acc);
+      ++cnt;
+    }
+    // I6's tree over a wave's lanes: at step s lane l < s adds lane l + s (the other lanes' values are not used afterwards)
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+      for (int k = 0; k < meshicp::NSUM; ++k) acc[k] = acc[k] + __shfl_down(acc[k], s);
+      cnt += __shfl_down(cnt, s);
+    }
+    __syncthreads();                                                          // the previous tile's readers are done
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < meshicp::NSUM; ++k) part_s[wave][k] = acc[k];
+      part_s[wave][meshicp::NSUM] = (double)cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x < dense::NPART) {
+      const int k = threadIdx.x;
+      part[((size_t)b * ntiles + tile) * dense::PART_DOUBLES + k] = (part_s[0][k] + part_s[1][k]) + (part_s[2][k] + part_s[3][k]);
+    }
+  }
+}
+
+// D5, D6: grid = B, one wave.  Lane k < 29 adds entry k of the item's tile rows in ascending tile order onto zero; lane 0 then runs
+// finish_pass (I6..I9) on the working pose and writes pose_out and the model frame of the next pass.
+__global__ __launch_bounds__(64) void dense_finish_kernel(const double *__restrict__ part, int ntiles, int pass, int solve,
+                                                          double *__restrict__ work, double *__restrict__ frames,
+                                                          double *__restrict__ pose_out, double *__restrict__ stats) {
+  __shared__ double sums[dense::NPART];
+  const int b = blockIdx.x;
+  if (stats[meshicp::NSTAT * (size_t)b + meshicp::ST_STATUS] != 0.0) return;
+  if (threadIdx.x < dense::NPART) {
+    const double *row = part + (size_t)b * ntiles * dense::PART_DOUBLES + threadIdx.x;
+    double s = 0.0;
+    for (int t = 0; t < ntiles; ++t) s = s + row[(size_t)t * dense::PART_DOUBLES];
+    sums[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double tot[meshicp::NSUM], p[7], X[12];
+  for (int k = 0; k < meshicp::NSUM; ++k) tot[k] = sums[k];
+  for (int e = 0; e < 7; ++e) p[e] = work[DENSE_POSE_DOUBLES * (size_t)b + e];
+  meshicp::finish_pass(tot, (int)sums[meshicp::NSUM], pass, solve, p, stats + meshicp::NSTAT * (size_t)b);
+  meshicp::model_frame(p, X);
+  for (int e = 0; e < 7; ++e) {
+    work[DENSE_POSE_DOUBLES * (size_t)b + e] = p[e];
+    pose_out[7 * (size_t)b + e] = p[e];
+  }
+  for (int e = 0; e < 12; ++e) frames[dense::FRAME_DOUBLES * (size_t)b + e] = X[e];
+}
+
 inline bool window_ok(int B, int WH, int WW) { return B >= 1 && B <= 65535 && WH >= 1 && WW >= 1 && (long)WH * WW <= (1L << 30); }
 
 // blocks per item of a launch over `items` lanes' worth of work per item
@@ -325,5 +460,94 @@ extern "C" int df_pose_vsd(const float *vertices, int V, const int *triangles, i
   hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles, tab, O, cam, fr, items, pose_gt, cloud_div, WH, WW,
                      cull, keys_g, side);
   hipLaunchKernelGGL(vsd_score_kernel, dim3(xb, B), dim3(RB), 0, st, keys_e, keys_g, fr, rays, O, items, WH, WW, cam.p22, cam.p23, table, NT, stats);
+  return check_launch(name);
+}
+
+// the parts of df_pose_refine_dense's scratch, one after another (each a multiple of 8 bytes): the key plane of B windows, the raster
+// pass's own tallies (not reported), the working poses, the model frames, a row per (item, tile)
+namespace {
+struct DenseScratch {
+  size_t keys, side, work, frames, part, total;
+};
+DenseScratch dense_scratch(int B, int WH, int WW) {
+  DenseScratch s;
+  s.keys = (size_t)B * WH * WW * sizeof(unsigned long long);
+  s.side = (size_t)B * pv::NSTAT * sizeof(long long);
+  s.work = (size_t)B * DENSE_POSE_DOUBLES * sizeof(double);
+  s.frames = (size_t)B * dense::FRAME_DOUBLES * sizeof(double);
+  s.part = (size_t)B * dense::tile_count((long long)WH * WW) * dense::PART_DOUBLES * sizeof(double);
+  s.total = s.keys + s.side + s.work + s.frames + s.part;
+  return s;
+}
+bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return b != nullptr && x < y + nb && y < x + na;
+}
+}  // namespace
+
+extern "C" size_t df_pose_refine_dense_scratch_bytes(int B, int WH, int WW) {
+  return window_ok(B, WH, WW) ? dense_scratch(B, WH, WW).total : 0;
+}
+
+extern "C" int df_pose_refine_dense(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale,
+                                    int O, const double *proj, const unsigned short *depth, int F, int IH, int IW, const double *rays,
+                                    const unsigned short *mask, int NM, const int *items, const double *pose_in, double cloud_div, int B,
+                                    int WH, int WW, int gate, int cull, int iters, double *pose_out, double *stats, void *scratch,
+                                    size_t scratch_bytes, df_stream_t stream) {
+  const char *name = "pose_refine_dense";
+  if (!vertices || !triangles || !tri_begin || !model_scale || !proj || !depth || !rays || !items || !pose_in || !pose_out || !stats || !scratch)
+    return set_error(DF_ERR_ARG, "%s: null pointer", name);
+  if (mask && NM < 1) return set_error(DF_ERR_ARG, "%s: a mask needs NM >= 1 frames, got %d", name, NM);
+  if (!objects_ok(O)) return set_error(DF_ERR_ARG, "%s: O = %d objects outside 1..%d", name, O, MAX_OBJECTS);
+  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
+  if (!window_ok(B, WH, WW)) return set_error(DF_ERR_ARG, "%s: B = %d outside 1..65535 or WH x WW = %d x %d outside 1..2^30", name, B, WH, WW);
+  if (gate < 0 || gate > dense::MAX_GATE) return set_error(DF_ERR_ARG, "%s: gate %d outside 0..%d", name, gate, dense::MAX_GATE);
+  if (iters < 0 || iters > meshicp::MAX_ITERS) return set_error(DF_ERR_ARG, "%s: iters %d outside 0..%d", name, iters, meshicp::MAX_ITERS);
+  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
+  if (!(cloud_div > 0.0 && cloud_div - cloud_div == 0.0)) return set_error(DF_ERR_ARG, "%s: cloud_div must be finite and > 0", name);
+  if (reinterpret_cast<uintptr_t>(rays) % 8 || reinterpret_cast<uintptr_t>(pose_in) % 8 || reinterpret_cast<uintptr_t>(pose_out) % 8 ||
+      reinterpret_cast<uintptr_t>(stats) % 8)
+    return set_error(DF_ERR_ARG, "%s: rays, pose_in, pose_out and stats must be 8-byte aligned", name);
+  const DenseScratch lay = dense_scratch(B, WH, WW);
+  if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, lay.total, proj)) return e;
+  int longest = 0;
+  if (int e = check_tri_begin(name, tri_begin, O, T, &longest)) return e;
+  const size_t npix = (size_t)IH * IW, pose_b = (size_t)B * 7 * sizeof(double), stats_b = (size_t)B * meshicp::NSTAT * sizeof(double);
+  const struct { const void *p; size_t n; } ins[] = {{vertices, (size_t)V * 12}, {triangles, (size_t)T * 12}, {depth, (size_t)F * npix * 2},
+                                                     {mask, (size_t)(mask ? NM : 0) * npix * 2}, {rays, npix * 24},
+                                                     {items, (size_t)B * pv::ITEM_INTS * 4}, {pose_in, pose_b}, {scratch, lay.total}};
+  for (const auto &in : ins)
+    if (ranges_overlap(pose_out, pose_b, in.p, in.n) || ranges_overlap(stats, stats_b, in.p, in.n))
+      return set_error(DF_ERR_ARG, "%s: pose_out and stats may not overlap the inputs or the scratch", name);
+  if (ranges_overlap(pose_out, pose_b, stats, stats_b)) return set_error(DF_ERR_ARG, "%s: pose_out and stats overlap", name);
+
+  hipStream_t st = to_stream(stream);
+  const long slots = (long)WH * WW;
+  char *base = static_cast<char *>(scratch);
+  unsigned long long *keys = reinterpret_cast<unsigned long long *>(base);
+  long long *side = reinterpret_cast<long long *>(base + lay.keys);
+  double *work = reinterpret_cast<double *>(base + lay.keys + lay.side);
+  double *frames = reinterpret_cast<double *>(base + lay.keys + lay.side + lay.work);
+  double *part = reinterpret_cast<double *>(base + lay.keys + lay.side + lay.work + lay.frames);
+  const Frames fr = {depth, mask, F, NM, IH, IW};
+  const ObjectTable tab = make_object_table(tri_begin, model_scale, O, T);
+  const Camera cam = make_camera(proj);
+  const int ntiles = dense::tile_count(slots);
+  // the tile blocks of an item: the cap of the score kernels, in tiles
+  int cap = cdiv(VERIFY_TARGET_BLOCKS, B) < RESOLVE_MAX_BLOCKS ? cdiv(VERIFY_TARGET_BLOCKS, B) : RESOLVE_MAX_BLOCKS;
+  cap = cap < 1 ? 1 : cap;
+  const int tb = item_blocks(longest, B, RASTER_MAX_BLOCKS), xb = ntiles < cap ? ntiles : cap;
+  if (hipMemsetAsync(side, 0, lay.side, st) != hipSuccess) return check_launch(name);
+  hipLaunchKernelGGL(dense_init_kernel, dim3(cdiv(B, RB)), dim3(RB), 0, st, items, pose_in, tab, O, F, mask ? 1 : 0, NM, cloud_div, B, work, frames,
+                     pose_out, stats);
+  for (int pass = 0; pass <= iters; ++pass) {
+    if (hipMemsetAsync(keys, 0xff, lay.keys, st) != hipSuccess) return check_launch(name);
+    // D1: P1, P2 of df_pose_verify, verbatim, from the working poses
+    hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles, tab, O, cam, fr, items, work, cloud_div, WH, WW,
+                       cull, keys, side);
+    hipLaunchKernelGGL(dense_accum_kernel, dim3(xb, B), dim3(RB), 0, st, keys, fr, rays, items, vertices, V, triangles, T, frames, stats, WH, WW, gate,
+                       cam.p22, cam.p23, cloud_div, ntiles, part);
+    hipLaunchKernelGGL(dense_finish_kernel, dim3(B), dim3(64), 0, st, part, ntiles, pass, pass < iters ? 1 : 0, work, frames, pose_out, stats);
+  }
   return check_launch(name);
 }

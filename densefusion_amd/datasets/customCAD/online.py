@@ -327,6 +327,19 @@ class RenderedPoseDataset(ChunkedViews):
         # VSD scores against the frames an item was cut from: only a dataset that keeps them hands over the loader's rays
         return errors.set_rays(self.udp.ray_map_on(self.device)) if self.keep_frames else errors
 
+    def dense_refiner(self):
+        """A ``lib.pose_refine_dense.DensePoseRefiner`` of the models' triangles, in file units with the renderer's model scale, camera
+        and frame size, carrying the loader's ray map: an item's index k names mesh k, and a pose in the units of the items' clouds is
+        refined against the frame the item was cut from.  ``ValueError`` in point-cloud mode (there are no triangles to draw) and without
+        ``keep_frames`` (there is no frame to refine against)."""
+        if self.meshes is None:
+            raise ValueError('dense_refiner needs triangles: a scene or raster mesh (a point cloud has none)')
+        if not self.keep_frames:
+            raise ValueError('dense_refiner needs the frames the items were cut from: RenderedPoseDataset(keep_frames=True)')
+        from ...lib.pose_refine_dense import DensePoseRefiner
+        refiner = DensePoseRefiner(self.meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
+        return refiner.set_rays(self.udp.ray_map_on(self.device))
+
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small
 

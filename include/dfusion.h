@@ -944,6 +944,64 @@ int df_pose_vsd(const float *vertices, int V, const int *triangles, int T, const
                 int WH, int WW, int cull, long long *stats, void *scratch, size_t scratch_bytes, df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dense, projective point-to-plane ICP of B estimated poses against their whole depth windows (densefusion_amd/lib/pose_refine_dense.py):
+ * the form of ICP depth trackers use.  Per pass the CAD mesh of each item is drawn at its current pose into the item's window by
+ * df_pose_verify's own raster pass, every drawn node is associated with the depth observed at the same node, and the pose moves so as to
+ * bring the observed points onto the planes of the triangles drawn there.  Association is by pixel, so visibility and self-occlusion are
+ * the z-buffer's; the whole window takes part and a mask is optional.  The pose moves on the device between passes with no host round
+ * trip.  No allocation, no synchronisation, the caller's stream; the only atomics are the raster's integer minima, there is no
+ * floating-point atomic: two identical calls give identical bytes, and an item's outputs depend on its own record, pose, object, frame
+ * and mask only, not on B, on the launch shape or on the items next to it.  Everything is fp64, one rounding per operation in exactly the
+ * order written below (no contraction), with the dot and cross products of df_mesh_closest; only + - * / sqrt appear, so a restatement
+ * matches bit for bit (tests/pose_dense_np.py).  The rules are densefusion_amd/csrc/pose_dense_core.h.  df_mesh_icp, df_pose_verify and
+ * df_pose_vsd, their kernels and their outputs are unchanged.
+ *
+ * df_pose_refine_dense_scratch_bytes: B*WH*WW 64-bit keys, B*12 64-bit tallies of the raster pass, per item the working pose (7 doubles)
+ *   and its model frame (16 doubles), and 32 doubles per (item, tile of 2048 window slots); 0 for sizes the call refuses (host only).
+ * df_pose_refine_dense: df_pose_verify's arguments with `gate` in tol's place, and with
+ *   DEVICE: rays [IH][IW][3] fp64, the loader's ray map as for df_pose_vsd; pose_in [B][7] fp64 in pose's place; pose_out [B][7] fp64;
+ *   stats [B][6] fp64 = df_mesh_icp's columns {status, inliers and rms of the first pass, inliers and rms of the last pass, steps taken};
+ *   status 0 ok, 1 few inliers, 2 degenerate, 3 bad item; scratch (8-byte aligned).
+ *   DF_ERR_ARG, before anything is launched or written: every refusal of df_pose_verify (with gate outside 0..65535 for tol); a null
+ *   rays, pose_in, pose_out or stats, or one that is not 8-byte aligned; iters outside 0..64; pose_out or stats overlapping a device input
+ *   (vertices, triangles, depth, mask, rays, items, pose_in), the scratch or each other.
+ *   Per item:
+ *   S0 of df_mesh_icp: (q, t) = pose_in with q normalised and the sign rule; stats = 0.  A bad item (P0 of df_pose_verify) has status 3:
+ *       nothing is read through its record, pose_out = (q, t) and stats stay as they are now.  An empty triangle range is not bad: it
+ *       draws nothing and finds no inlier.  (A zero or NaN quaternion gives NaNs, draws nothing and so ends as `few inliers`.)
+ *   Then pass k = 0 .. iters, D1..D5 for every item whose status is 0, and D6's solve and update as well when k < iters:
+ *   D1. Draw: the item's key plane is set to "no key"; P1 and P2 of df_pose_verify, verbatim (the same kernel), from the current (q, t).
+ *   D2. Per existing node (r, q) of the window (df_pose_verify's item record and slots): cr = key >> 32 or "not rendered"; co =
+ *       depth[frame][r][q]; m as in P3.  The node is a candidate when it took a key, co != 65535, |co - cr| <= gate as integers and,
+ *       with mask != NULL, m holds.  All integer: which nodes take part never depends on rounding.
+ *   D3. The observed point: z = -p23 / (p22 + (1.0 - (double)co / 65534.0)), S2's formula with its sign (negative in front of the
+ *       camera); p_k = (rays[r][q][k] z) / cloud_div for k = 0..2, the point in the units of the poses (what df_preprocess_objects_cad
+ *       writes for this node and code, up to its fp32 roundings); x = X p with X = [R^T | o] of the current (q, t) by I1, I2 of
+ *       df_mesh_icp: x_j = ((X[j][0] p_0 + X[j][1] p_1) + X[j][2] p_2) + X[j][3].
+ *   D4. The plane: tri = the low 32 bits of the key, with the vertices A, B, C of triangles[tri] widened exactly from fp32.  f =
+ *       model_scale[object] / cloud_div, once per item; a = A f, e1 = B f - a, e2 = C f - a (each product, then the difference);
+ *       n = e1 x e2; nn = n . n.  No face (nn > 0 fails): no inlier.  sn = sqrt(nn); nh = n / sn; w = x - a; r = nh . w;
+ *       J = (x x nh, nh), six numbers; d2 = r r.  The node is an inlier when each of the eight numbers J, r, d2 is finite.
+ *   D5. The 28 sums of I6 of df_mesh_icp (A, G, D by its `accumulate`) and the count over the inliers, in an order that is a function of
+ *       (WH, WW, slot) only.  The window's slots 0 .. WH*WW-1 are cut into tiles of 2048: tile i holds the slots 2048 i .. 2048 i + 2047
+ *       below WH*WW.  Within a tile, lane l of 256 adds the tile's slots 2048 i + l, + 256, ... in ascending order onto 0; in each group of
+ *       64 lanes a binary tree (s = 32, 16, .., 1: lane l < s adds lane l + s); the four group totals as (T0 + T1) + (T2 + T3): I6's lane
+ *       order and tree.  The tile totals are then added onto 0 in ascending tile order.  rms = sqrt(D / count), 0 with no inlier.
+ *   D6. I6's stats and I7..I9 of df_mesh_icp through the same function, unchanged: last inliers and rms = count, rms, on pass 0 the first
+ *       as well; count < 6: status 1; a pivot <= 2^-40 of the largest diagonal entry: status 2 (one flat wall); otherwise the model-frame
+ *       step, steps taken += 1.  A frozen item (status != 0) keeps its pose and its stats; whether it is still drawn is not part of the
+ *       contract.
+ *   I10 of df_mesh_icp: pose_out = (q, t), a unit quaternion with w >= 0; the last pass (k = iters) only scores.
+ *   Launches per pass: the clear of the key planes, the raster, the accumulation (one row per (item, tile) to the scratch by plain
+ *   stores) and the finish (the tile rows in order, the solve and the update; it also writes the next pass's X). */
+size_t df_pose_refine_dense_scratch_bytes(int B, int WH, int WW);
+int df_pose_refine_dense(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale, int O,
+                         const double *proj, const unsigned short *depth, int F, int IH, int IW, const double *rays,
+                         const unsigned short *mask, int NM, const int *items, const double *pose_in, double cloud_div, int B, int WH,
+                         int WW, int gate, int cull, int iters, double *pose_out, double *stats, void *scratch, size_t scratch_bytes,
+                         df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]

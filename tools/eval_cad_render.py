@@ -41,6 +41,13 @@ per entry.  VSD, the visible surface discrepancy (``df_pose_vsd``), draws both p
 ``--verify_margin`` and compares them with the depth frame the item came from: ``--bop_delta`` x the diameter is its visibility tolerance,
 tau runs over 0.05 .. 0.5 x the diameter, and the log gives the recall of VSD below 0.05 .. 0.5 averaged over the tau.  The mean AR is over
 the three errors.  Without ``--bop`` nothing changes by a byte.
+``--dense K`` (default 0: off) adds the dense, projective ICP step (``df_pose_refine_dense``): every mask source is scored
+once more as ``<source>_dense``, the refiner's pose taking K steps against the whole depth window of the item's crop box grown by
+``--verify_margin`` (the model is drawn at the pose, every drawn node is matched with the depth observed there), and with ``--icp`` also
+as ``<source>_icp_dense``: the ICP pose, then the dense steps.  ``--dense_gate`` is the largest difference in depth codes between a drawn
+and an observed node that still takes part, ``--dense_mask`` lets only the nodes of the item's mask take part.  The new entries compose
+with ``--verify`` and ``--bop`` like the others; each logs the items the step left alone and the mean point-to-plane rms before and
+after.  Without ``--dense`` nothing changes by a byte.
 """
 from __future__ import annotations
 
@@ -93,6 +100,10 @@ def build_parser():
                     "user's parameter, not a measurement)")
     ap.add_argument("--bop_step", type=float, default=0.01, help="--bop: a surface of revolution counts as ceil(pi / step) rotations (the BOP toolkit's "
                     "0.01: 315); the user's parameter, not a measurement")
+    ap.add_argument("--dense", type=int, default=0, help="steps of dense projective ICP against the depth window (0 = off); scored as <source>_dense "
+                    "and, with --icp, <source>_icp_dense")
+    ap.add_argument("--dense_gate", type=int, default=16, help="--dense: depth codes a drawn and an observed node may differ by and still take part")
+    ap.add_argument("--dense_mask", action="store_true", help="--dense: only the nodes of the item's mask take part")
     views = ap.add_argument_group("views", "the views and the renderer, under the names of tools/render_cad_dataset.py")
     cad_render.add_view_arguments(views)
     cad_symmetry.add_sym_arguments(views)
@@ -169,6 +180,38 @@ class VerifyStep:
         mean = lambda a: float(a.mean()) if len(a) else 0.0
         return dict(items=len(score), passes=int(ok.sum()), mean_vsiou_pass=mean(score[ok]), mean_vsiou_miss=mean(score[~ok]),
                     took_last=int(taken.sum()), took_first=int((~taken).sum()), tol=self.tol, margin=self.margin)
+
+
+class DenseStep:
+    """``evaluate()``'s ``select_pose`` from a dataset's ``dense_refiner()`` (the dataset keeps its frames): the last candidate takes
+    ``--dense`` steps of dense projective ICP against the item's own depth frame in the window of its crop box grown by
+    ``--verify_margin`` (one size per call: the largest), and goes on to ``inner`` (a ``VerifyStep``) when there is one.  The stats stay on
+    the device until ``summary``."""
+
+    def __init__(self, dataset, opt, inner=None):
+        self.dataset, self.ref, self.inner = dataset, dataset.dense_refiner(), inner
+        self.iters, self.gate, self.use_mask, self.margin, self.cull = opt.dense, opt.dense_gate, bool(opt.dense_mask), opt.verify_margin, bool(dataset.cull)
+        self.stats = []
+
+    def __call__(self, indices, candidates, objs):
+        infos = [self.dataset.view_info(i) for i in indices]
+        dev = candidates[-1].device
+        depth = torch.stack([f["depth"] for f in infos])
+        mask = torch.stack([f["mask"] for f in infos]) if self.use_mask else None
+        window = (max(f["box"][1] - f["box"][0] for f in infos) + 2 * self.margin, max(f["box"][3] - f["box"][2] for f in infos) + 2 * self.margin)
+        rec = torch.tensor([[k, objs[k], f["box"][0] - self.margin, f["box"][2] - self.margin] for k, f in enumerate(infos)],
+                           dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        pose, stats = self.ref.refine(depth, candidates[-1].contiguous(), rec[:, 0], rec[:, 1], rec[:, 2:4], window, iters=self.iters,
+                                      gate=self.gate, mask=mask, cull=self.cull)
+        self.stats.append(stats)
+        return self.inner(indices, [pose], objs) if self.inner is not None else pose
+
+    def summary(self):
+        st = torch.cat(self.stats).cpu().numpy() if self.stats else np.zeros((0, 6))
+        mean = lambda a: float(a.mean()) if len(a) else 0.0
+        return dict(items=len(st), few=int((st[:, 0] == 1).sum()), degenerate=int((st[:, 0] == 2).sum()), bad_item=int((st[:, 0] == 3).sum()),
+                    mean_first_rms=mean(st[:, 2]), mean_last_rms=mean(st[:, 4]), mean_steps=mean(st[:, 5]), gate=self.gate, margin=self.margin,
+                    mask=self.use_mask)
 
 
 BOP_STEPS = [0.05 * k for k in range(1, 11)]                       # the ten BOP thresholds: x the diameter (MSSD), x 100 r pixels (MSPD)
@@ -282,10 +325,11 @@ class _PassLog:
         return self.fw.write(text)
 
 
-def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, verify=None, bop=None):
+def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, verify=None, bop=None, dense=False):
     """``evaluate()`` over ``dataset`` and the tallies of one mask source; with ``icp`` (an ``IcpStep``) the poses take that last step,
     with ``verify`` (a ``VerifyStep``) they are scored, or chosen, by render-and-compare; with ``bop`` the pose that is scored is also
-    scored by the BOP pose errors (``bop``: the dataset's ``BopScorer``; a ``BopStep`` of it goes around ``verify``)."""
+    scored by the BOP pose errors (``bop``: the dataset's ``BopScorer``; a ``BopStep`` of it goes around ``verify``); with ``dense`` the
+    pose first takes the dense steps (a ``DenseStep`` between the two)."""
     objlist = list(dataset.objlist)
     n = len(dataset) if opt.max_frames <= 0 else min(opt.max_frames, len(dataset))
     with open(os.path.join(opt.output_result_dir, "eval_result_logs_%s.txt" % source), "w") as fw:
@@ -293,8 +337,10 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, ver
             print(m)
             fw.write(m + "\n")
         steps = dict(**({} if icp is None else {"refine_pose": icp}), **({} if verify is None else {"select_pose": verify}))
+        if dense:
+            steps["select_pose"] = dense = DenseStep(dataset, opt, inner=verify)
         if bop is not None:
-            steps["select_pose"] = bop = BopStep(dataset, bop, inner=verify)
+            steps["select_pose"] = bop = BopStep(dataset, bop, inner=dense or verify)
         log = fw if verify is None else _PassLog(fw)
         success, served = evaluate(dataset, estimator, refiner, diameter, opt, log, **steps)
         success, served = success[:len(objlist)], served[:len(objlist)]
@@ -314,6 +360,11 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, ver
             out["icp"] = m = icp.summary()
             say("[{0} masks] ICP {1} steps: {2} items, {3} few inliers, {4} degenerate, mean rms {5:.6g} -> {6:.6g}".format(
                 source, icp.iters, m["items"], m["few"], m["degenerate"], m["mean_first_rms"], m["mean_last_rms"]))
+        if dense:
+            out["dense"] = m = dense.summary()
+            say("[{0} masks] dense {1} steps gate {2}{3}: {4} items, {5} few inliers, {6} degenerate, mean rms {7:.6g} -> {8:.6g}".format(
+                source, dense.iters, m["gate"], " masked" if m["mask"] else "", m["items"], m["few"], m["degenerate"], m["mean_first_rms"],
+                m["mean_last_rms"]))
         if verify is not None:
             out["verify"] = m = verify.summary(log.passed)
             say("[{0} masks] verify tol {1} margin {2}: mean vsiou {3:.6f} over {4} passes, {5:.6f} over {6} misses".format(
@@ -355,6 +406,8 @@ def main(argv=None):
         raise SystemExit("--bop_step takes a positive angle step and --bop_delta a finite fraction >= 0")
     if not 0 <= opt.verify_tol <= 65535 or not 0 <= opt.verify_margin <= 4096:
         raise SystemExit("--verify_tol takes 0..65535 codes and --verify_margin 0..4096 pixels")
+    if not 0 <= opt.dense <= 64 or not 0 <= opt.dense_gate <= 65535:
+        raise SystemExit("--dense takes 0..64 steps and --dense_gate 0..65535 codes")
     if not torch.cuda.is_available():
         raise SystemExit("eval_cad_render.py needs a GPU (densefusion_amd has no CPU path)")
     from densefusion_amd.datasets.customCAD.online import RenderedPoseDataset
@@ -378,7 +431,7 @@ def main(argv=None):
             # SegNet's masks need the scene renderer's label plane; the truth run of the same call renders the same scenes
             dataset = RenderedPoseDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=opt.cad_seed, frames=opt.cad_frames,
                                                        num=NUM_POINTS, scene=True if segnet is not None else None, **kw,
-                                                       **({"keep_frames": True} if opt.verify or opt.bop else {}))
+                                                       **({"keep_frames": True} if opt.verify or opt.bop or opt.dense else {}))
         except ValueError as e:
             raise SystemExit(f"eval_cad_render.py: {e}")
 
@@ -411,6 +464,14 @@ def main(argv=None):
             if opt.verify:                                          # per item the pose with the higher visible-surface IoU
                 name = source + "_icp_best"
                 result[name] = run_source(name, dataset, estimator, refiner, diameter, opt, icp=IcpStep(dataset, opt), verify=verifier(True), bop=scorer)
+                result[name]["sym_list"] = dataset.get_sym_list()
+        if opt.dense > 0:                                           # the same views once more: the dense steps after the refiner, and after ICP
+            for name, icp in [(source + "_dense", None)] + ([(source + "_icp_dense", True)] if opt.icp > 0 else []):
+                try:
+                    result[name] = run_source(name, dataset, estimator, refiner, diameter, opt, icp=IcpStep(dataset, opt) if icp else None,
+                                              verify=verifier(), bop=scorer, dense=True)
+                except ValueError as e:
+                    raise SystemExit(f"eval_cad_render.py: --dense: {e}")
                 result[name]["sym_list"] = dataset.get_sym_list()
     return result
 
