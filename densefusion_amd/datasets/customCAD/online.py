@@ -340,6 +340,20 @@ class RenderedPoseDataset(ChunkedViews):
         refiner = DensePoseRefiner(self.meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
         return refiner.set_rays(self.udp.ray_map_on(self.device))
 
+    def ppf_estimator(self, **model_options):
+        """A ``lib.pose_ppf.PpfEstimator`` of the models' meshes sampled in the units of the items' clouds (``model_options``: the keyword
+        arguments of ``lib.pose_ppf.PpfModels`` after ``cloud_div``), with the renderer's camera and frame size, carrying the loader's ray
+        map: an item's index k names mesh k, and the poses it finds are in the units ``dense_refiner()`` and ``pose_verifier()`` take.
+        ``ValueError`` in point-cloud mode (there is no surface to sample) and without ``keep_frames`` (there is no frame to vote on)."""
+        if self.meshes is None:
+            raise ValueError('ppf_estimator needs triangles: a scene or raster mesh (a point cloud has none)')
+        if not self.keep_frames:
+            raise ValueError('ppf_estimator needs the frames the items were cut from: RenderedPoseDataset(keep_frames=True)')
+        from ...lib.pose_ppf import PpfEstimator, PpfModels
+        models = PpfModels(self.meshes, self.model_scale, 10000.0, **model_options)
+        estimator = PpfEstimator(models, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
+        return estimator.set_rays(self.udp.ray_map_on(self.device))
+
     def get_num_points_mesh(self):
         return self.num_pt_mesh_large if self.refine else self.num_pt_mesh_small
 

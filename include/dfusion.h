@@ -1002,6 +1002,103 @@ int df_pose_refine_dense(const float *vertices, int V, const int *triangles, int
                          df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pose hypotheses of B items from depth alone, by point-pair-feature voting (Drost et al. 2010; densefusion_amd/lib/pose_ppf.py): a
+ * global search that needs the sampled CAD model and the item's depth window and no start pose.  Every pair of an oriented scene
+ * reference point and another scene point looks up the model pairs of the same quantised feature and votes for (model point, rotation
+ * about the normal); the best cell of each reference is a pose hypothesis, the hypotheses are clustered greedily and the K best clusters
+ * are returned, to be refined by df_pose_refine_dense and told apart by df_pose_verify.  No allocation, no synchronisation, the caller's
+ * stream; the votes are integer atomics and there is no floating-point atomic: two identical calls give identical bytes, and an item's
+ * outputs depend on its own record, object, frame and mask only.  Everything that decides a result is fp64, one rounding per operation
+ * in exactly the order written below (no contraction), with the dot and cross products of df_mesh_closest (dot: (a0 b0 + a1 b1) + a2 b2);
+ * only + - * / sqrt, comparisons and integer arithmetic appear: no angle is ever computed, every angle is binned by its cosine against a
+ * table the host passes, so a restatement matches bit for bit (tests/pose_ppf_np.py).  The rules are densefusion_amd/csrc/pose_ppf_core.h,
+ * compiled for the host (the model builder) and the device (the vote) alike.  df_pose_verify, df_pose_vsd, df_pose_refine_dense and
+ * df_mesh_icp, their kernels and their outputs are unchanged.
+ *
+ * Tables (HOST, launch arguments): ang_cos [NANG-1], the boundary cosines of the three feature angles, cos(k pi / NANG) for k = 1 ..
+ *   NANG-1; alpha_cos [NA/2-1], cos(2 pi k / NA) for k = 1 .. NA/2-1; alpha_cs [NA][2], (cos, sin) of the sector centres (k + 1/2) 2 pi /
+ *   NA.  Both cosine tables must descend strictly inside (-1, 1).  The bin of a value v in a table is the number of its boundaries b
+ *   with v <= b.
+ * The rule of a pair, shared by model and scene:
+ *   F1. Oriented pair (p1, n1), (p2, n2): d = p2 - p1, L = sqrt(d . d); dropped unless L > 0 and finite.  fd = L / dist_step; dropped
+ *       unless fd < ND; distance bin = (int)fd.
+ *   F2. c1 = (d . n1) / L, c2 = (d . n2) / L, c3 = n1 . n2; a NaN drops the pair; each is binned in ang_cos.
+ *   F3. key = ((distance bin NANG + bin1) NANG + bin2) NANG + bin3; NKEY = ND NANG^3.
+ *   L1. The rotation R(n) that takes a unit normal n to +x: k = 1 + n_x; k < 2^-20: R = diag(-1, -1, 1); otherwise rows
+ *       (1 - (n_y n_y + n_z n_z) / k, n_y, n_z), (-n_y, 1 - (n_y n_y) / k, -((n_y n_z) / k)), (-n_z, -((n_y n_z) / k), 1 - (n_z n_z) / k).
+ *   L2. The angle of p2 about n1 as a unit vector: y = R_1 . d, z = R_2 . d (rows 1 and 2), m = sqrt(y y + z z); dropped unless m > 0 and
+ *       finite; (c, s) = (y / m, -z / m): the turn about +x that brings the point into the half plane z = 0, y > 0.
+ * df_ppf_model_sizes (host): buckets = O (NKEY + 1) and entries = the sum of NM_o (NM_o - 1), the sizes of bucket_begin and of the entry
+ *   arrays df_ppf_model_build needs at most; DF_ERR_ARG when either passes INT_MAX, O is outside 1..64, ND outside 1..64, NANG outside
+ *   1..32 or an object has fewer than 2 or more than 1024 points.
+ * df_ppf_model_build (host, like df_mesh_tree_build; it reads no mesh: sampling the surface is the caller's): points, normals [NM][3]
+ *   fp64 in the units of the poses, the normals of unit length; point_begin [O+1]; dist_step [O].
+ *   M1. For every ordered pair i != j of an object (i, j counted from the object's first point) that keeps a key (F1..F3) and an angle
+ *       (L1, L2 with n1 = n_i): the entry (i, (float)c, (float)s).
+ *   M2. The entries of an object sorted stably by key, in ascending (i, j) within a key; bucket_begin[o][k] .. bucket_begin[o][k+1]-1
+ *       are the entries of key k of object o in entry_point [.] int32 and entry_cs [.][2] fp32; the objects follow one another; *used =
+ *       the entries written.
+ *   DF_ERR_ARG: a null pointer; what df_ppf_model_sizes refuses; NA odd or outside 2..64; NM_o NA 4 > 150 KiB (the accumulator of one
+ *   reference must fit the LDS of a compute unit); point_begin not running from 0 to NM; a dist_step that is not finite or <= 0; an
+ *   ang_cos that does not descend inside (-1, 1).
+ * df_pose_ppf_scratch_bytes: 8 doubles per (item, grid node), 20 per (item, reference) and one 64-bit count per item; 0 for sizes the call
+ *   refuses (host only).  After a call the last B 64-bit words of that many bytes hold, per item, the table entries its scene pairs
+ *   visited (V2): a diagnostic for tools/pose_ppf_bench.py and the tests, not an output.
+ * df_pose_ppf:
+ *   DEVICE: model_points, model_normals [NM][3] fp64, bucket_begin [O][NKEY+1], entry_point and entry_cs with n_entries entries, as
+ *   df_ppf_model_build wrote them; depth, mask, items and rays as for df_pose_refine_dense; pose_out [B][K][7] fp64; votes_out
+ *   [B][K][2] int32 = (score, members); stats [B][4] fp64 = (status, usable grid nodes, references with a hypothesis, clusters);
+ *   hyp_out [B][NR][8] fp64 = (q, t, votes) per reference, or NULL; scratch (8-byte aligned).
+ *   HOST, read during the call: point_begin [O+1], dist_step [O], cluster_dist [O] (the units of the poses), the three tables, proj.
+ *   DF_ERR_ARG, before anything is launched or written: every refusal of df_pose_verify about pointers, mask, B, the window, F, IH, IW,
+ *   proj, cloud_div and the scratch; every refusal of df_ppf_model_build; a bad alpha_cos or an alpha_cs entry outside -1..1; a
+ *   cluster_dist that is not finite or < 0; cluster_trace outside -1..3; step or ref_step outside 1..64; reach outside 1..8; gate outside
+ *   0..65535; K outside 1..16; more than 16384 grid nodes or 4096 references; n_entries or O (NKEY + 1) above INT_MAX; a pointer not
+ *   aligned to its element (entry_cs to 8 bytes); an output overlapping a device input, the scratch or another output.
+ *   Item record, window and P0 (bad item: status 3, every other output of the item zero, nothing read through the record) are
+ *   df_pose_verify's.
+ *   N1. Grid: GH = ceil(WH / step), GW = ceil(WW / step), G = GH GW; grid node (gr, gc), index gr GW + gc, is the node (r0 + gr step,
+ *       c0 + gc step).  There is no compaction: an invalid node keeps its slot and casts no vote.  A node "counts" when it lies in the
+ *       frame, its code co != 65535 and, with a mask, the mask holds the item's value there.  Its point is D3 of df_pose_refine_dense
+ *       before the transform: z = -p23 / (p22 + (1.0 - (double)co / 65534.0)); p_k = (rays[r][q][k] z) / cloud_div.
+ *   N2. Normal: per axis the two neighbours at -reach and +reach nodes of the frame (columns for dx, rows for dy); a neighbour takes
+ *       part when it counts and |co_nb - co| <= gate as integers.  Both take part: d = P(+) - P(-); one: P(+) - P or P - P(-); none: no
+ *       normal.  n = dx x dy; nn = n . n must be > 0 and finite; nh = n / sqrt(nn), negated when nh . p > 0 (the camera is the origin).
+ *       A grid node is usable when it counts and has a normal.
+ *   V1. References: the grid nodes whose gr and gc are multiples of ref_step, RH = ceil(GH / ref_step) rows of RW = ceil(GW / ref_step);
+ *       reference index rr RW + rc; NR = RH RW.  An unusable reference has no hypothesis.  Per (item, reference) an accumulator
+ *       acc [NM_o][NA] of uint32, zeroed.
+ *   V2. For every other usable grid node: key by F1..F3 with (p1, n1) the reference; (c_s, s_s) by L1, L2.  For every entry (i, c_m,
+ *       s_m) of the object's bucket of that key, widened exactly to fp64: c = c_m c_s + s_m s_s, s = s_m c_s - c_m s_s (the model angle
+ *       less the scene angle); j = the bin of c in alpha_cos; sector = j when s >= 0, NA - 1 - j otherwise; acc[i][sector] += 1.
+ *   V3. The winner is the largest count, then the lowest i, then the lowest sector.  A count of 0: no hypothesis (votes 0, pose zeros).
+ *   H1. With (ca, sa) = alpha_cs[sector], Rs = R(n_ref), Rm = R(n_i): A = Rx Rm, rows Rm_0, ca Rm_1 - sa Rm_2, sa Rm_1 + ca Rm_2;
+ *       R = Rs^T A, R[j][k] = (Rs[0][j] A[0][k] + Rs[1][j] A[1][k]) + Rs[2][j] A[2][k]; t_j = p_ref[j] - R_j . m_i.
+ *   H2. q from R by the largest of (trace, R00, R11, R22) = (tr, ..), tried in this order with >= (a tie goes to the earlier): s =
+ *       sqrt(1 + tr), f = 0.5 / s, q = (0.5 s, (R21 - R12) f, (R02 - R20) f, (R10 - R01) f); for R00: s = sqrt(((1 + R00) - R11) - R22),
+ *       q = ((R21 - R12) f, 0.5 s, (R01 + R10) f, (R02 + R20) f); for R11: s = sqrt(((1 + R11) - R00) - R22), q = ((R02 - R20) f,
+ *       (R01 + R10) f, 0.5 s, (R12 + R21) f); for R22: s = sqrt(((1 + R22) - R00) - R11), q = ((R10 - R01) f, (R02 + R20) f,
+ *       (R12 + R21) f, 0.5 s).
+ *   H3. q normalised with the sign rule of S0 of df_mesh_icp; hypothesis = (q, t, votes).
+ *   C1. Per item the hypotheses with votes > 0 in the order (votes descending, reference index ascending).
+ *   C2. In that order a hypothesis joins the first cluster, in creation order, whose first member (Rc, tc) is near: with R = the matrix
+ *       of its q by I1 of df_mesh_icp, (R_0 . Rc_0 + R_1 . Rc_1) + R_2 . Rc_2 >= cluster_trace (the host passes 1 + 2 cos theta) and
+ *       (t - tc) . (t - tc) <= cluster_dist[object] cluster_dist[object]; otherwise it founds a cluster.  A cluster's score is the
+ *       integer sum of its members' votes, its pose its first member's: nothing is averaged.
+ *   C3. Rank k < K of pose_out and votes_out: the k-th cluster by (score descending, creation order ascending); a score above INT_MAX
+ *       is reported as INT_MAX; missing ranks stay zero.  status = 0, or 1 when the item has no hypothesis. */
+int df_ppf_model_sizes(const int *point_begin, int O, int ND, int NANG, size_t *buckets, size_t *entries);
+int df_ppf_model_build(const double *points, const double *normals, int NM, const int *point_begin, const double *dist_step, int O, int ND,
+                       int NANG, int NA, const double *ang_cos, int *bucket_begin, int *entry_point, float *entry_cs, size_t *used);
+size_t df_pose_ppf_scratch_bytes(int B, int WH, int WW, int step, int ref_step);
+int df_pose_ppf(const double *model_points, const double *model_normals, int NM, const int *point_begin, const double *dist_step,
+                const double *cluster_dist, int O, const int *bucket_begin, const int *entry_point, const float *entry_cs, size_t n_entries,
+                int ND, int NANG, int NA, const double *ang_cos, const double *alpha_cos, const double *alpha_cs, const double *proj,
+                const unsigned short *depth, int F, int IH, int IW, const double *rays, const unsigned short *mask, int NMK, const int *items,
+                double cloud_div, int B, int WH, int WW, int step, int reach, int gate, int ref_step, int K, double cluster_trace,
+                double *pose_out, int *votes_out, double *stats, double *hyp_out, void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Building block, exposed for unit parity tests and for callers that want single layers: channels-last
  * convolution / per-point GEMM on the fp32 matrix cores with the fused epilogue.
  *   out[b][oy][ox][out_coff + n] = act( sum_{ky,kx,c} in[b][oy*stride - pad + ky*dil][ox*stride - pad + kx*dil][in_coff + c]
