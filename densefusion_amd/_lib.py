@@ -171,6 +171,9 @@ SIGNATURES = {
     "df_pose_refine_dense_scratch_bytes": (_sz, [_i, _i, _i]),
     "df_pose_refine_dense": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_double, _i, _i, _i,
                                   _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "df_pose_refine_contour_scratch_bytes": (_sz, [_i, _i, _i]),
+    "df_pose_refine_contour": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, ctypes.c_double, _i, _i, _i,
+                                    _i, _i, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
     "df_pose_sym_error": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "df_ppf_model_sizes": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "df_ppf_model_build": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

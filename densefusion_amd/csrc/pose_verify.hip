@@ -14,6 +14,7 @@
 #include "mesh_objects.h"
 #include "pose_verify_core.h"
 #include "pose_dense_core.h"
+#include "pose_contour_core.h"
 #include "pose_vsd_core.h"
 
 namespace df {
@@ -22,6 +23,7 @@ namespace {
 namespace pv = poseverify;
 namespace vsd = posevsd;
 namespace dense = posedense;
+namespace contour = posecontour;
 static_assert(pv::MAX_OBJECTS == MAX_OBJECTS, "item_bad's objects are those of the object table (mesh_objects.h)");
 
 // Workgroups a launch aims at over all items: 8 per compute unit of a 256-CU part.  The blocks per item are capped at this over B (and
@@ -351,6 +353,207 @@ __global__ __launch_bounds__(64) void dense_finish_kernel(const double *__restri
   for (int e = 0; e < 12; ++e) frames[dense::FRAME_DOUBLES * (size_t)b + e] = X[e];
 }
 
+// ---- df_pose_refine_contour (E1..E6 of its comment in include/dfusion.h; the rules are pose_contour_core.h) -----------------------------
+// The dense call's launches as they stand, with a status row of their own stride ([B][6], in the scratch) that the finish copies into the
+// caller's [B][8] rows.  Once per call the observed outline and its feature map; per pass an accumulation of the outline pairs with the
+// dense one's shape, into a second set of tile rows.
+
+// the caller's rows after S0: the six dense columns and no pairs
+__global__ __launch_bounds__(RB) void contour_stats_kernel(const double *__restrict__ stats6, int B, double *__restrict__ stats) {
+  const int b = blockIdx.x * RB + threadIdx.x;
+  if (b >= B) return;
+  for (int e = 0; e < contour::NSTAT; ++e) stats[contour::NSTAT * (size_t)b + e] = e < meshicp::NSTAT ? stats6[meshicp::NSTAT * (size_t)b + e] : 0.0;
+}
+
+// the node at (wr, wc) of an item's window as E1 sees it: wr, wc may lie outside the window
+__device__ inline contour::Node observed_node(const unsigned short *__restrict__ df, const unsigned short *__restrict__ mf, int mv, int IH, int IW,
+                                              int r0, int c0, int WH, int WW, int wr, int wc) {
+  contour::Node n = {false, false, pv::NO_OBSERVATION};
+  const long long r = (long long)r0 + wr, q = (long long)c0 + wc;
+  if (wr < 0 || wr >= WH || wc < 0 || wc >= WW || r < 0 || r >= IH || q < 0 || q >= IW) return n;
+  const size_t p = (size_t)r * IW + (size_t)q;
+  n.exists = true;
+  n.code = df[p];
+  n.on = n.code != pv::NO_OBSERVATION && (!mf || mf[p] == mv);
+  return n;
+}
+
+// E1 and E2's first pass: grid = (strip blocks, items).  A workgroup takes row strips of 256 columns: the outline flags of the strip and
+// of `reach` columns on either side go to LDS (each from the node's code and its four neighbours'), then lane l finds the nearest flagged
+// column to its own.  g: [B][WH][WW] int32.
+__global__ __launch_bounds__(RB) void contour_rows_kernel(Frames fr, const int *__restrict__ items, const double *__restrict__ stats6, int WH, int WW,
+                                                          int edge_step, int reach, int *__restrict__ g) {
+  __shared__ unsigned char flag_s[contour::STRIP + 2 * contour::MAX_REACH];
+  const int b = blockIdx.y;
+  if (stats6[meshicp::NSTAT * (size_t)b + meshicp::ST_STATUS] != 0.0) return;  // a bad item: nothing is read through its record
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  const size_t npix = (size_t)fr.IH * fr.IW;
+  const unsigned short *df = fr.depth + (size_t)item[pv::IT_FRAME] * npix;
+  const unsigned short *mf = fr.mask ? fr.mask + (size_t)item[pv::IT_MASK_FRAME] * npix : nullptr;
+  const int r0 = item[pv::IT_R0], c0 = item[pv::IT_C0], mv = item[pv::IT_MASK_VALUE];
+  const int chunks = (WW + contour::STRIP - 1) / contour::STRIP;
+  const long long strips = (long long)WH * chunks;                            // <= 2^30
+  int *gb = g + (size_t)b * WH * WW;
+  for (long long s = blockIdx.x; s < strips; s += gridDim.x) {
+    const int wr = (int)(s / chunks), first = (int)(s - (long long)wr * chunks) * contour::STRIP - reach;
+    __syncthreads();                                                          // the previous strip's readers are done
+    for (int i = threadIdx.x; i < contour::STRIP + 2 * reach; i += RB) {
+      const int wc = first + i;
+      const contour::Node c = observed_node(df, mf, mv, fr.IH, fr.IW, r0, c0, WH, WW, wr, wc);
+      bool edge = false;
+      if (c.on) {
+        const contour::Node nb[4] = {observed_node(df, mf, mv, fr.IH, fr.IW, r0, c0, WH, WW, wr - 1, wc),
+                                     observed_node(df, mf, mv, fr.IH, fr.IW, r0, c0, WH, WW, wr + 1, wc),
+                                     observed_node(df, mf, mv, fr.IH, fr.IW, r0, c0, WH, WW, wr, wc - 1),
+                                     observed_node(df, mf, mv, fr.IH, fr.IW, r0, c0, WH, WW, wr, wc + 1)};
+        edge = contour::outline(c, nb, edge_step);
+      }
+      flag_s[i] = edge ? 1 : 0;
+    }
+    __syncthreads();
+    const int wc = first + reach + (int)threadIdx.x;
+    if (wc < WW) gb[(size_t)wr * WW + wc] = contour::row_nearest(flag_s, first, wc, reach, WW);
+  }
+}
+
+// E2's second pass: a lane per window slot, along the rows, so that a wave reads 64 neighbouring columns of each row it scans
+__global__ __launch_bounds__(RB) void contour_columns_kernel(const int *__restrict__ g, Frames fr, const int *__restrict__ items,
+                                                             const double *__restrict__ stats6, int WH, int WW, int reach,
+                                                             int *__restrict__ feat) {
+  const int b = blockIdx.y;
+  if (stats6[meshicp::NSTAT * (size_t)b + meshicp::ST_STATUS] != 0.0) return;
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  const int slots = WH * WW;                                                  // <= 2^30
+  const int *gb = g + (size_t)b * slots;
+  int *fb = feat + (size_t)b * slots;
+  for (long long s = (long long)blockIdx.x * RB + threadIdx.x; s < slots; s += (long long)gridDim.x * RB) {
+    int r = 0, q = 0;
+    const int wr = (int)(s / WW), wc = (int)(s - (long long)wr * WW);
+    fb[s] = pv::slot_node((int)s, item[pv::IT_R0], item[pv::IT_C0], WW, fr.IH, fr.IW, &r, &q) ? contour::column_nearest(gb, WH, WW, wr, wc, reach)
+                                                                                                : contour::NONE;
+  }
+}
+
+// the node at (wr, wc) of an item's window as E3 sees it, from the key plane
+__device__ inline contour::Node drawn_node(const unsigned long long *__restrict__ kb, int IH, int IW, int r0, int c0, int WH, int WW, int wr,
+                                           int wc) {
+  contour::Node n = {false, false, pv::NO_CODE};
+  const long long r = (long long)r0 + wr, q = (long long)c0 + wc;
+  if (wr < 0 || wr >= WH || wc < 0 || wc >= WW || r < 0 || r >= IH || q < 0 || q >= IW) return n;
+  n.exists = true;
+  n.code = pv::key_code(kb[(size_t)wr * WW + wc]);
+  n.on = n.code != pv::NO_CODE;
+  return n;
+}
+
+// E3..E5: dense_accum_kernel's shape and order (tile blocks x items, lane l takes a tile's slots l, l + 256, .. in ascending order, I6's
+// tree by shuffles, the four waves in LDS, a plain store of the tile's row), over the outline pairs: a drawn-outline node reads its
+// feature, the two codes and the two rays, and adds its two terms, k = 0 first.
+__global__ __launch_bounds__(RB) void contour_accum_kernel(const unsigned long long *__restrict__ keys, const int *__restrict__ feat, Frames fr,
+                                                           const double *__restrict__ rays, const int *__restrict__ items,
+                                                           const double *__restrict__ frames, const double *__restrict__ stats6, int WH, int WW,
+                                                           int edge_step, double contour_scale, double p22, double p23, double cloud_div,
+                                                           int ntiles, double *__restrict__ part) {
+  __shared__ double part_s[RB / 64][dense::NPART];
+  const int b = blockIdx.y;
+  if (stats6[meshicp::NSTAT * (size_t)b + meshicp::ST_STATUS] != 0.0) return;
+  int item[pv::ITEM_INTS];
+  load_item(items, b, item);
+  double X[12];
+  const double *fb = frames + dense::FRAME_DOUBLES * (size_t)b;
+#pragma unroll
+  for (int e = 0; e < 12; ++e) X[e] = fb[e];
+  const int slots = WH * WW;                                                  // <= 2^30
+  const size_t npix = (size_t)fr.IH * fr.IW;
+  const unsigned long long *kb = keys + (size_t)b * slots;
+  const int *eb = feat + (size_t)b * slots;
+  const unsigned short *df = fr.depth + (size_t)item[pv::IT_FRAME] * npix;
+  const int r0 = item[pv::IT_R0], c0 = item[pv::IT_C0];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    double acc[meshicp::NSUM];
+#pragma unroll
+    for (int k = 0; k < meshicp::NSUM; ++k) acc[k] = 0.0;
+    int cnt = 0;
+    for (int j = 0; j < dense::SWEEPS; ++j) {
+      const long long sl = (long long)tile * dense::TILE + j * RB + threadIdx.x;
+      if (sl >= slots) continue;
+      const int wr = (int)(sl / WW), wc = (int)(sl - (long long)wr * WW);
+      const contour::Node c = drawn_node(kb, fr.IH, fr.IW, r0, c0, WH, WW, wr, wc);
+      if (!c.on) continue;
+      const contour::Node nb[4] = {drawn_node(kb, fr.IH, fr.IW, r0, c0, WH, WW, wr - 1, wc), drawn_node(kb, fr.IH, fr.IW, r0, c0, WH, WW, wr + 1, wc),
+                                   drawn_node(kb, fr.IH, fr.IW, r0, c0, WH, WW, wr, wc - 1), drawn_node(kb, fr.IH, fr.IW, r0, c0, WH, WW, wr, wc + 1)};
+      if (!contour::outline(c, nb, edge_step)) continue;
+      const int e = eb[sl];
+      int re = 0, qe = 0;
+      if (e < 0 || e >= slots || !pv::slot_node(e, r0, c0, WW, fr.IH, fr.IW, &re, &qe)) continue;   // none; the rest never holds for a feature
+      const size_t pc = (size_t)((long long)r0 + wr) * fr.IW + (size_t)((long long)c0 + wc), pe = (size_t)re * fr.IW + qe;
+      const double ray_c[3] = {rays[3 * pc], rays[3 * pc + 1], rays[3 * pc + 2]};
+      const double ray_e[3] = {rays[3 * pe], rays[3 * pe + 1], rays[3 * pe + 2]};
+      double term[contour::PAIR_TERMS * meshicp::TERM_DOUBLES];
+      if (!contour::pair_terms(c.code, ray_c, df[pe], ray_e, p22, p23, cloud_div, X, contour_scale, term)) continue;
+      meshicp::accumulate(term, acc);
+      meshicp::accumulate(term + meshicp::TERM_DOUBLES, acc);
+      ++cnt;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+#pragma unroll
+      for (int k = 0; k < meshicp::NSUM; ++k) acc[k] = acc[k] + __shfl_down(acc[k], s);
+      cnt += __shfl_down(cnt, s);
+    }
+    __syncthreads();                                                          // the previous tile's readers are done
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < meshicp::NSUM; ++k) part_s[wave][k] = acc[k];
+      part_s[wave][meshicp::NSUM] = (double)cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x < dense::NPART) {
+      const int k = threadIdx.x;
+      part[((size_t)b * ntiles + tile) * dense::PART_DOUBLES + k] = (part_s[0][k] + part_s[1][k]) + (part_s[2][k] + part_s[3][k]);
+    }
+  }
+}
+
+// E5, E6: dense_finish_kernel with two row sets: lane k < 29 adds entry k of the plane rows and, separately, of the outline rows in
+// ascending tile order onto zero; lane 0 forms S = P + C, runs finish_pass with P's count on the item's own six columns and copies them,
+// with the pass's pairs, into the caller's row.
+__global__ __launch_bounds__(64) void contour_finish_kernel(const double *__restrict__ part, const double *__restrict__ cpart, int ntiles, int pass,
+                                                            int solve, double *__restrict__ work, double *__restrict__ frames,
+                                                            double *__restrict__ pose_out, double *__restrict__ stats6,
+                                                            double *__restrict__ stats) {
+  __shared__ double sums[2][dense::NPART];
+  const int b = blockIdx.x;
+  if (stats6[meshicp::NSTAT * (size_t)b + meshicp::ST_STATUS] != 0.0) return;
+  if (threadIdx.x < dense::NPART) {
+    const size_t at = (size_t)b * ntiles * dense::PART_DOUBLES + threadIdx.x;
+    double sp = 0.0, sc = 0.0;
+    for (int t = 0; t < ntiles; ++t) sp = sp + part[at + (size_t)t * dense::PART_DOUBLES];
+    for (int t = 0; t < ntiles; ++t) sc = sc + cpart[at + (size_t)t * dense::PART_DOUBLES];
+    sums[0][threadIdx.x] = sp;
+    sums[1][threadIdx.x] = sc;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double tot[meshicp::NSUM], p[7], X[12];
+  contour::add_sums(sums[0], sums[1], tot);
+  for (int e = 0; e < 7; ++e) p[e] = work[DENSE_POSE_DOUBLES * (size_t)b + e];
+  double *s6 = stats6 + meshicp::NSTAT * (size_t)b, *s8 = stats + contour::NSTAT * (size_t)b;
+  meshicp::finish_pass(tot, (int)sums[0][meshicp::NSUM], pass, solve, p, s6);
+  meshicp::model_frame(p, X);
+  for (int e = 0; e < 7; ++e) {
+    work[DENSE_POSE_DOUBLES * (size_t)b + e] = p[e];
+    pose_out[7 * (size_t)b + e] = p[e];
+  }
+  for (int e = 0; e < 12; ++e) frames[dense::FRAME_DOUBLES * (size_t)b + e] = X[e];
+  for (int e = 0; e < meshicp::NSTAT; ++e) s8[e] = s6[e];
+  if (pass == 0) s8[contour::ST_FIRST_PAIRS] = sums[1][meshicp::NSUM];
+  s8[contour::ST_LAST_PAIRS] = sums[1][meshicp::NSUM];
+}
+
 inline bool window_ok(int B, int WH, int WW) { return B >= 1 && B <= 65535 && WH >= 1 && WW >= 1 && (long)WH * WW <= (1L << 30); }
 
 // blocks per item of a launch over `items` lanes' worth of work per item
@@ -548,6 +751,110 @@ extern "C" int df_pose_refine_dense(const float *vertices, int V, const int *tri
     hipLaunchKernelGGL(dense_accum_kernel, dim3(xb, B), dim3(RB), 0, st, keys, fr, rays, items, vertices, V, triangles, T, frames, stats, WH, WW, gate,
                        cam.p22, cam.p23, cloud_div, ntiles, part);
     hipLaunchKernelGGL(dense_finish_kernel, dim3(B), dim3(64), 0, st, part, ntiles, pass, pass < iters ? 1 : 0, work, frames, pose_out, stats);
+  }
+  return check_launch(name);
+}
+
+// the parts of df_pose_refine_contour's scratch: the dense call's, in its order; the six dense columns of every item at the stride the
+// dense kernels read a status through; the feature map, one int32 per window slot (rounded up to 8 bytes); a second row per (item, tile).
+// The first pass of the feature transform keeps its plane in the key planes, which no pass has drawn into yet.
+namespace {
+struct ContourScratch {
+  DenseScratch dense;
+  size_t stats6, feat, cpart, total;
+};
+ContourScratch contour_scratch(int B, int WH, int WW) {
+  ContourScratch s;
+  s.dense = dense_scratch(B, WH, WW);
+  s.stats6 = (size_t)B * meshicp::NSTAT * sizeof(double);
+  s.feat = (((size_t)B * WH * WW * sizeof(int) + 7) / 8) * 8;
+  s.cpart = s.dense.part;
+  s.total = s.dense.total + s.stats6 + s.feat + s.cpart;
+  return s;
+}
+}  // namespace
+
+extern "C" size_t df_pose_refine_contour_scratch_bytes(int B, int WH, int WW) {
+  return window_ok(B, WH, WW) ? contour_scratch(B, WH, WW).total : 0;
+}
+
+extern "C" int df_pose_refine_contour(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale,
+                                      int O, const double *proj, const unsigned short *depth, int F, int IH, int IW, const double *rays,
+                                      const unsigned short *mask, int NM, const int *items, const double *pose_in, double cloud_div, int B,
+                                      int WH, int WW, int gate, int cull, int iters, int edge_step, int reach, double contour_scale,
+                                      double *pose_out, double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream) {
+  const char *name = "pose_refine_contour";
+  if (!vertices || !triangles || !tri_begin || !model_scale || !proj || !depth || !rays || !items || !pose_in || !pose_out || !stats || !scratch)
+    return set_error(DF_ERR_ARG, "%s: null pointer", name);
+  if (mask && NM < 1) return set_error(DF_ERR_ARG, "%s: a mask needs NM >= 1 frames, got %d", name, NM);
+  if (!objects_ok(O)) return set_error(DF_ERR_ARG, "%s: O = %d objects outside 1..%d", name, O, MAX_OBJECTS);
+  if (V <= 0 || T <= 0 || !sizes_ok(F, IH, IW)) return set_error(DF_ERR_ARG, "%s: bad sizes", name);
+  if (!window_ok(B, WH, WW)) return set_error(DF_ERR_ARG, "%s: B = %d outside 1..65535 or WH x WW = %d x %d outside 1..2^30", name, B, WH, WW);
+  if (gate < 0 || gate > dense::MAX_GATE) return set_error(DF_ERR_ARG, "%s: gate %d outside 0..%d", name, gate, dense::MAX_GATE);
+  if (iters < 0 || iters > meshicp::MAX_ITERS) return set_error(DF_ERR_ARG, "%s: iters %d outside 0..%d", name, iters, meshicp::MAX_ITERS);
+  if (cull != 0 && cull != 1) return set_error(DF_ERR_ARG, "%s: cull %d is neither 0 nor 1", name, cull);
+  if (edge_step < 0 || edge_step > contour::MAX_EDGE_STEP)
+    return set_error(DF_ERR_ARG, "%s: edge_step %d outside 0..%d", name, edge_step, contour::MAX_EDGE_STEP);
+  if (reach < 0 || reach > contour::MAX_REACH) return set_error(DF_ERR_ARG, "%s: reach %d outside 0..%d", name, reach, contour::MAX_REACH);
+  if (!(contour_scale >= 0.0 && contour_scale - contour_scale == 0.0))
+    return set_error(DF_ERR_ARG, "%s: contour_scale must be finite and >= 0", name);
+  if (!(cloud_div > 0.0 && cloud_div - cloud_div == 0.0)) return set_error(DF_ERR_ARG, "%s: cloud_div must be finite and > 0", name);
+  if (reinterpret_cast<uintptr_t>(rays) % 8 || reinterpret_cast<uintptr_t>(pose_in) % 8 || reinterpret_cast<uintptr_t>(pose_out) % 8 ||
+      reinterpret_cast<uintptr_t>(stats) % 8)
+    return set_error(DF_ERR_ARG, "%s: rays, pose_in, pose_out and stats must be 8-byte aligned", name);
+  const ContourScratch lay = contour_scratch(B, WH, WW);
+  if (int e = check_scratch_and_proj(name, scratch, scratch_bytes, lay.total, proj)) return e;
+  int longest = 0;
+  if (int e = check_tri_begin(name, tri_begin, O, T, &longest)) return e;
+  const size_t npix = (size_t)IH * IW, pose_b = (size_t)B * 7 * sizeof(double), stats_b = (size_t)B * contour::NSTAT * sizeof(double);
+  const struct { const void *p; size_t n; } ins[] = {{vertices, (size_t)V * 12}, {triangles, (size_t)T * 12}, {depth, (size_t)F * npix * 2},
+                                                     {mask, (size_t)(mask ? NM : 0) * npix * 2}, {rays, npix * 24},
+                                                     {items, (size_t)B * pv::ITEM_INTS * 4}, {pose_in, pose_b}, {scratch, lay.total}};
+  for (const auto &in : ins)
+    if (ranges_overlap(pose_out, pose_b, in.p, in.n) || ranges_overlap(stats, stats_b, in.p, in.n))
+      return set_error(DF_ERR_ARG, "%s: pose_out and stats may not overlap the inputs or the scratch", name);
+  if (ranges_overlap(pose_out, pose_b, stats, stats_b)) return set_error(DF_ERR_ARG, "%s: pose_out and stats overlap", name);
+
+  hipStream_t st = to_stream(stream);
+  const long slots = (long)WH * WW;
+  const DenseScratch &dl = lay.dense;
+  char *base = static_cast<char *>(scratch);
+  unsigned long long *keys = reinterpret_cast<unsigned long long *>(base);
+  long long *side = reinterpret_cast<long long *>(base + dl.keys);
+  double *work = reinterpret_cast<double *>(base + dl.keys + dl.side);
+  double *frames = reinterpret_cast<double *>(base + dl.keys + dl.side + dl.work);
+  double *part = reinterpret_cast<double *>(base + dl.keys + dl.side + dl.work + dl.frames);
+  double *stats6 = reinterpret_cast<double *>(base + dl.total);
+  int *feat = reinterpret_cast<int *>(base + dl.total + lay.stats6);
+  double *cpart = reinterpret_cast<double *>(base + dl.total + lay.stats6 + lay.feat);
+  int *rows = reinterpret_cast<int *>(keys);                                  // the first feature pass's plane: B * slots int32
+  const Frames fr = {depth, mask, F, NM, IH, IW};
+  const ObjectTable tab = make_object_table(tri_begin, model_scale, O, T);
+  const Camera cam = make_camera(proj);
+  const int ntiles = dense::tile_count(slots);
+  int cap = cdiv(VERIFY_TARGET_BLOCKS, B) < RESOLVE_MAX_BLOCKS ? cdiv(VERIFY_TARGET_BLOCKS, B) : RESOLVE_MAX_BLOCKS;
+  cap = cap < 1 ? 1 : cap;
+  const int tb = item_blocks(longest, B, RASTER_MAX_BLOCKS), xb = ntiles < cap ? ntiles : cap;
+  const long strips = (long)WH * cdiv(WW, contour::STRIP);
+  const int sb = (int)(strips < cap ? strips : cap), cb = item_blocks(slots, B, RESOLVE_MAX_BLOCKS);
+  if (hipMemsetAsync(side, 0, dl.side, st) != hipSuccess) return check_launch(name);
+  hipLaunchKernelGGL(dense_init_kernel, dim3(cdiv(B, RB)), dim3(RB), 0, st, items, pose_in, tab, O, F, mask ? 1 : 0, NM, cloud_div, B, work, frames,
+                     pose_out, stats6);
+  hipLaunchKernelGGL(contour_stats_kernel, dim3(cdiv(B, RB)), dim3(RB), 0, st, stats6, B, stats);
+  // E1, E2, once per call
+  hipLaunchKernelGGL(contour_rows_kernel, dim3(sb, B), dim3(RB), 0, st, fr, items, stats6, WH, WW, edge_step, reach, rows);
+  hipLaunchKernelGGL(contour_columns_kernel, dim3(cb, B), dim3(RB), 0, st, rows, fr, items, stats6, WH, WW, reach, feat);
+  for (int pass = 0; pass <= iters; ++pass) {
+    if (hipMemsetAsync(keys, 0xff, dl.keys, st) != hipSuccess) return check_launch(name);
+    // D1..D5 as they stand, then E3..E5 over the same key plane
+    hipLaunchKernelGGL(verify_raster_kernel, dim3(tb, B), dim3(RB), 0, st, vertices, V, triangles, tab, O, cam, fr, items, work, cloud_div, WH, WW,
+                       cull, keys, side);
+    hipLaunchKernelGGL(dense_accum_kernel, dim3(xb, B), dim3(RB), 0, st, keys, fr, rays, items, vertices, V, triangles, T, frames, stats6, WH, WW, gate,
+                       cam.p22, cam.p23, cloud_div, ntiles, part);
+    hipLaunchKernelGGL(contour_accum_kernel, dim3(xb, B), dim3(RB), 0, st, keys, feat, fr, rays, items, frames, stats6, WH, WW, edge_step,
+                       contour_scale, cam.p22, cam.p23, cloud_div, ntiles, cpart);
+    hipLaunchKernelGGL(contour_finish_kernel, dim3(B), dim3(64), 0, st, part, cpart, ntiles, pass, pass < iters ? 1 : 0, work, frames, pose_out,
+                       stats6, stats);
   }
   return check_launch(name);
 }

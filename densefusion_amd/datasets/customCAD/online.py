@@ -340,6 +340,17 @@ class RenderedPoseDataset(ChunkedViews):
         refiner = DensePoseRefiner(self.meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
         return refiner.set_rays(self.udp.ray_map_on(self.device))
 
+    def contour_refiner(self):
+        """A ``lib.pose_refine_contour.ContourPoseRefiner`` built as ``dense_refiner()`` builds its refiner, with the same two
+        ``ValueError``s: the dense ICP with an outline term, which holds views of one or two faces that the planes alone leave free."""
+        if self.meshes is None:
+            raise ValueError('contour_refiner needs triangles: a scene or raster mesh (a point cloud has none)')
+        if not self.keep_frames:
+            raise ValueError('contour_refiner needs the frames the items were cut from: RenderedPoseDataset(keep_frames=True)')
+        from ...lib.pose_refine_contour import ContourPoseRefiner
+        refiner = ContourPoseRefiner(self.meshes, self.model_scale, self.proj_mat, self.image_dims, cloud_div=10000.0, device=self.device)
+        return refiner.set_rays(self.udp.ray_map_on(self.device))
+
     def ppf_estimator(self, **model_options):
         """A ``lib.pose_ppf.PpfEstimator`` of the models' meshes sampled in the units of the items' clouds (``model_options``: the keyword
         arguments of ``lib.pose_ppf.PpfModels`` after ``cloud_div``), with the renderer's camera and frame size, carrying the loader's ray

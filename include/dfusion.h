@@ -1002,6 +1002,55 @@ int df_pose_refine_dense(const float *vertices, int V, const int *triangles, int
                          df_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * df_pose_refine_dense with an outline term (densefusion_amd/lib/pose_refine_contour.py).  Planes alone leave a direction free on a view
+ * of one flat wall or of two faces of a box (D6's status 2); the object's outline holds it.  Once per call the outline of the observed
+ * object is found and every node learns its nearest outline node; per pass the outline of the drawn model is found in the key plane and
+ * each of its nodes is pulled, across the image only, towards the observed outline node nearest to it.  The pairs' sums are added to
+ * the planes' before the solve.  Like the dense call: no allocation, no synchronisation, the caller's stream, no floating-point atomic,
+ * two identical calls give identical bytes, an item's row depends on its own record, pose, object, frame and mask only.  E1..E3 are
+ * integer; E4 is fp64, one rounding per operation in the order written (no contraction), only + - * / appear; a restatement matches bit
+ * for bit (tests/pose_contour_np.py).  The rules are densefusion_amd/csrc/pose_contour_core.h.  df_pose_refine_dense, df_pose_verify,
+ * df_pose_vsd, df_pose_ppf and df_mesh_icp, their kernels and their outputs are unchanged: verify_raster_kernel and the dense
+ * accumulation are launched as they stand.
+ *
+ * df_pose_refine_contour_scratch_bytes: df_pose_refine_dense_scratch_bytes, then per item the six dense columns (6 doubles, at the
+ *   stride the dense kernels read a status through), one int32 per window slot for the feature map (the B*WH*WW of them rounded up to a
+ *   multiple of 8 bytes), and a second set of 32 doubles per (item, tile); 0 for sizes the call refuses (host only).
+ * df_pose_refine_contour: df_pose_refine_dense's arguments, and before pose_out edge_step in 0..65535 (codes), reach in 0..64 (nodes)
+ *   and contour_scale, finite and >= 0.  stats [B][8] fp64 = the six columns of df_pose_refine_dense, then the outline pairs of the first
+ *   and of the last pass.
+ *   DF_ERR_ARG, before anything is launched or written: every refusal of df_pose_refine_dense (stats being [B][8] in the overlap rule),
+ *   and edge_step, reach or contour_scale out of range.
+ *   Per item: S0 and the bad-item rule of df_pose_refine_dense (a bad item's columns 6 and 7 are 0).  For a good item:
+ *   E1. The observed outline, once per call, all integer.  A node exists when it lies inside the window and the frame.  on(r, q): co !=
+ *       65535 and, with a mask, m holds.  A node is an observed-outline node when it is on and at least one of (r-1, q), (r+1, q),
+ *       (r, q-1), (r, q+1) exists and is either not on or has co_nb - co > edge_step.  A neighbour that does not exist never makes an
+ *       outline: an object cut by the frame or the window has no outline there.
+ *   E2. The feature map, once per call, all integer.  Every existing node stores the slot of the observed-outline node of its own window
+ *       with the smallest dr^2 + dq^2, among equals the lowest slot, and "none" when that minimum exceeds reach^2.
+ *   Then pass k = 0 .. iters for every item whose status is 0: D1..D5 of df_pose_refine_dense, unchanged, give the plane sums P and their
+ *   count, and
+ *   E3. The drawn outline: E1's rule with "took a key" for on and cr for co.
+ *   E4. A drawn-outline node c whose feature e is not "none" forms a pair.  a = X p(c, cr_c) and x = X p(e, co_e) with p by D3 (the code
+ *       and the ray of the node named) and X the pass's model frame; w = x - a.  For k = 0, 1: n_k = (X[0][k], X[1][k], X[2][k]), the
+ *       camera's x and y axes in the model frame; J = (x x n_k, n_k), each of the six then multiplied by contour_scale; r = (n_k . w)
+ *       contour_scale; d2 = 0.  The pair counts when all fourteen numbers are finite; its two terms go through I6's `accumulate`, k = 0
+ *       first.
+ *   E5. The outline sums C and the pair count are reduced in D5's order by the slot of c (the same tiles, lanes and tree, a row of its
+ *       own per tile).  S = P + C entry by entry for A and G, one add each; D, the count and the rms are P's.
+ *   E6. D6 through the same function, unchanged, on S; the few-inlier rule uses P's count.  Columns 6 and 7 = the pair count of pass 0
+ *       and of the last pass the item took part in.
+ *   With contour_scale == 0, or when no pair forms, pose_out and the six dense columns equal df_pose_refine_dense's byte for byte.
+ *   Launches: once per call the init, the outline with the feature transform's row pass (a row strip in LDS) and its column pass; per pass
+ *   the dense call's clear, raster and accumulation, the outline accumulation and a finish that adds both row sets in order. */
+size_t df_pose_refine_contour_scratch_bytes(int B, int WH, int WW);
+int df_pose_refine_contour(const float *vertices, int V, const int *triangles, int T, const int *tri_begin, const double *model_scale, int O,
+                           const double *proj, const unsigned short *depth, int F, int IH, int IW, const double *rays,
+                           const unsigned short *mask, int NM, const int *items, const double *pose_in, double cloud_div, int B, int WH,
+                           int WW, int gate, int cull, int iters, int edge_step, int reach, double contour_scale, double *pose_out,
+                           double *stats, void *scratch, size_t scratch_bytes, df_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pose hypotheses of B items from depth alone, by point-pair-feature voting (Drost et al. 2010; densefusion_amd/lib/pose_ppf.py): a
  * global search that needs the sampled CAD model and the item's depth window and no start pose.  Every pair of an oriented scene
  * reference point and another scene point looks up the model pairs of the same quantised feature and votes for (model point, rotation

@@ -48,6 +48,15 @@ as ``<source>_icp_dense``: the ICP pose, then the dense steps.  ``--dense_gate``
 and an observed node that still takes part, ``--dense_mask`` lets only the nodes of the item's mask take part.  The new entries compose
 with ``--verify`` and ``--bop`` like the others; each logs the items the step left alone and the mean point-to-plane rms before and
 after.  Without ``--dense`` nothing changes by a byte.
+``--contour K`` (default 0: off) adds the dense ICP with an outline term (``df_pose_refine_contour``), which holds the views
+of one or two faces that ``--dense`` hands back as degenerate: every mask source is scored once more as ``<source>_contour`` and, with
+``--icp``, as ``<source>_icp_contour``, K steps in the window ``--dense`` uses.  ``--contour_scale`` weighs an outline residual against a
+plane residual, ``--contour_reach`` is the farthest outline node (in nodes) a drawn-outline node pairs with, ``--contour_edge_step`` the depth
+step (codes) between neighbours that counts as an outline (65535: only the border of what was observed or drawn), ``--contour_gate`` the
+plane term's gate and ``--contour_mask`` lets only the nodes of the item's mask take part (and bound the observed outline).  The entries
+compose with ``--verify`` and ``--bop``; each log says how many items were left alone, the mean rms and the mean outline pairs first ->
+last.  ``--ppf_contour`` makes the ``--ppf`` chain's cluster steps use this call, with ``--ppf_dense`` steps and ``--ppf_dense_gate``.
+Without these flags nothing changes by a byte.
 ``--ppf K`` (default 0: off) adds the pose search that needs no network (``df_pose_ppf``): every mask source is scored once
 more as ``<source>_ppf``.  Per item the K best clusters of point-pair-feature votes are taken from the nodes of the item's mask in the
 window of its crop box grown by ``--verify_margin`` (``--ppf_points`` samples a model, every ``--ppf_step``-th node, every
@@ -111,6 +120,14 @@ def build_parser():
                     "and, with --icp, <source>_icp_dense")
     ap.add_argument("--dense_gate", type=int, default=16, help="--dense: depth codes a drawn and an observed node may differ by and still take part")
     ap.add_argument("--dense_mask", action="store_true", help="--dense: only the nodes of the item's mask take part")
+    ap.add_argument("--contour", type=int, default=0, help="steps of dense ICP with an outline term (0 = off); scored as <source>_contour and, with "
+                    "--icp, <source>_icp_contour")
+    ap.add_argument("--contour_scale", type=float, default=0.1, help="--contour, --ppf_contour: weight of an outline residual against a plane residual")
+    ap.add_argument("--contour_reach", type=int, default=6, help="--contour, --ppf_contour: nodes to the farthest observed-outline node a drawn one pairs with")
+    ap.add_argument("--contour_edge_step", type=int, default=65535, help="--contour, --ppf_contour: depth codes between neighbours above which the nearer is an outline node")
+    ap.add_argument("--contour_gate", type=int, default=16, help="--contour: depth codes a drawn and an observed node may differ by and still take part")
+    ap.add_argument("--contour_mask", action="store_true", help="--contour: only the nodes of the item's mask take part")
+    ap.add_argument("--ppf_contour", action="store_true", help="--ppf: the cluster poses take their steps with the outline term")
     ap.add_argument("--ppf", type=int, default=0, help="clusters of point-pair-feature votes to refine and choose from (0 = off); scored as <source>_ppf")
     ap.add_argument("--ppf_points", type=int, default=400, help="--ppf: surface samples per model")
     ap.add_argument("--ppf_step", type=int, default=1, help="--ppf: every this many nodes of the window is a scene point")
@@ -205,6 +222,7 @@ class DenseStep:
     def __init__(self, dataset, opt, inner=None):
         self.dataset, self.ref, self.inner = dataset, dataset.dense_refiner(), inner
         self.iters, self.gate, self.use_mask, self.margin, self.cull = opt.dense, opt.dense_gate, bool(opt.dense_mask), opt.verify_margin, bool(dataset.cull)
+        self.more = {}                                              # what a ``ContourStep`` adds to the call
         self.stats = []
 
     def __call__(self, indices, candidates, objs):
@@ -216,7 +234,7 @@ class DenseStep:
         rec = torch.tensor([[k, objs[k], f["box"][0] - self.margin, f["box"][2] - self.margin] for k, f in enumerate(infos)],
                            dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
         pose, stats = self.ref.refine(depth, candidates[-1].contiguous(), rec[:, 0], rec[:, 1], rec[:, 2:4], window, iters=self.iters,
-                                      gate=self.gate, mask=mask, cull=self.cull)
+                                      gate=self.gate, mask=mask, cull=self.cull, **self.more)
         self.stats.append(stats)
         return self.inner(indices, [pose], objs) if self.inner is not None else pose
 
@@ -226,6 +244,21 @@ class DenseStep:
         return dict(items=len(st), few=int((st[:, 0] == 1).sum()), degenerate=int((st[:, 0] == 2).sum()), bad_item=int((st[:, 0] == 3).sum()),
                     mean_first_rms=mean(st[:, 2]), mean_last_rms=mean(st[:, 4]), mean_steps=mean(st[:, 5]), gate=self.gate, margin=self.margin,
                     mask=self.use_mask)
+
+
+class ContourStep(DenseStep):
+    """``DenseStep`` from a dataset's ``contour_refiner()``: the ``--contour`` steps of the dense ICP with the outline term."""
+
+    def __init__(self, dataset, opt, inner=None):
+        self.dataset, self.ref, self.inner = dataset, dataset.contour_refiner(), inner
+        self.iters, self.gate, self.use_mask, self.margin, self.cull = opt.contour, opt.contour_gate, bool(opt.contour_mask), opt.verify_margin, bool(dataset.cull)
+        self.more = dict(edge_step=opt.contour_edge_step, reach=opt.contour_reach, contour_scale=opt.contour_scale)
+        self.stats = []
+
+    def summary(self):
+        st = torch.cat(self.stats).cpu().numpy() if self.stats else np.zeros((0, 8))
+        mean = lambda a: float(a.mean()) if len(a) else 0.0
+        return dict(DenseStep.summary(self), mean_first_pairs=mean(st[:, 6]), mean_last_pairs=mean(st[:, 7]), **self.more)
 
 
 class PpfStep:
@@ -238,7 +271,8 @@ class PpfStep:
     def __init__(self, dataset, opt, inner=None):
         self.dataset, self.inner = dataset, inner
         self.est = dataset.ppf_estimator(points=opt.ppf_points)
-        self.ref, self.ver = dataset.dense_refiner(), dataset.pose_verifier()
+        self.ref, self.ver = dataset.contour_refiner() if opt.ppf_contour else dataset.dense_refiner(), dataset.pose_verifier()
+        self.more = dict(edge_step=opt.contour_edge_step, reach=opt.contour_reach, contour_scale=opt.contour_scale) if opt.ppf_contour else {}
         self.k, self.step, self.ref_step, self.gate = opt.ppf, opt.ppf_step, opt.ppf_ref_step, opt.ppf_gate
         self.iters, self.dense_gate, self.tol, self.margin, self.cull = opt.ppf_dense, opt.ppf_dense_gate, opt.verify_tol, opt.verify_margin, bool(dataset.cull)
         self.stats, self.kept = [], []
@@ -255,7 +289,7 @@ class PpfStep:
                                                ref_step=self.ref_step, k=K, mask=mask)
         each = rec.repeat_interleave(K, dim=0)
         refined, _ = self.ref.refine(depth, pose.reshape(B * K, 7), each[:, 0], each[:, 1], each[:, 2:4], window, iters=self.iters,
-                                     gate=self.dense_gate, cull=self.cull)
+                                     gate=self.dense_gate, cull=self.cull, **self.more)
         score = vsiou(self.ver.score(depth, refined, each[:, 0], each[:, 1], each[:, 2:4], window, self.tol, mask=mask, cull=self.cull)).reshape(B, K)
         score = torch.where(votes[:, :, 0] > 0, score, torch.full_like(score, -1.0))      # a missing rank never wins
         kept = score.argmax(dim=1)                                   # the first of the largest: ties to the lower rank
@@ -387,12 +421,13 @@ class _PassLog:
         return self.fw.write(text)
 
 
-def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, verify=None, bop=None, dense=False, ppf=False):
+def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, verify=None, bop=None, dense=False, ppf=False, contour=False):
     """``evaluate()`` over ``dataset`` and the tallies of one mask source; with ``icp`` (an ``IcpStep``) the poses take that last step,
     with ``verify`` (a ``VerifyStep``) they are scored, or chosen, by render-and-compare; with ``bop`` the pose that is scored is also
     scored by the BOP pose errors (``bop``: the dataset's ``BopScorer``; a ``BopStep`` of it goes around ``verify``); with ``dense`` the
     pose first takes the dense steps (a ``DenseStep`` between the two); with ``ppf`` the pose is the best refined cluster of the
-    point-pair-feature votes (a ``PpfStep`` in that place)."""
+    point-pair-feature votes (a ``PpfStep`` in that place); with ``contour`` it takes the steps with the outline term (a ``ContourStep``
+    in that place)."""
     objlist = list(dataset.objlist)
     n = len(dataset) if opt.max_frames <= 0 else min(opt.max_frames, len(dataset))
     with open(os.path.join(opt.output_result_dir, "eval_result_logs_%s.txt" % source), "w") as fw:
@@ -404,8 +439,10 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, ver
             steps["select_pose"] = dense = DenseStep(dataset, opt, inner=verify)
         if ppf:
             steps["select_pose"] = ppf = PpfStep(dataset, opt, inner=verify)
+        if contour:
+            steps["select_pose"] = contour = ContourStep(dataset, opt, inner=verify)
         if bop is not None:
-            steps["select_pose"] = bop = BopStep(dataset, bop, inner=dense or ppf or verify)
+            steps["select_pose"] = bop = BopStep(dataset, bop, inner=dense or ppf or contour or verify)
         log = fw if verify is None else _PassLog(fw)
         success, served = evaluate(dataset, estimator, refiner, diameter, opt, log, **steps)
         success, served = success[:len(objlist)], served[:len(objlist)]
@@ -430,6 +467,13 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, ver
             say("[{0} masks] dense {1} steps gate {2}{3}: {4} items, {5} few inliers, {6} degenerate, mean rms {7:.6g} -> {8:.6g}".format(
                 source, dense.iters, m["gate"], " masked" if m["mask"] else "", m["items"], m["few"], m["degenerate"], m["mean_first_rms"],
                 m["mean_last_rms"]))
+        if contour:
+            out["contour"] = m = contour.summary()
+            say("[{0} masks] contour {1} steps gate {2}{3}, scale {4:g}, reach {5}, edge step {6}: {7} items, {8} few inliers, {9} degenerate "
+                "left alone".format(source, contour.iters, m["gate"], " masked" if m["mask"] else "", m["contour_scale"], m["reach"], m["edge_step"],
+                                    m["items"], m["few"], m["degenerate"]))
+            say("[{0} masks] contour: mean rms {1:.6g} -> {2:.6g}, mean outline pairs {3:.1f} -> {4:.1f}".format(
+                source, m["mean_first_rms"], m["mean_last_rms"], m["mean_first_pairs"], m["mean_last_pairs"]))
         if ppf:
             out["ppf"] = m = ppf.summary()
             say("[{0} masks] ppf top {1} of {2} points, step {3}, every {4}th a reference, gate {5}, {6} dense steps gate {7}: {8} items, {9} without "
@@ -437,6 +481,10 @@ def run_source(source, dataset, estimator, refiner, diameter, opt, icp=None, ver
                                                       m["items"], m["no_hypothesis"], " ".join("%d: %d" % (r, n) for r, n in enumerate(m["kept_rank"]))))
             say("[{0} masks] ppf: mean usable nodes {1:.1f}, hypotheses {2:.1f}, clusters {3:.1f} an item".format(
                 source, m["mean_usable"], m["mean_hypotheses"], m["mean_clusters"]))
+            if ppf.more:                                            # --ppf_contour
+                m["contour"] = dict(ppf.more)
+                say("[{0} masks] ppf: the cluster steps carry the outline term, scale {1:g}, reach {2}, edge step {3}".format(
+                    source, ppf.more["contour_scale"], ppf.more["reach"], ppf.more["edge_step"]))
         if verify is not None:
             out["verify"] = m = verify.summary(log.passed)
             say("[{0} masks] verify tol {1} margin {2}: mean vsiou {3:.6f} over {4} passes, {5:.6f} over {6} misses".format(
@@ -484,6 +532,12 @@ def main(argv=None):
             or not 0 <= opt.ppf_gate <= 65535 or not 0 <= opt.ppf_dense <= 64 or not 0 <= opt.ppf_dense_gate <= 65535):
         raise SystemExit("--ppf takes 0..16 clusters, --ppf_points 2..1024, --ppf_step and --ppf_ref_step 1..64, --ppf_gate and --ppf_dense_gate "
                          "0..65535 codes and --ppf_dense 0..64 steps")
+    if (not 0 <= opt.contour <= 64 or not 0 <= opt.contour_gate <= 65535 or not 0 <= opt.contour_edge_step <= 65535 or not 0 <= opt.contour_reach <= 64
+            or not (opt.contour_scale >= 0 and opt.contour_scale < float("inf"))):
+        raise SystemExit("--contour takes 0..64 steps, --contour_gate and --contour_edge_step 0..65535 codes, --contour_reach 0..64 nodes and "
+                         "--contour_scale a finite weight >= 0")
+    if opt.ppf_contour and not opt.ppf > 0:
+        raise SystemExit("--ppf_contour needs --ppf")
     if not torch.cuda.is_available():
         raise SystemExit("eval_cad_render.py needs a GPU (densefusion_amd has no CPU path)")
     from densefusion_amd.datasets.customCAD.online import RenderedPoseDataset
@@ -507,7 +561,7 @@ def main(argv=None):
             # SegNet's masks need the scene renderer's label plane; the truth run of the same call renders the same scenes
             dataset = RenderedPoseDataset.from_options(opt, opt.cad_model, opt.cad_distractor, first_seed=opt.cad_seed, frames=opt.cad_frames,
                                                        num=NUM_POINTS, scene=True if segnet is not None else None, **kw,
-                                                       **({"keep_frames": True} if opt.verify or opt.bop or opt.dense or opt.ppf else {}))
+                                                       **({"keep_frames": True} if opt.verify or opt.bop or opt.dense or opt.ppf or opt.contour else {}))
         except ValueError as e:
             raise SystemExit(f"eval_cad_render.py: {e}")
 
@@ -548,6 +602,14 @@ def main(argv=None):
                                               verify=verifier(), bop=scorer, dense=True)
                 except ValueError as e:
                     raise SystemExit(f"eval_cad_render.py: --dense: {e}")
+                result[name]["sym_list"] = dataset.get_sym_list()
+        if opt.contour > 0:                                         # the same views once more: the dense steps with the outline term
+            for name, icp in [(source + "_contour", None)] + ([(source + "_icp_contour", True)] if opt.icp > 0 else []):
+                try:
+                    result[name] = run_source(name, dataset, estimator, refiner, diameter, opt, icp=IcpStep(dataset, opt) if icp else None,
+                                              verify=verifier(), bop=scorer, contour=True)
+                except ValueError as e:
+                    raise SystemExit(f"eval_cad_render.py: --contour: {e}")
                 result[name]["sym_list"] = dataset.get_sym_list()
         if opt.ppf > 0:                                             # the same views once more: the pose found from depth alone
             name = source + "_ppf"
